@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- encode + VQ + decode throughput of the MI355X path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs one rank per GPU over RCCL.  Either the caller starts the ranks (python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or a bare
@@ -21,6 +21,7 @@ Extra objects on the line:
                   FLOPs per launch / its average duration measured with HIP events on the launch stream during the
                   timed steps (one event pair per kernel launch, recorded inside the library: mvq_profile_begin/_end),
                   against the fp32 MFMA peak (157.3 TFLOP/s).
+  ms_per_step  -- wall time of one timed step (the --steps timed steps, after --warmup untimed ones).
   cpu_baseline -- the torch-CPU restatement of the same path (oracle/dac24_torch.py, "port") timed on this node's
                   host cores on a bounded sample, rank 0 / N=1 only.
 """
@@ -49,7 +50,7 @@ TOKENS_PER_SEGMENT = 75
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=positive_int, default=5, help="timed steps (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="1-s segments per GPU per step")
     ap.add_argument("--torch-optim", action="store_true", help="train workload: torch.optim.AdamW + torch clip_grad_norm_ "
@@ -73,7 +74,39 @@ def parse():
                     help="f32 (default, the headline): the exact fp32 fma chains of the arithmetic contract.  bf16x6: the OPT-IN, "
                          "NON-PARITY mode -- the wide units' 7-tap convs as six bf16 piece products per fp32 product (fp32-accurate, "
                          "not bit-identical to the oracle; a separate line with its own dtype, never the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): y, the "
+                         "decoded waveform [B, 1, T] (train: y_hat and the scalar loss).  At most 64 MB in all: a larger batch is "
+                         "cut to a fixed, seeded sample of its segments.  With several ranks every rank writes <name>_rank<r>.npy")
     return ap.parse_args()
+
+
+def positive_int(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {n}")
+    return n
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def dump_arrays(outs, budget=DUMP_BYTES_MAX):
+    """{name: tensor} -> {name: float32 numpy array}, within `budget` bytes in all: an array too large for what is left keeps
+    a fixed, seeded sample of its rows along dim 0 (the same rows for the same shape on every run)."""
+    import numpy as np
+    res, left = {}, budget
+    for name, x in outs.items():
+        x = x.detach()
+        if x.dim() > 0 and x.numel() * 4 > left:
+            row = max(1, x[0].numel()) * 4
+            n = max(1, left // row)
+            keep = np.sort(np.random.default_rng(0).choice(x.shape[0], size=min(n, x.shape[0]), replace=False))
+            x = x[torch.as_tensor(keep, device=x.device)]
+        a = x.float().cpu().numpy()
+        res[name] = a
+        left -= a.nbytes
+    return res
 
 
 class KernelEvents:
@@ -357,6 +390,7 @@ def main():
               "pass --allow-overrides to measure it anyway (the line lists them)", file=sys.stderr)
         sys.exit(2)
     ops.set_arith(args.arith)                                    # "f32" unless the opt-in, non-parity mode was asked for
+    torch.manual_seed(1234 + rank)                               # train: the ctx dropout masks; inputs below are seeded too
 
     sd = synth.proposed_model_state(7, rvq_books=args.books, rvq_embed=args.embed)
     train = args.workload == "train"
@@ -400,6 +434,7 @@ def main():
                 total = crit(out["y_hat"], out["tgt"])
                 opt.zero_grad(set_to_none=True)
                 total.backward()
+            last_loss[0] = total.detach()
             if dist:
                 phase("grad_allreduce", lambda: mdist.allreduce_grads(params, B, group=grp))
             if args.torch_optim:
@@ -419,6 +454,7 @@ def main():
 
     collect_phases = False
     launches_per_step = 0
+    last_loss = [None]
     for w in range(args.warmup):
         if w == args.warmup - 1 and not args.no_kernel_events:  # count the launches of one step: the event pool is sized from it
             ops.profile_begin()
@@ -445,6 +481,10 @@ def main():
     elapsed = time.perf_counter() - t0
     summ = kev.summary() if kev else None
     collect_phases = False
+    # what the last timed step returned, taken before any further step runs (the unprofiled steps below overwrite y)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_arrays({"y_hat": y, "loss": last_loss[0].reshape(1)} if train else {"y": y})
 
     # the same steps once more WITHOUT the per-launch events (the two event records per launch sit between back-to-back
     # kernels): reported next to the headline so the instrumentation's cost is a number, not an assumption
@@ -616,8 +656,16 @@ def main():
         if not sweep_ok:
             print("[bench] batch sweep: a small-batch output differs from the same segments of the headline batch", file=sys.stderr, flush=True)
             spot_ok = False
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": str(args.dump_outputs), "arrays": {k: list(v.shape) for k, v in dumped.items()}}
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
+    if dumped is not None:
+        import numpy as np
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        for k, v in dumped.items():
+            np.save(d / (f"{k}_rank{rank}.npy" if world > 1 else f"{k}.npy"), v)
     if dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -31,9 +31,12 @@ patched) and records inputs-by-seed + expected outputs of:
      ``(A_ENC, A_QUANT, T_ENC, T_DEC, c_lat)``, RVQ 10 x 128 from the script's constants) swept over ``books_use`` 1..3 as its
      ``eval_proposed`` does (...:504): per sweep point y, the z_run handed to T_DEC, per-book idx + margins, psnr_batch.
      (``python tests/golden/make_golden.py g11`` regenerates this fixture alone.)
+  G12 the same ``ProposedWrapper``'s state-dict layout: parameter / buffer name -> shape, as JSON
+     (``python tests/golden/make_golden.py g12`` regenerates this fixture alone.)
   G5 psnr_batch / psnr_global_peak_db (Evaluation/compare_dacvsproposal_5_eval.py:180-185, ...6_latency.py:204-214)
-Only data is stored (arrays), never reference source.  Inputs are re-created from seeds by tests/golden_inputs.py.
+Only data is stored (arrays; G12: names and shapes), never reference source.  Inputs are re-created from seeds by tests/golden_inputs.py.
 """
+import json
 import sys
 from pathlib import Path
 
@@ -124,10 +127,23 @@ def make_g11():
     np.savez_compressed(OUT / "g11_proposed_wrapper.npz", **g)
 
 
+def make_g12():
+    """G12: state-dict names and shapes of compare_dacvsproposal_3.5_eval.py's ProposedWrapper (...3.5_eval.py:485)."""
+    e35 = ref_import.eval35()
+    da, dt = T.DAC(), T.DAC()
+    net = e35.ProposedWrapper(da.encoder, da.quantizer, dt.encoder, dt.decoder, c_lat=1024)
+    shapes = {k: list(v.shape) for k, v in net.state_dict().items()}
+    body = ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(shapes.items()))
+    (OUT / "g12_proposed_wrapper_state_shapes.json").write_text("{\n" + body + "\n}\n")
+
+
 def main():
     assert ref_import.available(), "reference not mounted"
     if sys.argv[1:] == ["g11"]:
         make_g11()
+        return
+    if sys.argv[1:] == ["g12"]:
+        make_g12()
         return
     tr, ev, e5 = ref_import.training(), ref_import.evaluation(), ref_import.eval5()
 
@@ -293,6 +309,7 @@ def main():
                         losses=np.array([float(l1), float(st), float(me), float(total)], np.float64),
                         psnr=np.array(e5.psnr_batch(tg, yh), np.float64))
     make_g11()
+    make_g12()
     for f in sorted(OUT.glob("*.npz")):
         print(f.name, f.stat().st_size // 1024, "KiB")
 

@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads and exports every symbol include/mvq.h declares; host-side logic that needs no GPU
 (shape helpers, packed sizes, state-dict compatibility of the module mirror, loud failure without a device)."""
 import ctypes
+import json
 import re
 from pathlib import Path
 
@@ -98,16 +99,9 @@ def test_proposed_wrapper_mirrors_the_3_5_eval_script():
     assert not res.missing_keys and not res.unexpected_keys
     res = net.load_state_dict(synth.proposed_model_state(3, rvq_books=3, rvq_embed=128), strict=False)     # "trained with 3"
     assert sorted(res.missing_keys) == [f"vq.books.{i}" for i in range(3, 10)] and not res.unexpected_keys
-    ref = "/root/reference/Evaluation/compare_dacvsproposal_3.5_eval.py"
-    import os
-    if os.path.exists(ref):                                       # build container only: same key set as the reference's own class
-        from oracle import dac24_torch as T, ref_import
-        e35 = ref_import.eval35()
-        rd, rt = T.DAC(), T.DAC()
-        theirs = e35.ProposedWrapper(rd.encoder, rd.quantizer, rt.encoder, rt.decoder, c_lat=1024)
-        a = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-        b = {k: tuple(v.shape) for k, v in theirs.state_dict().items()}
-        assert a == b
+    # same state-dict layout (names and shapes) as the reference's own class: fixture G12 (tests/golden/make_golden.py)
+    want = json.loads((ROOT / "tests" / "golden" / "g12_proposed_wrapper_state_shapes.json").read_text())
+    assert {k: list(v.shape) for k, v in net.state_dict().items()} == want
 
 
 def test_no_cpu_fallback():
