@@ -172,18 +172,17 @@ def lib():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        # a timing build (pieces of kernels compiled out) or an A/B override in the environment must never pass for the product
+        # an A/B override in the environment must never pass for the product
         flags = int(handle.mvq_build_flags())
         if flags & 0xFFFF and _os.environ.get("MVQ_ALLOW_TIMING_BUILD") != "1":
-            raise MvqError(f"{SO_PATH}: mvq_build_flags() = {flags:#x} (timing build or MVQ_NO_DMA / MVQ_ROWFAST_MAX_KB / "
-                           "MVQ_NO_TOKEN_RVQ in the environment; include/mvq.h).  Only tools/conv_microbench.py-style A/B runs "
-                           "may load it: set MVQ_ALLOW_TIMING_BUILD=1 to do so.")
+            raise MvqError(f"{SO_PATH}: mvq_build_flags() = {flags:#x} (MVQ_NO_DMA in the environment; include/mvq.h).  "
+                           "Only A/B runs may load it: set MVQ_ALLOW_TIMING_BUILD=1 to do so.")
         _lib = handle
     return _lib
 
 
 def build_flags() -> int:
-    """mvq_build_flags() of the loaded library (0 = product build, no A/B override in the environment)."""
+    """mvq_build_flags() of the loaded library (0 = no A/B override in the environment)."""
     return int(lib().mvq_build_flags())
 
 

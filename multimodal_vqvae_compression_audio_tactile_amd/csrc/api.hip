@@ -30,9 +30,6 @@ hipEvent_t prof_event()
 }
 }  // namespace
 bool prof_enabled() { return g_prof_on; }
-// environment overrides a launcher has honoured (MVQ_NO_DMA, MVQ_ROWFAST_MAX_KB, MVQ_NO_TOKEN_RVQ): part of mvq_build_flags()
-static unsigned g_env_flags = 0;
-void note_env_override(unsigned bit) { __atomic_fetch_or(&g_env_flags, bit, __ATOMIC_RELAXED); }
 int prof_begin(const char* kernel_name, double flops, hipStream_t s)
 {
     if (!g_prof_on) return -1;
@@ -162,21 +159,7 @@ int mvq_profile_end2(mvq_profile_entry* out, int max_entries, int* n_entries, in
 }
 
 int mvq_abi_version(void) { return 3; }
-unsigned mvq_build_flags(void)
-{
-    /* every conv translation unit is compiled with the same flags (one Makefile rule); also peek at the environment knobs so
-     * that a process which has not launched anything yet already reports them */
-    if (getenv("MVQ_NO_DMA")) mvq::note_env_override(MVQ_BF_ENV_NO_DMA);
-    if (getenv("MVQ_ROWFAST_MAX_KB")) mvq::note_env_override(MVQ_BF_ENV_ROWFAST);
-    if (getenv("MVQ_NO_TOKEN_RVQ")) mvq::note_env_override(MVQ_BF_ENV_NO_TOKEN_RVQ);
-    if (getenv("MVQ_LN_TILE32")) mvq::note_env_override(0x800);
-    if (getenv("MVQ_LAT_MAX_TILES")) mvq::note_env_override(MVQ_BF_ENV_LAT_TILES);
-    if (getenv("MVQ_NO_DAC_RVQ_LAT")) mvq::note_env_override(0x2000);
-    if (getenv("MVQ_NO_LN_LAT")) mvq::note_env_override(0x4000);
-    if (getenv("MVQ_SMALL_TILE_MAX")) mvq::note_env_override(0x8000);
-    if (getenv("MVQ_F16_NO192") || getenv("MVQ_F16_NO_WIDE")) mvq::note_env_override(0x20);      // tile A/B knobs of the opt-in f16x3 mode
-    return mvq::conv_compile_flags() | __atomic_load_n(&mvq::g_env_flags, __ATOMIC_RELAXED);
-}
+unsigned mvq_build_flags(void) { return getenv("MVQ_NO_DMA") ? 0x100u : 0u; }
 const char* mvq_last_error(void) { return g_err; }
 
 int mvq_device_query(int* cu_count, int* lds_bytes_per_cu, char* arch, int arch_len)

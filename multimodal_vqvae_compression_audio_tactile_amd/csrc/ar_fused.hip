@@ -44,7 +44,6 @@ struct ArK {                 // kernel-side copy of mvq_ar_args + derived pointe
     // chunk-local buffers (workspace): per item rows of pitch 16 (GEMM operands) or pitch Tlat (residual partners of pitch-Tlat outputs)
     float *q16, *qT, *Q16, *ctx16, *y1T, *hdn16, *h16, *zpT, *rN16, *rD16, *qD16;
     unsigned* bar;           // [0] arrival counter, [1] error word
-    unsigned long long* ts;  // MVQ_AR_TIMING: block 0's clock before / after every grid barrier (null: off)
     int nblocks;
 };
 
@@ -343,13 +342,7 @@ void ar_loop_kernel(const ArKT kt_unused)
                         a.r_tokens[(size_t)bd * Tl + s + i] = ld_act(k.rD16 + (size_t)bd * CHUNK + i);
                     }
             }
-            {
-                const ArK& kk = args_here().k;
-                unsigned long long* const ts = kk.ts;
-                if (ts && blockIdx.x == 0 && threadIdx.x == 0 && gen < 120) { ts[2 * gen] = wall_clock64(); ts[256 + 2 * gen] = clock64(); }
-                if (!grid_sync(kk, gen, s_ok)) return;
-                if (ts && blockIdx.x == 0 && threadIdx.x == 0 && gen <= 120) { ts[2 * gen - 1] = wall_clock64(); ts[256 + 2 * gen - 1] = clock64(); }
-            }
+            if (!grid_sync(args_here().k, gen, s_ok)) return;
         }
     }
 }
@@ -417,7 +410,7 @@ size_t mvq_ar_workspace_bytes(int batch, int t_lat)
     const size_t c = mvq::C_LAT, p = mvq::CHUNK;
     const size_t f16 = (size_t)batch * p, fT = (size_t)batch * t_lat;
     const size_t floats = c * f16 * 5 /* q16 Q16 ctx16 hdn16 rN16 */ + (size_t)mvq::C_FF * f16 + 2 * (size_t)mvq::D_CODE * f16 + c * fT * 3 /* qT y1T zpT */;
-    return floats * sizeof(float) + 256 /* alignment */ + 256 /* barrier words */ + 8192 /* stage clocks */;
+    return floats * sizeof(float) + 256 /* alignment */ + 256 /* barrier words */;
 }
 
 // argument checks + workspace carving shared by the two forms; returns MVQ_OK with `done` set when there is nothing to do
@@ -448,9 +441,6 @@ static int ar_prepare(const mvq_ar_args* args, void* workspace, size_t workspace
     char* p = reinterpret_cast<char*>(workspace);
     p += (256 - reinterpret_cast<uintptr_t>(p) % 256) % 256;
     k.bar = reinterpret_cast<unsigned*>(p); p += 256;
-    static const bool timing = getenv("MVQ_AR_TIMING") != nullptr;      // debugging aid: per-stage clocks, printed by mvq_ar_check
-    k.ts = timing ? reinterpret_cast<unsigned long long*>(p) : nullptr;
-    p += 8192;
     auto take = [&](size_t floats) { float* q = reinterpret_cast<float*>(p); p += floats * sizeof(float); return q; };
     const size_t f16 = (size_t)a.batch * CHUNK, fT = (size_t)a.batch * a.t_lat;
     k.q16 = take(C_LAT * f16); k.Q16 = take(C_LAT * f16); k.ctx16 = take(C_LAT * f16); k.hdn16 = take(C_LAT * f16); k.rN16 = take(C_LAT * f16);
@@ -489,7 +479,7 @@ int mvq_ar_latents_f32(const mvq_ar_args* args, void* workspace, size_t workspac
     const int want = a.batch * (C_FF / 16);
     k.nblocks = want < cus ? want : cus;
     if (k.nblocks < 1) k.nblocks = 1;
-    if (hipMemsetAsync(k.bar, 0, k.ts ? 256 + 8192 : 256, st) != hipSuccess) return fail(MVQ_EHIP, "ar_latents: memset failed");
+    if (hipMemsetAsync(k.bar, 0, 256, st) != hipSuccess) return fail(MVQ_EHIP, "ar_latents: memset failed");
     void* kargs[] = {&kt};
     const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(ar_loop_kernel), dim3((unsigned)k.nblocks), dim3(NTHR), kargs, (unsigned)lds, st);
     if (e != hipSuccess) {
@@ -590,29 +580,6 @@ int mvq_ar_check(const void* workspace, void* stream)
     unsigned host[2] = {0, 0};
     if (hipMemcpyAsync(host, p, sizeof(host), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return MVQ_EHIP;
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return MVQ_EHIP;
-    if (getenv("MVQ_AR_TIMING")) {
-        static unsigned long long ts[512];
-        if (hipMemcpy(ts, p + 256, sizeof(ts), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "[ar timing] stage: work us / barrier us (block 0; 100 MHz clock)\n");
-            for (int i = 1; i < 120 && ts[2 * i] != 0; ++i)
-                fprintf(stderr, "  %3d: %7.2f / %6.2f   shader clock %.0f MHz\n", i, (double)(ts[2 * i] - ts[2 * i - 1]) / 100.0, (double)(ts[2 * i + 1] - ts[2 * i]) / 100.0,
-                        (double)(ts[256 + 2 * i] - ts[256 + 2 * i - 1]) / ((double)(ts[2 * i] - ts[2 * i - 1]) / 100.0));
-        }
-    }
-    if (getenv("MVQ_AR_TIMING")) {
-        static unsigned long long ts[512];
-        if (hipMemcpy(ts, p + 256, sizeof(ts), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "[ar timing] stage: work us / barrier us (block 0; 100 MHz clock)\n");
-            for (int i = 1; i < 120 && ts[2 * i] != 0; ++i)
-                fprintf(stderr, "  %3d: %7.2f / %6.2f   shader clock %.0f MHz\n", i, (double)(ts[2 * i] - ts[2 * i - 1]) / 100.0, (double)(ts[2 * i + 1] - ts[2 * i]) / 100.0,
-                        (double)(ts[256 + 2 * i] - ts[256 + 2 * i - 1]) / ((double)(ts[2 * i] - ts[2 * i - 1]) / 100.0));
-        }
-    }
-    if (getenv("MVQ_AR_TIMING")) {
-        unsigned long long d[8];
-        if (hipMemcpy(d, p + 256 + 500 * 8, sizeof(d), hipMemcpyDeviceToHost) == hipSuccess)
-            fprintf(stderr, "[ln phases, cycles] load %llu sync %llu chain1 %llu d+syncs %llu chain2 %llu sync+out %llu\n", d[1] - d[0], d[2] - d[1], d[3] - d[2], d[4] - d[3], d[5] - d[4], d[6] - d[5]);
-    }
     if (host[1] != 0) { mvq::set_last_error("ar_latents: a grid barrier gave up (the grid was not co-resident)"); return MVQ_EHIP; }
     return MVQ_OK;
 }

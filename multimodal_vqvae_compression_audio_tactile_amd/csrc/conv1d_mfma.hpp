@@ -102,79 +102,15 @@ struct ConvArgs {
     int name_len;
 };
 
-// ---- timing-build fence ------------------------------------------------------------------------------------------------------
-// MVQ_EXP (pieces of a kernel compiled out: WRONG RESULTS by construction, only the clock is read), MVQ_KGROUP / MVQ_KPREFETCH
-// (operand-read grouping A/B), MVQ_NO_RES_PREFETCH and MVQ_ASM_READS > 1 exist for tools/conv_microbench.py's timing builds
-// only (MVQ_ASM_READS=0, the compiler-scheduled operand loop, is a correct fallback for a toolchain the ISA lint rejects: it
-// builds without the fence and shows up as an informational bit).  They compile only together with -DMVQ_TIMING_BUILD, and such a library reports itself through
-// mvq_build_flags() (include/mvq.h) -- _lib.lib() refuses to load it unless the caller opted in, bench.py prints the value.
-#ifndef MVQ_KPREFETCH
-#define MVQ_KPREFETCH 1
-#endif
-#ifndef MVQ_ASM_READS
-#define MVQ_ASM_READS 1
-#endif
-#if (defined(MVQ_EXP) || defined(MVQ_KGROUP) || defined(MVQ_NO_RES_PREFETCH) || MVQ_KPREFETCH != 1 || MVQ_ASM_READS > 1) && !defined(MVQ_TIMING_BUILD)
-#error "MVQ_EXP / MVQ_KGROUP / MVQ_KPREFETCH / MVQ_NO_RES_PREFETCH / MVQ_ASM_READS are timing-build switches: add -DMVQ_TIMING_BUILD (the library then reports mvq_build_flags() != 0)"
-#endif
-// bits of mvq_build_flags() that come from the compilation (api.hip adds the environment bits)
-#define MVQ_BF_TIMING_BUILD 0x1
-#define MVQ_BF_EXP 0x2
-#define MVQ_BF_KGROUP 0x4
-#define MVQ_BF_NO_RES_PREFETCH 0x8
-#define MVQ_BF_ASM_READS 0x10
-#define MVQ_BF_ASM_READS_OFF 0x10000     /* informational: compiler-scheduled operand loop (correct, slower) */
-#define MVQ_BF_ENV_NO_DMA 0x100
-#define MVQ_BF_ENV_ROWFAST 0x200
-#define MVQ_BF_ENV_NO_TOKEN_RVQ 0x400
-#define MVQ_BF_ENV_LAT_TILES 0x1000
-#define MVQ_BF_ENV_SMALL_TILES 0x8000
-constexpr unsigned conv_compile_flags()
-{
-    unsigned f = 0;
-#ifdef MVQ_TIMING_BUILD
-    f |= MVQ_BF_TIMING_BUILD;
-#endif
-#ifdef MVQ_EXP
-    f |= MVQ_BF_EXP;
-#endif
-#if defined(MVQ_KGROUP) || MVQ_KPREFETCH != 1
-    f |= MVQ_BF_KGROUP;
-#endif
-#ifdef MVQ_NO_RES_PREFETCH
-    f |= MVQ_BF_NO_RES_PREFETCH;
-#endif
-#if MVQ_ASM_READS > 1
-    f |= MVQ_BF_ASM_READS;
-#elif MVQ_ASM_READS == 0
-    f |= MVQ_BF_ASM_READS_OFF;
-#endif
-    return f;
-}
-// environment overrides (A/B measurements) seen by a launcher: recorded once, reported by mvq_build_flags()
-void note_env_override(unsigned bit);
-
-// k-steps per operand-read group (see conv1d_mfma_body): 1 in a product build.  Timing builds: -DMVQ_KGROUP=n fixes the group
-// size, -DMVQ_KPREFETCH=0 selects the single-buffered form (reads of a group, wait, its MFMAs).
-constexpr int kgroup_steps(int ns, int regs_per_step)
-{
-#ifdef MVQ_KGROUP
-    return MVQ_KGROUP < ns ? MVQ_KGROUP : ns;
-#else
-    (void)ns; (void)regs_per_step;
-    return 1;
-#endif
-}
-
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
-// ---- hand-placed operand reads of the LDS-DMA K loop (MVQ_ASM_READS = G k-steps per group; 1 in a product build; 0 = compiler-scheduled) ------
+// ---- hand-placed operand reads of the LDS-DMA K loop ----------------------------------------------------------------------------
 // Left to itself the compiler feeds the MFMAs with ds_read2_b32 pairs, whose 8-bit offsets reach 255 dwords, so it re-bases the
 // LDS address with a v_add per k-step (16 per 56-MFMA chunk on the 7-tap tile) -- vector instructions the fp32 MFMAs pay for
 // (DESIGN.md section 6b).  This form issues every read as ds_read_b32 with a 16-bit immediate offset from three per-chunk base
-// addresses (1 VALU per chunk instead of 16), double-buffered: [reads of group g+1][s_waitcnt lgkmcnt(#reads of g+1)][MFMAs of
-// group g].  Measured (same box, 256-segment step): G = 1 331.5 -> 329.0 ms, every -m gpu test bit-exact; G = 2 / 4 are 1 % / 4 %
-// SLOWER than the compiler's schedule (as its own grouped forms are).
+// addresses (1 VALU per chunk instead of 16), double-buffered: [reads of k-step s+1][s_waitcnt lgkmcnt(#reads of s+1)][MFMAs of
+// k-step s].  Measured (same box, 256-segment step): 331.5 -> 329.0 ms, every -m gpu test bit-exact; reading two or four k-steps
+// per wait was 1 % / 4 % SLOWER than the compiler's schedule (as its own grouped forms are).
 //
 // What makes the counted wait sound, and what keeps the compiler out of it:
 //  * LDS reads of one wave return in order, and a counted lgkmcnt(N) only ever waits LONGER when something else (a scalar load)
@@ -265,89 +201,62 @@ __device__ __forceinline__ void lds_dma_burst(const float* const* src, unsigned 
                      : "=&s"(keep) : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "v"(src[5]), "v"(src[6]), "v"(src[7]), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
 }
 
-template <int KS, int STRIDE, int DIL, int BM, int XP, int MT, int NT, int NS, int G>
+template <int KS, int STRIDE, int DIL, int BM, int XP, int MT, int NT, int NS>
 struct AsmOperandLoop {
-    static constexpr int NG = (NS + G - 1) / G;
     template <int S, int I>
-    static __device__ __forceinline__ void load_a(float (&av)[G][MT], unsigned a_addr)
+    static __device__ __forceinline__ void load_a(float (&av)[MT], unsigned a_addr)
     {
         if constexpr (I < MT) {
-            av[S % G][I] = lds_read_imm<(2 * S * BM + I * 32) * 4>(a_addr);
+            av[I] = lds_read_imm<(2 * S * BM + I * 32) * 4>(a_addr);
             load_a<S, I + 1>(av, a_addr);
         }
     }
     template <int S, int J>
-    static __device__ __forceinline__ void load_b(float (&bv)[G][NT], unsigned b_same, unsigned b_cross)
+    static __device__ __forceinline__ void load_b(float (&bv)[NT], unsigned b_same, unsigned b_cross)
     {
         if constexpr (J < NT) {
             constexpr int k0 = 2 * S;
             constexpr int off0 = (k0 / KS) * XP + (k0 % KS) * DIL;
             constexpr bool cross = ((k0 + 1) / KS) != (k0 / KS);
-            bv[S % G][J] = lds_read_imm<(off0 + J * 32 * STRIDE) * 4>(cross ? b_cross : b_same);
+            bv[J] = lds_read_imm<(off0 + J * 32 * STRIDE) * 4>(cross ? b_cross : b_same);
             load_b<S, J + 1>(bv, b_same, b_cross);
         }
     }
-    template <int GI, int U>
-    static __device__ __forceinline__ void load_group(float (&av)[G][MT], float (&bv)[G][NT], unsigned a_addr, unsigned b_same, unsigned b_cross)
+    template <int S>
+    static __device__ __forceinline__ void load_step(float (&av)[MT], float (&bv)[NT], unsigned a_addr, unsigned b_same, unsigned b_cross)
     {
-        if constexpr (U < G && GI * G + U < NS) {
-            load_a<GI * G + U, 0>(av, a_addr);
-            load_b<GI * G + U, 0>(bv, b_same, b_cross);
-            load_group<GI, U + 1>(av, bv, a_addr, b_same, b_cross);
-        }
+        load_a<S, 0>(av, a_addr);
+        load_b<S, 0>(bv, b_same, b_cross);
     }
-    template <int GI>
-    static constexpr int group_reads() { return ((GI * G + G <= NS) ? G : (NS - GI * G > 0 ? NS - GI * G : 0)) * (MT + NT); }
-    template <int GI, int U>
-    static __device__ __forceinline__ void mfma_group(f32x16_t (&acc)[MT][NT], const float (&av)[G][MT], const float (&bv)[G][NT])
+    static __device__ __forceinline__ void mfma_step(f32x16_t (&acc)[MT][NT], const float (&av)[MT], const float (&bv)[NT])
     {
-        if constexpr (U < G && GI * G + U < NS) {
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+        for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[U][i], bv[U][j], acc[i][j], 0, 0, 0);
-            mfma_group<GI, U + 1>(acc, av, bv);
-        }
+            for (int j = 0; j < NT; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
     }
-    // the counted wait of group GI: the first k-step's registers ride through the s_waitcnt itself, the others (G > 1, timing
-    // builds) through empty asm statements behind it (volatile asm statements keep their order)
-    template <int GI, int PW, int U>
-    static __device__ __forceinline__ void wait_group(float (&av)[G][MT], float (&bv)[G][NT])
+    // k-steps S, S+1, ... ; buffers alternate (av0/bv0 for even steps)
+    template <int S>
+    static __device__ __forceinline__ void run_from(f32x16_t (&acc)[MT][NT], float (&av0)[MT], float (&bv0)[NT], float (&av1)[MT],
+                                                    float (&bv1)[NT], unsigned a_addr, unsigned b_same, unsigned b_cross)
     {
-        if constexpr (U < G && GI * G + U < NS) {
-            if constexpr (U == 0) lgkm_wait_step<PW, MT, NT>(av[0], bv[0]);
-            else {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) asm volatile("" : "+v"(av[U][i]));
-#pragma unroll
-                for (int j = 0; j < NT; ++j) asm volatile("" : "+v"(bv[U][j]));
+        if constexpr (S < NS) {
+            if constexpr (S + 1 < NS) {
+                if constexpr ((S + 1) % 2 == 0) load_step<S + 1>(av0, bv0, a_addr, b_same, b_cross);
+                else load_step<S + 1>(av1, bv1, a_addr, b_same, b_cross);
             }
-            wait_group<GI, PW, U + 1>(av, bv);
-        }
-    }
-    // groups GI, GI+1, ... ; buffers alternate (av0/bv0 for even groups)
-    template <int GI>
-    static __device__ __forceinline__ void run_from(f32x16_t (&acc)[MT][NT], float (&av0)[G][MT], float (&bv0)[G][NT], float (&av1)[G][MT],
-                                                    float (&bv1)[G][NT], unsigned a_addr, unsigned b_same, unsigned b_cross)
-    {
-        if constexpr (GI < NG) {
-            if constexpr (GI + 1 < NG) {
-                if constexpr ((GI + 1) % 2 == 0) load_group<GI + 1, 0>(av0, bv0, a_addr, b_same, b_cross);
-                else load_group<GI + 1, 0>(av1, bv1, a_addr, b_same, b_cross);
-            }
-            // LDS reads return in order: group GI has landed once at most the reads of group GI+1 are outstanding.  The wait
-            // re-defines group GI's registers (tied operands): their consumers depend on the wait, not on the reads.
-            constexpr int pending = (GI + 1 < NG) ? group_reads<GI + 1>() : 0;
-            constexpr int PW = pending > 15 ? 15 : pending;
+            // LDS reads return in order: k-step S has landed once at most the reads of k-step S+1 are outstanding.  The wait
+            // re-defines k-step S's registers (tied operands): their consumers depend on the wait, not on the reads.
+            constexpr int PW = (S + 1 < NS) ? MT + NT : 0;
             __builtin_amdgcn_sched_barrier(0);         // nothing (no scalar load, no VALU) between the reads and their wait
-            if constexpr (GI % 2 == 0) wait_group<GI, PW, 0>(av0, bv0);
-            else wait_group<GI, PW, 0>(av1, bv1);
+            if constexpr (S % 2 == 0) lgkm_wait_step<PW, MT, NT>(av0, bv0);
+            else lgkm_wait_step<PW, MT, NT>(av1, bv1);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (GI % 2 == 0) mfma_group<GI, 0>(acc, av0, bv0);
-            else mfma_group<GI, 0>(acc, av1, bv1);
+            if constexpr (S % 2 == 0) mfma_step(acc, av0, bv0);
+            else mfma_step(acc, av1, bv1);
             __builtin_amdgcn_sched_barrier(0);
-            run_from<GI + 1>(acc, av0, bv0, av1, bv1, a_addr, b_same, b_cross);
+            run_from<S + 1>(acc, av0, bv0, av1, bv1, a_addr, b_same, b_cross);
         }
     }
 };
@@ -498,11 +407,7 @@ struct ConvTile {
                 const bool ok = g >= 0 && g < Tin;
                 f32x4 q = xv[u];
                 if (!ok) q = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#if defined(MVQ_EXP) && (MVQ_EXP & 8)
-                if (false) {
-#else
                 if (snake_in) {
-#endif
                     const float al = Al[ci0 + cl], inv = Al[Cin + ci0 + cl];
                     q.x = det_snake(q.x, al, inv); q.y = det_snake(q.y, al, inv);
                     q.z = det_snake(q.z, al, inv); q.w = det_snake(q.w, al, inv);
@@ -617,57 +522,41 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
     // one chunk of MFMAs out of LDS buffer `buf`; operands of k-step s+1 are fetched before the MFMAs of step s
     // (Skipping the MFMAs of column subtiles that lie past the end of the row was measured: +0.3 % -- the block lasts as long
     // as its busiest wave.  Rows with a mostly empty last tile are split into two launches instead: conv_tail_width.)
-    // Operand reads may be issued in GROUPS of KG k-steps, one group ahead of the MFMAs that consume them ([reads of group
-    // g+1][MFMAs of group g], one lgkmcnt wait per group).  Measured on the real layers (round 3, gpurun_out/r3c): KG = 4
-    // double-buffered and KG = 7 single-buffered are 3-5 % SLOWER than KG = 1 on the 7-tap layers (133 vs 138.5 TFLOP/s),
-    // KG = 2 equal, although a bare LDS-fed MFMA loop with batched reads reaches 151-153 TFLOP/s (tools/mfma_probe.hip): in
-    // the real loop the gap to that figure is the DMA issue (4 %), the per-chunk wait + barrier (1.3 %) and the epilogue
-    // (1.6 %), not the read schedule (timing builds with each piece removed, gpurun_out/r3d).
-    // The default therefore stays one k-step per group (operands of step s+1 fetched before the MFMAs of step s); the
-    // grouped forms remain selectable for A/B builds (kgroup_steps).
+    // The operands of k-step s+1 are fetched before the MFMAs of step s, one k-step at a time.  Reading GROUPS of KG k-steps one
+    // group ahead was measured on the real layers (round 3): KG = 4 double-buffered and KG = 7 single-buffered
+    // are 3-5 % SLOWER than KG = 1 on the 7-tap layers (133 vs 138.5 TFLOP/s), KG = 2 equal, although a bare LDS-fed MFMA loop
+    // with batched reads reaches 151-153 TFLOP/s (tools/mfma_probe.hip): in the real loop the gap to that figure is the DMA
+    // issue (4 %), the per-chunk wait + barrier (1.3 %) and the epilogue (1.6 %), not the read schedule (timing builds with
+    // each piece removed, profiles/r03_timing_experiments.json).
     constexpr int NS = C::KC / 2;                                       // k-steps per chunk
-    constexpr int KG = kgroup_steps(NS, MT + NT);
-    constexpr int NG = (NS + KG - 1) / KG;
-    constexpr bool KPRE = MVQ_KPREFETCH != 0;
     auto mfma_chunk = [&](int buf) __attribute__((always_inline)) {
         const float* wsrc = Ws + buf * C::W_FLOATS + a_base;
         const float* xs_same = Xs + buf * C::X_FLOATS + b_same;
         const float* xs_cross = Xs + buf * C::X_FLOATS + b_cross;
-        float av[KPRE ? 2 : 1][KG][MT], bv[KPRE ? 2 : 1][KG][NT];
-        auto load_group = [&](int g, int pb) __attribute__((always_inline)) {
+        float av[2][MT], bv[2][NT];
+        auto load_step = [&](int st, int pb) __attribute__((always_inline)) {
+            const int k0 = 2 * st;
+            const int off0 = (k0 / KS) * C::XTP + (k0 % KS) * DIL;
+            const bool cross = ((k0 + 1) / KS) != (k0 / KS);
+            const float* xsp = cross ? xs_cross : xs_same;
 #pragma unroll
-            for (int u = 0; u < KG; ++u) {
-                const int st = g * KG + u;
-                if (st < NS) {
-                    const int k0 = 2 * st;
-                    const int off0 = (k0 / KS) * C::XTP + (k0 % KS) * DIL;
-                    const bool cross = ((k0 + 1) / KS) != (k0 / KS);
-                    const float* xsp = cross ? xs_cross : xs_same;
+            for (int i = 0; i < MT; ++i) av[pb][i] = wsrc[k0 * C::BM + i * 32];
 #pragma unroll
-                    for (int i = 0; i < MT; ++i) av[pb][u][i] = wsrc[k0 * C::BM + i * 32];
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) bv[pb][u][j] = xsp[off0 + j * 32 * STRIDE];
-                }
-            }
+            for (int j = 0; j < NT; ++j) bv[pb][j] = xsp[off0 + j * 32 * STRIDE];
         };
-        if (KPRE) load_group(0, 0);
+        load_step(0, 0);
 #pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int pb = KPRE ? (g & 1) : 0;
-            if (KPRE) { if (g + 1 < NG) load_group(g + 1, (g + 1) & 1); }
-            else load_group(g, 0);
+        for (int s = 0; s < NS; ++s) {
+            const int pb = s & 1;
+            if (s + 1 < NS) load_step(s + 1, (s + 1) & 1);
 #pragma unroll
-            for (int u = 0; u < KG; ++u)
-                if (g * KG + u < NS) {
+            for (int i = 0; i < MT; ++i)
 #pragma unroll
-                    for (int i = 0; i < MT; ++i)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[pb][u][i], bv[pb][u][j], acc[i][j], 0, 0, 0);
-                }
-            // the reads (of group g+1 when prefetching, of this group otherwise) first, then the MFMAs of group g
-            __builtin_amdgcn_sched_group_barrier(0x100, (MT + NT) * KG, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, MT * NT * KG, 0);
+                for (int j = 0; j < NT; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[pb][i], bv[pb][j], acc[i][j], 0, 0, 0);
+            // the reads of step s+1 first, then the MFMAs of step s
+            __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
         }
     };
 
@@ -734,95 +623,32 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
             for (int u = NFULL; u < NU; ++u) {
                 if (live[u]) lds_dma_burst<1, C::NTHR * 16>(src + u, dst0 + (unsigned)(u * C::NTHR * 16));
             }
-#if !(defined(MVQ_EXP) && (MVQ_EXP & 64))               // timing build: pointers not advanced (same chunk re-read)
 #pragma unroll
             for (int u = 0; u < NU; ++u) src[u] += step_b[u];
-#endif
         };
-        [[maybe_unused]] auto mfma_chunk_dma = [&](int stage, bool issue_next, int next_stage) __attribute__((always_inline)) {
-            const float* wsrc = smem + stage * C::DMA_STAGE_FLOATS + a_base;
-            const float* xs_same = smem + stage * C::DMA_STAGE_FLOATS + C::W_FLOATS + bd_same;
-            const float* xs_cross = smem + stage * C::DMA_STAGE_FLOATS + C::W_FLOATS + bd_cross;
-            float av[KPRE ? 2 : 1][KG][MT], bv[KPRE ? 2 : 1][KG][NT];
-            auto load_group = [&](int g, int pb) __attribute__((always_inline)) {
-#pragma unroll
-                for (int u = 0; u < KG; ++u) {
-                    const int st = g * KG + u;
-                    if (st < NS) {
-                        const int k0 = 2 * st;
-                        const int off0 = (k0 / KS) * XP + (k0 % KS) * DIL;
-                        const bool cross = ((k0 + 1) / KS) != (k0 / KS);
-                        const float* xsp = cross ? xs_cross : xs_same;
-#pragma unroll
-                        for (int i = 0; i < MT; ++i) av[pb][u][i] = wsrc[k0 * C::BM + i * 32];
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) bv[pb][u][j] = xsp[off0 + j * 32 * STRIDE];
-                    }
-                }
-            };
-            load_group(0, 0);
-            if (issue_next) dma_chunk(next_stage);         // behind the first operand reads: issued while those are in flight
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                const int pb = KPRE ? (g & 1) : 0;
-                if (KPRE) { if (g + 1 < NG) load_group(g + 1, (g + 1) & 1); }
-                else if (g > 0) load_group(g, 0);
-#pragma unroll
-                for (int u = 0; u < KG; ++u)
-                    if (g * KG + u < NS) {
-#pragma unroll
-                        for (int i = 0; i < MT; ++i)
-#pragma unroll
-                            for (int j = 0; j < NT; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[pb][u][i], bv[pb][u][j], acc[i][j], 0, 0, 0);
-                    }
-                __builtin_amdgcn_sched_group_barrier(0x100, (MT + NT) * KG, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, MT * NT * KG, 0);
-            }
-        };
-#if MVQ_ASM_READS > 0
-        using AL = AsmOperandLoop<KS, STRIDE, DIL, C::BM, XP, MT, NT, NS, MVQ_ASM_READS>;
+        using AL = AsmOperandLoop<KS, STRIDE, DIL, C::BM, XP, MT, NT, NS>;
         auto mfma_chunk_asm = [&](int stage, bool issue_next, int next_stage) __attribute__((always_inline)) {
             const unsigned sb = lds0 + (unsigned)(stage * C::DMA_STAGE_FLOATS * 4);
             const unsigned a_addr = sb + (unsigned)(a_base * 4);
             const unsigned b_s = sb + (unsigned)((C::W_FLOATS + bd_same) * 4), b_c = sb + (unsigned)((C::W_FLOATS + bd_cross) * 4);
-            float av0[MVQ_ASM_READS][MT], bv0[MVQ_ASM_READS][NT], av1[MVQ_ASM_READS][MT], bv1[MVQ_ASM_READS][NT];
-            AL::template load_group<0, 0>(av0, bv0, a_addr, b_s, b_c);
-            if (issue_next) dma_chunk(next_stage);
+            float av0[MT], bv0[NT], av1[MT], bv1[NT];
+            AL::template load_step<0>(av0, bv0, a_addr, b_s, b_c);
+            if (issue_next) dma_chunk(next_stage);         // behind the first operand reads: issued while those are in flight
             AL::template run_from<0>(acc, av0, bv0, av1, bv1, a_addr, b_s, b_c);
         };
-#define MVQ_CHUNK mfma_chunk_asm
-#else
-#define MVQ_CHUNK mfma_chunk_dma
-#endif
         dma_chunk(0);
         if (n_chunks > 1) dma_chunk(1);
         int st_c = 0, st_n2 = 2;                       // stage of chunk c / of chunk c+2
-#ifdef MVQ_EXP      // TIMING EXPERIMENTS ONLY (wrong results): bit 0 = no DMA in the steady state, bit 1 = no wait / barrier per chunk
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int c = 0; c < n_chunks; ++c) {
-            if (!(MVQ_EXP & 2)) {
-                if (c + 1 >= n_chunks) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (n_issue == NU) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU - 1) : "memory");
-                __syncthreads();
-            }
-            MVQ_CHUNK(c & 1, (MVQ_EXP & 1) ? false : (c + 2 < n_chunks), 2);
-        }
-#else
         for (int c = 0; c < n_chunks; ++c) {
             // chunk c has landed when at most the DMA_NU instructions of chunk c+1 are still outstanding
             if (c + 1 >= n_chunks) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if (n_issue == NU) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU - 1) : "memory");
             __syncthreads();                          // ... in every wave; and stage (c+2)%3 is free (read during chunk c-1)
-            MVQ_CHUNK(st_c, c + 2 < n_chunks, st_n2);
+            mfma_chunk_asm(st_c, c + 2 < n_chunks, st_n2);
             st_c = st_c == 2 ? 0 : st_c + 1;
             st_n2 = st_n2 == 2 ? 0 : st_n2 + 1;
         }
-#endif
-#undef MVQ_CHUNK
       }
     } else {
     tile.load_chunk(0, wreg, xv, xs);
@@ -860,11 +686,7 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
                 const float al = a.alpha_mid[row], inv = Ep[EP_MID * C::BM + row];
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-#if defined(MVQ_EXP) && (MVQ_EXP & 16)
-                    Ht[row * C::BNP + (wn * NT + j) * 32 + l31] = acc[i][j][r] + bv + al * inv;
-#else
                     Ht[row * C::BNP + (wn * NT + j) * 32 + l31] = det_snake(acc[i][j][r] + bv, al, inv);
-#endif
                     acc[i][j][r] = 0.0f;
                 }
             }
@@ -879,12 +701,8 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int i = 0; i < MT; ++i) aw[0][g][i] = w2[(size_t)(2 * g) * a.Mpad + i * 32];
-#if defined(MVQ_EXP) && (MVQ_EXP & 32)
-        for (int grp = 0; grp < 1; ++grp) {
-#else
 #pragma unroll
         for (int grp = 0; grp < K2 / G; ++grp) {
-#endif
             if (grp + 1 < K2 / G) {
 #pragma unroll
                 for (int g = 0; g < G; ++g)
@@ -913,19 +731,6 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
     // tanh and the global stores run row-contiguous: 16-byte residual loads and stores when rows are aligned,
     // 4-byte but fully coalesced otherwise.  (ConvTranspose phases whose count does not divide BM keep the
     // direct per-lane store.)
-#if defined(MVQ_EXP) && (MVQ_EXP & 4)
-    {   // TIMING EXPERIMENT: no epilogue (one store keeps the accumulators alive)
-        float sink = 0.0f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sink += acc[i][j][r];
-        if (sink == 123.456f) a.y[0] = sink;
-        return;
-    }
-#endif
     const bool has_res = (UPS == 0) && a.residual != nullptr;
     const bool snake_out = a.alpha_out != nullptr;
     const bool do_tanh = a.act == 1;
@@ -999,11 +804,7 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
     // four.  (Timing builds without the epilogue: the fused C = 64 unit 108 -> 120 TFLOP/s, C = 128 126 -> 135: most of that
     // was exposed latency of these loads, not arithmetic.)
     constexpr int NVQ = BMH * C::BN / 4;
-#ifdef MVQ_NO_RES_PREFETCH                              // A/B builds
-    constexpr bool PRE_RES = false;
-#else
     constexpr bool PRE_RES = (UPS == 0) && (NVQ % C::NTHR == 0) && (NVQ / C::NTHR <= 16);
-#endif
     constexpr int RES_IT = PRE_RES ? NVQ / C::NTHR : 1;
     // REGULAR quad mapping (ConvCfg::REG_GEOM): a thread keeps its JN column quads (c4 = q_c0 + j * CQ) and its rows advance by the
     // constant RSTEP per step, so iteration it = (row step it / JN, column group it % JN).  Everything that depends only on the
@@ -1467,12 +1268,7 @@ inline hipError_t launch_conv1d_mfma(const ConvArgs& a_in, hipStream_t stream)
     // When the whole packed weight fits L2 comfortably (k = 1 convs), put the R row tiles of a column tile back to back
     // on one XCD instead: x is then read from HBM once instead of R times.
     a.row_fast = 0;
-    static const size_t row_fast_max = [] {                        // MVQ_ROWFAST_MAX_KB: A/B override of the 2.5 MB threshold
-        const char* e = getenv("MVQ_ROWFAST_MAX_KB");
-        if (e) note_env_override(MVQ_BF_ENV_ROWFAST);
-        return e ? (size_t)atol(e) * 1024 : ((size_t)5 << 19);
-    }();
-    if (R > 1 && (size_t)a.Cin * KS * a.Mpad * sizeof(float) <= row_fast_max) {               // <= 2.5 MB
+    if (R > 1 && (size_t)a.Cin * KS * a.Mpad * sizeof(float) <= ((size_t)5 << 19)) {          // <= 2.5 MB
         a.row_fast = (int)R;
         grid = dim3(((gx + 7) / 8) * 8 * R, 1);
     }
@@ -1501,10 +1297,10 @@ inline hipError_t launch_conv1d_mfma(const ConvArgs& a_in, hipStream_t stream)
 
 // LDS-DMA staging (conv1d_mfma_body) needs 16-byte rows and no Snake on load (the DMA cannot transform what it copies).
 // Dispatchers use this to pick the instantiation whose 3-stage ring fits three blocks per CU (smaller CK where needed).
-// MVQ_NO_DMA=1 in the environment switches it off (A/B measurements).
+// MVQ_NO_DMA=1 in the environment switches it off (A/B measurements; reported by mvq_build_flags).
 inline bool conv_dma_rows_ok(const ConvArgs& a)
 {
-    static const bool off = [] { const bool o = getenv("MVQ_NO_DMA") != nullptr; if (o) note_env_override(MVQ_BF_ENV_NO_DMA); return o; }();
+    static const bool off = getenv("MVQ_NO_DMA") != nullptr;
     return !off && !a.alpha_in && a.Tin % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
 }
 
@@ -1549,18 +1345,11 @@ inline bool conv_underfilled(const ConvArgs& a)
 // 157 TFLOP/s, profiles/r05_*B6*), the 768-channel decoder level 180 -- while four times as many quarter tiles fill their last
 // round, at ~0.85 of the big tile's per-block rate (less operand reuse).  The form with the better fill x rate wins, up to 600
 // big tiles; beyond that the big one always.  Measured at six segments (gpurun_out/g4): 11.60 -> 11.04 ms per step.
-// MVQ_SMALL_TILE_MAX=n replaces the rule by `big < n` (A/B runs).
 inline bool conv_prefer_small_tiles(const ConvArgs& a)
 {
     if (a.Mpad % 64 != 0) return false;
     if (a.vp_seg) return false;                       // virtually packed rows: the LDS-DMA 128-row tiles only
     const long big = (long)a.B * ((a.Ncols + 127) / 128) * ((a.Mrows + 127) / 128);
-    static const long cap = [] {
-        const char* e = getenv("MVQ_SMALL_TILE_MAX");               // A/B knob (reported by mvq_build_flags)
-        if (e) note_env_override(MVQ_BF_ENV_SMALL_TILES);
-        return e ? atol(e) : -1L;
-    }();
-    if (cap >= 0) return big < cap;
     if (big < 160) return true;
     if (big >= 600) return false;                     // 2.3 rounds and up: the big tiles (and their split tail launch) fill well enough
     const long small = 4 * big;

@@ -476,11 +476,10 @@ hipError_t launch_bf16x3_split(const float* x, void* xs, int batch, int c, int t
 // rows per weight slice = the row tile of the kernel that will read the image: 128 where Cout allows, else 96 (C = 192)
 int bf16x6_tile_rows(int cout) { return cout % 128 == 0 ? 128 : (cout % 96 == 0 ? 96 : 0); }
 // f16x3 (two pieces: smaller slices): a 192-row tile on 2 x 2 waves where it divides Cout and 128 does not (C = 192: the activation
-// tile is staged once instead of twice, 10 instead of 12 operand reads per 18 MFMAs); MVQ_F16_NO192=1: A/B knob
+// tile is staged once instead of twice, 10 instead of 12 operand reads per 18 MFMAs)
 int f16x3_tile_rows(int cout)
 {
-    static const bool no192 = getenv("MVQ_F16_NO192") != nullptr;
-    if (cout % 128 != 0 && cout % 192 == 0 && !no192) return 192;
+    if (cout % 128 != 0 && cout % 192 == 0) return 192;
     return bf16x6_tile_rows(cout);
 }
 
@@ -577,9 +576,8 @@ hipError_t launch_conv_k7_f16x3(const void* xs, const unsigned* xamax, const voi
     } else if (bm == 128) {
         // Rows of >= 2 048 columns: 128 x 256 tile, wave tile 64 x 128 -- 0.5 instead of 0.67 operand reads per MFMA and half the weight
         // staging per MFMA.  The loop is power-bound, so less energy per MFMA is a higher clock (the guide's rule 28): 355 -> 365 and
-        // 368 -> 383 TFLOP/s on the T = 3 000 layers, 233.1 -> 231.0 ms per step.  MVQ_F16_NO_WIDE=1: A/B knob.
-        static const bool no_wide = getenv("MVQ_F16_NO_WIDE") != nullptr;
-        if (!no_wide && t >= 2048) {
+        // 368 -> 383 TFLOP/s on the T = 3 000 layers, 233.1 -> 231.0 ms per step.
+        if (t >= 2048) {
             switch (dil) {
                 case 1: return launch_k7bf<1, 2, 4, 2, 2, 3, 2>(a, s);
                 case 3: return launch_k7bf<3, 2, 4, 2, 2, 3, 2>(a, s);

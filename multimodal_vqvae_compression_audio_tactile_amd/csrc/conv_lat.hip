@@ -64,16 +64,8 @@ static hipError_t launch_lat(const ConvArgs& a_in, hipStream_t s)
 // whose operands are shared by a whole block, win -- and the K chain is long enough to pay for a wave's fixed cost (its index
 // setup and the element-wise epilogue): a short chain on many tiles (the 1x1 conv of a T = 600 unit at one segment: 1 824 tiles,
 // 192 k-steps) stays on the 64 x 64 tiles.  A very long chain (dec.in at six segments: 2 784 tiles x 1 792 k-steps) still wins at
-// up to twice the tile count.  MVQ_LAT_MAX_TILES overrides the tile threshold (A/B runs; 0 switches the form off).
-static long lat_max_tiles()
-{
-    static const long v = [] {
-        const char* e = getenv("MVQ_LAT_MAX_TILES");
-        if (e) note_env_override(MVQ_BF_ENV_LAT_TILES);
-        return e ? atol(e) : 2048L;
-    }();
-    return v;
-}
+// up to twice the tile count.
+constexpr long LAT_MAX_TILES = 2048;
 
 bool conv_lat_wanted(const ConvArgs& a, int ks)
 {
@@ -81,10 +73,9 @@ bool conv_lat_wanted(const ConvArgs& a, int ks)
     if (a.B <= 0 || a.Ncols <= 0 || a.up_s > 1) return false;            // transposed convs: the polyphase scatter store loses (80 -> 95 us)
     const long tiles = (long)a.B * ((a.Ncols + 15) / 16) * ((a.Mrows + 15) / 16);
     const long steps = (long)a.Cin * ks / 4;
-    const long cap = lat_max_tiles();
-    if (tiles <= cap / 2) return true;
-    if (tiles <= cap) return steps >= 512;
-    return tiles <= 2 * cap && steps >= 1536;
+    if (tiles <= LAT_MAX_TILES / 2) return true;
+    if (tiles <= LAT_MAX_TILES) return steps >= 512;
+    return tiles <= 2 * LAT_MAX_TILES && steps >= 1536;
 }
 
 hipError_t launch_conv_lat(const ConvArgs& a, int ks, int stride, int dil, hipStream_t s)

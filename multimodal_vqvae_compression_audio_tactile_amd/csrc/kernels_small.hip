@@ -552,11 +552,7 @@ hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamm
         // The per-token chain (2 x C dependent operations) is latency, not bandwidth: what shortens a call is MORE BLOCKS walking
         // chains side by side.  8-token tiles (32 KB of LDS at C = 1024: five blocks per CU) put 2 400 blocks on the 19 200 tokens
         // of a 256-segment batch where the 32-token tile (128 KB, one block per CU) put 600 -- round 4: 2.3 -> see DESIGN 6c ms per step.
-        static const bool ln32 = getenv("MVQ_LN_TILE32") != nullptr;       // A/B knob (reported by mvq_build_flags)
-        if (ln32) note_env_override(0x800);
-        static const bool no_lat = getenv("MVQ_NO_LN_LAT") != nullptr;     // A/B knob (reported by mvq_build_flags)
-        if (no_lat) note_env_override(0x4000);
-        if (n <= 1024 && C % 64 == 0 && ln_lat_lds_floats(C) * sizeof(float) <= 64 * 1024 && !no_lat && !ln32) {
+        if (n <= 1024 && C % 64 == 0 && ln_lat_lds_floats(C) * sizeof(float) <= 64 * 1024) {
             LnIo io{};
             io.x = x; io.x_sb = sb; io.x_sc = sc;
             io.sub = sub; io.sub_sb = sb; io.sub_sc = sc;
@@ -566,7 +562,7 @@ hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamm
             hipLaunchKernelGGL(layernorm_c_lat_kernel, dim3((n + LN_LAT_TOK - 1) / LN_LAT_TOK), dim3(256), ln_lat_lds_floats(C) * sizeof(float), s, io, B, C, T);
             return hipGetLastError();
         }
-        if (n > 64 && !ln32 && ((size_t)C * 8 + 16) * sizeof(float) <= 64 * 1024)
+        if (n > 64 && ((size_t)C * 8 + 16) * sizeof(float) <= 64 * 1024)
             hipLaunchKernelGGL(layernorm_c_tile_kernel<8>, dim3((n + 7) / 8), dim3(256), ((size_t)C * 8 + 16) * sizeof(float), s,
                                x, pe, gamma, beta, y, B, C, T, sb, sc, eps, do_tanh, post_scale, sub);
         else if (n <= 64)

@@ -604,12 +604,7 @@ hipError_t launch_rvq_ema_forward(const float* z, const float* books, float* q_o
     const int N = B * T;
     if (N == 0) return hipSuccess;
     // a handful of tokens (latency regime): one block per token, nothing staged
-    static const bool no_token_form = [] {                                          // A/B measurements; reported by mvq_build_flags()
-        const bool o = getenv("MVQ_NO_TOKEN_RVQ") != nullptr;
-        if (o) mvq::note_env_override(0x400 /* MVQ_BF_ENV_NO_TOKEN_RVQ */);
-        return o;
-    }();
-    if (N <= 256 && D == 96 && K <= 512 && (reinterpret_cast<uintptr_t>(books) & 15) == 0 && !no_token_form) {   // CODE_DIM = 96 (Training/...5.py:68)
+    if (N <= 256 && D == 96 && K <= 512 && (reinterpret_cast<uintptr_t>(books) & 15) == 0) {   // CODE_DIM = 96 (Training/...5.py:68)
         // (Measured and not kept, both bit-equal: both halves of the NEXT book in flight -- does not fit 256 VGPRs beside the half row a
         // thread keeps; whole rows in LDS, 256 codes per pass, the next pass in flight -- 53 instead of 43 us per 16-token chunk: only
         // half the threads walk chains, and they are twice as long.  gpurun_out/j1.)
@@ -619,7 +614,7 @@ hipError_t launch_rvq_ema_forward(const float* z, const float* books, float* q_o
         hipLaunchKernelGGL(kern, dim3(N), dim3(512), ((size_t)K * 52 + 3 * 96 + 16) * sizeof(float), s, z, books, q_out, idx_out, B, T, nb, K, update_residual);
         return hipGetLastError();
     }
-    if (N <= 256 && D % 4 == 0 && D <= 128 && !no_token_form) {
+    if (N <= 256 && D % 4 == 0 && D <= 128) {
         hipLaunchKernelGGL(rvq_ema_forward_token_kernel, dim3(N), dim3(256), 0, s, z, books, q_out, idx_out, B, D, T, nb, K, update_residual);
         return hipGetLastError();
     }
@@ -1208,10 +1203,9 @@ hipError_t launch_dac_rvq(const float* z, const float* in_w, const float* in_b, 
     if (B * T == 0) return hipSuccess;
     if (Dc != 8) return hipErrorInvalidValue;
     // a handful of tokens (one segment is 75, the reference's batch of six 450): the latency form, one token per block
-    static const bool no_lat = [] { const bool o = getenv("MVQ_NO_DAC_RVQ_LAT") != nullptr; if (o) mvq::note_env_override(0x2000); return o; }();
     const bool aligned = ((reinterpret_cast<uintptr_t>(in_w) | reinterpret_cast<uintptr_t>(out_w) | reinterpret_cast<uintptr_t>(cb) |
                            reinterpret_cast<uintptr_t>(cbn_pre)) & 15) == 0;
-    if (B * T <= 1024 && K == 1024 && cbn_pre && cn2_pre && aligned && !no_lat) {
+    if (B * T <= 1024 && K == 1024 && cbn_pre && cn2_pre && aligned) {
         switch (C) {
             case 1024: return launch_dac_rvq_lat_t<64>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre);
             case 512:  return launch_dac_rvq_lat_t<32>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre);

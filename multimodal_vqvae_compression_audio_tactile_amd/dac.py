@@ -42,7 +42,7 @@ USE_STACKS = not PLAN_OVERRIDES            # tests flip this to compare the two 
 
 def plan_overrides():
     """Names of the launch-plan / arithmetic A/B switches seen in the environment at import (empty in a product run)."""
-    return sorted(PLAN_OVERRIDES) + sorted(HOST_ENV_SEEN) + sorted(ops.ARITH_ENV_SEEN)
+    return sorted(PLAN_OVERRIDES) + sorted(HOST_ENV_SEEN)
 
 
 class _Packed:

@@ -8,7 +8,6 @@ autocast, Evaluation/compare_dacvsproposal_5_eval.py:441) are widened to fp32: t
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
@@ -102,7 +101,7 @@ def conv1d(x, wp, cout, ks, bias=None, stride=1, dil=1, pad=0, alpha_in=None, re
 
 
 def build_flags() -> int:
-    """mvq_build_flags() (include/mvq.h): 0 = product build with no A/B override in the environment."""
+    """mvq_build_flags() (include/mvq.h): 0 = no A/B override in the environment."""
     return _lib.build_flags()
 
 
@@ -161,7 +160,7 @@ def residual_unit(x, w7p, b7, alpha_a, alpha_b, w1p, b1, dil, alpha_next=None, x
     B, C, T = x.shape
     # the fused single-launch form, unless an opt-in arithmetic mode claims the unit's 7-tap conv (then: split + matrix-core conv +
     # the exact 1x1 with its skip, as for the wide units)
-    unfuse = w7q is not None and x_snaked is not None and not _KEEP_FUSED
+    unfuse = w7q is not None and x_snaked is not None
     if _lib.lib().mvq_residual_unit_scratch_floats(B, C, T, dil) == 0 and not unfuse:
         return residual_unit_fused(x, w7p, b7, alpha_a, alpha_b, w1p, b1, dil, alpha_next, alpha_dual, tvalid, x_snaked)
     if x_snaked is not None and w7q is not None:      # opt-in modes (set_arith): non-parity, fp32-class
@@ -178,10 +177,6 @@ def residual_unit(x, w7p, b7, alpha_a, alpha_b, w1p, b1, dil, alpha_next=None, x
 # 7-tap convs of the wide ResidualUnits (C a multiple of 128, or of 96: C = 192) through the three-piece bf16 split: fp32-accurate,
 # not bit-identical; everything else keeps the exact path.
 _ARITH = "f32"
-# A/B knobs of the opt-in modes, read ONCE at import and reported (dac.plan_overrides / bench.py `plan_overrides`)
-ARITH_ENV_SEEN = {k: os.environ[k] for k in ("MVQ_ARITH_KEEP_FUSED", "MVQ_BF16X6_NO96") if k in os.environ}
-_KEEP_FUSED = ARITH_ENV_SEEN.get("MVQ_ARITH_KEEP_FUSED") == "1"
-_NO96 = ARITH_ENV_SEEN.get("MVQ_BF16X6_NO96") == "1"
 
 
 def set_arith(mode: str) -> None:
@@ -215,8 +210,6 @@ class arith:
 def bf16x6_eligible(c: int) -> bool:
     if _ARITH not in ("bf16x6", "f16x3") or c % 16 != 0:
         return False
-    if _NO96:                                             # A/B knob: 128-row tiles only
-        return c % 128 == 0
     return c % 128 == 0 or c % 96 == 0
 
 

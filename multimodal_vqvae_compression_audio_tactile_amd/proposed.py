@@ -279,8 +279,7 @@ class _ProposedBase(nn.Module):
     # to the launch-per-stage loop and SLOWER -- 1.22 against 0.99 ms for one segment, 1.74 against 1.09 ms for six.  The stages are
     # 5-45 us of dependent chain each; at that length the command processor already has the next launch queued behind the running
     # kernel, so a launch boundary costs less than the ~4 us a grid barrier (a device-scope atomic, an L2 write-back and an
-    # invalidate across eight XCDs) does.  Kept as an opt-in (MVQ_AR_FUSED_MAX_BATCH) with its parity tests: it is the place where
-    # per-stage clocks can be read (MVQ_AR_TIMING=1), which is how the LayerNorm / GEMM-epilogue round trips of round 5 were found.
+    # invalidate across eight XCDs) does.  Kept as an opt-in (MVQ_AR_FUSED_MAX_BATCH) with its parity tests.
     AR_FUSED_MAX_BATCH = int(_dac.HOST_ENV_SEEN.get("MVQ_AR_FUSED_MAX_BATCH", "0"))
 
     # The loop as ONE HOST CALL of the same stand-alone launches (mvq_ar_latents_staged_f32), for up to this many segments: at one
