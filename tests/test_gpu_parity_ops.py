@@ -17,6 +17,17 @@ def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
+# column split (conv_tail_width): B x row tiles >= 128, full 128-column tiles in one launch, the remainder in a second launch of a
+# narrower tile.  T = 600 -> four 128-column tiles + a 96-column tail; T = 423 -> three + a 64-column tail.  Each case is listed
+# with the tail instantiation it must launch (test_conv1d_split_cases_launch_their_tail), so that a dispatch change cannot turn
+# them silently into unsplit cases.
+CONV_SPLIT_CASES = [
+    ((128, 32, 600, 128, 7, 1, 9, 27, False, False, True, False), "conv1d_mfma_kernel<7, 1, 9, 4, 1, 3, 4, 1, 0>"),
+    ((128, 32, 600, 128, 7, 1, 1, 3, True, True, False, False), "conv1d_mfma_kernel<7, 1, 1, 4, 1, 3, 4, 1, 0>"),
+    ((128, 64, 600, 128, 1, 1, 1, 0, False, True, True, False), "conv1d_mfma_kernel<1, 1, 1, 16, 1, 3, 4, 1, 0>"),
+    ((128, 32, 423, 128, 7, 1, 3, 9, False, True, True, False), "conv1d_mfma_kernel<7, 1, 3, 4, 2, 1, 2, 2, 0>"),
+]
+
 CONV_CASES = [
     # (B, Cin, Tin, Cout, ks, stride, dil, pad, alpha_in, residual, alpha_out, tanh)
     (2, 64, 700, 64, 7, 1, 1, 3, True, False, True, False),      # BM=64 tile, RU conv7 d1
@@ -61,17 +72,17 @@ CONV_CASES = [
     (3, 64, 20000, 128, 4, 2, 1, 1, False, False, False, False),  # strided s=2
     (4, 256, 9000, 512, 10, 5, 1, 3, False, False, False, False), # strided s=5
     (8, 1024, 75, 1024, 3, 1, 1, 1, False, False, False, False),  # k3 at the latent rate, 128x96 tile
-    # column split (conv_tail_width): T = 600 -> four 128-column tiles + one 96-column tail launch; T = 3000-ish -> 64-column tail
+    # no column split: B x row tiles < 128, so a tail launch could not fill the chip (conv_tail_width) -- these grids (< 160 big
+    # tiles) take the 64 x 64 tiles instead, one launch over the whole row
     (16, 256, 600, 256, 7, 1, 9, 27, False, False, True, False),
     (8, 512, 600, 512, 7, 1, 1, 3, True, True, False, False),
     (6, 768, 600, 768, 1, 1, 1, 0, False, True, True, False),
     (4, 256, 3000, 256, 7, 1, 3, 9, False, True, True, False),
+    *(c for c, _ in CONV_SPLIT_CASES),
 ]
 
 
-@pytest.mark.parametrize("case", CONV_CASES, ids=[f"c{i}" for i in range(len(CONV_CASES))])
-def test_conv1d_bit_exact(case, orc, dev):
-    from multimodal_vqvae_compression_audio_tactile_amd import ops
+def _conv_case_inputs(case):
     B, Cin, Tin, Cout, ks, stride, dil, pad, ai, res, ao, th = case
     r = _rng(hash(case) % (2 ** 31))
     x = r.standard_normal((B, Cin, Tin)).astype(np.float32)
@@ -79,18 +90,47 @@ def test_conv1d_bit_exact(case, orc, dev):
     b = (0.1 * r.standard_normal(Cout)).astype(np.float32)
     alpha_in = r.uniform(0.5, 1.5, Cin).astype(np.float32) if ai else None
     alpha_out = r.uniform(0.5, 1.5, Cout).astype(np.float32) if ao else None
-    Tout = orc.conv1d_out_len(Tin, ks, stride, dil, pad)
+    Tout = (Tin + 2 * pad - dil * (ks - 1) - 1) // stride + 1
     resid = r.standard_normal((B, Cout, Tout)).astype(np.float32) if res else None
-    want = orc.conv1d(x, w, b, stride, dil, pad, alpha_in, resid, alpha_out, th)
+    return x, w, b, alpha_in, resid, alpha_out
+
+
+def _run_conv_case(case, inputs, dev):
+    from multimodal_vqvae_compression_audio_tactile_amd import ops
+    B, Cin, Tin, Cout, ks, stride, dil, pad, ai, res, ao, th = case
+    x, w, b, alpha_in, resid, alpha_out = inputs
     wp = ops.pack_conv1d(_t(w, dev))
     got = ops.conv1d(_t(x, dev), wp, Cout, ks, bias=_t(b, dev), stride=stride, dil=dil, pad=pad,
                      alpha_in=None if alpha_in is None else _t(alpha_in, dev),
                      residual=None if resid is None else _t(resid, dev),
                      alpha_out=None if alpha_out is None else _t(alpha_out, dev), tanh=th)
     torch.cuda.synchronize()
-    got = got.cpu().numpy()
+    return got
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=[f"c{i}" for i in range(len(CONV_CASES))])
+def test_conv1d_bit_exact(case, orc, dev):
+    B, Cin, Tin, Cout, ks, stride, dil, pad, ai, res, ao, th = case
+    inputs = _conv_case_inputs(case)
+    x, w, b, alpha_in, resid, alpha_out = inputs
+    want = orc.conv1d(x, w, b, stride, dil, pad, alpha_in, resid, alpha_out, th)
+    got = _run_conv_case(case, inputs, dev).cpu().numpy()
     assert got.shape == want.shape
     assert np.array_equal(got, want), f"max abs diff {np.abs(got - want).max()}"
+
+
+@pytest.mark.parametrize("case,tail", CONV_SPLIT_CASES, ids=[f"split{i}" for i in range(len(CONV_SPLIT_CASES))])
+def test_conv1d_split_cases_launch_their_tail(case, tail, dev):
+    """The column-split entries of CONV_CASES really are split: one launch of full 128-column tiles plus the tail launch."""
+    from multimodal_vqvae_compression_audio_tactile_amd import ops
+    inputs = _conv_case_inputs(case)
+    ops.profile_begin()
+    try:
+        _run_conv_case(case, inputs, dev)
+    finally:
+        prof = ops.profile_end()
+    assert tail in prof and len(prof) == 2, prof
+    assert all(v["launches"] == 1 for v in prof.values()), prof
 
 
 CONVTR_CASES = [
