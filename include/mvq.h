@@ -36,7 +36,9 @@ extern "C" {
 #define MVQ_ACT_TANH 1
 #define MVQ_ACT_GELU 2   /* exact-erf GELU (nn.GELU() of CrossPredictor.ffn); MFMA-tiled, non-transposed shapes only */
 
-/* ABI version.  3 (round 5): whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
+/* ABI version.  3 (round 5): whole-stack entry points (additive since, same version: the full-sequence attention pair
+ * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
+ * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model).  Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
  * mvq_build_flags() exists. */
@@ -221,6 +223,16 @@ int mvq_attention_f32(const float* q, const float* k, const float* v, float* ctx
                       int batch, int heads, int dh, int tq, int tk,
                       size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
 
+/* The same attention for whole sequences: the CrossPredictor of the packet-loss-concealment model runs once over the full
+ * latent sequence (PLC/PLC1.py:349-422; Tq = Tk = T_lat, 75 per 1-s segment, up to the PosEnc1D bound of 8192).  Same
+ * addressing and the same arithmetic as mvq_attention_f32 (oracle/c/oracle.c::orc_attention order: score = one fma chain
+ * over d ascending from +0 divided by sqrtf(dh); max; det_exp; l summed over j ascending; p_j / l; ctx[d] one fma chain
+ * over j ascending), so on every shape mvq_attention_f32 accepts the results are bit-equal.  Tq, Tk <= 8192; Tk may be 0
+ * (ctx = 0).  Larger shapes, or a dh whose query tile does not fit 160 KiB of LDS, return MVQ_EINVAL before any launch. */
+int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float* ctx,
+                          int batch, int heads, int dh, int tq, int tk,
+                          size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
+
 /* y = gelu_erf(x) elementwise (nn.GELU() in CrossPredictor.ffn). */
 int mvq_gelu_f32(const float* x, float* y, size_t n, void* stream);
 
@@ -289,6 +301,23 @@ int mvq_scale_tanh_bwd_f32(const float* u, const float* g, float scale, float* g
 int mvq_attention_bwd_f32(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
                           int batch, int heads, int dh, int tq, int tk,
                           size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
+/* Backward of mvq_attention_seq_f32 for Tq, Tk <= 512 and dh <= 256 (the 1-, 2- and 4-s PLC training segments): gq, gk,
+ * gv from g = dL/dctx, same addressing.  scratch: mvq_attention_seq_bwd_scratch_bytes(batch, heads, tq, tk) bytes of device
+ * memory (P and dS, 2*batch*heads*tq*tk floats), 16-byte aligned.  Not bit-exact (checked against float64 autograd). */
+size_t mvq_attention_seq_bwd_scratch_bytes(int batch, int heads, int tq, int tk);
+int mvq_attention_seq_bwd_f32(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
+                              void* scratch, int batch, int heads, int dh, int tq, int tk,
+                              size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
+/* Packet-loss fill (PLC/PLC1.py:401-410) on [batch, c, t] tensors with element (b,c,t) at b*stride_b + c*stride_c + t
+ * (0,0 = contiguous; stride_b = t, stride_c = batch*t is the token-folded [C, B*T] layout); mask is uint8 [batch, t],
+ * contiguous, non-zero = token lost.
+ *   zt_in    = zt * (~mask)                    an IEEE multiply by 1 or 0, as torch's: -0 kept, NaN and inf give NaN
+ *   z_filled = where(mask, z_pred, zt_in)      either output may be NULL (not written); z_pred may be NULL with z_filled
+ *   _bwd: g_zpred = where(mask, g, 0)          torch.where's backward w.r.t. z_pred */
+int mvq_plc_mask_fill_f32(const float* zt, const float* z_pred, const uint8_t* mask, float* zt_in, float* z_filled,
+                          int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream);
+int mvq_plc_mask_fill_bwd_f32(const float* g, const uint8_t* mask, float* g_zpred,
+                              int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream);
 int mvq_mul_scaled_f32(const float* a, const float* b, float scale, float* out, size_t n, void* stream);
 int mvq_transpose2d_f32(const float* in, float* out, int rows, int cols, void* stream);
 int mvq_rowsum_f32(const float* in, float* out, int rows, int cols, int accumulate, void* stream);

@@ -6,6 +6,8 @@ Drop-in surface:
   * ``ResidualVQEMA`` / ``CrossPredictor`` / ``TokenNorm`` / ``PosEnc1D`` / ``AllPredAR`` / ``AllPredAR3`` (the compare_dacvsproposal_3.py
     variant) / ``ProposedEval`` / ``ProposedWrapper`` (compare_dacvsproposal_3.5_eval.py)
     -- the reference's own modules, same constructors and state-dict keys;
+  * ``AllPredPLC`` / ``build_plc`` / ``make_token_loss_mask`` and the masked metrics -- packet-loss concealment (plc.py,
+    PLC/PLC1.py and PLC/PLC1_eval.py), its predictor on the full-sequence attention kernels;
   * ``safe_l1`` / ``MultiResSTFTLoss`` / ``MelCosineLoss`` / ``TrainingLoss`` -- the training losses (losses.py) and
     ``train`` -- the HIP-backed autograd Functions behind ``AllPredAR.forward_step(...); total.backward()``;
   * ``Resample`` / ``resample_to`` -- torchaudio.transforms.Resample as the reference calls it; ``stsim_batch``;
@@ -23,6 +25,8 @@ from .dac import DAC, Decoder, Encoder, ResidualVectorQuantize, VectorQuantize, 
 from .proposed import (AllPredAR, AllPredAR3, CrossPredictor, PosEnc1D, ProposedEval, ProposedWrapper, ResidualVQEMA, TokenNorm,  # noqa: F401
                        psnr_batch, psnr_global_peak_db, align_by_xcorr, crop_match, align_pair_24k,
                        psnr_3k_aligned_batch)
+from .plc import (AllPredPLC, make_token_loss_mask, mae_subset, masked_metrics, psnr_subset_db, snr_subset_db,  # noqa: F401
+                  token_to_sample_mask)
 
 
 def build_proposed(state_dict=None, rvq_books=8, rvq_embed=512, n_codebooks=32, device="cuda", cls=None):
@@ -31,6 +35,17 @@ def build_proposed(state_dict=None, rvq_books=8, rvq_embed=512, n_codebooks=32, 
     da, dt = DAC(n_codebooks=n_codebooks), DAC(n_codebooks=n_codebooks)
     net = (cls or ProposedEval)(da.encoder, da.quantizer, dt.encoder, dt.decoder, c_lat=1024,
                                rvq_books=rvq_books, rvq_embed=rvq_embed)
+    if state_dict is not None:
+        net.load_state_dict(state_dict, strict=True)
+    return net.to(device).eval()
+
+
+def build_plc(state_dict=None, n_codebooks=32, device="cuda"):
+    """Assemble AllPredPLC as the reference does (build_backbones + AllPredPLC(...), PLC/PLC1_eval.py:540-548): two DAC-24k
+    instances, audio encoder / quantiser and tactile encoder / decoder, c_lat = 1024; optionally load a checkpoint's
+    ``ckpt["model"]`` with strict=True."""
+    da, dt = DAC(n_codebooks=n_codebooks), DAC(n_codebooks=n_codebooks)
+    net = AllPredPLC(da.encoder, da.quantizer, dt.encoder, dt.decoder, c_lat=1024)
     if state_dict is not None:
         net.load_state_dict(state_dict, strict=True)
     return net.to(device).eval()

@@ -910,6 +910,71 @@ int mvq_attention_bwd_f32(const float* q, const float* k, const float* v, const 
     return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_bwd");
 }
 
+static const int kAttnSeqMaxT = 8192, kAttnSeqBwdMaxT = 512, kAttnSeqBwdMaxDh = 256;
+
+int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float* ctx,
+                          int batch, int heads, int dh, int tq, int tk,
+                          size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream)
+{
+    if (batch < 0 || heads <= 0 || dh <= 0 || tq < 0 || tk < 0 || tq > kAttnSeqMaxT || tk > kAttnSeqMaxT)
+        return fail(MVQ_EINVAL, "attention_seq: bad shape (Tq, Tk <= %d)", kAttnSeqMaxT);
+    int qt = 0, kt = 0;
+    size_t nf = 0;
+    if (!mvq::attn_seq_plan(dh, tk, &qt, &kt, &nf)) return fail(MVQ_EINVAL, "attention_seq: dh = %d does not fit a query tile in LDS", dh);
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !ctx || (tk > 0 && (!k || !v))) return fail(MVQ_EINVAL, "attention_seq: null tensor");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_seq(q, k, v, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq");
+}
+
+size_t mvq_attention_seq_bwd_scratch_bytes(int batch, int heads, int tq, int tk)
+{
+    if (batch <= 0 || heads <= 0 || tq <= 0 || tk <= 0) return 0;
+    return (size_t)2 * batch * heads * (size_t)tq * tk * sizeof(float);
+}
+
+int mvq_attention_seq_bwd_f32(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
+                              void* scratch, int batch, int heads, int dh, int tq, int tk,
+                              size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream)
+{
+    if (batch < 0 || heads <= 0 || dh <= 0 || dh > kAttnSeqBwdMaxDh || tq < 0 || tk < 0 || tq > kAttnSeqBwdMaxT || tk > kAttnSeqBwdMaxT)
+        return fail(MVQ_EINVAL, "attention_seq_bwd: bad shape (Tq, Tk <= %d, dh <= %d)", kAttnSeqBwdMaxT, kAttnSeqBwdMaxDh);
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !g || !gq || (tk > 0 && (!k || !v || !gk || !gv || !scratch))) return fail(MVQ_EINVAL, "attention_seq_bwd: null tensor");
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(MVQ_EINVAL, "attention_seq_bwd: scratch must be 16-byte aligned");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_seq_bwd(q, k, v, g, gq, gk, gv, static_cast<float*>(scratch), batch, heads, dh, tq, tk,
+                                                 q_stride_b, q_stride_c, k_stride_b, k_stride_c, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq_bwd");
+}
+
+int mvq_plc_mask_fill_f32(const float* zt, const float* z_pred, const uint8_t* mask, float* zt_in, float* z_filled,
+                          int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream)
+{
+    if (batch < 0 || c < 0 || t < 0) return fail(MVQ_EINVAL, "plc_mask_fill: bad shape");
+    if ((size_t)batch * c * t == 0) return MVQ_OK;
+    if (!zt || !mask || (!zt_in && !z_filled) || (z_filled && !z_pred)) return fail(MVQ_EINVAL, "plc_mask_fill: null tensor");
+    if (stride_b == 0 && stride_c == 0) { stride_b = (size_t)c * t; stride_c = (size_t)t; }
+    hipError_t e = mvq::launch_plc_mask_fill(zt, z_pred, mask, zt_in, z_filled, batch, c, t, stride_b, stride_c, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "plc_mask_fill");
+}
+
+int mvq_plc_mask_fill_bwd_f32(const float* g, const uint8_t* mask, float* g_zpred,
+                              int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream)
+{
+    if (batch < 0 || c < 0 || t < 0) return fail(MVQ_EINVAL, "plc_mask_fill_bwd: bad shape");
+    if ((size_t)batch * c * t == 0) return MVQ_OK;
+    if (!g || !mask || !g_zpred) return fail(MVQ_EINVAL, "plc_mask_fill_bwd: null tensor");
+    if (stride_b == 0 && stride_c == 0) { stride_b = (size_t)c * t; stride_c = (size_t)t; }
+    hipError_t e = mvq::launch_plc_mask_fill_bwd(g, mask, g_zpred, batch, c, t, stride_b, stride_c, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "plc_mask_fill_bwd");
+}
+
 int mvq_mul_scaled_f32(const float* a, const float* b, float scale, float* out, size_t n, void* stream)
 {
     if ((!a || !b || !out) && n) return fail(MVQ_EINVAL, "mul_scaled: null tensor");

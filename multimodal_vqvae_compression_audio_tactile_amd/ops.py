@@ -509,6 +509,100 @@ def attention_kv_slice(q, k_all, v_all, heads, folded_batch, s, tk):
     return ctx
 
 
+# ---------------------------------------------- full-sequence attention and the packet-loss fill (PLC/PLC1.py:349-422)
+ATTN_SEQ_MAX_T = 8192          # PosEnc1D(max_len=8192): the reference itself fails beyond
+ATTN_SEQ_BWD_MAX_T = 512
+
+
+def attention_fits(dh, tq, tk) -> bool:
+    """True when mvq_attention_f32 (one head slice in 64 KiB of LDS) accepts the shape."""
+    return tq <= 64 and tk <= 64 and dh * (tq + 2 * tk) + tq * tk <= 16384
+
+
+def attention_bwd_fits(dh, tq, tk) -> bool:
+    """True when mvq_attention_bwd_f32 accepts the shape (Tq, Tk <= 32 and its LDS staging fits 64 KiB)."""
+    return tq <= 32 and tk <= 32 and dh * (2 * tq + 2 * tk) + 2 * tq * tk <= 16384
+
+
+def _attn_dims(q, k, folded_batch):
+    B, C, Tq = q.shape
+    Tk = k.shape[2]
+    if folded_batch is None:
+        return B, Tq, Tk, (0, 0, 0, 0)
+    B = folded_batch
+    if q.shape[0] != 1 or Tq % B or Tk % B:
+        raise MvqError("attention: folded tensors must be [1, C, B*T]")
+    Tq, Tk = Tq // B, Tk // B
+    return B, Tq, Tk, (Tq, B * Tq, Tk, B * Tk)
+
+
+def attention_seq(q, k, v, heads, folded_batch=None):
+    """softmax(Q K^T / sqrt(dh)) V over whole sequences (Tq, Tk <= 8192): the arithmetic of ``attention`` -- bit-equal to it
+    wherever that kernel accepts the shape -- without its 64-token limit."""
+    q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v")
+    B, Tq, Tk, strides = _attn_dims(q, k, folded_batch)
+    C = q.shape[1]
+    ctx = torch.empty_like(q)
+    check(_lib.lib().mvq_attention_seq_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), ctx.data_ptr(), B, heads, C // heads,
+                                           Tq, Tk, *strides, _stream()), "mvq_attention_seq_f32")
+    return ctx
+
+
+def attention_seq_bwd(q, k, v, g, heads, folded_batch=None):
+    """-> (gq, gk, gv) of attention_seq for Tq, Tk <= 512."""
+    q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v"); g = _dev(g, "g")
+    B, Tq, Tk, strides = _attn_dims(q, k, folded_batch)
+    C = q.shape[1]
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    nbytes = _lib.lib().mvq_attention_seq_bwd_scratch_bytes(B, heads, Tq, Tk) if Tq <= ATTN_SEQ_BWD_MAX_T and Tk <= ATTN_SEQ_BWD_MAX_T else 0
+    scratch = torch.empty(max(nbytes // 4, 4), device=q.device, dtype=torch.float32)
+    check(_lib.lib().mvq_attention_seq_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), gq.data_ptr(),
+                                               gk.data_ptr(), gv.data_ptr(), scratch.data_ptr(), B, heads, C // heads, Tq, Tk,
+                                               *strides, _stream()), "mvq_attention_seq_bwd_f32")
+    return gq, gk, gv
+
+
+def _mask_u8(mask, B, T, device):
+    if not isinstance(mask, torch.Tensor) or mask.device != device:
+        raise MvqError("plc_mask_fill: mask must be a tensor on the device of zt")
+    m = mask.reshape(mask.shape[0], -1) if mask.dim() == 3 else mask            # [B,1,T] or [B,T]
+    if tuple(m.shape) != (B, T):
+        raise MvqError(f"plc_mask_fill: mask shape {tuple(mask.shape)} does not match [B={B}, T={T}]")
+    m = m.contiguous()
+    if m.dtype == torch.bool:
+        return m.view(torch.uint8)                                              # 0 / 1 bytes: a view, no launch
+    return m if m.dtype == torch.uint8 else (m != 0).view(torch.uint8)
+
+
+def plc_mask_fill(zt, z_pred, mask, folded_batch=None, want_zt_in=True):
+    """-> (zt_in, z_filled): zt_in = zt * (~mask), z_filled = where(mask, z_pred, zt_in) (PLC/PLC1.py:401-410).
+    mask: bool / uint8 [B, T] or [B, 1, T] (True = token lost).  Token-folded [1,C,B*T] inputs with ``folded_batch=B``.
+    ``z_pred=None`` computes zt_in alone (z_filled is None)."""
+    zt = _dev(zt, "zt")
+    if z_pred is not None:
+        z_pred = _dev(z_pred, "z_pred")
+        if z_pred.shape != zt.shape:
+            raise MvqError("plc_mask_fill: z_pred must have the shape of zt")
+    B, C, T, sb, sc = _fold_dims(zt, folded_batch)
+    m = _mask_u8(mask, B, T, zt.device)
+    zt_in = torch.empty_like(zt) if (want_zt_in or z_pred is None) else None
+    zf = torch.empty_like(zt) if z_pred is not None else None
+    check(_lib.lib().mvq_plc_mask_fill_f32(zt.data_ptr(), _p(z_pred), m.data_ptr(), _p(zt_in), _p(zf),
+                                           B, C, T, sb, sc, _stream()), "mvq_plc_mask_fill_f32")
+    return zt_in, zf
+
+
+def plc_mask_fill_bwd(g, mask, folded_batch=None):
+    """g_zpred = where(mask, g, 0): the gradient of z_filled w.r.t. z_pred."""
+    g = _dev(g, "g")
+    B, C, T, sb, sc = _fold_dims(g, folded_batch)
+    m = _mask_u8(mask, B, T, g.device)
+    gz = torch.empty_like(g)
+    check(_lib.lib().mvq_plc_mask_fill_bwd_f32(g.data_ptr(), m.data_ptr(), gz.data_ptr(), B, C, T, sb, sc, _stream()),
+          "mvq_plc_mask_fill_bwd_f32")
+    return gz
+
+
 _AR_CHECKED = set()
 
 

@@ -111,6 +111,13 @@ class CrossPredictor(nn.Module):
                              eps=self.ln_kv.eps, folded_batch=folded_batch)
         return self._lin["k"](kv), self._lin["v"](kv)
 
+    def _chunk_kernels_fit(self, Q, K, fb, bwd=False):
+        """The AR chunks (16 tokens) stay on the chunk attention kernels; only longer calls -- the PLC predictor over a whole
+        latent sequence -- take the full-sequence ones."""
+        n = fb or 1
+        tq, tk = Q.shape[-1] // n, K.shape[-1] // n
+        return ops.attention_fits(self.dh, tq, tk) and (not bwd or ops.attention_bwd_fits(self.dh, tq, tk))
+
     @torch.no_grad()
     def run(self, zt_prev, za, folded_batch=None, kv_all=None, kv_slice=None):
         """zt_prev[B,C,Tq], za[B,C,Tk] (or both token-folded [1,C,B*T] with folded_batch=B) -> same layout.
@@ -125,7 +132,9 @@ class CrossPredictor(nn.Module):
         else:
             kv = ops.layernorm_c(za, self.ln_kv.weight.detach(), self.ln_kv.bias.detach(), pe=pe, eps=self.ln_kv.eps,
                                  folded_batch=fb)
-            ctx = ops.attention(L["q"](q), L["k"](kv), L["v"](kv), self.h, folded_batch=fb)
+            Q, K, V = L["q"](q), L["k"](kv), L["v"](kv)
+            attn = ops.attention if self._chunk_kernels_fit(Q, K, fb) else ops.attention_seq   # whole-sequence calls (PLC)
+            ctx = attn(Q, K, V, self.h, folded_batch=fb)
         y1 = L["o"](ctx, residual=q)                                        # out(ctx) + q
         hdn = ops.layernorm_c(y1, self.ffn[0].weight.detach(), self.ffn[0].bias.detach(), eps=self.ffn[0].eps,
                               folded_batch=fb)
@@ -139,7 +148,8 @@ class CrossPredictor(nn.Module):
         q = train.LayerNormC.apply(zt_prev, self.ln_q.weight, self.ln_q.bias, pe, self.ln_q.eps, fb)
         kv = train.LayerNormC.apply(za, self.ln_kv.weight, self.ln_kv.bias, pe, self.ln_kv.eps, fb)
         Q, K, V = lin("q", self.q_proj, q), lin("k", self.k_proj, kv), lin("v", self.v_proj, kv)
-        ctx = train.Attention.apply(Q, K, V, self.h, fb)
+        attn = train.Attention if self._chunk_kernels_fit(Q, K, fb, bwd=True) else train.AttentionSeq
+        ctx = attn.apply(Q, K, V, self.h, fb)
         if self.training and self.drop.p > 0:
             ctx = train.Dropout.apply(ctx, float(self.drop.p))
         y1 = lin("o", self.out, ctx, q)

@@ -14,6 +14,7 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   encoder_fwd                 mvq_encoder_fwd_f32        A_ENC(a) / T_ENC(t), ...5.py:294,296 (whole stack: `stack` = ops.Stack(...).id)
   decoder_fwd                 mvq_decoder_fwd_f32        T_DEC(z), ...5.py:322
   decoder_bwd_input           mvq_decoder_fwd_saving_f32 + mvq_decoder_bwd_input_f32: dL/dz of T_DEC, ...5.py:393
+  attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
 
 Weights are the PACKED images of ``ops.pack_conv1d`` / ``ops.pack_conv_transpose1d`` (made once per weight load).  Import this module
 to register (``import multimodal_vqvae_compression_audio_tactile_amd.torch_ops``); the package does not import it by itself.
@@ -135,4 +136,14 @@ def _(z, gy, stack):
 
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
-              "ema_update_f32")
+              "ema_update_f32", "attention_seq_f32")
+
+
+@torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
+def attention_seq_f32(q: Tensor, k: Tensor, v: Tensor, heads: int) -> Tensor:
+    return ops.attention_seq(q, k, v, heads)
+
+
+@attention_seq_f32.register_fake
+def _(q, k, v, heads):
+    return q.new_empty(q.shape)

@@ -97,6 +97,37 @@ class Attention(Function):
         return gq, gk, gv, None, None
 
 
+class AttentionSeq(Function):
+    """Full-sequence attention (ops.attention_seq / attention_seq_bwd): the PLC predictor's call over all T_lat tokens."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, fb):
+        ctx.save_for_backward(q, k, v)
+        ctx.heads, ctx.fb = heads, fb
+        return ops.attention_seq(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb)
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v = ctx.saved_tensors
+        gq, gk, gv = ops.attention_seq_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb)
+        return gq, gk, gv, None, None
+
+
+class PlcFill(Function):
+    """z_filled = where(mask, z_pred, zt * ~mask) (PLC/PLC1.py:401-410); the gradient reaches z_pred only (zt comes from
+    the frozen encoder)."""
+
+    @staticmethod
+    def forward(ctx, zt, z_pred, mask, fb):
+        ctx.mask, ctx.fb = mask, fb
+        return ops.plc_mask_fill(zt.detach(), z_pred.detach(), mask, folded_batch=fb, want_zt_in=False)[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        gz = ops.plc_mask_fill_bwd(_c(g), ctx.mask, folded_batch=ctx.fb) if ctx.needs_input_grad[1] else None
+        return None, gz, None, None
+
+
 class Dropout(Function):
     """x * mask / (1-p); the keep-mask comes from torch's generator (as nn.Dropout's does), the multiply is ours."""
 
