@@ -38,7 +38,8 @@ extern "C" {
 
 /* ABI version.  3 (round 5): whole-stack entry points (additive since, same version: the full-sequence attention pair
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
- * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model).  Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
+ * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
+ * mvq_subset_stats_f32).  Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
  * mvq_build_flags() exists. */
@@ -318,6 +319,27 @@ int mvq_plc_mask_fill_f32(const float* zt, const float* z_pred, const uint8_t* m
                           int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream);
 int mvq_plc_mask_fill_bwd_f32(const float* g, const uint8_t* mask, float* g_zpred,
                               int batch, int c, int t, size_t stride_b, size_t stride_c, void* stream);
+/* PLC evaluation (PLC/PLC1_eval.py:270-333,601-663, PLC/PLC1_low_mid_high_eval.py:264-288).
+ * mvq_frame_subsets: token mask (uint8 [t_lat], non-zero = lost) -> frame_mask uint8 [t_frames] with frame f on token
+ *   clip(floor(double(f*hop) / (double(t_wave)/double(t_lat))), 0, t_lat-1) (numpy float64), and the ascending frame indices
+ *   of the lost / kept frames in cols_masked / cols_unmasked (t_frames ints each); counts[0..1] = their lengths, on the
+ *   device.  t_lat = 0 or t_wave = 0: counts are 0 and frame_mask is all 0.  t_frames <= 32768.
+ * mvq_mel_ssim_f32: n images, one block each; image i is described by desc[5i..5i+4] = {x column base, y column base, x max
+ *   index, y max index, list offset (-1: columns 0..w-1)} into the mel plane mel [rows = 64, ld] and maxv[n_maxv], and its
+ *   width w = widths[i] (device, clamped to [0, max_width]); columns are base + cols[offset + j].  Values are
+ *   mel / max(maxv, 1e-8).  mode MVQ_SSIM_SSIM: the 7x7 uniform-window SSIM of skimage's defaults (data_range 1), the mean of
+ *   the map cropped by 3; w = 1..6 and mode MVQ_SSIM_NORM: max(0, 1 - |A-B|/(|A|+|B|+1e-12)); w = 0: NaN.  out: double [n].
+ *   max_width <= 32768 and rows == 64, else MVQ_EINVAL before any launch.  Deterministic, independent of the other images.
+ * mvq_subset_stats_f32: ref, est [t] with sample n on token floor(float(n) / float(t/t_lat)) (token_to_sample_mask);
+ *   out double[8] = lost side {count, sum |r-e|, sum r^2, sum (r-e)^2}, then the kept side.  t <= 2^24. */
+#define MVQ_SSIM_NORM 0
+#define MVQ_SSIM_SSIM 1
+int mvq_frame_subsets(const uint8_t* latent_mask, int t_lat, long long t_wave, int hop, int t_frames, uint8_t* frame_mask,
+                      int* cols_masked, int* cols_unmasked, int* counts, void* stream);
+int mvq_mel_ssim_f32(const float* mel, int rows, size_t ld, const float* maxv, int n_maxv, const int* desc, const int* cols,
+                     size_t n_cols, const int* widths, int n, int max_width, int mode, double* out, void* stream);
+int mvq_subset_stats_f32(const float* ref, const float* est, long long t, const uint8_t* latent_mask, int t_lat, double* out,
+                         void* stream);
 int mvq_mul_scaled_f32(const float* a, const float* b, float scale, float* out, size_t n, void* stream);
 int mvq_transpose2d_f32(const float* in, float* out, int rows, int cols, void* stream);
 int mvq_rowsum_f32(const float* in, float* out, int rows, int cols, int accumulate, void* stream);

@@ -7,7 +7,8 @@ Drop-in surface:
     variant) / ``ProposedEval`` / ``ProposedWrapper`` (compare_dacvsproposal_3.5_eval.py)
     -- the reference's own modules, same constructors and state-dict keys;
   * ``AllPredPLC`` / ``build_plc`` / ``make_token_loss_mask`` and the masked metrics -- packet-loss concealment (plc.py,
-    PLC/PLC1.py and PLC/PLC1_eval.py), its predictor on the full-sequence attention kernels;
+    PLC/PLC1.py and PLC/PLC1_eval.py), its predictor on the full-sequence attention kernels; its evaluation
+    (``stsim_mel_with_mask`` / ``stsim_mel_global`` / ``mae_global`` / ``frame_token_mask`` / ``evaluate_file``);
   * ``safe_l1`` / ``MultiResSTFTLoss`` / ``MelCosineLoss`` / ``TrainingLoss`` -- the training losses (losses.py) and
     ``train`` -- the HIP-backed autograd Functions behind ``AllPredAR.forward_step(...); total.backward()``;
   * ``Resample`` / ``resample_to`` -- torchaudio.transforms.Resample as the reference calls it; ``stsim_batch``;
@@ -26,7 +27,8 @@ from .proposed import (AllPredAR, AllPredAR3, CrossPredictor, PosEnc1D, Proposed
                        psnr_batch, psnr_global_peak_db, align_by_xcorr, crop_match, align_pair_24k,
                        psnr_3k_aligned_batch)
 from .plc import (AllPredPLC, make_token_loss_mask, mae_subset, masked_metrics, psnr_subset_db, snr_subset_db,  # noqa: F401
-                  token_to_sample_mask)
+                  token_to_sample_mask, frame_token_mask, stsim_mel_with_mask, stsim_mel_global, mae_global, evaluate_file,
+                  make_category_token_loss_mask, category_mask_fn)
 
 
 def build_proposed(state_dict=None, rvq_books=8, rvq_embed=512, n_codebooks=32, device="cuda", cls=None):

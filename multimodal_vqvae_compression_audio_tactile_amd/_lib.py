@@ -100,6 +100,9 @@ EXPORTS = {
     "mvq_attention_seq_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_plc_mask_fill_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_void_p]),
     "mvq_plc_mask_fill_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_size_t] * 2 + [c_void_p]),
+    "mvq_frame_subsets": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_int, c_int] + [c_void_p] * 5),
+    "mvq_mel_ssim_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
+    "mvq_subset_stats_f32": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "mvq_mul_scaled_f32": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
     "mvq_transpose2d_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mvq_rowsum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -975,6 +975,44 @@ int mvq_plc_mask_fill_bwd_f32(const float* g, const uint8_t* mask, float* g_zpre
     return e == hipSuccess ? MVQ_OK : hipfail(e, "plc_mask_fill_bwd");
 }
 
+static const int kMelSsimMaxWidth = 32768, kMelRows = 64, kSubsetMaxT = 1 << 24;
+
+int mvq_frame_subsets(const uint8_t* latent_mask, int t_lat, long long t_wave, int hop, int t_frames, uint8_t* frame_mask,
+                      int* cols_masked, int* cols_unmasked, int* counts, void* stream)
+{
+    if (t_lat < 0 || t_wave < 0 || hop <= 0 || t_frames < 0 || t_frames > kMelSsimMaxWidth)
+        return fail(MVQ_EINVAL, "frame_subsets: bad shape (0 <= frames <= %d, hop > 0)", kMelSsimMaxWidth);
+    if (!counts || (t_frames > 0 && (!frame_mask || !cols_masked || !cols_unmasked)) || (t_lat > 0 && !latent_mask))
+        return fail(MVQ_EINVAL, "frame_subsets: null tensor");
+    const double spt = (t_lat > 0 && t_wave > 0) ? (double)t_wave / (double)t_lat : 0.0;
+    hipError_t e = mvq::launch_frame_subsets(latent_mask, spt > 0.0 ? t_lat : 0, spt, hop, t_frames, frame_mask, cols_masked,
+                                             cols_unmasked, counts, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "frame_subsets");
+}
+
+int mvq_mel_ssim_f32(const float* mel, int rows, size_t ld, const float* maxv, int n_maxv, const int* desc, const int* cols,
+                     size_t n_cols, const int* widths, int n, int max_width, int mode, double* out, void* stream)
+{
+    if (rows != kMelRows) return fail(MVQ_EINVAL, "mel_ssim: rows = %d (the mel front end has %d)", rows, kMelRows);
+    if (n < 0 || max_width < 0 || max_width > kMelSsimMaxWidth || (size_t)max_width > ld || ld > (size_t)1 << 30)
+        return fail(MVQ_EINVAL, "mel_ssim: bad shape (width <= %d and <= ld)", kMelSsimMaxWidth);
+    if (mode != MVQ_SSIM_NORM && mode != MVQ_SSIM_SSIM) return fail(MVQ_EINVAL, "mel_ssim: unknown mode %d", mode);
+    if (n == 0) return MVQ_OK;
+    if (!mel || !maxv || n_maxv <= 0 || !desc || !widths || !out || (n_cols > 0 && !cols)) return fail(MVQ_EINVAL, "mel_ssim: null tensor");
+    hipError_t e = mvq::launch_mel_ssim(mel, ld, maxv, n_maxv, desc, cols, n_cols, widths, n, max_width, mode, out, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "mel_ssim");
+}
+
+int mvq_subset_stats_f32(const float* ref, const float* est, long long t, const uint8_t* latent_mask, int t_lat, double* out,
+                         void* stream)
+{
+    if (t < 0 || t > kSubsetMaxT || t_lat < 0) return fail(MVQ_EINVAL, "subset_stats: bad shape (0 <= T <= %d)", kSubsetMaxT);
+    if (!out || (t > 0 && (!ref || !est)) || (t_lat > 0 && !latent_mask)) return fail(MVQ_EINVAL, "subset_stats: null tensor");
+    const float spt = (t_lat > 0 && t > 0) ? (float)((double)t / (double)t_lat) : 1.0f;
+    hipError_t e = mvq::launch_subset_stats(ref, est, (int)t, latent_mask, t > 0 ? t_lat : 0, spt, out, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "subset_stats");
+}
+
 int mvq_mul_scaled_f32(const float* a, const float* b, float scale, float* out, size_t n, void* stream)
 {
     if ((!a || !b || !out) && n) return fail(MVQ_EINVAL, "mul_scaled: null tensor");

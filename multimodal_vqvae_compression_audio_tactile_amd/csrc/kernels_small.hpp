@@ -73,6 +73,12 @@ hipError_t launch_plc_mask_fill(const float* zt, const float* zp, const uint8_t*
                                 int B, int C, int T, size_t sb, size_t sc, hipStream_t s);
 hipError_t launch_plc_mask_fill_bwd(const float* g, const uint8_t* mask, float* gzp, int B, int C, int T, size_t sb, size_t sc,
                                     hipStream_t s);
+hipError_t launch_frame_subsets(const uint8_t* lat, int t_lat, double spt, int hop, int t_f, uint8_t* fmask, int* cols_m,
+                                int* cols_u, int* counts, hipStream_t s);                                  // mel_ssim.hip
+hipError_t launch_mel_ssim(const float* M, size_t ld, const float* maxv, int n_maxv, const int* desc, const int* cols, size_t n_cols,
+                           const int* widths, int n, int max_width, int mode, double* out, hipStream_t s);
+hipError_t launch_subset_stats(const float* ref, const float* est, int T, const uint8_t* lat, int t_lat, float spt, double* out,
+                               hipStream_t s);
 hipError_t launch_mul_scaled(const float* a, const float* b, float scale, float* out, size_t n, hipStream_t s);
 hipError_t launch_transpose2d(const float* in, float* out, int rows, int cols, hipStream_t s);
 hipError_t launch_rowsum(const float* in, float* out, int rows, int cols, int accumulate, hipStream_t s);

@@ -234,6 +234,21 @@ class TrainingLoss(nn.Module):
 
 
 @torch.no_grad()
+def mel_plane(ref_1T, est_1T):
+    """The un-normalised 64-band HTK mel magnitudes of both signals (512/128, center / reflect, |stft| clamped at 1e-8) as one
+    plane [64, 2*B*nfr] (ref items first), their per-item maxima [2B] (ops.mel_max) and nfr = 1 + T // 128: the front end of
+    stsim_batch and of the PLC ST-SIM (plc.py).  Inputs of equal length."""
+    r, e = _prep(ref_1T), _prep(est_1T)
+    if r.shape != e.shape:
+        raise ops.MvqError("mel_plane: crop_match the signals first (equal lengths)")
+    sp = _Spectra(r, e, MEL_NFFT, MEL_HOP, 1e-8)
+    mp = _MelPlan.get(r.device)
+    M = ops.conv1d(sp.mag.reshape(1, mp.Fp, 2 * sp.Nh), mp.wp, mp.n_mels, 1)
+    maxv, _ = ops.mel_max(M, mp.n_mels, sp.B, sp.nfr)
+    return M[0], maxv, sp.nfr
+
+
+@torch.no_grad()
 def stsim_batch(ref_1T, est_1T):
     """Spectro-temporal similarity per item (Evaluation/compare_dacvsproposal_5_eval.py:142-177): 0.5*(1 + mean over
     frames of the cosine between the max-normalised 64-band HTK mel magnitudes, n_fft 512, hop 128).  Returns a list of

@@ -603,6 +603,83 @@ def plc_mask_fill_bwd(g, mask, folded_batch=None):
     return gz
 
 
+# ------------------------------------------------------------ PLC evaluation (csrc/mel_ssim.hip)
+MEL_SSIM_MAX_WIDTH = 32768      # frames of one image (8192 tokens = 20481 frames)
+MEL_SSIM_ROWS = 64
+SSIM_MODES = {"norm": 0, "ssim": 1}
+
+
+def _u8_vec(mask, name):
+    if not isinstance(mask, torch.Tensor) or mask.device.type != "cuda":
+        raise MvqError(f"{name}: mask must be a tensor on the device")
+    m = mask.reshape(-1).contiguous()
+    if m.dtype == torch.bool:
+        return m.view(torch.uint8)
+    return m if m.dtype == torch.uint8 else (m != 0).view(torch.uint8)
+
+
+def frame_subsets(latent_mask, T_wave, n_frames, hop=128, out_counts=None):
+    """Token mask [T_lat] -> (frame_mask uint8 [n_frames], cols int32 [2, n_frames], counts int32 [2]): the float64
+    frame -> token rule of compute_stsim_mel_with_mask and the compacted frame lists of the lost (cols[0]) and kept (cols[1])
+    sides, of which the first counts[0] / counts[1] entries are valid (the counts stay on the device).  ``out_counts`` (an int32 view
+    of length 2) receives the counts instead of a fresh tensor."""
+    m = _u8_vec(latent_mask, "frame_subsets")
+    if n_frames < 0 or n_frames > MEL_SSIM_MAX_WIDTH or T_wave < 0 or hop <= 0:
+        raise MvqError(f"frame_subsets: n_frames = {n_frames} outside [0, {MEL_SSIM_MAX_WIDTH}]")
+    dev = m.device
+    fm = torch.empty(n_frames, device=dev, dtype=torch.uint8)
+    cols = torch.empty(2, n_frames, device=dev, dtype=torch.int32)
+    counts = out_counts if out_counts is not None else torch.empty(2, device=dev, dtype=torch.int32)
+    if counts.dtype != torch.int32 or counts.numel() != 2 or not counts.is_contiguous() or counts.device != dev:
+        raise MvqError("frame_subsets: out_counts must be a contiguous int32 [2] on the device")
+    check(_lib.lib().mvq_frame_subsets(_p(m) if m.numel() else None, m.numel(), int(T_wave), int(hop), int(n_frames),
+                                       _p(fm) if n_frames else None, _p(cols[0]) if n_frames else None,
+                                       _p(cols[1]) if n_frames else None, counts.data_ptr(), _stream()), "mvq_frame_subsets")
+    return fm, cols, counts
+
+
+def mel_ssim(mel, maxv, desc, widths, max_width, cols=None, mode="ssim"):
+    """Scores of N mel image pairs -> float64 [N] (one launch, csrc/mel_ssim.hip).  mel: the un-normalised [64, ld] plane;
+    maxv: float32 per-item maxima (ops.mel_max); desc: int32 [N, 5] = (x column base, y column base, x max index, y max index,
+    list offset or -1); widths: int32 [N] on the device, each <= max_width (a host bound); cols: int32 column lists.
+    mode "ssim" (skimage's defaults; widths 1..6 fall through to the norm formula) or "norm"; width 0 gives NaN."""
+    mel = _dev(mel, "mel"); maxv = _dev(maxv, "maxv")
+    if mel.dim() == 3 and mel.shape[0] == 1:
+        mel = mel[0]
+    if mel.dim() != 2 or mel.shape[0] != MEL_SSIM_ROWS:
+        raise MvqError(f"mel_ssim: the mel plane must be [{MEL_SSIM_ROWS}, ld], got {tuple(mel.shape)}")
+    if mode not in SSIM_MODES:
+        raise MvqError(f"mel_ssim: mode {mode!r} is not one of {sorted(SSIM_MODES)}")
+    if not 0 <= int(max_width) <= min(MEL_SSIM_MAX_WIDTH, mel.shape[1]):
+        raise MvqError(f"mel_ssim: max_width = {max_width} outside [0, min({MEL_SSIM_MAX_WIDTH}, ld = {mel.shape[1]})]")
+    for t, name in ((desc, "desc"), (widths, "widths")) + (((cols, "cols"),) if cols is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.device != mel.device or t.dtype != torch.int32:
+            raise MvqError(f"mel_ssim: {name} must be an int32 tensor on the device of mel")
+    desc, widths = desc.contiguous(), widths.contiguous()
+    n = widths.numel()
+    if tuple(desc.shape) != (n, 5):
+        raise MvqError(f"mel_ssim: desc must be [N = {n}, 5], got {tuple(desc.shape)}")
+    cols = cols.contiguous() if cols is not None else None
+    out = torch.empty(n, device=mel.device, dtype=torch.float64)
+    check(_lib.lib().mvq_mel_ssim_f32(mel.data_ptr(), mel.shape[0], mel.stride(0), maxv.data_ptr(), maxv.numel(), desc.data_ptr(),
+                                      _p(cols), 0 if cols is None else cols.numel(), widths.data_ptr(), n, int(max_width),
+                                      SSIM_MODES[mode], out.data_ptr(), _stream()), "mvq_mel_ssim_f32")
+    return out
+
+
+def subset_stats(ref, est, latent_mask):
+    """-> float64 [8]: per side (lost, kept) the count, sum |r-e|, sum r^2, sum (r-e)^2 of ref / est [T] under the float32
+    sample -> token rule of token_to_sample_mask (one launch)."""
+    ref = _dev(ref, "ref").reshape(-1); est = _dev(est, "est").reshape(-1)
+    if ref.numel() != est.numel():
+        raise MvqError("subset_stats: ref and est must have the same length")
+    m = _u8_vec(latent_mask, "subset_stats")
+    out = torch.empty(8, device=ref.device, dtype=torch.float64)
+    check(_lib.lib().mvq_subset_stats_f32(ref.data_ptr(), est.data_ptr(), ref.numel(), _p(m) if m.numel() else None, m.numel(),
+                                          out.data_ptr(), _stream()), "mvq_subset_stats_f32")
+    return out
+
+
 _AR_CHECKED = set()
 
 

@@ -15,6 +15,7 @@ is kept (same state-dict keys) and stays unused.
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Optional
 
 import torch
@@ -151,3 +152,172 @@ def masked_metrics(ref_vec, est_vec, latent_mask, peak: float) -> dict:
             "snr_masked": snr_subset_db(r, e, sm), "snr_unmasked": snr_subset_db(r, e, ~sm),
             "psnr_masked": psnr_subset_db(r, e, sm, peak), "psnr_unmasked": psnr_subset_db(r, e, ~sm, peak)}
 
+
+
+# ------------------------------------------ mel ST-SIM and the pass-1 file evaluation (PLC/PLC1_eval.py:270-333,585-663)
+TARGET_SR = 24000         # PLC/PLC1_eval.py:66-67 (model rate = ST-SIM rate)
+MAX_ALIGN_SHIFT = 400     # ...:77
+MEL_HOP = 128             # ...:81
+ROW_KEYS = ("len_samples", "psnr_global_db", "stsim_global", "psnr_masked_db", "psnr_unmasked_db", "snr_masked_db",
+            "snr_unmasked_db", "mae_masked", "mae_unmasked", "stsim_masked", "stsim_unmasked")   # eval_metrics.csv after "stem"
+
+
+def _backend(backend):
+    if backend not in ops.SSIM_MODES:
+        raise ValueError(f"backend must be 'ssim' (skimage's SSIM) or 'norm' (the reference without scikit-image), not {backend!r}")
+    return backend
+
+
+def frame_token_mask(latent_mask: torch.Tensor, T_wave: int) -> torch.Tensor:
+    """Token mask [T_lat] -> frame mask [1 + T_wave // 128] (bool, on the mask's device): frame f belongs to token
+    floor(f * 128 / (T_wave / T_lat)) computed in float64, clipped to [0, T_lat-1] (PLC/PLC1_eval.py:312-318).  All False
+    when T_lat or T_wave is 0."""
+    fm, _, _ = ops.frame_subsets(latent_mask, int(T_wave), 1 + int(T_wave) // MEL_HOP, MEL_HOP)
+    return fm.bool()
+
+
+def _stsim_device(ref_1T, est_1T, latent_mask, backend):
+    """float64 [1] (global) or [3] (global, masked, unmasked) on the device: two launches after the mel front end."""
+    from .losses import mel_plane
+    M, maxv, nfr = mel_plane(ref_1T, est_1T)
+    dev = M.device
+    if latent_mask is None:
+        desc = torch.tensor([[0, nfr, 0, 1, -1]], dtype=torch.int32).to(dev)
+        widths = torch.full((1,), nfr, dtype=torch.int32, device=dev)
+        return ops.mel_ssim(M, maxv, desc, widths, nfr, mode=backend)
+    widths = torch.full((3,), nfr, dtype=torch.int32, device=dev)
+    _, cols, _ = ops.frame_subsets(latent_mask, ref_1T.shape[-1], nfr, MEL_HOP, out_counts=widths[1:])
+    desc = torch.tensor([[0, nfr, 0, 1, -1], [0, nfr, 0, 1, 0], [0, nfr, 0, 1, nfr]], dtype=torch.int32).to(dev)
+    return ops.mel_ssim(M, maxv, desc, widths, nfr, cols=cols.reshape(-1), mode=backend)
+
+
+@torch.no_grad()
+def stsim_mel_with_mask(ref_1T, est_1T, latent_mask, backend: str = "ssim"):
+    """compute_stsim_mel_with_mask (PLC/PLC1_eval.py:270-333) on the device -> (global, masked, unmasked) floats.  ref_1T,
+    est_1T: aligned [1, T] at 24 kHz; latent_mask: [T_lat] bool.  The masked / unmasked images are the concatenated frame
+    columns of each side; an empty side is NaN, a side of 1..6 frames is scored by the norm formula (the reference's
+    fall-through when skimage refuses it).  backend "ssim": skimage's structural_similarity (restated, DESIGN.md section 11);
+    "norm": the reference as it runs without scikit-image.  One device->host copy."""
+    _backend(backend)
+    return tuple(_stsim_device(ref_1T, est_1T, latent_mask.reshape(-1), backend).cpu().tolist())
+
+
+@torch.no_grad()
+def stsim_mel_global(ref_1T, est_1T, backend: str = "ssim") -> float:
+    """compute_stsim_mel_global (PLC/PLC1_low_mid_high_eval.py:264-288): the same score over the whole mel image."""
+    _backend(backend)
+    return float(_stsim_device(ref_1T, est_1T, None, backend).cpu()[0])
+
+
+@torch.no_grad()
+def mae_global(ref_1T, est_1T) -> float:
+    """mean |r - e| (PLC/PLC1_low_mid_high_eval.py:214-217)."""
+    r = ref_1T.reshape(-1).to(torch.float32); e = est_1T.reshape(-1).to(torch.float32)
+    return float((r - e).abs().mean().cpu())
+
+
+def _sanitize(x):
+    """sanitize_wave (PLC/PLC1_eval.py:94-96)."""
+    return torch.nan_to_num(x, nan=0.0, posinf=0.9999, neginf=-0.9999).clamp(-1.0, 1.0)
+
+
+def _row_from(stats, stsim, T, T_lat, peak, shift):
+    """The CSV row from the subset sums (ops.subset_stats) and the three ST-SIMs, on the host in float64."""
+    nan, eps = float("nan"), METRIC_EPS
+    pk = max(float(peak), eps)
+    db = lambda num, mse: 10.0 * math.log10(num / (mse + eps))
+    row = {"len_samples": int(T)}
+    d2_all = stats[3] + stats[7]
+    row["psnr_global_db"] = db(pk * pk, d2_all / T) if T else nan
+    row["stsim_global"] = stsim[0]
+    sides = {}
+    for name, (c, a, r2, d2) in (("masked", stats[0:4]), ("unmasked", stats[4:8])):
+        if c == 0 or T_lat == 0 or T == 0:
+            sides[name] = (nan, nan, nan)
+        else:
+            sides[name] = (db(pk * pk, d2 / c), db(r2 / c, d2 / c), a / c)
+    for name in ("masked", "unmasked"):
+        row[f"psnr_{name}_db"], row[f"snr_{name}_db"], row[f"mae_{name}"] = sides[name]
+    row["stsim_masked"], row["stsim_unmasked"] = stsim[1], stsim[2]
+    row = {k: row[k] for k in ROW_KEYS}
+    row["mae_global"] = (stats[1] + stats[5]) / T if T else nan
+    row["best_shift"] = int(shift)
+    return row
+
+
+@torch.no_grad()
+def evaluate_file(net, a_raw, asr, t_raw, tsr, peak, *, mask=None, mask_fn=None, max_shift: int = MAX_ALIGN_SHIFT,
+                  backend: str = "ssim") -> dict:
+    """One pass-1 iteration of PLC/PLC1_eval.py:eval_model (lines 601-663) for one file: a_raw [C, T_a] at ``asr``, t_raw
+    [C, T_t] at ``tsr`` (raw amplitude), ``peak`` the global tactile peak.  Scale, resample to 24 kHz, crop to L, sanitize,
+    ``net.forward_step`` (``mask`` / ``mask_fn`` as AllPredPLC takes them; default the reference's packet draw), de-normalise,
+    crop, align (+-max_shift), crop, global PSNR, the three mel ST-SIMs and the six masked figures.  Returns the
+    eval_metrics.csv keys after "stem" (ROW_KEYS) plus "mae_global" (PLC1_low_mid_high_eval.py's third figure) and
+    "best_shift".  Two device->host copies: the alignment shift and the final row."""
+    from .resample import resample_to
+    _backend(backend)
+    dev = next(net.predict.parameters()).device
+    a_raw = a_raw.to(device=dev, dtype=torch.float32)
+    t_raw = t_raw.to(device=dev, dtype=torch.float32)
+    scale = t_raw.abs().amax().clamp_min(1e-8)                          # max(float(|t|.max()), 1e-8), kept on the device
+    aw = resample_to(a_raw[:1], asr, TARGET_SR)                         # channels resample independently: [:1] first
+    tw = resample_to(t_raw[:1] / scale, tsr, TARGET_SR)
+    L = min(aw.shape[-1], tw.shape[-1])
+    a_1T = _sanitize(aw[..., :L]).unsqueeze(0)
+    t_1T = _sanitize(tw[..., :L]).unsqueeze(0)
+    out = net.forward_step(a_1T, t_1T, mask=mask, mask_fn=mask_fn)
+    ref = resample_to(t_raw[:1], tsr, TARGET_SR)
+    return metrics_stage(ref, out["y_hat"][0] * scale, out["latent_mask"][0, 0], peak, max_shift, backend)
+
+
+@torch.no_grad()
+def metrics_stage(ref, est, latent_mask, peak, max_shift: int = MAX_ALIGN_SHIFT, backend: str = "ssim") -> dict:
+    """The metric half of evaluate_file (PLC/PLC1_eval.py:628-663): ref [1, T_ref] and the de-normalised est [1, T_est] at
+    24 kHz on the device, latent_mask [T_lat] -> the row.  Crop, align, crop, then two launches of subset sums and the mel
+    front end + frame subsets + SSIM; two device->host copies (the shift and the row)."""
+    from .proposed import align_by_xcorr, crop_match
+    _backend(backend)
+    lm = latent_mask.reshape(-1)
+    ref_c, est_c = crop_match(ref, est)
+    ref_a, est_a, shift = align_by_xcorr(ref_c, est_c, max_shift)       # device->host copy 1: the shift
+    ref_a, est_a = crop_match(ref_a, est_a)
+    ref_a, est_a = ref_a.contiguous(), est_a.contiguous()
+    T = ref_a.shape[-1]
+    stats = ops.subset_stats(ref_a, est_a, lm)
+    stsim = _stsim_device(ref_a, est_a, lm, backend)
+    vals = torch.cat([stats, stsim]).cpu().tolist()                    # device->host copy 2: the row
+    return _row_from(vals[:8], vals[8:], T, lm.numel(), peak, shift)
+
+
+def make_category_token_loss_mask(category: str, batch_size: int, T_lat: int, tokens_per_sec: float, device) -> torch.Tensor:
+    """Burst loss of one fixed category (PLC/PLC1_low_mid_high_eval.py:372-418): bursts drawn with Python's ``random``
+    (seed it as the reference does), host logic.  -> bool [B, T_lat]."""
+    import random
+    if T_lat <= 0:
+        return torch.zeros(batch_size, 0, dtype=torch.bool, device=device)
+    if category not in CAT_BURST_MS:
+        raise ValueError(f"Unknown category: {category}")
+    min_ms, max_ms = CAT_BURST_MS[category]
+    nb_min, nb_max = CAT_N_BURSTS[category]
+    mask = torch.zeros(batch_size, T_lat, dtype=torch.bool)
+    for b in range(batch_size):
+        min_tok = max(1, int(round(min_ms * tokens_per_sec / 1000.0)))
+        max_tok = min(max(min_tok, int(round(max_ms * tokens_per_sec / 1000.0))), T_lat)
+        for _ in range(random.randint(nb_min, nb_max)):
+            L_b = random.randint(min_tok, max_tok)
+            if L_b >= T_lat:
+                mask[b, :] = True
+                break
+            s = random.randint(0, max(0, T_lat - L_b))
+            mask[b, s:s + L_b] = True
+    return mask.to(device)
+
+
+CAT_BURST_MS = {"low": (20.0, 120.0), "medium": (120.0, 320.0), "high": (320.0, 1000.0)}   # ...low_mid_high_eval.py:88-92
+CAT_N_BURSTS = {"low": (1, 2), "medium": (1, 3), "high": (1, 4)}                            # ...:95-99
+
+
+def category_mask_fn(category: str):
+    """mask_fn for AllPredPLC.forward_step / evaluate_file: the category model's mask with tokens_per_sec = T_lat (its
+    forward_step, ...low_mid_high_eval.py:460-471)."""
+    return lambda B, T_lat, device: make_category_token_loss_mask(category, B, T_lat, float(T_lat), device)

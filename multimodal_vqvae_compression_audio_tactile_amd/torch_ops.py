@@ -15,6 +15,7 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   decoder_fwd                 mvq_decoder_fwd_f32        T_DEC(z), ...5.py:322
   decoder_bwd_input           mvq_decoder_fwd_saving_f32 + mvq_decoder_bwd_input_f32: dL/dz of T_DEC, ...5.py:393
   attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
+  mel_ssim_f32                mvq_mel_ssim_f32           mel ST-SIM of column-listed image pairs (PLC/PLC1_eval.py:270-333)
 
 Weights are the PACKED images of ``ops.pack_conv1d`` / ``ops.pack_conv_transpose1d`` (made once per weight load).  Import this module
 to register (``import multimodal_vqvae_compression_audio_tactile_amd.torch_ops``); the package does not import it by itself.
@@ -136,7 +137,7 @@ def _(z, gy, stack):
 
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
-              "ema_update_f32", "attention_seq_f32")
+              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32")
 
 
 @torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
@@ -147,3 +148,14 @@ def attention_seq_f32(q: Tensor, k: Tensor, v: Tensor, heads: int) -> Tensor:
 @attention_seq_f32.register_fake
 def _(q, k, v, heads):
     return q.new_empty(q.shape)
+
+
+@torch.library.custom_op(f"{NS}::mel_ssim_f32", mutates_args=())
+def mel_ssim_f32(mel: Tensor, maxv: Tensor, desc: Tensor, widths: Tensor, cols: Optional[Tensor], max_width: int,
+                 mode: str) -> Tensor:
+    return ops.mel_ssim(mel, maxv, desc, widths, max_width, cols=cols, mode=mode)
+
+
+@mel_ssim_f32.register_fake
+def _(mel, maxv, desc, widths, cols, max_width, mode):
+    return mel.new_empty((widths.shape[0],), dtype=torch.float64)
