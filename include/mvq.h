@@ -521,7 +521,9 @@ int mvq_mul_dtanh_f32(const float* g, const float* y, float* out, size_t n, void
  * consumer needs), one fused launch per ResidualUnit of width 64 / 96 / 128, zero-padded rows where a length is not a multiple of
  * 4, and at throughput batch sizes the virtually packed (encoder tail) / packed (decoder head) latent-rate rows.  Intermediates
  * live in a caller-provided WORKSPACE (mvq_*_workspace_bytes, laid out by a deterministic first-fit arena); nothing is allocated
- * or synchronised, so a call can be captured into a hipGraph.  Results are bit-identical to the per-layer entry points above
+ * or synchronised, so a call can be captured into a hipGraph.  A call sizes its plan before it enqueues anything: a workspace
+ * smaller than the plan needs (at most the matching query) is refused with MVQ_EINVAL and nothing is launched -- also when the
+ * query was made before mvq_stack_set_plan changed the thresholds.  Results are bit-identical to the per-layer entry points above
  * (tests/test_gpu_stacks.py) and to oracle/c/oracle.c.
  *
  *   mvq_encoder_fwd_f32        x[batch, 1, t]            -> z[batch, d_latent, mvq_encoder_out_len(t)]

@@ -41,14 +41,13 @@ inline int conv_len(int tin, int ks, int stride, int dil, int pad)
 }
 
 // ---- workspace arena: first fit over a free list, deterministic for a given call sequence.  `base == nullptr`: planning run
-// (only the peak is wanted); otherwise the same sequence hands out real addresses.
+// (only the peak is wanted); otherwise the same sequence hands out real addresses, which plan_run has checked to fit.
 struct Arena {
     char* base = nullptr;
-    size_t cap = 0, peak = 0;
+    size_t peak = 0;
     std::vector<std::pair<size_t, size_t>> free_;          // (offset, bytes), sorted by offset, coalesced
     std::map<size_t, size_t> live;                         // offset -> bytes
     size_t top = 0;
-    bool overflow = false;
     float* alloc(size_t floats)
     {
         const size_t n = up(floats * sizeof(float) + 16);
@@ -68,7 +67,6 @@ struct Arena {
     }
     float* at(size_t off)
     {
-        if (base && off + live[off] > cap) overflow = true;
         return base ? reinterpret_cast<float*>(base + off) : reinterpret_cast<float*>(ALIGN + off);      // planning: fake, never dereferenced
     }
     void release(float* p)
@@ -291,16 +289,17 @@ int prepare_weights(mvq_stack& s, const float* const* params, void* blob, size_t
 }
 
 // ---- plan execution ------------------------------------------------------------------------------------------------------------
+// A plan function walks the plan once: it takes its buffers from `ar` and issues every launch through launch(), which runs the
+// callable only on a real walk and only while every earlier launch succeeded (the first failure is kept).  A dry walk hands out
+// the same offsets as the real one and launches nothing.
 struct Run {
     Arena ar;
     bool dry = true;
     void* stream = nullptr;
     int rc = MVQ_OK;
     bool ok() const { return rc == MVQ_OK; }
-    void call(int r) { if (rc == MVQ_OK && r != MVQ_OK) rc = r; }
+    template <class F> void launch(F f) { if (!dry && rc == MVQ_OK) rc = f(); }
 };
-
-struct Act { float* p = nullptr; int c = 0, rows = 0; };        // [B, c, rows] activation in the workspace
 
 // one ResidualUnit through mvq_residual_unit_padded_f32 (one fused launch for C in {64, 96, 128}; otherwise the two launches with
 // the intermediate in the arena)
@@ -309,9 +308,8 @@ void run_unit(Run& r, const Unit& u, int B, int C, int T, const float* x, const 
 {
     const size_t sc = mvq_residual_unit_scratch_floats(B, C, T, u.c7.dil);
     float* scratch = sc ? r.ar.alloc(sc) : nullptr;
-    if (!r.dry)
-        r.call(mvq_residual_unit_padded_f32(x, x_snaked, u.c7.wp, u.c7.bias, u.alpha_a, u.alpha_b, u.c1.wp, u.c1.bias, alpha_next, y, y2, alpha2,
-                                            scratch, B, C, T, u.c7.dil, tvalid, r.stream));
+    r.launch([&] { return mvq_residual_unit_padded_f32(x, x_snaked, u.c7.wp, u.c7.bias, u.alpha_a, u.alpha_b, u.c1.wp, u.c1.bias, alpha_next, y, y2,
+                                                       alpha2, scratch, B, C, T, u.c7.dil, tvalid, r.stream); });
     r.ar.release(scratch);
 }
 
@@ -363,9 +361,8 @@ void encoder_plan(Run& r, const mvq_stack& s, const float* x, float* z, int B, i
     const bool wide0 = s.blocks[0].width >= s.presnaked_min_c;
     float* h = r.ar.alloc((size_t)B * s.first.cout * t);
     float* hs = wide0 ? r.ar.alloc((size_t)B * s.first.cout * t) : nullptr;
-    if (!r.dry)
-        r.call(mvq_conv1d_padded_f32(x, s.first.wp, s.first.bias, nullptr, nullptr, nullptr, h, hs, hs ? s.blocks[0].ru[0].alpha_a : nullptr, B, 1, T,
-                                     s.first.cout, 7, 1, 1, 3, MVQ_ACT_NONE, 0, r.stream));
+    r.launch([&] { return mvq_conv1d_padded_f32(x, s.first.wp, s.first.bias, nullptr, nullptr, nullptr, h, hs, hs ? s.blocks[0].ru[0].alpha_a : nullptr,
+                                                B, 1, T, s.first.cout, 7, 1, 1, 3, MVQ_ACT_NONE, 0, r.stream); });
     for (int i = 0; i < nb && r.ok(); ++i) {
         const Block& b = s.blocks[i];
         const bool last = i == nb - 1;
@@ -379,32 +376,28 @@ void encoder_plan(Run& r, const mvq_stack& s, const float* x, float* z, int B, i
             // latent-rate layers on virtually packed rows: y[B, C, rows] carries vt valid columns + a zero tail; the k3 conv maps
             // rows -> rows (its padding is that zero tail); the tail is cut off by the final strided copy
             float* y = r.ar.alloc((size_t)B * d.cout * vrows);
-            if (!r.dry)
-                r.call(mvq_conv1d_vpacked_f32(h, d.wp, d.bias, nullptr, a_out, y, nullptr, nullptr, B, d.cin, t, t, d.cout, d.ks, d.stride, 1, d.pad,
-                                              MVQ_ACT_NONE, s.vpack_seg, d.stride * vrows, vrows, r.stream));
+            r.launch([&] { return mvq_conv1d_vpacked_f32(h, d.wp, d.bias, nullptr, a_out, y, nullptr, nullptr, B, d.cin, t, t, d.cout, d.ks, d.stride, 1,
+                                                         d.pad, MVQ_ACT_NONE, s.vpack_seg, d.stride * vrows, vrows, r.stream); });
             r.ar.release(h);
             float* y3 = r.ar.alloc((size_t)B * s.last.cout * vrows);
-            if (!r.dry) {
-                r.call(mvq_conv1d_vpacked_f32(y, s.last.wp, s.last.bias, nullptr, nullptr, y3, nullptr, nullptr, B, s.last.cin, vrows, vt, s.last.cout, 3, 1, 1,
-                                              1, MVQ_ACT_NONE, s.vpack_seg, vrows, vrows, r.stream));
-                r.call(mvq_copy3d_f32(y3, (size_t)s.last.cout * vrows, (size_t)vrows, z, (size_t)s.last.cout * vt, (size_t)vt, B, s.last.cout, vt, r.stream));
-            }
+            r.launch([&] { return mvq_conv1d_vpacked_f32(y, s.last.wp, s.last.bias, nullptr, nullptr, y3, nullptr, nullptr, B, s.last.cin, vrows, vt,
+                                                         s.last.cout, 3, 1, 1, 1, MVQ_ACT_NONE, s.vpack_seg, vrows, vrows, r.stream); });
+            r.launch([&] { return mvq_copy3d_f32(y3, (size_t)s.last.cout * vrows, (size_t)vrows, z, (size_t)s.last.cout * vt, (size_t)vt, B, s.last.cout, vt,
+                                                 r.stream); });
             r.ar.release(y); r.ar.release(y3);
             return;
         }
         const bool wide_next = !last && s.blocks[i + 1].width >= s.presnaked_min_c;
         float* y = r.ar.alloc((size_t)B * d.cout * tout);
         float* y2 = wide_next ? r.ar.alloc((size_t)B * d.cout * tout) : nullptr;
-        if (!r.dry)
-            r.call(mvq_conv1d_padded_f32(h, d.wp, d.bias, nullptr, nullptr, a_out, y, y2, y2 ? s.blocks[i + 1].ru[0].alpha_a : nullptr, B, d.cin, t, d.cout,
-                                         d.ks, d.stride, 1, d.pad, MVQ_ACT_NONE, 0, r.stream));
+        r.launch([&] { return mvq_conv1d_padded_f32(h, d.wp, d.bias, nullptr, nullptr, a_out, y, y2, y2 ? s.blocks[i + 1].ru[0].alpha_a : nullptr, B, d.cin,
+                                                    t, d.cout, d.ks, d.stride, 1, d.pad, MVQ_ACT_NONE, 0, r.stream); });
         r.ar.release(h);
         h = y; hs = y2; t = tout;
     }
     if (!r.ok()) return;
-    if (!r.dry)
-        r.call(mvq_conv1d_padded_f32(h, s.last.wp, s.last.bias, nullptr, nullptr, nullptr, z, nullptr, nullptr, B, s.last.cin, t, s.last.cout, 3, 1, 1, 1,
-                                     MVQ_ACT_NONE, 0, r.stream));
+    r.launch([&] { return mvq_conv1d_padded_f32(h, s.last.wp, s.last.bias, nullptr, nullptr, nullptr, z, nullptr, nullptr, B, s.last.cin, t, s.last.cout,
+                                                3, 1, 1, 1, MVQ_ACT_NONE, 0, r.stream); });
     r.ar.release(h);
 }
 
@@ -431,9 +424,8 @@ float* decoder_block(Run& r, const mvq_stack& s, const Block& b, int B, float* x
     const size_t n = (size_t)B * up_.cout * rows;
     float* h = r.ar.alloc(n);
     float* hs = wide ? r.ar.alloc(n) : nullptr;
-    if (!r.dry)
-        r.call(mvq_conv_transpose1d_op_f32(x, up_.wp, up_.bias, nullptr, nullptr, h, hs, hs ? b.ru[0].alpha_a : nullptr, B, up_.cin, rows_in, up_.cout,
-                                           up_.stride, up_.pad, up_.opad, arg_rows, tv, r.stream));
+    r.launch([&] { return mvq_conv_transpose1d_op_f32(x, up_.wp, up_.bias, nullptr, nullptr, h, hs, hs ? b.ru[0].alpha_a : nullptr, B, up_.cin, rows_in,
+                                                      up_.cout, up_.stride, up_.pad, up_.opad, arg_rows, tv, r.stream); });
     r.ar.release(x);
     *t_out = tn; *rows_out = rows;
     return run_units(r, s, b, B, rows, h, hs, alpha_after, tv);
@@ -446,6 +438,9 @@ bool decoder_use_packed(const mvq_stack& s, int B, int t)
            (up_.cout * up_.stride) % 128 == 0 && ((t - 1) * up_.stride - 2 * up_.pad + 2 * up_.stride) % 4 == 0;
 }
 
+int hip_rc(hipError_t e, const char* what) { return e == hipSuccess ? MVQ_OK : sfail(MVQ_EHIP, "%s failed", what); }
+hipStream_t hip_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
 // z[B, C, t] -> y[B, d_out, Tout]
 void decoder_plan(Run& r, const mvq_stack& s, const float* z, float* y_out, int B, int t)
 {
@@ -457,26 +452,22 @@ void decoder_plan(Run& r, const mvq_stack& s, const float* z, float* y_out, int 
         // PACKED latent-rate rows (include/mvq.h): model.0 and the first block's transposed conv on rows of pack_seg segments
         const int per = ceil4(t + 3), seg = s.pack_seg, G = (B + seg - 1) / seg, L = seg * per;
         float* zp = r.ar.alloc((size_t)G * c0.cin * L);
-        if (!r.dry) {
-            if (hipMemsetAsync(zp, 0, (size_t)G * c0.cin * L * 4, reinterpret_cast<hipStream_t>(r.stream)) != hipSuccess) r.call(sfail(MVQ_EHIP, "decoder_fwd: memset failed"));
-            for (int j = 0; j < seg && j < B; ++j)               // items j, j + seg, ... sit at column j * per of consecutive rows
-                r.call(mvq_copy3d_f32(z + (size_t)j * c0.cin * t, (size_t)seg * c0.cin * t, (size_t)t, zp + (size_t)j * per, (size_t)c0.cin * L, (size_t)L,
-                                      (B - j + seg - 1) / seg, c0.cin, t, r.stream));
-        }
+        r.launch([&] { return hip_rc(hipMemsetAsync(zp, 0, (size_t)G * c0.cin * L * 4, hip_stream(r.stream)), "decoder_fwd: memset"); });
+        for (int j = 0; j < seg && j < B; ++j)                   // items j, j + seg, ... sit at column j * per of consecutive rows
+            r.launch([&] { return mvq_copy3d_f32(z + (size_t)j * c0.cin * t, (size_t)seg * c0.cin * t, (size_t)t, zp + (size_t)j * per, (size_t)c0.cin * L,
+                                                 (size_t)L, (B - j + seg - 1) / seg, c0.cin, t, r.stream); });
         const Block& b0 = s.blocks[0];
         float* hp = r.ar.alloc((size_t)G * c0.cout * L);
-        if (!r.dry)
-            r.call(mvq_conv1d_packed_rows_f32(zp, c0.wp, c0.bias, nullptr, b0.alpha, hp, nullptr, nullptr, G, c0.cin, c0.cout, 7, 1, 3, MVQ_ACT_NONE, seg, per, t,
-                                              r.stream));
+        r.launch([&] { return mvq_conv1d_packed_rows_f32(zp, c0.wp, c0.bias, nullptr, b0.alpha, hp, nullptr, nullptr, G, c0.cin, c0.cout, 7, 1, 3,
+                                                         MVQ_ACT_NONE, seg, per, t, r.stream); });
         r.ar.release(zp);
         const Conv& up_ = b0.res;
         const int tout = (t - 1) * up_.stride - 2 * up_.pad + 2 * up_.stride;
         const bool wide = b0.width >= s.presnaked_min_c;
         float* u = r.ar.alloc((size_t)B * up_.cout * tout);
         float* us = wide ? r.ar.alloc((size_t)B * up_.cout * tout) : nullptr;
-        if (!r.dry)
-            r.call(mvq_conv_transpose1d_packed_rows_f32(hp, up_.wp, up_.bias, nullptr, nullptr, u, us, us ? b0.ru[0].alpha_a : nullptr, G, up_.cin, up_.cout,
-                                                        up_.stride, up_.pad, seg, per, t, B, r.stream));
+        r.launch([&] { return mvq_conv_transpose1d_packed_rows_f32(hp, up_.wp, up_.bias, nullptr, nullptr, u, us, us ? b0.ru[0].alpha_a : nullptr, G, up_.cin,
+                                                                   up_.cout, up_.stride, up_.pad, seg, per, t, B, r.stream); });
         r.ar.release(hp);
         const float* nxt = nb > 1 ? s.blocks[1].alpha : s.alpha_last;
         h = run_units(r, s, b0, B, tout, u, us, nxt, 0);
@@ -491,16 +482,13 @@ void decoder_plan(Run& r, const mvq_stack& s, const float* z, float* y_out, int 
         if (t % 4 && t > 0 && c0.cin % 32 == 0) {
             rows = ceil4(t);
             zp = r.ar.alloc((size_t)B * c0.cin * rows);
-            if (!r.dry) {
-                if (hipMemsetAsync(zp, 0, (size_t)B * c0.cin * rows * 4, reinterpret_cast<hipStream_t>(r.stream)) != hipSuccess) r.call(sfail(MVQ_EHIP, "decoder_fwd: memset failed"));
-                r.call(mvq_copy3d_f32(z, (size_t)c0.cin * t, (size_t)t, zp, (size_t)c0.cin * rows, (size_t)rows, B, c0.cin, t, r.stream));
-            }
+            r.launch([&] { return hip_rc(hipMemsetAsync(zp, 0, (size_t)B * c0.cin * rows * 4, hip_stream(r.stream)), "decoder_fwd: memset"); });
+            r.launch([&] { return mvq_copy3d_f32(z, (size_t)c0.cin * t, (size_t)t, zp, (size_t)c0.cin * rows, (size_t)rows, B, c0.cin, t, r.stream); });
             zin = zp; tvalid = t;
         }
         h = r.ar.alloc((size_t)B * c0.cout * rows);
-        if (!r.dry)
-            r.call(mvq_conv1d_padded_f32(zin, c0.wp, c0.bias, nullptr, nullptr, s.blocks[0].alpha, h, nullptr, nullptr, B, c0.cin, rows, c0.cout, 7, 1, 1, 3,
-                                         MVQ_ACT_NONE, tvalid, r.stream));
+        r.launch([&] { return mvq_conv1d_padded_f32(zin, c0.wp, c0.bias, nullptr, nullptr, s.blocks[0].alpha, h, nullptr, nullptr, B, c0.cin, rows, c0.cout,
+                                                    7, 1, 1, 3, MVQ_ACT_NONE, tvalid, r.stream); });
         r.ar.release(zp);
         tv = t;
     }
@@ -512,17 +500,12 @@ void decoder_plan(Run& r, const mvq_stack& s, const float* z, float* y_out, int 
     }
     if (!r.ok()) return;
     const Conv& cl = s.last;
-    if (rows == tv) {
-        if (!r.dry)
-            r.call(mvq_conv1d_padded_f32(h, cl.wp, cl.bias, nullptr, nullptr, nullptr, y_out, nullptr, nullptr, B, cl.cin, rows, cl.cout, 7, 1, 1, 3, MVQ_ACT_TANH, 0,
-                                         r.stream));
-    } else {
-        float* y = r.ar.alloc((size_t)B * cl.cout * rows);
-        if (!r.dry) {
-            r.call(mvq_conv1d_padded_f32(h, cl.wp, cl.bias, nullptr, nullptr, nullptr, y, nullptr, nullptr, B, cl.cin, rows, cl.cout, 7, 1, 1, 3, MVQ_ACT_TANH, 0,
-                                         r.stream));
-            r.call(mvq_copy3d_f32(y, (size_t)cl.cout * rows, (size_t)rows, y_out, (size_t)cl.cout * tv, (size_t)tv, B, cl.cout, tv, r.stream));
-        }
+    const bool padded = rows != tv;                                    // the last conv writes the padded rows, a copy cuts them off
+    float* y = padded ? r.ar.alloc((size_t)B * cl.cout * rows) : y_out;
+    r.launch([&] { return mvq_conv1d_padded_f32(h, cl.wp, cl.bias, nullptr, nullptr, nullptr, y, nullptr, nullptr, B, cl.cin, rows, cl.cout, 7, 1, 1, 3,
+                                                MVQ_ACT_TANH, 0, r.stream); });
+    if (padded) {
+        r.launch([&] { return mvq_copy3d_f32(y, (size_t)cl.cout * rows, (size_t)rows, y_out, (size_t)cl.cout * tv, (size_t)tv, B, cl.cout, tv, r.stream); });
         r.ar.release(y);
     }
     r.ar.release(h);
@@ -568,43 +551,37 @@ void decoder_saving_plan(Run& r, const mvq_stack& s, const float* z, float* y_ou
     const int nb = (int)s.blocks.size();
     // every producer emits (raw -> saved, Snake for its consumer -> workspace): no conv evaluates Snake while staging
     float* hs = r.ar.alloc((size_t)B * s.first.cout * t);
-    if (!r.dry)
-        r.call(mvq_conv1d_padded_f32(z, s.first.wp, s.first.bias, nullptr, nullptr, nullptr, S(L.blk[0].x_in), hs, s.blocks[0].alpha, B, s.first.cin, t, s.first.cout,
-                                     7, 1, 1, 3, MVQ_ACT_NONE, 0, r.stream));
+    r.launch([&] { return mvq_conv1d_padded_f32(z, s.first.wp, s.first.bias, nullptr, nullptr, nullptr, S(L.blk[0].x_in), hs, s.blocks[0].alpha, B,
+                                                s.first.cin, t, s.first.cout, 7, 1, 1, 3, MVQ_ACT_NONE, 0, r.stream); });
     for (int i = 0; i < nb && r.ok(); ++i) {
         const Block& b = s.blocks[i];
         const SavedLayout::Blk& k = L.blk[i];
         const size_t n = (size_t)B * k.c * k.t;
         float* us = r.ar.alloc(n);
-        if (!r.dry)
-            r.call(mvq_conv_transpose1d_op_f32(hs, b.res.wp, b.res.bias, nullptr, nullptr, S(k.r_x[0]), us, b.ru[0].alpha_a, B, b.res.cin, k.t_in, b.res.cout,
-                                               b.res.stride, b.res.pad, b.res.opad, 0, 0, r.stream));
+        r.launch([&] { return mvq_conv_transpose1d_op_f32(hs, b.res.wp, b.res.bias, nullptr, nullptr, S(k.r_x[0]), us, b.ru[0].alpha_a, B, b.res.cin, k.t_in,
+                                                          b.res.cout, b.res.stride, b.res.pad, b.res.opad, 0, 0, r.stream); });
         r.ar.release(hs);
         hs = us;
         for (int j = 0; j < 3; ++j) {
             const Unit& u = b.ru[j];
             float* t7s = r.ar.alloc(n);
-            if (!r.dry)
-                r.call(mvq_conv1d_padded_f32(hs, u.c7.wp, u.c7.bias, nullptr, nullptr, nullptr, S(k.t7[j]), t7s, u.alpha_b, B, k.c, k.t, k.c, 7, 1, u.c7.dil,
-                                             u.c7.pad, MVQ_ACT_NONE, 0, r.stream));
+            r.launch([&] { return mvq_conv1d_padded_f32(hs, u.c7.wp, u.c7.bias, nullptr, nullptr, nullptr, S(k.t7[j]), t7s, u.alpha_b, B, k.c, k.t, k.c, 7, 1,
+                                                        u.c7.dil, u.c7.pad, MVQ_ACT_NONE, 0, r.stream); });
             r.ar.release(hs);
             const float* nxt = j < 2 ? b.ru[j + 1].alpha_a : (i + 1 < nb ? s.blocks[i + 1].alpha : s.alpha_last);
             float* out = S(j < 2 ? k.r_x[j + 1] : (i + 1 < nb ? L.blk[i + 1].x_in : L.hl));
             float* outs = r.ar.alloc(n);
-            if (!r.dry)
-                r.call(mvq_conv1d_padded_f32(t7s, u.c1.wp, u.c1.bias, nullptr, S(k.r_x[j]), nullptr, out, outs, nxt, B, k.c, k.t, k.c, 1, 1, 1, 0, MVQ_ACT_NONE, 0,
-                                             r.stream));
+            r.launch([&] { return mvq_conv1d_padded_f32(t7s, u.c1.wp, u.c1.bias, nullptr, S(k.r_x[j]), nullptr, out, outs, nxt, B, k.c, k.t, k.c, 1, 1, 1, 0,
+                                                        MVQ_ACT_NONE, 0, r.stream); });
             r.ar.release(t7s);
             hs = outs;
         }
     }
     if (!r.ok()) return;
-    if (!r.dry) {
-        r.call(mvq_conv1d_padded_f32(hs, s.last.wp, s.last.bias, nullptr, nullptr, nullptr, S(L.y), nullptr, nullptr, B, s.last.cin, L.t_out, s.last.cout, 7, 1, 1, 3,
-                                     MVQ_ACT_TANH, 0, r.stream));
-        if (hipMemcpyAsync(y_out, S(L.y), (size_t)B * s.last.cout * L.t_out * 4, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(r.stream)) != hipSuccess)
-            r.call(sfail(MVQ_EHIP, "decoder_fwd_saving: copy of y failed"));
-    }
+    r.launch([&] { return mvq_conv1d_padded_f32(hs, s.last.wp, s.last.bias, nullptr, nullptr, nullptr, S(L.y), nullptr, nullptr, B, s.last.cin, L.t_out,
+                                                s.last.cout, 7, 1, 1, 3, MVQ_ACT_TANH, 0, r.stream); });
+    r.launch([&] { return hip_rc(hipMemcpyAsync(y_out, S(L.y), (size_t)B * s.last.cout * L.t_out * 4, hipMemcpyDeviceToDevice, hip_stream(r.stream)),
+                                 "decoder_fwd_saving: copy of y"); });
     r.ar.release(hs);
 }
 
@@ -616,11 +593,11 @@ void decoder_bwd_plan(Run& r, const mvq_stack& s, const char* saved, const float
     const Conv& cl = s.last;
     const size_t ny = (size_t)B * cl.cout * L.t_out;
     float* g = r.ar.alloc(ny);
-    if (!r.dry) r.call(mvq_mul_dtanh_f32(gy, S(L.y), g, ny, r.stream));
+    r.launch([&] { return mvq_mul_dtanh_f32(gy, S(L.y), g, ny, r.stream); });
     {
         float* g2 = r.ar.alloc((size_t)B * cl.cin * L.t_out);
-        if (!r.dry)
-            r.call(mvq_conv1d_dgrad_f32(g, cl.wd, S(L.hl), s.alpha_last, nullptr, g2, B, cl.cin, L.t_out, cl.cout, L.t_out, 7, 1, 1, 3, r.stream));
+        r.launch([&] { return mvq_conv1d_dgrad_f32(g, cl.wd, S(L.hl), s.alpha_last, nullptr, g2, B, cl.cin, L.t_out, cl.cout, L.t_out, 7, 1, 1, 3,
+                                                   r.stream); });
         r.ar.release(g);
         g = g2;
     }
@@ -631,46 +608,41 @@ void decoder_bwd_plan(Run& r, const mvq_stack& s, const char* saved, const float
         for (int j = 2; j >= 0; --j) {
             const Unit& u = b.ru[j];
             float* g1 = r.ar.alloc(n);
-            if (!r.dry)
-                r.call(mvq_conv1d_dgrad_f32(g, u.c1.wd, S(k.t7[j]), u.alpha_b, nullptr, g1, B, k.c, k.t, k.c, k.t, 1, 1, 1, 0, r.stream));
+            r.launch([&] { return mvq_conv1d_dgrad_f32(g, u.c1.wd, S(k.t7[j]), u.alpha_b, nullptr, g1, B, k.c, k.t, k.c, k.t, 1, 1, 1, 0, r.stream); });
             float* g2 = r.ar.alloc(n);
-            if (!r.dry)
-                r.call(mvq_conv1d_dgrad_f32(g1, u.c7.wd, S(k.r_x[j]), u.alpha_a, g, g2, B, k.c, k.t, k.c, k.t, 7, 1, u.c7.dil, u.c7.pad, r.stream));
+            r.launch([&] { return mvq_conv1d_dgrad_f32(g1, u.c7.wd, S(k.r_x[j]), u.alpha_a, g, g2, B, k.c, k.t, k.c, k.t, 7, 1, u.c7.dil, u.c7.pad,
+                                                       r.stream); });
             r.ar.release(g1); r.ar.release(g);
             g = g2;
         }
         float* gx = r.ar.alloc((size_t)B * k.cin * k.t_in);
-        if (!r.dry)
-            r.call(mvq_conv1d_dgrad_f32(g, b.res.wd, S(k.x_in), b.alpha, nullptr, gx, B, k.cin, k.t_in, b.res.cout, k.t, b.res.ks, b.res.stride, 1, b.res.pad,
-                                        r.stream));
+        r.launch([&] { return mvq_conv1d_dgrad_f32(g, b.res.wd, S(k.x_in), b.alpha, nullptr, gx, B, k.cin, k.t_in, b.res.cout, k.t, b.res.ks, b.res.stride, 1,
+                                                   b.res.pad, r.stream); });
         r.ar.release(g);
         g = gx;
     }
     if (!r.ok()) return;
-    if (!r.dry)
-        r.call(mvq_conv1d_dgrad_f32(g, s.first.wd, nullptr, nullptr, nullptr, gz, B, s.first.cin, t, s.first.cout, t, 7, 1, 1, 3, r.stream));
+    r.launch([&] { return mvq_conv1d_dgrad_f32(g, s.first.wd, nullptr, nullptr, nullptr, gz, B, s.first.cin, t, s.first.cout, t, 7, 1, 1, 3, r.stream); });
     r.ar.release(g);
 }
 
+// workspace bytes of one plan: its peak plus the slack for aligning the caller's pointer
 template <class F> size_t plan_peak(F f)
 {
     Run r;
-    r.dry = true;
     f(r);
     return r.ar.peak + ALIGN;
 }
+// the plan is sized by a dry walk first: a short workspace is refused before anything is enqueued
 template <class F> int plan_run(void* ws, size_t ws_bytes, void* stream, const char* what, F f)
 {
+    const size_t need = plan_peak(f);
+    if (ws_bytes < need) return sfail(MVQ_EINVAL, "%s: workspace too small (see the matching *_workspace_bytes query)", what);
     Run r;
     r.dry = false;
     r.stream = stream;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(ws);
-    const size_t shift = (ALIGN - a % ALIGN) % ALIGN;
-    if (ws_bytes < shift) return sfail(MVQ_EINVAL, "%s: workspace too small", what);
-    r.ar.base = reinterpret_cast<char*>(ws) + shift;
-    r.ar.cap = ws_bytes - shift;
+    r.ar.base = reinterpret_cast<char*>(ws) + (ALIGN - reinterpret_cast<uintptr_t>(ws) % ALIGN) % ALIGN;
     f(r);
-    if (r.ar.overflow) return sfail(MVQ_EINVAL, "%s: workspace too small (see the matching *_workspace_bytes query)", what);
     return r.rc;
 }
 
@@ -745,7 +717,7 @@ int mvq_encoder_fwd_f32(const mvq_stack* s, const float* x, float* z, void* work
     if (enc_wants_vpack(*s, batch)) {
         const int rc = plan_run(workspace, workspace_bytes, stream, "encoder_fwd", [&](Run& r) { encoder_plan(r, *s, x, z, batch, t, true); });
         if (rc != MVQ_EUNSUPPORTED) return rc;         // no LDS-DMA form for this shape / MVQ_NO_DMA: the plain plan (same results)
-        }
+    }
     return plan_run(workspace, workspace_bytes, stream, "encoder_fwd", [&](Run& r) { encoder_plan(r, *s, x, z, batch, t, false); });
 }
 

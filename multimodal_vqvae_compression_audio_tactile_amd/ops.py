@@ -1045,6 +1045,7 @@ class Stack:
     def __init__(self, kind, desc, handle, blob=None):
         import weakref
         self.kind, self.desc, self.handle, self.blob = kind, desc, handle, blob
+        self._ws_bytes = {}          # (batch, t) -> mvq_*_workspace_bytes: the query walks the plan, so it runs once per shape
         self.id = id(self)
         Stack._BY_ID[self.id] = weakref.ref(self)
 
@@ -1128,15 +1129,19 @@ class Stack:
 
     def set_plan(self, vpack_min_batch=0, pack_min_batch=0):
         check(_lib.lib().mvq_stack_set_plan(self.handle, int(vpack_min_batch), int(pack_min_batch)), "mvq_stack_set_plan")
+        self._ws_bytes.clear()                                   # the thresholds change the plans, hence their workspace
 
     def out_len(self, t):
         L = _lib.lib()
         return int(L.mvq_encoder_out_len(self.handle, int(t)) if self.kind == "encoder" else L.mvq_decoder_out_len(self.handle, int(t)))
 
     def _ws(self, x, B, t):
-        L = _lib.lib()
-        n = L.mvq_encoder_workspace_bytes(self.handle, B, t) if self.kind == "encoder" else L.mvq_decoder_workspace_bytes(self.handle, B, t)
-        return torch.empty(max(int(n), 256), device=x.device, dtype=torch.uint8)
+        n = self._ws_bytes.get((B, t))
+        if n is None:
+            L = _lib.lib()
+            query = L.mvq_encoder_workspace_bytes if self.kind == "encoder" else L.mvq_decoder_workspace_bytes
+            n = self._ws_bytes[(B, t)] = max(int(query(self.handle, B, t)), 256)
+        return torch.empty(n, device=x.device, dtype=torch.uint8)
 
     def encoder_fwd(self, x):
         """x[B, 1, T] -> z[B, d_latent, Tl]: mvq_encoder_fwd_f32."""

@@ -309,6 +309,32 @@ def test_stack_handles_name_the_upstream_state_dict():
         ops.Stack.encoder(64, (), 1024)
 
 
+
+def test_stack_workspace_queries_are_fixed_per_shape():
+    """mvq_*_workspace_bytes is a deterministic dry walk of the plan: the same bytes on every query and from every handle of the
+    same description, pinned here per (batch, t); ops.Stack asks once per shape and forgets the answer in set_plan."""
+    from multimodal_vqvae_compression_audio_tactile_amd import _lib, dac, ops
+    L = _lib.lib()
+    enc_t, dec_t = (100, 320 * 18, 24000), (1, 18, 75)
+    want_enc = {1: [103680, 5899520, 24577280], 6: [615680, 35390720, 147457280], 31: [3175680, 182846720, 761857280],
+                32: [3278080, 188744960, 786433280], 48: [4916480, 283116800, 1179649280], 256: [26215680, 1509950720, 6291457280]}
+    want_dec = {1: [665600, 12151552, 50674432], 6: [3983360, 72900352, 304037632], 31: [20572160, 376644352, 1570853632],
+                32: [21235712, 388794112, 1621526272], 48: [31852544, 583190272, 2432288512], 256: [169871360, 3110340352, 12972197632]}
+    for _ in range(2):
+        enc, dec = ops.Stack.encoder(64, dac.ENC_RATES, 1024), ops.Stack.decoder(1024, 1536, dac.DEC_RATES)
+        for B in want_enc:
+            for _ in range(2):
+                assert [L.mvq_encoder_workspace_bytes(enc.handle, B, t) for t in enc_t] == want_enc[B], B
+                assert [L.mvq_decoder_workspace_bytes(dec.handle, B, t) for t in dec_t] == want_dec[B], B
+    # the Python side: one query per shape, cleared when the thresholds change
+    ws = enc._ws(torch.empty(0), 1, 100)
+    assert ws.numel() == 103680 and enc._ws_bytes == {(1, 100): 103680}
+    enc.set_plan(vpack_min_batch=1)
+    assert enc._ws_bytes == {}
+    # the shape tests/test_gpu_stacks.py pins: switching the packed decoder head on at B = 1 raises the decoder's workspace
+    dec.set_plan(vpack_min_batch=1, pack_min_batch=1)
+    assert L.mvq_decoder_workspace_bytes(dec.handle, 1, 18) == 12154880 > want_dec[1][1]
+
 def test_opt_in_mode_entry_points_validate_their_arguments():
     """The bf16x6 / f16x3 entry points (include/mvq.h) refuse bad shapes before any device access, accept empty batches, and size
     their images as documented."""

@@ -112,3 +112,96 @@ def test_encoder_stack_falls_back_without_the_dma_form(dev):
     x = torch.randn(40, 1, 640, device=dev)
     z = enc(x)
     assert z.shape == (40, 64, 80) and torch.equal(z, enc.forward_plan(x))
+
+
+SENTINEL = 0xA5                                                      # workspace bytes; outputs are pre-filled with OUT_SENTINEL
+OUT_SENTINEL = -1234.5
+
+
+def _refused(call, nbytes, room, outs):
+    """`call(ws_ptr, ws_bytes)` with `nbytes` cut from a sentinel-filled buffer of `room` bytes must be refused with MVQ_EINVAL
+    before anything is enqueued: no conv / residual-unit launch, the whole buffer and every output untouched."""
+    from multimodal_vqvae_compression_audio_tactile_amd import _lib, ops
+    L = _lib.lib()
+    big = torch.full((room,), SENTINEL, dtype=torch.uint8, device=outs[0].device)
+    before = [o.clone() for o in outs]
+    ops.profile_begin()
+    rc = call(big.data_ptr(), nbytes)
+    launched = ops.profile_end()
+    assert rc == -1 and b"workspace" in L.mvq_last_error(), (rc, L.mvq_last_error())
+    assert launched == {}, launched
+    assert bool((big == SENTINEL).all())
+    for o, b in zip(outs, before):
+        assert torch.equal(o, b)
+    return big
+
+
+@pytest.mark.parametrize("B", [1, 48])
+def test_short_workspace_is_refused_before_any_launch(B, dev):
+    """A workspace smaller than the plan needs is refused with MVQ_EINVAL and nothing launched, at the latency tiles (B = 1) and
+    with the packed / virtually packed latent-rate rows (B = 48); the query's size runs and equals the module path.  The encoder's
+    and the inference decoder's plans are the queries' largest, so one ALIGN (256 bytes) less is short; the decoder query also
+    covers the saving forward and the backward, whose plans need about half of it, so those two get a quarter."""
+    from multimodal_vqvae_compression_audio_tactile_amd import _lib, synth
+    from multimodal_vqvae_compression_audio_tactile_amd.ops import _stream
+    L = _lib.lib()
+    mdl, _ = _models(dev)
+    for p in mdl.decoder.parameters():
+        p.requires_grad_(False)
+    enc, dec = mdl.encoder.stack(), mdl.decoder.stack()
+    x = synth.tactile_segments(B, seed=3).to(dev)
+    T = x.shape[-1]
+    z_ref = mdl.encoder(x)
+    t = z_ref.shape[-1]
+    q = L.mvq_encoder_workspace_bytes(enc.handle, B, T)
+    z = torch.full_like(z_ref, OUT_SENTINEL)
+    enc_call = lambda ws, n: L.mvq_encoder_fwd_f32(enc.handle, x.data_ptr(), z.data_ptr(), ws, n, B, T, _stream())
+    big = _refused(enc_call, q - 256, q, [z])
+    assert enc_call(big.data_ptr(), q) == 0 and torch.equal(z, z_ref)
+
+    y_ref = mdl.decoder(z_ref)
+    zz = z_ref.clone().requires_grad_(True)
+    gy = torch.randn(y_ref.shape, generator=torch.Generator().manual_seed(B)).to(dev)
+    mdl.decoder(zz).backward(gy)
+    q = L.mvq_decoder_workspace_bytes(dec.handle, B, t)
+    y = torch.full_like(y_ref, OUT_SENTINEL)
+    dec_call = lambda ws, n: L.mvq_decoder_fwd_f32(dec.handle, z_ref.data_ptr(), y.data_ptr(), ws, n, B, t, _stream())
+    big = _refused(dec_call, q - 256, q, [y])
+    assert dec_call(big.data_ptr(), q) == 0 and torch.equal(y, y_ref)
+
+    ns = L.mvq_decoder_saved_bytes(dec.handle, B, t)
+    saved = torch.full((ns,), SENTINEL, dtype=torch.uint8, device=dev)
+    y = torch.full_like(y_ref, OUT_SENTINEL)
+    sav_call = lambda ws, n: L.mvq_decoder_fwd_saving_f32(dec.handle, z_ref.data_ptr(), y.data_ptr(), saved.data_ptr(), ns, ws, n, B, t, _stream())
+    big = _refused(sav_call, q // 4, q, [y, saved])
+    assert sav_call(big.data_ptr(), q) == 0 and torch.equal(y, y_ref)
+    gz = torch.full_like(z_ref, OUT_SENTINEL)
+    bwd_call = lambda ws, n: L.mvq_decoder_bwd_input_f32(dec.handle, saved.data_ptr(), ns, gy.data_ptr(), gz.data_ptr(), ws, n, B, t, _stream())
+    big = _refused(bwd_call, q // 4, q, [gz, saved])
+    assert bwd_call(big.data_ptr(), q) == 0 and torch.equal(gz, zz.grad)
+
+
+def test_workspace_queried_before_set_plan_is_not_trusted(dev):
+    """mvq_stack_set_plan(1, 1) switches the packed decoder head on at B = 1, t = 18 and so raises the workspace it needs
+    (pinned in tests/test_abi_and_host.py).  A buffer sized before the switch is refused with nothing launched; ops.Stack forgets
+    its cached size in set_plan, so the module path then runs and equals the Python plan under the same threshold."""
+    from multimodal_vqvae_compression_audio_tactile_amd import _lib
+    from multimodal_vqvae_compression_audio_tactile_amd.ops import _stream
+    L = _lib.lib()
+    mdl, _ = _models(dev)
+    dec = mdl.decoder
+    st = dec.stack()
+    B, t = 1, 18
+    z = torch.randn(B, 1024, t, generator=torch.Generator().manual_seed(18)).to(dev)
+    st.decoder_fwd(z)                                                # caches the size of the default plan
+    q_old = L.mvq_decoder_workspace_bytes(st.handle, B, t)
+    assert st._ws_bytes[(B, t)] == q_old
+    st.set_plan(vpack_min_batch=1, pack_min_batch=1)
+    assert L.mvq_decoder_workspace_bytes(st.handle, B, t) > q_old
+    y = torch.full((B, 1, st.out_len(t)), OUT_SENTINEL, device=dev)
+    call = lambda ws, n: L.mvq_decoder_fwd_f32(st.handle, z.data_ptr(), y.data_ptr(), ws, n, B, t, _stream())
+    _refused(call, q_old, q_old, [y])
+    y = st.decoder_fwd(z)
+    dec.PACK_MIN_BATCH = 1                                           # the Python plan under the same threshold
+    assert dec._use_packed_latents(z)
+    assert torch.equal(y, dec.forward_plan(z))
