@@ -199,6 +199,21 @@ int mvq_dac_rvq_prepared_f32(const float* z, const float* in_w, const float* in_
                              const int32_t* nq_item, int batch, int c, int t, int nq_use, int k, int dc, void* stream);
 
 
+/* The receiver's look-ups (what the transmitted indices decode to; the straight-through forms of the two quantisers above cannot
+ * be reproduced without the encoder-side residual).  Every index read is clamped to [0, K), so a corrupt index cannot read out
+ * of bounds; indices are int64 as the Python side holds them.
+ * ResidualVQEMA dequantise: idx[nb_use, B*T] (token b*T+t), books[>=nb_use, K, D] (16-byte aligned, D % 4 == 0):
+ *   q(b,d,t) = ((+0 + e_0[idx_0][d]) + e_1[idx_1][d]) + ...  in book order (nb_use = 0 writes zeros),
+ *   stored at b*out_sb + d*out_sd + t: [B,D,T] is (D*T, T) (0,0 = that), the token-folded [D, B*T] is (T, B*T). */
+int mvq_rvq_dequant_f32(const int64_t* idx, const float* books, float* q_out, int batch, int dim, int t, int nb_use, int k,
+                        size_t out_sb, size_t out_sd, void* stream);
+/* dac ResidualVectorQuantize.from_codes: codes[B,nq_use,T]; codebook[>=nq_use,K,Dc], out_w[.,C,Dc], out_b[.,C] as in
+ * mvq_dac_rvq_f32 (codebook and out_w 16-byte aligned).  p_i = codebook_i[code_i] (the raw row); zq_i(c) = fma chain over the
+ * Dc code dims ascending from +0, then + out_b; zq = ((0 + zq_0) + zq_1) + ... in stage order -> zq[B,C,T];
+ * z_p[B,nq_use*Dc,T] = the raw rows (NULL = not written).  C % 64 == 0, nq_use <= 32, Dc = 8. */
+int mvq_dac_rvq_from_codes_f32(const int64_t* codes, const float* codebook, const float* out_w, const float* out_b, float* zq,
+                               float* z_p, int batch, int c, int t, int nq_use, int k, int dc, void* stream);
+
 /* ---- predictor / glue primitives (CrossPredictor, TokenNorm, PosEnc1D) --------------------------- */
 
 /* y = post_scale * tanh?( LayerNorm_C(x + pe?) ), normalising over the channel axis (eps, biased variance).

@@ -691,6 +691,33 @@ int mvq_dac_rvq_items_f32(const float* z, const float* in_w, const float* in_b, 
                                     batch, c, t, nq_use, k, dc, stream);
 }
 
+int mvq_rvq_dequant_f32(const int64_t* idx, const float* books, float* q_out, int batch, int dim, int t, int nb_use, int k,
+                        size_t out_sb, size_t out_sd, void* stream)
+{
+    if (batch < 0 || t < 0 || dim <= 0 || dim % 4 != 0 || nb_use < 0 || k <= 0)
+        return fail(MVQ_EINVAL, "rvq_dequant: bad shape B=%d D=%d T=%d nb=%d K=%d", batch, dim, t, nb_use, k);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!q_out || (nb_use > 0 && (!idx || !books))) return fail(MVQ_EINVAL, "rvq_dequant: null tensor");
+    if (reinterpret_cast<uintptr_t>(books) & 15) return fail(MVQ_EINVAL, "rvq_dequant: books must be 16-byte aligned");
+    if (out_sb == 0 && out_sd == 0) { out_sb = (size_t)dim * t; out_sd = (size_t)t; }
+    hipError_t e = mvq::launch_rvq_dequant(idx, books, q_out, batch, dim, t, nb_use, k, out_sb, out_sd, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "rvq_dequant");
+}
+
+int mvq_dac_rvq_from_codes_f32(const int64_t* codes, const float* codebook, const float* out_w, const float* out_b, float* zq,
+                               float* z_p, int batch, int c, int t, int nq_use, int k, int dc, void* stream)
+{
+    if (batch < 0 || t < 0 || c <= 0 || c % 64 != 0 || nq_use <= 0 || nq_use > 32 || k <= 0 || dc != 8)
+        return fail(MVQ_EINVAL, "dac_rvq_from_codes: bad shape B=%d C=%d T=%d nq=%d K=%d Dc=%d (C %% 64 == 0, nq <= 32, Dc = 8)",
+                    batch, c, t, nq_use, k, dc);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!codes || !codebook || !out_w || !out_b || !zq) return fail(MVQ_EINVAL, "dac_rvq_from_codes: null tensor");
+    if ((reinterpret_cast<uintptr_t>(codebook) | reinterpret_cast<uintptr_t>(out_w)) & 15)
+        return fail(MVQ_EINVAL, "dac_rvq_from_codes: codebook and out_w must be 16-byte aligned");
+    hipError_t e = mvq::launch_dac_rvq_from_codes(codes, codebook, out_w, out_b, zq, z_p, batch, c, t, nq_use, k, dc, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "dac_rvq_from_codes");
+}
+
 int mvq_dac_rvq_prepare_f32(const float* codebook, float* cb_normalised, float* cb_norm2, int nq, int k, int dc, void* stream)
 {
     if (nq < 0 || k <= 0 || dc <= 0) return fail(MVQ_EINVAL, "dac_rvq_prepare: bad shape");

@@ -116,4 +116,8 @@ hipError_t launch_dac_rvq(const float* z, const float* in_w, const float* in_b, 
                           int B, int C, int T, int nq, int K, int Dc, hipStream_t s,
                           const float* cbn_pre = nullptr, const float* cn2_pre = nullptr);
 hipError_t launch_dac_rvq_prepare(const float* cb, float* cbn, float* cn2, int nq, int K, int Dc, hipStream_t s);
+hipError_t launch_rvq_dequant(const int64_t* idx, const float* books, float* q, int B, int D, int T, int nb, int K,
+                              size_t out_sb, size_t out_sd, hipStream_t s);
+hipError_t launch_dac_rvq_from_codes(const int64_t* codes, const float* cb, const float* out_w, const float* out_b, float* zq,
+                                     float* z_p, int B, int C, int T, int nq, int K, int Dc, hipStream_t s);
 }  // namespace mvq

@@ -9,6 +9,8 @@
 //  (3) dac_rvq: the 32-stage DAC residual quantiser (K = 1024, Dc = 8) fused into ONE launch: in_proj, L2
 //      normalisation, cosine search against the LDS-resident normalised codebook, straight-through out_proj
 //      and residual update, all stages for a block's 16 tokens with the residual held in registers.
+//  (4) the receiver's two table look-ups: rvq_dequant (ResidualVQEMA indices -> the summed code vectors) and
+//      dac_rvq_from_codes (upstream ResidualVectorQuantize.from_codes).  Every index is clamped to [0, K) on read.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
@@ -1218,6 +1220,120 @@ hipError_t launch_dac_rvq(const float* z, const float* in_w, const float* in_b, 
         case 256:  return launch_dac_rvq_t<16, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
     }
     return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Receiver look-ups (include/mvq.h: mvq_rvq_dequant_f32, mvq_dac_rvq_from_codes_f32).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int clamp_code(int64_t v, int K)
+{
+    return v < 0 ? 0 : (v >= K ? K - 1 : (int)v);
+}
+
+// One thread per (token, 4-dim piece): q = ((+0 + e_0[idx_0]) + e_1[idx_1]) + ... in book order, one 16-byte load of each
+// book row piece.  Tokens run fastest across the lanes, so the index reads and the four output rows are coalesced.
+__global__ __launch_bounds__(256) void rvq_dequant_kernel(const int64_t* __restrict__ idx, const float* __restrict__ books,
+                                                          float* __restrict__ q, int B, int D, int T, int nb, int K,
+                                                          size_t out_sb, size_t out_sd)
+{
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    const size_t N = (size_t)B * T;
+    const size_t total = N * (size_t)(D >> 2);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t n = i % N;
+        const int j = (int)(i / N);
+        v4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int bk = 0; bk < nb; ++bk) {
+            const int id = clamp_code(idx[(size_t)bk * N + n], K);
+            const v4 e = *reinterpret_cast<const v4*>(books + ((size_t)bk * K + id) * D + 4 * j);
+            acc = acc + e;
+        }
+        const int b = (int)(n / T), t = (int)(n % T);
+        float* o = q + (size_t)b * out_sb + (size_t)(4 * j) * out_sd + t;
+        o[0] = acc.x;
+        o[out_sd] = acc.y;
+        o[2 * out_sd] = acc.z;
+        o[3 * out_sd] = acc.w;
+    }
+}
+
+hipError_t launch_rvq_dequant(const int64_t* idx, const float* books, float* q, int B, int D, int T, int nb, int K,
+                              size_t out_sb, size_t out_sd, hipStream_t s)
+{
+    const size_t total = (size_t)B * T * (D / 4);
+    if (total == 0) return hipSuccess;
+    size_t blocks = (total + 255) / 256; if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(rvq_dequant_kernel, dim3((unsigned)blocks), dim3(256), 0, s, idx, books, q, B, D, T, nb, K, out_sb, out_sd);
+    return hipGetLastError();
+}
+
+// from_codes: a block owns FC_TOK tokens x FC_CH channels (16 x 64).  The raw codebook rows of its tokens for every stage
+// ([nq][FC_TOK][8], 16 KiB at 32 stages) are gathered into LDS once; then lane (token, channel group) runs the stages in order
+// for its four channels: zq_i = fma chain over the 8 code dims from +0, + out_b; z_q = ((0 + zq_0) + zq_1) + ...
+// Blocks of the first channel tile also write z_p (the raw rows, [B, nq*8, T]).
+constexpr int FC_TOK = 16, FC_CH = 64, FC_DC = 8, FC_MAX_NQ = 32;
+
+__global__ __launch_bounds__(256) void dac_rvq_from_codes_kernel(
+    const int64_t* __restrict__ codes, const float* __restrict__ cb, const float* __restrict__ out_w,
+    const float* __restrict__ out_b, float* __restrict__ zq, float* __restrict__ z_p, int B, int C, int T, int nq, int K)
+{
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) float p_s[FC_MAX_NQ][FC_TOK][FC_DC];
+    const int tid = threadIdx.x;
+    const size_t N = (size_t)B * T;
+    const size_t n0 = (size_t)blockIdx.x * FC_TOK;
+    const bool write_zp = z_p != nullptr && blockIdx.y == 0;
+    for (int e = tid; e < nq * FC_TOK * 2; e += 256) {                   // (stage, token, half row)
+        const int h = e & 1, tk = (e >> 1) % FC_TOK, st = e / (2 * FC_TOK);
+        const size_t n = n0 + tk;
+        v4 r = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (n < N) {
+            const int b = (int)(n / T), t = (int)(n % T);
+            const int id = clamp_code(codes[((size_t)b * nq + st) * T + t], K);
+            r = *reinterpret_cast<const v4*>(cb + ((size_t)st * K + id) * FC_DC + 4 * h);
+            if (write_zp) {
+                float* o = z_p + ((size_t)b * nq * FC_DC + (size_t)st * FC_DC + 4 * h) * T + t;
+                o[0] = r.x; o[(size_t)T] = r.y; o[2 * (size_t)T] = r.z; o[3 * (size_t)T] = r.w;
+            }
+        }
+        *reinterpret_cast<v4*>(&p_s[st][tk][4 * h]) = r;
+    }
+    __syncthreads();
+    const int tk = tid % FC_TOK, cg = tid / FC_TOK;                       // 16 channel groups of 4 channels (stride 16)
+    const size_t n = n0 + tk;
+    if (n >= N) return;
+    const int b = (int)(n / T), t = (int)(n % T);
+    const int c0 = blockIdx.y * FC_CH + cg;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int st = 0; st < nq; ++st) {
+        const v4 pa = *reinterpret_cast<const v4*>(&p_s[st][tk][0]);
+        const v4 pb = *reinterpret_cast<const v4*>(&p_s[st][tk][4]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + 16 * u;
+            const float* wr = out_w + ((size_t)st * C + c) * FC_DC;
+            const v4 wa = *reinterpret_cast<const v4*>(wr);
+            const v4 wb = *reinterpret_cast<const v4*>(wr + 4);
+            float a = 0.0f;
+            a = dfma(wa.x, pa.x, a); a = dfma(wa.y, pa.y, a); a = dfma(wa.z, pa.z, a); a = dfma(wa.w, pa.w, a);
+            a = dfma(wb.x, pb.x, a); a = dfma(wb.y, pb.y, a); a = dfma(wb.z, pb.z, a); a = dfma(wb.w, pb.w, a);
+            const float zqi = a + out_b[(size_t)st * C + c];
+            acc[u] = acc[u] + zqi;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) zq[((size_t)b * C + c0 + 16 * u) * T + t] = acc[u];
+}
+
+hipError_t launch_dac_rvq_from_codes(const int64_t* codes, const float* cb, const float* out_w, const float* out_b, float* zq,
+                                     float* z_p, int B, int C, int T, int nq, int K, int Dc, hipStream_t s)
+{
+    const size_t N = (size_t)B * T;
+    if (N == 0) return hipSuccess;
+    if (Dc != FC_DC || C % FC_CH || nq <= 0 || nq > FC_MAX_NQ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dac_rvq_from_codes_kernel, dim3((unsigned)((N + FC_TOK - 1) / FC_TOK), (unsigned)(C / FC_CH)), dim3(256), 0, s,
+                       codes, cb, out_w, out_b, zq, z_p, B, C, T, nq, K);
+    return hipGetLastError();
 }
 
 }  // namespace mvq

@@ -659,6 +659,17 @@ class ResidualVectorQuantize(nn.Module):
         return zq, codes, latents, zero, zero.clone()
 
 
+    @torch.no_grad()
+    def from_codes(self, codes):
+        """upstream ``ResidualVectorQuantize.from_codes``: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T], codes).
+        z_p holds the raw codebook rows, z_q the sum of out_proj_i(z_p_i) in stage order (mvq_dac_rvq_from_codes_f32)."""
+        _, _, cb, out_w, out_b, _ = self._weights()
+        if codes.dim() != 3 or codes.shape[1] > self.n_codebooks:
+            raise MvqError(f"from_codes: codes must be [B, nq <= {self.n_codebooks}, T], got {tuple(codes.shape)}")
+        z_q, z_p = ops.dac_rvq_from_codes(codes.to(cb.device), cb, out_w, out_b)
+        return z_q, z_p, codes
+
+
 class DAC(nn.Module):
     """encoder / quantizer / decoder with the 24 kHz hyper-parameters; ``encode`` / ``decode`` as upstream."""
 

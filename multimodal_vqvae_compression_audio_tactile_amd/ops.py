@@ -456,6 +456,67 @@ def dac_rvq(z, in_w, in_b, codebook, out_w, out_b, n_q, nq_item=None, prepared=N
     return zq, codes.long(), lat
 
 
+def _codes_i64(x, name):
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise MvqError(f"{name}: expected an integer tensor on a HIP device")
+    if x.dtype.is_floating_point or x.dtype == torch.bool:
+        raise MvqError(f"{name}: expected an integer tensor, got {x.dtype}")
+    return x.to(torch.int64).contiguous()
+
+
+def rvq_dequant(idx, books, n_books_use=None, out=None, out_strides=None):
+    """The receiver side of ResidualVQEMA: idx[nb, B, T] (int) -> q[B, D, T] = e_0[idx_0] + e_1[idx_1] + ... (book order, from +0).
+    ``out`` / ``out_strides`` = (batch stride, dim stride): write into another layout instead (token-folded [1, D, B*T] is
+    (T, B*T)).  Indices are clamped to [0, K) in the kernel; validate untrusted ones on the host (bitstream.unpack_indices)."""
+    idx = _codes_i64(idx, "idx"); books = _dev(books, "books")
+    if idx.dim() != 3:
+        raise MvqError(f"rvq_dequant: idx must be [n_books, B, T], got {tuple(idx.shape)}")
+    if books.dim() != 3 or idx.device != books.device:
+        raise MvqError("rvq_dequant: books must be [n_books, K, D] on idx's device")
+    nb_all, K, D = books.shape
+    nb = min(idx.shape[0], nb_all) if n_books_use is None else max(0, min(int(n_books_use), idx.shape[0], nb_all))
+    _, B, T = idx.shape
+    if out is None:
+        out = torch.empty(B, D, T, device=books.device, dtype=torch.float32)
+        out_strides = (D * T, T)
+    elif (not isinstance(out, torch.Tensor) or out.device != books.device or out.dtype != torch.float32
+          or not out.is_contiguous() or out_strides is None):
+        raise MvqError("rvq_dequant: out must be a contiguous fp32 tensor on the books' device, given with out_strides")
+    sb, sd = int(out_strides[0]), int(out_strides[1])
+    if sb < 0 or sd < 0 or (B and T and (B - 1) * sb + (D - 1) * sd + T > out.numel()):
+        raise MvqError(f"rvq_dequant: [B={B}, D={D}, T={T}] at strides ({sb}, {sd}) reaches past the {out.numel()}-element out")
+    check(_lib.lib().mvq_rvq_dequant_f32(idx.data_ptr(), books.data_ptr(), out.data_ptr(), B, D, T, nb, K,
+                                         sb, sd, _stream()), "mvq_rvq_dequant_f32")
+    return out
+
+
+def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True):
+    """upstream ResidualVectorQuantize.from_codes: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T] or None).
+    z_q = sum over stages of out_proj_i(codebook_i[code_i]) in stage order; the first nq stages of the stacked weights."""
+    codes = _codes_i64(codes, "codes"); codebook = _dev(codebook, "codebook")
+    out_w = _dev(out_w, "out_w"); out_b = _dev(out_b, "out_b")
+    if codes.dim() != 3 or codebook.dim() != 3 or out_w.dim() != 3 or out_b.dim() != 2:
+        raise MvqError("dac_rvq_from_codes: codes [B,nq,T], codebook [nq,K,Dc], out_w [nq,C,Dc], out_b [nq,C] expected")
+    if len({codes.device, codebook.device, out_w.device, out_b.device}) != 1:
+        raise MvqError("dac_rvq_from_codes: all tensors must be on one device")
+    B, nq, T = codes.shape
+    _, K, Dc = codebook.shape
+    C = out_w.shape[1]
+    if nq > min(codebook.shape[0], out_w.shape[0], out_b.shape[0]):
+        raise MvqError(f"dac_rvq_from_codes: {nq} code rows for {codebook.shape[0]} codebooks / {out_w.shape[0]} out_w / "
+                       f"{out_b.shape[0]} out_b stages")
+    if out_w.shape[2] != Dc or out_b.shape[1] != C:
+        raise MvqError(f"dac_rvq_from_codes: out_w {tuple(out_w.shape)} / out_b {tuple(out_b.shape)} do not match Dc={Dc}, C={C}")
+    zq = torch.empty(B, C, T, device=codes.device, dtype=torch.float32)
+    z_p = torch.empty(B, nq * Dc, T, device=codes.device, dtype=torch.float32) if want_z_p else None
+    if nq == 0:
+        zq.zero_()
+        return zq, z_p
+    check(_lib.lib().mvq_dac_rvq_from_codes_f32(codes.data_ptr(), codebook.data_ptr(), out_w.data_ptr(), out_b.data_ptr(),
+                                                zq.data_ptr(), _p(z_p), B, C, T, nq, K, Dc, _stream()), "mvq_dac_rvq_from_codes_f32")
+    return zq, z_p
+
+
 def layernorm_c(x, gamma, beta, pe=None, eps=1e-5, do_tanh=False, post_scale=1.0, folded_batch=None, sub=None):
     """LayerNorm over channels of x[B,C,T] (of x - sub when ``sub`` is given); with ``folded_batch=B`` x is the
     token-folded [1,C,B*T] layout."""
@@ -506,6 +567,20 @@ def attention_kv_slice(q, k_all, v_all, heads, folded_batch, s, tk):
     ctx = torch.empty_like(q)
     check(_lib.lib().mvq_attention_f32(q.data_ptr(), k_all.data_ptr() + 4 * s, v_all.data_ptr() + 4 * s, ctx.data_ptr(),
                                        B, heads, C // heads, Tq, tk, Tq, B * Tq, Ta, B * Ta, _stream()), "mvq_attention_f32")
+    return ctx
+
+
+def attention_into_(ctx, q, k, v, heads, batch, tq, tk, q_strides, k_strides, q_col=0, k_col=0):
+    """ctx = attention of ``batch`` query groups against their own key groups, on views of token-folded [1, C, N] tensors:
+    group g's query column i / channel c sits at q_col + g*q_strides[0] + c*q_strides[1] + i (ctx shares that addressing),
+    its keys likewise from k_col with k_strides.  Writes into ``ctx`` (the receiver's chunk-as-batch calls)."""
+    C = q.shape[1]
+    if batch and tq and (q_col + (batch - 1) * q_strides[0] + (C - 1) * q_strides[1] + tq > q.numel()
+                         or (tk and k_col + (batch - 1) * k_strides[0] + (C - 1) * k_strides[1] + tk > k.numel())):
+        raise MvqError("attention_into_: a group reaches past the end of its tensor")
+    check(_lib.lib().mvq_attention_f32(q.data_ptr() + 4 * q_col, k.data_ptr() + 4 * k_col, v.data_ptr() + 4 * k_col,
+                                       ctx.data_ptr() + 4 * q_col, batch, heads, C // heads, tq, tk, int(q_strides[0]),
+                                       int(q_strides[1]), int(k_strides[0]), int(k_strides[1]), _stream()), "mvq_attention_f32")
     return ctx
 
 
@@ -753,6 +828,18 @@ def fold_column_into_(dst_folded, col, src, t, batch):
     check(_lib.lib().mvq_copy3d_f32(src.data_ptr() + 4 * t, C * T, T, dst_folded.data_ptr() + 4 * col, n, B * n,
                                     B, C, 1, _stream()), "mvq_copy3d_f32")
     return dst_folded
+
+
+def copy_strided_(dst, dst_col, dst_strides, src, src_col, src_strides, batch, c, n):
+    """dst[dst_col + b*ds0 + ch*ds1 + i] = src[src_col + b*ss0 + ch*ss1 + i] for b < batch, ch < c, i < n (flat fp32 offsets;
+    a zero stride repeats).  Bounds are checked against both tensors."""
+    for t, col, (s0, s1) in ((dst, dst_col, dst_strides), (src, src_col, src_strides)):
+        if batch and c and n and col + (batch - 1) * s0 + (c - 1) * s1 + n > t.numel():
+            raise MvqError("copy_strided_: the copy reaches past the end of a tensor")
+    check(_lib.lib().mvq_copy3d_f32(src.data_ptr() + 4 * src_col, int(src_strides[0]), int(src_strides[1]),
+                                    dst.data_ptr() + 4 * dst_col, int(dst_strides[0]), int(dst_strides[1]), batch, c, n, _stream()),
+          "mvq_copy3d_f32")
+    return dst
 
 
 def sub(a, b):

@@ -22,6 +22,7 @@ import math
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -119,15 +120,18 @@ class CrossPredictor(nn.Module):
         return ops.attention_fits(self.dh, tq, tk) and (not bwd or ops.attention_bwd_fits(self.dh, tq, tk))
 
     @torch.no_grad()
-    def run(self, zt_prev, za, folded_batch=None, kv_all=None, kv_slice=None):
+    def run(self, zt_prev, za, folded_batch=None, kv_all=None, kv_slice=None, attend=None):
         """zt_prev[B,C,Tq], za[B,C,Tk] (or both token-folded [1,C,B*T] with folded_batch=B) -> same layout.
-        kv_all = keys_values(...) with kv_slice = (s, tk): attend to columns [s, s+tk) of the precomputed K / V."""
+        kv_all = keys_values(...) with kv_slice = (s, tk): attend to columns [s, s+tk) of the precomputed K / V.
+        attend: a callable Q -> ctx that does the attention itself (the receiver's chunk-as-batch calls)."""
         fb = folded_batch
         pe = self.pos.pe
         q = ops.layernorm_c(zt_prev, self.ln_q.weight.detach(), self.ln_q.bias.detach(), pe=pe, eps=self.ln_q.eps,
                             folded_batch=fb)
         L = self._lin
-        if kv_all is not None:
+        if attend is not None:
+            ctx = attend(L["q"](q))
+        elif kv_all is not None:
             ctx = ops.attention_kv_slice(L["q"](q), kv_all[0], kv_all[1], self.h, fb, kv_slice[0], kv_slice[1])
         else:
             kv = ops.layernorm_c(za, self.ln_kv.weight.detach(), self.ln_kv.bias.detach(), pe=pe, eps=self.ln_kv.eps,
@@ -177,6 +181,7 @@ class ResidualVQEMA(nn.Module):
                                        for _ in range(n_books)])
         self.decay = float(decay)
         self.n_books, self.n_embed = int(n_books), int(n_embed)
+        self.dim = int(dim)
         self._stack = _Packed()
 
     def stacked(self) -> torch.Tensor:
@@ -189,6 +194,16 @@ class ResidualVQEMA(nn.Module):
         if len(self.books) == 0:
             return torch.zeros_like(z)
         return ops.rvq_ema_forward(z, self.stacked(), n_books_use, return_indices=return_indices)
+
+    @torch.no_grad()
+    def from_indices(self, idx, n_books_use: Optional[int] = None, out=None, out_strides=None):
+        """The receiver's dequantisation: idx[nb, B, T] -> qD[B, D, T] = ((+0 + e_0[idx_0]) + e_1[idx_1]) + ... over the first
+        min(nb, n_books_use) books.  (The forward's straight-through sum needs the encoder-side residual: round-off apart.)"""
+        if len(self.books) == 0:
+            if out is None:
+                return torch.zeros(idx.shape[1], self.dim, idx.shape[2], device=idx.device)
+            return out.zero_()
+        return ops.rvq_dequant(idx.to(self.books[0].device), self.stacked(), n_books_use, out=out, out_strides=out_strides)
 
     @torch.no_grad()
     def ema_step(self, z_tokens):
@@ -378,6 +393,105 @@ class _ProposedBase(nn.Module):
         z_run, _, idx = self._ar_latents(qa, self.T_ENC(t_1T), books_use, want_indices=True)
         return z_run, codes, idx
 
+    # ------------------------------------------------------------------------------------------------------------- receiver
+    @torch.no_grad()
+    def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False):
+        """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
+        indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
+        TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
+        qa = A_QUANT.from_codes(codes).  Round-off apart it equals the transmitter's z_run (the quantisers' straight-through
+        sums need encoder-side values the receiver does not have).
+
+        z_pred depends on the loop only through column 0 of chunks s > 0 (z_run[s-1], the LAST token of the chunk before,
+        which itself does not depend on the loop), so the receiver is two dependent passes instead of one pass per chunk
+        (_rx_two_pass); the result is bit-equal to the per-chunk loop."""
+        if idx is None:
+            raise MvqError("decode_latents: idx (the RVQ indices [n_books, B, T_lat]) is required")
+        dev = self.proj_up.weight.device
+        idx = torch.as_tensor(idx).to(dev)
+        if idx.dim() != 3:
+            raise MvqError(f"decode_latents: idx must be [n_books, B, T_lat], got {tuple(idx.shape)}")
+        _, B, Tlat = idx.shape
+        C = self.proj_up.out_channels
+        if not tactile_only:                 # the audio side must describe the same items as idx (checked before any launch)
+            if qa is None:
+                if audio_codes is None:
+                    raise MvqError("decode_latents: audio_codes (or qa) is required unless tactile_only")
+                audio_codes = torch.as_tensor(audio_codes)
+                if audio_codes.dim() != 3 or audio_codes.shape[0] != B:
+                    raise MvqError(f"decode_latents: audio codes {tuple(audio_codes.shape)} do not match idx's batch B={B}")
+            elif qa.dim() != 3 or qa.shape[0] != B or qa.shape[1] != C:
+                raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
+        if B == 0 or Tlat == 0:
+            return torch.zeros(B, C, Tlat, device=dev)
+        if tactile_only:                                                      # z_pred absent, as in the transmitter
+            return self._pu(self.vq.from_indices(idx, books_use))
+        if qa is None:
+            qa = self.A_QUANT.from_codes(audio_codes.to(dev))[0]
+        qa = ops._dev(qa.to(dev), "qa")                                       # fp32, contiguous
+        if qa.shape[0] != B or qa.shape[1] != C:
+            raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
+        return self._rx_two_pass(qa, idx, books_use)
+
+    def _rx_two_pass(self, qa, idx, books_use):
+        """Layout: every [.., B*Tlat] tensor of the plan is token-folded and PADDED per chunk -- column (b*NC + c)*16 + i holds
+        token c*16 + i of item b (NC chunks, the tail chunk's columns past its end are filler) -- so "chunk" is a batch index of
+        stride 16 and every chunk with 16 queries and 16 keys is ONE attention call (chunk as batch).  The tail chunk and chunks
+        whose audio is shorter (ka < 16, ka = 0: whole-file mode) get calls of their own, which overwrite the big call's
+        results for those chunks.  Per-token kernels (LayerNorm, GEMMs) give the same bits whatever the batching.
+          pass 1: every token with a zero query input (q = LN(PE[i])), z_run = proj_up(qD) + z_pred;
+          pass 2: one query per chunk, input z_run[s-1], attending to its own chunk's keys; the result replaces position 0.
+        Chunk 0 takes part in pass 2 with a zero input, recomputing its position 0 exactly as pass 1 did."""
+        pr, L = self.predict, self.predict._lin
+        B, C, Ta_in = qa.shape
+        Tlat = idx.shape[2]
+        if idx.shape[1] != B or qa.dtype != torch.float32 or not qa.is_contiguous():
+            raise MvqError("_rx_two_pass: qa must be contiguous fp32 with idx's batch")   # every buffer below is sized from B
+        CH = AR_CHUNK_TOK
+        NC = (Tlat + CH - 1) // CH
+        P, G = NC * CH, B * NC
+        N = B * P
+        dev = qa.device
+        Ta = min(Ta_in, Tlat)
+        ka = [min(Ta, min(Tlat, s + CH)) - min(Ta, s) for s in range(0, Tlat, CH)]
+        nt = [min(Tlat, s + CH) - s for s in range(0, Tlat, CH)]
+        odd = [c for c in range(NC) if nt[c] != CH or ka[c] != CH]
+        # K, V of every chunk (PosEnc restarts per chunk: column i of a group takes pe[i])
+        qa_p = (torch.zeros if Ta < P else torch.empty)(1, C, N, device=dev)
+        ops.copy_strided_(qa_p, 0, (P, N), qa, 0, (C * Ta_in, Ta_in), B, C, Ta)
+        kv = ops.layernorm_c(qa_p, pr.ln_kv.weight.detach(), pr.ln_kv.bias.detach(), pe=pr.pos.pe, eps=pr.ln_kv.eps, folded_batch=G)
+        K, V = L["k"](kv), L["v"](kv)
+        # qD of every token in one dequantisation
+        qD_p = torch.empty(1, CODE_DIM, N, device=dev)
+        self.vq.from_indices(idx, books_use, out=qD_p, out_strides=(P, N))
+
+        def attend(Q, tq, q_strides, q_col_of):
+            ctx = torch.empty_like(Q)
+            if len(odd) < NC:
+                ops.attention_into_(ctx, Q, K, V, pr.h, G, tq, CH, q_strides, (CH, N))
+            for c in odd:
+                ops.attention_into_(ctx, Q, K, V, pr.h, B, min(tq, nt[c]), ka[c], (q_strides[0] * NC, q_strides[1]), (P, N),
+                                    q_col=q_col_of(c), k_col=c * CH)
+            return ctx
+
+        # pass 1
+        zero = torch.zeros(1, C, N, device=dev)
+        z_pred = pr.run(zero, None, folded_batch=G, attend=lambda Q: attend(Q, CH, (CH, N), lambda c: c * CH))
+        z_run_p = self._pu(qD_p, residual=z_pred)
+        # pass 2: column b*NC + c <- z_run[b, :, c*16 - 1] (zero for c = 0)
+        if NC > 1:
+            x2 = torch.empty(1, C, G, device=dev)
+            ops.copy_strided_(x2, 1, (1, G), z_run_p, CH - 1, (CH, N), G - 1, C, 1)
+            ops.copy_strided_(x2, 0, (NC, G), zero, 0, (0, 0), B, C, 1)
+            z_pred2 = pr.run(x2, None, folded_batch=G, attend=lambda Q: attend(Q, 1, (1, G), lambda c: c))
+            qD2 = torch.empty(1, CODE_DIM, G, device=dev)
+            ops.copy_strided_(qD2, 0, (1, G), qD_p, 0, (CH, N), G, CODE_DIM, 1)
+            z2 = self._pu(qD2, residual=z_pred2)
+            ops.copy_strided_(z_run_p, 0, (CH, N), z2, 0, (1, G), G, C, 1)
+        z_run = torch.empty(B, C, Tlat, device=dev)
+        ops.copy_strided_(z_run, 0, (C * Tlat, Tlat), z_run_p, 0, (P, N), B, C, Tlat)
+        return z_run
+
     def _ar_latents_train(self, qa, zt):
         """The same loop recorded for autograd: z_hat of chunk c feeds column 0 of chunk c+1's zt_prev WITH gradient
         (the reference writes z_hat into z_run in place and slices it back, Training/...5.py:303-319)."""
@@ -436,6 +550,52 @@ class ProposedEval(_ProposedBase):
     @torch.no_grad()
     def forward_eval_tactile_only(self, t_1T, books_use=None):
         return self.T_DEC(self.encode_latents_tactile_only(t_1T, books_use))
+
+
+    # ---------------------------------------------------------------------------------------------------------- receiver
+    @torch.no_grad()
+    def decode(self, audio_codes, idx, books_use=None):
+        """Receiver: T_DEC(decode_latents(audio_codes, idx)) -- the waveform from the transmitted codes alone."""
+        return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use))
+
+    @torch.no_grad()
+    def decode_latents_tactile_only(self, idx, books_use=None):
+        return self.decode_latents(None, idx, books_use=books_use, tactile_only=True)
+
+    @torch.no_grad()
+    def decode_tactile_only(self, idx, books_use=None):
+        return self.T_DEC(self.decode_latents_tactile_only(idx, books_use))
+
+    @torch.no_grad()
+    def compress(self, a_1T, t_1T, books_use=None):
+        """-> (tactile_payloads, audio_payloads): one bitstream.pack_indices payload per item, the RVQ indices [nb, Tlat] at
+        K = n_embed and the 32 audio code rows [32, Ta] at K = the DAC codebook size."""
+        from . import bitstream
+        _, codes, idx = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use)
+        idx, codes = idx.cpu().numpy(), codes.cpu().numpy()
+        k_audio = self.A_QUANT.codebook_size
+        return ([bitstream.pack_indices(idx[:, b], self.vq.n_embed) for b in range(idx.shape[1])],
+                [bitstream.pack_indices(codes[b], k_audio) for b in range(codes.shape[0])])
+
+    @torch.no_grad()
+    def decompress(self, tactile_payloads, audio_payloads, books_use=None):
+        """The waveform [B,1,T] from compress()'s payloads (items of one length): unpack, then decode()."""
+        from . import bitstream
+        if len(tactile_payloads) != len(audio_payloads):
+            raise MvqError("decompress: one tactile and one audio payload per item")
+        idx = [self._payload(bitstream, p, self.vq.n_embed, "tactile") for p in tactile_payloads]
+        codes = [self._payload(bitstream, p, self.A_QUANT.codebook_size, "audio") for p in audio_payloads]
+        dev = self.proj_up.weight.device
+        idx_t = torch.from_numpy(np.stack(idx, axis=1)).to(dev)
+        codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
+        return self.decode(codes_t, idx_t, books_use=books_use)
+
+    @staticmethod
+    def _payload(bitstream, payload, k_expected, what):
+        idx, k = bitstream.unpack_indices(payload)
+        if k != k_expected:
+            raise ValueError(f"decompress: {what} payload has K = {k}, the model's codebook has {k_expected}")
+        return idx
 
 
 RVQ_N_BOOKS_MAX = 10  # Evaluation/compare_dacvsproposal_3.5_eval.py:68

@@ -14,6 +14,8 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   encoder_fwd                 mvq_encoder_fwd_f32        A_ENC(a) / T_ENC(t), ...5.py:294,296 (whole stack: `stack` = ops.Stack(...).id)
   decoder_fwd                 mvq_decoder_fwd_f32        T_DEC(z), ...5.py:322
   decoder_bwd_input           mvq_decoder_fwd_saving_f32 + mvq_decoder_bwd_input_f32: dL/dz of T_DEC, ...5.py:393
+  rvq_dequant                 mvq_rvq_dequant_f32        receiver: ResidualVQEMA indices -> summed code vectors [B,D,T]
+  dac_rvq_from_codes          mvq_dac_rvq_from_codes_f32 receiver: upstream ResidualVectorQuantize.from_codes -> (z_q, z_p)
   attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
   mel_ssim_f32                mvq_mel_ssim_f32           mel ST-SIM of column-listed image pairs (PLC/PLC1_eval.py:270-333)
 
@@ -137,7 +139,7 @@ def _(z, gy, stack):
 
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
-              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32")
+              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes")
 
 
 @torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
@@ -159,3 +161,24 @@ def mel_ssim_f32(mel: Tensor, maxv: Tensor, desc: Tensor, widths: Tensor, cols: 
 @mel_ssim_f32.register_fake
 def _(mel, maxv, desc, widths, cols, max_width, mode):
     return mel.new_empty((widths.shape[0],), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{NS}::rvq_dequant", mutates_args=())
+def rvq_dequant(idx: Tensor, books: Tensor, n_use: int) -> Tensor:
+    return ops.rvq_dequant(idx, books, n_books_use=n_use)
+
+
+@rvq_dequant.register_fake
+def _(idx, books, n_use):
+    return books.new_empty(idx.shape[1], books.shape[-1], idx.shape[2])
+
+
+@torch.library.custom_op(f"{NS}::dac_rvq_from_codes", mutates_args=())
+def dac_rvq_from_codes(codes: Tensor, codebook: Tensor, out_w: Tensor, out_b: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.dac_rvq_from_codes(codes, codebook, out_w, out_b)
+
+
+@dac_rvq_from_codes.register_fake
+def _(codes, codebook, out_w, out_b):
+    B, nq, T = codes.shape
+    return out_w.new_empty(B, out_w.shape[1], T), out_w.new_empty(B, nq * codebook.shape[-1], T)
