@@ -201,13 +201,75 @@ __device__ __forceinline__ void lds_dma_burst(const float* const* src, unsigned 
                      : "=&s"(keep) : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "v"(src[5]), "v"(src[6]), "v"(src[7]), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
 }
 
-template <int KS, int STRIDE, int DIL, int BM, int XP, int MT, int NT, int NS>
+// ---- the same burst with UNIFORM-ADVANCE addressing: every piece of the burst reads from one wave-uniform
+// 64-bit base (an SGPR pair that scalar ALU advances once per chunk) plus a per-lane 32-bit byte offset that never changes, so the
+// K loop carries no vector pointer arithmetic.  Same M0 sequence as above (tools/isa_lint.py R4 checks the shape, not the operands).
+#define MVQ_DMAU_FIRST(i) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #i ", %[base]\n\t"
+#define MVQ_DMAU_NEXT(i) "s_add_u32 m0, m0, %[inc]\n\t" MVQ_DMAU_FIRST(i)
+template <int N, int INC>
+__device__ __forceinline__ void lds_dma_burst_uni(const unsigned* off, unsigned long long base, unsigned dst)
+{
+    static_assert(N >= 1 && N <= 8, "pieces per burst");
+    unsigned keep;
+    if constexpr (N == 1)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMA_TAIL : "=&s"(keep) : "v"(off[0]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 2)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 3)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 4)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMAU_NEXT(4) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 5)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMAU_NEXT(4) MVQ_DMAU_NEXT(5) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 6)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMAU_NEXT(4) MVQ_DMAU_NEXT(5) MVQ_DMAU_NEXT(6) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), "v"(off[5]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else if constexpr (N == 7)
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMAU_NEXT(4) MVQ_DMAU_NEXT(5) MVQ_DMAU_NEXT(6) MVQ_DMAU_NEXT(7) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), "v"(off[5]), "v"(off[6]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+    else
+        asm volatile(MVQ_DMA_HEAD MVQ_DMAU_FIRST(1) MVQ_DMAU_NEXT(2) MVQ_DMAU_NEXT(3) MVQ_DMAU_NEXT(4) MVQ_DMAU_NEXT(5) MVQ_DMAU_NEXT(6) MVQ_DMAU_NEXT(7) MVQ_DMAU_NEXT(8) MVQ_DMA_TAIL
+                     : "=&s"(keep) : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), "v"(off[5]), "v"(off[6]), "v"(off[7]), [base] "s"(base), [dst] "s"(dst), [inc] "n"(INC) : "memory", "scc");
+}
+// One piece under a lane mask: the wave-instruction that holds the last, partly filled 1 KiB of the weight or of the activation
+// pieces (mask == 0 in a wave that has no such piece: an LDS-DMA with EXEC == 0 moves nothing).  EXEC is set and put back inside the
+// statement, so the compiler sees straight-line code and the K loop has no branch for it; the M0 sequence sits between the two.
+__device__ __forceinline__ void lds_dma_masked_uni(unsigned off, unsigned long long base, unsigned dst, unsigned long long mask)
+{
+    unsigned keep;
+    unsigned long long keep_exec;
+    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %[mask]\n\t"
+                 "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %[base]\n\ts_mov_b32 m0, %0\n\t"
+                 "s_mov_b64 exec, %1"
+                 : "=&s"(keep), "=&s"(keep_exec) : "v"(off), [base] "s"(base), [dst] "s"(dst), [mask] "s"(mask) : "memory");
+}
+
+// A wave-uniform address as an SGPR pair the LDS-DMA may read.  The block index reaches the body through an integer division, i.e.
+// in vector registers, and for an "s" operand the compiler would hand the asm that VGPR pair: v_readfirstlane makes it scalar.
+// A VMEM instruction that reads an SGPR written by the vector ALU needs five wait states the compiler cannot place inside an
+// asm statement: the s_nop 4, which re-defines the value (tied operand), supplies them.
+__device__ __forceinline__ unsigned long long dma_scalar_base(const float* p)
+{
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    unsigned long long s = ((unsigned long long)hi << 32) | lo;
+    asm volatile("s_nop 4" : "+s"(s));
+    return s;
+}
+
+// BASE: a compile-time byte offset folded into every read's immediate (the ring stage of the stage-unrolled loop), so the
+// three base addresses are the same registers for all three stages.
+template <int KS, int STRIDE, int DIL, int BM, int XP, int MT, int NT, int NS, int BASE = 0>
 struct AsmOperandLoop {
     template <int S, int I>
     static __device__ __forceinline__ void load_a(float (&av)[MT], unsigned a_addr)
     {
         if constexpr (I < MT) {
-            av[I] = lds_read_imm<(2 * S * BM + I * 32) * 4>(a_addr);
+            av[I] = lds_read_imm<BASE + (2 * S * BM + I * 32) * 4>(a_addr);
             load_a<S, I + 1>(av, a_addr);
         }
     }
@@ -218,7 +280,7 @@ struct AsmOperandLoop {
             constexpr int k0 = 2 * S;
             constexpr int off0 = (k0 / KS) * XP + (k0 % KS) * DIL;
             constexpr bool cross = ((k0 + 1) / KS) != (k0 / KS);
-            bv[J] = lds_read_imm<(off0 + J * 32 * STRIDE) * 4>(cross ? b_cross : b_same);
+            bv[J] = lds_read_imm<BASE + (off0 + J * 32 * STRIDE) * 4>(cross ? b_cross : b_same);
             load_b<S, J + 1>(bv, b_same, b_cross);
         }
     }
@@ -578,6 +640,124 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
         constexpr int D_CROSS_D = XP - (KS - 1) * DIL;
         const int bd_same = b_base + h * D_SAME;
         const int bd_cross = b_base + h * D_CROSS_D;
+        const unsigned lds0 = (unsigned)(size_t)smem;                    // LDS byte address of the ring
+        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+        using AL = AsmOperandLoop<KS, STRIDE, DIL, C::BM, XP, MT, NT, NS>;
+        // one chunk out of ring stage `stage` (run time); issue() requests the chunk two ahead behind the first operand reads, i.e.
+        // while those are in flight
+        auto chunk_rt = [&](int stage, auto&& issue) __attribute__((always_inline)) {
+            const unsigned sb = lds0 + (unsigned)(stage * C::DMA_STAGE_FLOATS * 4);
+            const unsigned a_addr = sb + (unsigned)(a_base * 4);
+            const unsigned b_s = sb + (unsigned)((C::W_FLOATS + bd_same) * 4), b_c = sb + (unsigned)((C::W_FLOATS + bd_cross) * 4);
+            float av0[MT], bv0[NT], av1[MT], bv1[NT];
+            AL::template load_step<0>(av0, bv0, a_addr, b_s, b_c);
+            issue();
+            AL::template run_from<0>(acc, av0, bv0, av1, bv1, a_addr, b_s, b_c);
+        };
+        // ---- UNIFORM-ADVANCE form: the block's every piece lies inside its row, so a wave-instruction is a
+        // scalar base + a constant per-lane offset, and the steady-state loop, unrolled by the three ring stages, holds MFMAs,
+        // operand reads at immediate offsets, the DMA bursts and scalar instructions -- no vector ALU work and no branch but the back
+        // edge.  The pieces are dealt per KIND so that a wave-instruction never mixes the two bases: the WI_W = ceil(W_VEC / 64)
+        // weight instructions go round the waves (slot u of wave w: instruction u * NW + w, the same pieces as in the per-lane form),
+        // the WI_X activation instructions continue the round where the weights stopped (no wave issues more than one instruction
+        // above another).  The last instruction of a kind may be partly filled (96-row tiles: 672 weight pieces = 10.5 instructions)
+        // or absent in some waves: it runs under a lane mask (lds_dma_masked_uni).  Cost of dealing per kind: that one extra partly
+        // filled instruction per chunk (14 instead of 13 wave-instructions per chunk and block on the 96-row 7-tap tile; no LDS).
+        // A block that has a piece outside its row (edge tiles: zero padding) or remaps pieces (virtually packed rows) keeps the
+        // per-lane pointers below; the decision is uniform per block.
+        constexpr int NW = WAVES_M * WAVES_N;
+        constexpr int XPC = CK * C::XV;                                   // activation pieces per chunk
+        constexpr int WI_W = (C::W_VEC + 63) / 64, WI_X = (XPC + 63) / 64;
+        constexpr int NU_W = (WI_W + NW - 1) / NW, NU_X = (WI_X + NW - 1) / NW;
+        constexpr int NF_W = C::W_VEC / C::NTHR, NF_X = XPC / C::NTHR;     // slots every wave issues with all 64 lanes: one burst
+        static_assert(NU_W - NF_W <= 1 && NU_X - NF_X <= 1, "at most one masked instruction per kind");
+        constexpr int NI_MIN = (WI_W + WI_X) / NW;                       // DMA instructions per chunk of the wave that issues fewest (the others: one more)
+        constexpr bool UNI_OK = (size_t)3 * C::DMA_STAGE_FLOATS * 4 <= 65536 && NF_W <= 8 && NF_X <= 8;   // stage offsets fit the ds_read immediates
+        bool uni = false;
+        if constexpr (UNI_OK) uni = !a.vp_seg && g_al >= 0 && g_al + 4 * C::XV <= a.Tin && (long long)CK * a.Tin < (1ll << 29);
+        if (uni) {
+          if constexpr (UNI_OK) {
+            unsigned woff[NU_W], xoff[NU_X];
+#pragma unroll
+            for (int u = 0; u < NU_W; ++u) {
+                int p = tid + u * C::NTHR;
+                p = p < C::W_VEC ? p : C::W_VEC - 1;
+                const int row = p / (C::BM / 4), c4 = p - row * (C::BM / 4);
+                woff[u] = (unsigned)(row * a.Mpad + c4 * 4) * 4u;      // row < CK * KS (a few dozen): fits 32 bits for any real Mpad
+            }
+            const int xw = (wave_u + NW - WI_W % NW) % NW;               // this wave's first activation instruction
+#pragma unroll
+            for (int j = 0; j < NU_X; ++j) {
+                int q = (xw + j * NW) * 64 + lane;
+                q = q < XPC ? q : XPC - 1;
+                const int cl = q / C::XV, v = q - cl * C::XV;
+                xoff[j] = (unsigned)(cl * a.Tin + 4 * v) * 4u;
+            }
+            unsigned long long mask_w = 0, mask_x = 0;
+            if constexpr (NU_W > NF_W) mask_w = __ballot(tid + NF_W * C::NTHR < C::W_VEC);
+            if constexpr (NU_X > NF_X) mask_x = __ballot((xw + NF_X * NW) * 64 + lane < XPC);
+            unsigned long long wbase = dma_scalar_base(a.wp + m0);
+            unsigned long long xbase = dma_scalar_base(tile.xb + g_al);
+            const unsigned wstep = (unsigned)(CK * KS * a.Mpad) * 4u, xstep = (unsigned)(CK * a.Tin) * 4u;
+            const unsigned wdst0 = lds0 + (unsigned)(wave_u * 1024), xdst0 = lds0 + (unsigned)(C::W_FLOATS * 4) + (unsigned)(xw * 1024);
+            auto dma_uni = [&](int stage) __attribute__((always_inline)) {
+                const unsigned so = (unsigned)(stage * C::DMA_STAGE_FLOATS * 4);
+                if constexpr (NF_W > 0) lds_dma_burst_uni<NF_W, C::NTHR * 16>(woff, wbase, wdst0 + so);
+                if constexpr (NU_W > NF_W) lds_dma_masked_uni(woff[NU_W - 1], wbase, wdst0 + so + (unsigned)(NF_W * C::NTHR * 16), mask_w);
+                if constexpr (NF_X > 0) lds_dma_burst_uni<NF_X, C::NTHR * 16>(xoff, xbase, xdst0 + so);
+                if constexpr (NU_X > NF_X) lds_dma_masked_uni(xoff[NU_X - 1], xbase, xdst0 + so + (unsigned)(NF_X * C::NTHR * 16), mask_x);
+                wbase += wstep;
+                xbase += xstep;
+            };
+            // operand bases of stage 0; the stage is part of the immediates
+            const unsigned a_addr0 = lds0 + (unsigned)(a_base * 4);
+            const unsigned b_s0 = lds0 + (unsigned)((C::W_FLOATS + bd_same) * 4), b_c0 = lds0 + (unsigned)((C::W_FLOATS + bd_cross) * 4);
+            // chunk out of ring stage STAGE (compile time); the DMA of the chunk two ahead goes out behind the first operand reads
+            auto chunk_uni = [&](auto STAGE_) __attribute__((always_inline)) {
+                constexpr int STAGE = decltype(STAGE_)::value;
+                using ALS = AsmOperandLoop<KS, STRIDE, DIL, C::BM, XP, MT, NT, NS, STAGE * C::DMA_STAGE_FLOATS * 4>;
+                float av0[MT], bv0[NT], av1[MT], bv1[NT];
+                ALS::template load_step<0>(av0, bv0, a_addr0, b_s0, b_c0);
+                dma_uni((STAGE + 2) % 3);
+                ALS::template run_from<0>(acc, av0, bv0, av1, bv1, a_addr0, b_s0, b_c0);
+            };
+            // The K loop for a wave that issues NWAIT DMA instructions per chunk: chunk c has landed when at most the NWAIT
+            // instructions of chunk c+1 are outstanding -- the per-wave count, as in the per-lane form; vmcnt takes an immediate, so
+            // the choice between the two counts is made once, in front of the loop (two copies of it).
+            auto k_loop_uni = [&](auto NWAIT_) __attribute__((always_inline)) {
+                constexpr int NWAIT = decltype(NWAIT_)::value;
+                int c = 0;
+                // steady state: three chunks per trip, each with a chunk two ahead to request
+                for (; c + 5 <= n_chunks; c += 3) {
+                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NWAIT) : "memory");
+                    __syncthreads();
+                    chunk_uni(std::integral_constant<int, 0>{});
+                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NWAIT) : "memory");
+                    __syncthreads();
+                    chunk_uni(std::integral_constant<int, 1>{});
+                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NWAIT) : "memory");
+                    __syncthreads();
+                    chunk_uni(std::integral_constant<int, 2>{});
+                }
+                // the last one to four chunks (c is a multiple of three: they start in stage 0), stage and issue decided at run time
+                int st_c = 0, st_n2 = 2;
+                for (; c < n_chunks; ++c) {
+                    if (c + 1 >= n_chunks) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NWAIT) : "memory");
+                    __syncthreads();
+                    chunk_rt(st_c, [&]() __attribute__((always_inline)) { if (c + 2 < n_chunks) dma_uni(st_n2); });
+                    st_c = st_c == 2 ? 0 : st_c + 1;
+                    st_n2 = st_n2 == 2 ? 0 : st_n2 + 1;
+                }
+            };
+            dma_uni(0);
+            if (n_chunks > 1) dma_uni(1);
+            // instructions this wave issues per chunk with a lane alive: NI_MIN, or one more where the round does not come out even
+            const int my_issue = (WI_W - wave_u + NW - 1) / NW + (WI_X - xw + NW - 1) / NW;
+            if ((WI_W + WI_X) % NW != 0 && my_issue > NI_MIN) k_loop_uni(std::integral_constant<int, NI_MIN + 1>{});
+            else k_loop_uni(std::integral_constant<int, NI_MIN>{});
+          }
+        } else {
         // per-lane source pointers of this thread's NU pieces (piece p = tid + u*NTHR of the stage), advanced per chunk
         const float* src[NU];
         bool live[NU];
@@ -609,8 +789,6 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
                 step_b[u] = ok ? st : 0;
             }
         }
-        const unsigned lds0 = (unsigned)(size_t)smem;                    // LDS byte address of the ring
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
         // DMA instructions this wave really issues per chunk (the last one is skipped by waves whose 64 pieces all lie past the end)
         const int n_issue = (NU - 1) * C::NTHR + wave_u * 64 < C::DMA_NV ? NU : NU - 1;
         // pieces every wave issues in full (the first NFULL of the NU): one burst; the last, partly empty piece on its own
@@ -626,16 +804,6 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
 #pragma unroll
             for (int u = 0; u < NU; ++u) src[u] += step_b[u];
         };
-        using AL = AsmOperandLoop<KS, STRIDE, DIL, C::BM, XP, MT, NT, NS>;
-        auto mfma_chunk_asm = [&](int stage, bool issue_next, int next_stage) __attribute__((always_inline)) {
-            const unsigned sb = lds0 + (unsigned)(stage * C::DMA_STAGE_FLOATS * 4);
-            const unsigned a_addr = sb + (unsigned)(a_base * 4);
-            const unsigned b_s = sb + (unsigned)((C::W_FLOATS + bd_same) * 4), b_c = sb + (unsigned)((C::W_FLOATS + bd_cross) * 4);
-            float av0[MT], bv0[NT], av1[MT], bv1[NT];
-            AL::template load_step<0>(av0, bv0, a_addr, b_s, b_c);
-            if (issue_next) dma_chunk(next_stage);         // behind the first operand reads: issued while those are in flight
-            AL::template run_from<0>(acc, av0, bv0, av1, bv1, a_addr, b_s, b_c);
-        };
         dma_chunk(0);
         if (n_chunks > 1) dma_chunk(1);
         int st_c = 0, st_n2 = 2;                       // stage of chunk c / of chunk c+2
@@ -645,10 +813,11 @@ __device__ __forceinline__ void conv1d_mfma_body(const ConvArgs& a)
             else if (n_issue == NU) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NU - 1) : "memory");
             __syncthreads();                          // ... in every wave; and stage (c+2)%3 is free (read during chunk c-1)
-            mfma_chunk_asm(st_c, c + 2 < n_chunks, st_n2);
+            chunk_rt(st_c, [&]() __attribute__((always_inline)) { if (c + 2 < n_chunks) dma_chunk(st_n2); });
             st_c = st_c == 2 ? 0 : st_c + 1;
             st_n2 = st_n2 == 2 ? 0 : st_n2 + 1;
         }
+        }   // per-lane pointer form
       }
     } else {
     tile.load_chunk(0, wreg, xv, xs);
