@@ -39,7 +39,8 @@ extern "C" {
 /* ABI version.  3 (round 5): whole-stack entry points (additive since, same version: the full-sequence attention pair
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
- * mvq_subset_stats_f32).  Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
+ * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32).
+ * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
  * mvq_build_flags() exists. */
@@ -213,6 +214,30 @@ int mvq_rvq_dequant_f32(const int64_t* idx, const float* books, float* q_out, in
  * z_p[B,nq_use*Dc,T] = the raw rows (NULL = not written).  C % 64 == 0, nq_use <= 32, Dc = 8. */
 int mvq_dac_rvq_from_codes_f32(const int64_t* codes, const float* codebook, const float* out_w, const float* out_b, float* zq,
                                float* z_p, int batch, int c, int t, int nq_use, int k, int dc, void* stream);
+
+/* The lossy-channel receiver (additive, same ABI version; no reference counterpart: the reference's PLC model masks the encoder's
+ * own latents).  A tactile item of T tokens travels as P = ceil(T / packet_tok) packets; packet p carries tokens
+ * [p*packet_tok, min(T, (p+1)*packet_tok)), ntok of them.  Its body holds nb*ntok indices of bits = ceil(log2 K) bits each,
+ * BOOK-major (element e = book*ntok + j at bits [e*bits, (e+1)*bits)), each index least-significant bit first, bits packed
+ * LSB-first into bytes; body_full = ceil(nb*packet_tok*bits / 8) bytes, a row is zero past its last element (pad bits, and the
+ * shorter tail packet).  packets.py (pack_bodies / unpack_bodies) is the numpy definition these kernels equal bit for bit.
+ * Covered: nb <= 255, 1 <= packet_tok <= 255, bits <= 24; anything else is MVQ_EINVAL "bad shape" before any launch.
+ *
+ * Pack: index (book i, item b, token t) is read at idx[i*s_book + b*s_item + t] (idx[nb,B,T]: (B*T, T); codes[B,nq,T]: (T, nq*T)),
+ * clamped to [0, K).  Writes EVERY byte of bodies[B, P, body_full].  One thread owns one byte: no atomics. */
+int mvq_idx_pack_packets_u8(const int64_t* idx, uint8_t* bodies, int batch, int nb, int t, int k, int packet_tok,
+                            size_t s_book, size_t s_item, void* stream);
+/* Unpack: bodies[B, P, body_full] and nb_recv[B, P] (books of the packet that arrived; 0 = lost; values above nb count as nb)
+ * -> idx[nb, B*T] (token b*T+t, the layout mvq_rvq_dequant_f32 reads) and nb_valid[B*T] = the token's packet's count.  Books at or
+ * above the count are written as 0; a value >= K is clamped to K-1, so a corrupt body cannot make a later look-up read out of
+ * bounds.  Writes every element of both outputs. */
+int mvq_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_t* idx, uint8_t* nb_valid, int batch, int nb, int t,
+                           int k, int packet_tok, void* stream);
+/* mvq_rvq_dequant_f32 with a per-token book count nb_valid[B*T] (token b*T+t; NULL = mvq_rvq_dequant_f32 itself):
+ *   q(b,d,t) = ((+0 + e_0[idx_0][d]) + e_1[idx_1][d]) + ...  over the first min(nb_use, nb_valid[b*T+t]) books; a count of 0
+ * writes +0 (RVQ is successively refinable: a partly delivered token is a lower-rate token).  Same strided output. */
+int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,
+                               int t, int nb_use, int k, size_t out_sb, size_t out_sd, void* stream);
 
 /* ---- predictor / glue primitives (CrossPredictor, TokenNorm, PosEnc1D) --------------------------- */
 

@@ -82,6 +82,9 @@ EXPORTS = {
     "mvq_dac_rvq_prepared_f32": (c_int, [c_void_p] * 12 + [c_int] * 6 + [c_void_p]),
     "mvq_rvq_dequant_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_dac_rvq_from_codes_f32": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    "mvq_idx_pack_packets_u8": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
+    "mvq_idx_unpack_packets": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
+    "mvq_rvq_dequant_layers_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_layernorm_c_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_float, c_int, c_float, c_void_p]),
     "mvq_attention_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_align_xcorr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -718,6 +718,60 @@ int mvq_dac_rvq_from_codes_f32(const int64_t* codes, const float* codebook, cons
     return e == hipSuccess ? MVQ_OK : hipfail(e, "dac_rvq_from_codes");
 }
 
+// ---- the lossy-channel receiver (kernels in packets.hip) ----
+namespace {
+// ceil(log2 K) when the packet kernels cover the shape (1..255 books and tokens per packet as the header holds them, at most 24
+// bits per index), -1 otherwise.
+inline int packet_bits(int batch, int nb, int t, int k, int packet_tok)
+{
+    if (batch < 0 || nb < 0 || nb > 255 || t < 0 || k < 1 || packet_tok < 1 || packet_tok > 255) return -1;
+    int bits = 0;
+    while (bits < 31 && (1u << bits) < (unsigned)k) ++bits;
+    return bits <= 24 ? bits : -1;
+}
+}  // namespace
+
+int mvq_idx_pack_packets_u8(const int64_t* idx, uint8_t* bodies, int batch, int nb, int t, int k, int packet_tok,
+                            size_t s_book, size_t s_item, void* stream)
+{
+    const int bits = packet_bits(batch, nb, t, k, packet_tok);
+    if (bits < 0)
+        return fail(MVQ_EINVAL, "idx_pack_packets: bad shape B=%d nb=%d T=%d K=%d packet_tok=%d (nb, packet_tok <= 255, ceil(log2 K) <= 24)",
+                    batch, nb, t, k, packet_tok);
+    if (batch == 0 || t == 0 || nb == 0 || bits == 0) return MVQ_OK;          // no output byte
+    if (!idx || !bodies) return fail(MVQ_EINVAL, "idx_pack_packets: null tensor");
+    hipError_t e = mvq::launch_idx_pack_packets(idx, bodies, batch, nb, t, k, bits, packet_tok, s_book, s_item, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "idx_pack_packets");
+}
+
+int mvq_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_t* idx, uint8_t* nb_valid, int batch, int nb, int t,
+                           int k, int packet_tok, void* stream)
+{
+    const int bits = packet_bits(batch, nb, t, k, packet_tok);
+    if (bits < 0)
+        return fail(MVQ_EINVAL, "idx_unpack_packets: bad shape B=%d nb=%d T=%d K=%d packet_tok=%d (nb, packet_tok <= 255, ceil(log2 K) <= 24)",
+                    batch, nb, t, k, packet_tok);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!nb_recv || !nb_valid || (nb > 0 && !idx) || (nb > 0 && bits > 0 && !bodies))
+        return fail(MVQ_EINVAL, "idx_unpack_packets: null tensor");
+    hipError_t e = mvq::launch_idx_unpack_packets(bodies, nb_recv, idx, nb_valid, batch, nb, t, k, bits, packet_tok, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "idx_unpack_packets");
+}
+
+int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,
+                               int t, int nb_use, int k, size_t out_sb, size_t out_sd, void* stream)
+{
+    if (!nb_valid) return mvq_rvq_dequant_f32(idx, books, q_out, batch, dim, t, nb_use, k, out_sb, out_sd, stream);
+    if (batch < 0 || t < 0 || dim <= 0 || dim % 4 != 0 || nb_use < 0 || k <= 0)
+        return fail(MVQ_EINVAL, "rvq_dequant_layers: bad shape B=%d D=%d T=%d nb=%d K=%d", batch, dim, t, nb_use, k);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!q_out || (nb_use > 0 && (!idx || !books))) return fail(MVQ_EINVAL, "rvq_dequant_layers: null tensor");
+    if (reinterpret_cast<uintptr_t>(books) & 15) return fail(MVQ_EINVAL, "rvq_dequant_layers: books must be 16-byte aligned");
+    if (out_sb == 0 && out_sd == 0) { out_sb = (size_t)dim * t; out_sd = (size_t)t; }
+    hipError_t e = mvq::launch_rvq_dequant_layers(idx, books, nb_valid, q_out, batch, dim, t, nb_use, k, out_sb, out_sd, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "rvq_dequant_layers");
+}
+
 int mvq_dac_rvq_prepare_f32(const float* codebook, float* cb_normalised, float* cb_norm2, int nq, int k, int dc, void* stream)
 {
     if (nq < 0 || k <= 0 || dc <= 0) return fail(MVQ_EINVAL, "dac_rvq_prepare: bad shape");

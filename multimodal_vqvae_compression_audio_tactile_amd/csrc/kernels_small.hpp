@@ -120,4 +120,11 @@ hipError_t launch_rvq_dequant(const int64_t* idx, const float* books, float* q, 
                               size_t out_sb, size_t out_sd, hipStream_t s);
 hipError_t launch_dac_rvq_from_codes(const int64_t* codes, const float* cb, const float* out_w, const float* out_b, float* zq,
                                      float* z_p, int B, int C, int T, int nq, int K, int Dc, hipStream_t s);
+// packets.hip: the lossy-channel receiver (bits = ceil(log2 K) <= 24, ptok >= 1)
+hipError_t launch_idx_pack_packets(const int64_t* idx, uint8_t* bodies, int B, int nb, int T, int K, int bits, int ptok,
+                                   size_t s_book, size_t s_item, hipStream_t s);
+hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_t* idx, uint8_t* nb_valid, int B, int nb,
+                                     int T, int K, int bits, int ptok, hipStream_t s);
+hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
+                                     int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
 }  // namespace mvq

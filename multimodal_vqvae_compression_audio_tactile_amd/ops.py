@@ -490,6 +490,97 @@ def rvq_dequant(idx, books, n_books_use=None, out=None, out_strides=None):
     return out
 
 
+def _nb_valid_u8(nb_valid, B, T, device, name):
+    if not isinstance(nb_valid, torch.Tensor) or nb_valid.device != device:
+        raise MvqError(f"{name}: nb_valid must be a tensor on the device of idx")
+    if nb_valid.dtype != torch.uint8 or tuple(nb_valid.shape) != (B, T):
+        raise MvqError(f"{name}: nb_valid must be uint8 [B={B}, T={T}], got {nb_valid.dtype} {tuple(nb_valid.shape)}")
+    return nb_valid.contiguous()
+
+
+def rvq_dequant_layers(idx, books, nb_valid, n_books_use=None, out=None, out_strides=None):
+    """rvq_dequant with a per-token book count: token (b, t) sums its first min(n_books_use, nb_valid[b, t]) books (a count of 0
+    gives +0: a lost token).  nb_valid: uint8 [B, T] on the device, or None (= rvq_dequant)."""
+    if nb_valid is None:
+        return rvq_dequant(idx, books, n_books_use, out=out, out_strides=out_strides)
+    idx = _codes_i64(idx, "idx"); books = _dev(books, "books")
+    if idx.dim() != 3:
+        raise MvqError(f"rvq_dequant_layers: idx must be [n_books, B, T], got {tuple(idx.shape)}")
+    if books.dim() != 3 or idx.device != books.device:
+        raise MvqError("rvq_dequant_layers: books must be [n_books, K, D] on idx's device")
+    nb_all, K, D = books.shape
+    nb = min(idx.shape[0], nb_all) if n_books_use is None else max(0, min(int(n_books_use), idx.shape[0], nb_all))
+    _, B, T = idx.shape
+    nbv = _nb_valid_u8(nb_valid, B, T, idx.device, "rvq_dequant_layers")
+    if out is None:
+        out = torch.empty(B, D, T, device=books.device, dtype=torch.float32)
+        out_strides = (D * T, T)
+    elif (not isinstance(out, torch.Tensor) or out.device != books.device or out.dtype != torch.float32
+          or not out.is_contiguous() or out_strides is None):
+        raise MvqError("rvq_dequant_layers: out must be a contiguous fp32 tensor on the books' device, given with out_strides")
+    sb, sd = int(out_strides[0]), int(out_strides[1])
+    if sb < 0 or sd < 0 or (B and T and (B - 1) * sb + (D - 1) * sd + T > out.numel()):
+        raise MvqError(f"rvq_dequant_layers: [B={B}, D={D}, T={T}] at strides ({sb}, {sd}) reaches past the {out.numel()}-element out")
+    check(_lib.lib().mvq_rvq_dequant_layers_f32(idx.data_ptr(), books.data_ptr(), nbv.data_ptr(), out.data_ptr(), B, D, T, nb, K,
+                                                sb, sd, _stream()), "mvq_rvq_dequant_layers_f32")
+    return out
+
+
+PACKET_MAX_BITS = 24           # the packet kernels cover ceil(log2 K) <= 24, nb and packet_tok <= 255 (include/mvq.h)
+
+
+def _packet_shape(name, k, nb, T, packet_tok):
+    """(P, body_full) after the checks the C ABI repeats."""
+    from .packets import body_bytes, n_packets
+    from .bitstream import index_bits
+    k, nb, T, packet_tok = int(k), int(nb), int(T), int(packet_tok)
+    if k < 1 or index_bits(k) > PACKET_MAX_BITS or not 0 <= nb <= 255 or T < 0 or not 1 <= packet_tok <= 255:
+        raise MvqError(f"{name}: K={k}, nb={nb}, T={T}, packet_tok={packet_tok} outside the packet kernels "
+                       f"(ceil(log2 K) <= {PACKET_MAX_BITS}, nb <= 255, 1 <= packet_tok <= 255)")
+    return n_packets(T, packet_tok), body_bytes(packet_tok, nb, k)
+
+
+def idx_pack_packets(idx, k, packet_tok, book_dim=0):
+    """Indices -> packet bodies uint8 [B, P, body_full] (packets.py's pack_bodies per item, bit for bit; indices clamped to
+    [0, K)).  idx is [nb, B, T] (``book_dim=0``, the RVQ indices) or [B, nb, T] (``book_dim=1``, DAC codes); read in place."""
+    idx = _codes_i64(idx, "idx")
+    if idx.dim() != 3 or book_dim not in (0, 1):
+        raise MvqError(f"idx_pack_packets: idx must be [nb, B, T] (book_dim=0) or [B, nb, T] (book_dim=1), got {tuple(idx.shape)}")
+    if book_dim == 0:
+        nb, B, T = idx.shape
+        s_book, s_item = B * T, T
+    else:
+        B, nb, T = idx.shape
+        s_book, s_item = T, nb * T
+    P, full = _packet_shape("idx_pack_packets", k, nb, T, packet_tok)
+    bodies = torch.empty(B, P, full, device=idx.device, dtype=torch.uint8)
+    check(_lib.lib().mvq_idx_pack_packets_u8(idx.data_ptr(), bodies.data_ptr(), B, nb, T, int(k), int(packet_tok), s_book, s_item,
+                                             _stream()), "mvq_idx_pack_packets_u8")
+    return bodies
+
+
+def idx_unpack_packets(bodies, nb_recv, k, nb, T, packet_tok):
+    """bodies uint8 [B, P, body_full] and nb_recv uint8 [B, P] (books of each packet that arrived, 0 = lost) ->
+    (idx int64 [nb, B, T], nb_valid uint8 [B, T]): packets.py's unpack_bodies per item, bit for bit."""
+    for t, name in ((bodies, "bodies"), (nb_recv, "nb_recv")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise MvqError(f"idx_unpack_packets: {name} must be a uint8 tensor on a HIP device")
+        if t.dtype != torch.uint8:
+            raise MvqError(f"idx_unpack_packets: {name} must be uint8, got {t.dtype}")
+    P, full = _packet_shape("idx_unpack_packets", k, nb, T, packet_tok)
+    if bodies.dim() != 3 or tuple(bodies.shape[1:]) != (P, full):
+        raise MvqError(f"idx_unpack_packets: bodies {tuple(bodies.shape)} for [B, P={P}, body_full={full}]")
+    B = bodies.shape[0]
+    if nb_recv.device != bodies.device or tuple(nb_recv.shape) != (B, P):
+        raise MvqError(f"idx_unpack_packets: nb_recv {tuple(nb_recv.shape)} for [B={B}, P={P}] on the device of bodies")
+    bodies, nb_recv = bodies.contiguous(), nb_recv.contiguous()
+    idx = torch.empty(int(nb), B, int(T), device=bodies.device, dtype=torch.int64)
+    nb_valid = torch.empty(B, int(T), device=bodies.device, dtype=torch.uint8)
+    check(_lib.lib().mvq_idx_unpack_packets(bodies.data_ptr(), nb_recv.data_ptr(), idx.data_ptr(), nb_valid.data_ptr(), B, int(nb),
+                                            int(T), int(k), int(packet_tok), _stream()), "mvq_idx_unpack_packets")
+    return idx, nb_valid
+
+
 def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True):
     """upstream ResidualVectorQuantize.from_codes: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T] or None).
     z_q = sum over stages of out_proj_i(codebook_i[code_i]) in stage order; the first nq stages of the stacked weights."""

@@ -196,13 +196,18 @@ class ResidualVQEMA(nn.Module):
         return ops.rvq_ema_forward(z, self.stacked(), n_books_use, return_indices=return_indices)
 
     @torch.no_grad()
-    def from_indices(self, idx, n_books_use: Optional[int] = None, out=None, out_strides=None):
+    def from_indices(self, idx, n_books_use: Optional[int] = None, out=None, out_strides=None, nb_valid=None):
         """The receiver's dequantisation: idx[nb, B, T] -> qD[B, D, T] = ((+0 + e_0[idx_0]) + e_1[idx_1]) + ... over the first
-        min(nb, n_books_use) books.  (The forward's straight-through sum needs the encoder-side residual: round-off apart.)"""
+        min(nb, n_books_use) books.  (The forward's straight-through sum needs the encoder-side residual: round-off apart.)
+        ``nb_valid`` (uint8 [B, T] on the device): token (b, t) sums only its first nb_valid[b, t] of those books -- what arrived
+        over a lossy channel; 0 gives a zero vector."""
         if len(self.books) == 0:
             if out is None:
                 return torch.zeros(idx.shape[1], self.dim, idx.shape[2], device=idx.device)
             return out.zero_()
+        if nb_valid is not None:
+            return ops.rvq_dequant_layers(idx.to(self.books[0].device), self.stacked(), nb_valid, n_books_use, out=out,
+                                          out_strides=out_strides)
         return ops.rvq_dequant(idx.to(self.books[0].device), self.stacked(), n_books_use, out=out, out_strides=out_strides)
 
     @torch.no_grad()
@@ -395,7 +400,8 @@ class _ProposedBase(nn.Module):
 
     # ------------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
-    def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False):
+    def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
+                       conceal="predict", plc=None):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -404,7 +410,16 @@ class _ProposedBase(nn.Module):
 
         z_pred depends on the loop only through column 0 of chunks s > 0 (z_run[s-1], the LAST token of the chunk before,
         which itself does not depend on the loop), so the receiver is two dependent passes instead of one pass per chunk
-        (_rx_two_pass); the result is bit-equal to the per-chunk loop."""
+        (_rx_two_pass); the result is bit-equal to the per-chunk loop.
+
+        Lossy channel: ``nb_valid`` ([B, T_lat] uint8 on the device: the books of each token that arrived; bool: all or none;
+        None = all, today's path).  A token sums only the books it has (qD over the first nb_valid[b, t] books); a token with
+        none is LOST and takes the audio-driven prediction uncorrected, z_hat = proj_up(0) + z_pred.  The recursion always runs
+        on those values; loss changes qD alone, so the two passes stay valid.  ``conceal`` is a post-pass over that z_run:
+        "predict" none; "zero" lost tokens become 0 (the unconcealed baseline AllPredPLC feeds its predictor); "plc"
+        where(lost, plc.predict(z_run * ~lost, qa), z_run) with ``plc`` an AllPredPLC.  The mask is never read on the host: the
+        launch sequence depends on shapes and ``conceal`` only, so a captured graph replays with another loss pattern written
+        into the same nb_valid buffer."""
         if idx is None:
             raise MvqError("decode_latents: idx (the RVQ indices [n_books, B, T_lat]) is required")
         dev = self.proj_up.weight.device
@@ -413,6 +428,22 @@ class _ProposedBase(nn.Module):
             raise MvqError(f"decode_latents: idx must be [n_books, B, T_lat], got {tuple(idx.shape)}")
         _, B, Tlat = idx.shape
         C = self.proj_up.out_channels
+        if conceal not in ("predict", "zero", "plc"):
+            raise MvqError(f"decode_latents: conceal must be 'predict', 'zero' or 'plc', not {conceal!r}")
+        if conceal == "plc":
+            if tactile_only:
+                raise MvqError("decode_latents: conceal='plc' predicts from the audio: not with tactile_only")
+            if plc is None or not hasattr(plc, "predict"):
+                raise MvqError("decode_latents: conceal='plc' needs plc (an AllPredPLC)")
+            if Tlat > ops.ATTN_SEQ_MAX_T:
+                raise MvqError(f"decode_latents: conceal='plc' at T_lat={Tlat} exceeds attention_seq's {ops.ATTN_SEQ_MAX_T} tokens")
+        if nb_valid is None:
+            conceal = "predict"                                               # every token arrived whole: nothing to conceal
+        else:
+            if not isinstance(nb_valid, torch.Tensor) or nb_valid.dtype not in (torch.uint8, torch.bool):
+                raise MvqError("decode_latents: nb_valid must be a uint8 or bool tensor [B, T_lat]")
+            if tuple(nb_valid.shape) != (B, Tlat):
+                raise MvqError(f"decode_latents: nb_valid {tuple(nb_valid.shape)} does not match idx's [B={B}, T_lat={Tlat}]")
         if not tactile_only:                 # the audio side must describe the same items as idx (checked before any launch)
             if qa is None:
                 if audio_codes is None:
@@ -422,18 +453,33 @@ class _ProposedBase(nn.Module):
                     raise MvqError(f"decode_latents: audio codes {tuple(audio_codes.shape)} do not match idx's batch B={B}")
             elif qa.dim() != 3 or qa.shape[0] != B or qa.shape[1] != C:
                 raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
+            Ta = (audio_codes if qa is None else qa).shape[2]
+            if conceal == "plc" and not 0 < Ta <= ops.ATTN_SEQ_MAX_T:
+                raise MvqError(f"decode_latents: conceal='plc' needs 1..{ops.ATTN_SEQ_MAX_T} audio tokens, got {Ta}")
         if B == 0 or Tlat == 0:
             return torch.zeros(B, C, Tlat, device=dev)
+        if nb_valid is not None:
+            nb_valid = nb_valid.to(dev).contiguous()
+            if nb_valid.dtype == torch.bool:                                  # all or none: 255 caps at the books there are
+                nb_valid = nb_valid.view(torch.uint8) * 255
         if tactile_only:                                                      # z_pred absent, as in the transmitter
-            return self._pu(self.vq.from_indices(idx, books_use))
+            z_run = self._pu(self.vq.from_indices(idx, books_use, nb_valid=nb_valid))
+            return z_run if conceal == "predict" else ops.plc_mask_fill(z_run, None, nb_valid == 0)[0]
         if qa is None:
             qa = self.A_QUANT.from_codes(audio_codes.to(dev))[0]
         qa = ops._dev(qa.to(dev), "qa")                                       # fp32, contiguous
         if qa.shape[0] != B or qa.shape[1] != C:
             raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
-        return self._rx_two_pass(qa, idx, books_use)
+        z_run = self._rx_two_pass(qa, idx, books_use, nb_valid)
+        if conceal == "predict":
+            return z_run
+        lost = nb_valid == 0
+        if conceal == "zero":
+            return ops.plc_mask_fill(z_run, None, lost)[0]                    # z_run * ~lost
+        zt_in, _ = ops.plc_mask_fill(z_run, None, lost)                       # what AllPredPLC's predictor is fed
+        return ops.plc_mask_fill(z_run, plc.predict(zt_in, qa), lost, want_zt_in=False)[1]
 
-    def _rx_two_pass(self, qa, idx, books_use):
+    def _rx_two_pass(self, qa, idx, books_use, nb_valid=None):
         """Layout: every [.., B*Tlat] tensor of the plan is token-folded and PADDED per chunk -- column (b*NC + c)*16 + i holds
         token c*16 + i of item b (NC chunks, the tail chunk's columns past its end are filler) -- so "chunk" is a batch index of
         stride 16 and every chunk with 16 queries and 16 keys is ONE attention call (chunk as batch).  The tail chunk and chunks
@@ -463,7 +509,7 @@ class _ProposedBase(nn.Module):
         K, V = L["k"](kv), L["v"](kv)
         # qD of every token in one dequantisation
         qD_p = torch.empty(1, CODE_DIM, N, device=dev)
-        self.vq.from_indices(idx, books_use, out=qD_p, out_strides=(P, N))
+        self.vq.from_indices(idx, books_use, out=qD_p, out_strides=(P, N), nb_valid=nb_valid)   # loss changes qD alone
 
         def attend(Q, tq, q_strides, q_col_of):
             ctx = torch.empty_like(Q)
@@ -554,17 +600,18 @@ class ProposedEval(_ProposedBase):
 
     # ---------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
-    def decode(self, audio_codes, idx, books_use=None):
-        """Receiver: T_DEC(decode_latents(audio_codes, idx)) -- the waveform from the transmitted codes alone."""
-        return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use))
+    def decode(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None):
+        """Receiver: T_DEC(decode_latents(audio_codes, idx)) -- the waveform from the transmitted codes alone.  ``nb_valid`` /
+        ``conceal`` / ``plc``: the lossy-channel arguments of decode_latents."""
+        return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc))
 
     @torch.no_grad()
-    def decode_latents_tactile_only(self, idx, books_use=None):
-        return self.decode_latents(None, idx, books_use=books_use, tactile_only=True)
+    def decode_latents_tactile_only(self, idx, books_use=None, nb_valid=None, conceal="predict"):
+        return self.decode_latents(None, idx, books_use=books_use, tactile_only=True, nb_valid=nb_valid, conceal=conceal)
 
     @torch.no_grad()
-    def decode_tactile_only(self, idx, books_use=None):
-        return self.T_DEC(self.decode_latents_tactile_only(idx, books_use))
+    def decode_tactile_only(self, idx, books_use=None, nb_valid=None, conceal="predict"):
+        return self.T_DEC(self.decode_latents_tactile_only(idx, books_use, nb_valid, conceal))
 
     @torch.no_grad()
     def compress(self, a_1T, t_1T, books_use=None):
@@ -589,6 +636,53 @@ class ProposedEval(_ProposedBase):
         idx_t = torch.from_numpy(np.stack(idx, axis=1)).to(dev)
         codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
         return self.decode(codes_t, idx_t, books_use=books_use)
+
+    @torch.no_grad()
+    def compress_packets(self, a_1T, t_1T, books_use=None, packet_tok=None):
+        """-> (infos, tactile_packets, audio_payloads) for a lossy channel: per item the session parameters
+        packets.StreamInfo(K, nb, T_lat, packet_tok) (sent reliably out of band), the list of framed packets (``bytes``, packets.py)
+        of its RVQ indices, and the audio codes as a v1 payload (the audio stream is assumed delivered, as the reference's PLC
+        model does).  The packet bodies of the batch are packed on the device and come back in one device->host copy."""
+        from . import bitstream, packets
+        packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
+        _, codes, idx = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use)
+        nb, B, T = idx.shape
+        info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
+        bodies = ops.idx_pack_packets(idx, info.K, packet_tok).cpu().numpy()
+        codes = codes.cpu().numpy()
+        k_audio = self.A_QUANT.codebook_size
+        return ([info] * B, [packets.frame(bodies[b], info) for b in range(B)],
+                [bitstream.pack_indices(codes[b], k_audio) for b in range(B)])
+
+    @torch.no_grad()
+    def decompress_packets(self, infos, tactile_packets, audio_payloads, books_use=None, conceal="predict", plc=None):
+        """-> (y [B,1,T], lost [B,T_lat] bool) from whatever packets arrived (missing, reordered, duplicated, thinned; items of
+        one StreamInfo): packets.gather per item on the host, ONE upload of the bodies and per-packet book counts, the bit
+        unpacking on the device, then decode(nb_valid=...).  ``lost``: the tokens no book of which arrived."""
+        from . import bitstream, packets
+        if not (len(infos) == len(tactile_packets) == len(audio_payloads)):
+            raise MvqError("decompress_packets: one StreamInfo, one packet list and one audio payload per item")
+        dev = self.proj_up.weight.device
+        B = len(infos)
+        if B == 0:
+            raise MvqError("decompress_packets: no items")
+        info = packets.StreamInfo(*infos[0])
+        if any(tuple(i) != tuple(info) for i in infos):
+            raise ValueError("decompress_packets: the items of a batch must share one StreamInfo")
+        if info.K != self.vq.n_embed:
+            raise ValueError(f"decompress_packets: the stream has K = {info.K}, the model's codebook has {self.vq.n_embed}")
+        P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
+        host = np.empty(B * P * (full + 1), np.uint8)                         # bodies, then nb_recv: one upload
+        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:].reshape(B, P)
+        for b in range(B):
+            hb[b], hr[b] = packets.gather(tactile_packets[b], info)
+        codes = [self._payload(bitstream, p, self.A_QUANT.codebook_size, "audio") for p in audio_payloads]
+        up = torch.from_numpy(host).to(dev)
+        idx, nb_valid = ops.idx_unpack_packets(up[:B * P * full].view(B, P, full), up[B * P * full:].view(B, P), info.K, info.nb,
+                                               info.T, info.packet_tok)
+        codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
+        y = self.decode(codes_t, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc)
+        return y, nb_valid == 0
 
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):

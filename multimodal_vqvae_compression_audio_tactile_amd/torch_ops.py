@@ -16,6 +16,9 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   decoder_bwd_input           mvq_decoder_fwd_saving_f32 + mvq_decoder_bwd_input_f32: dL/dz of T_DEC, ...5.py:393
   rvq_dequant                 mvq_rvq_dequant_f32        receiver: ResidualVQEMA indices -> summed code vectors [B,D,T]
   dac_rvq_from_codes          mvq_dac_rvq_from_codes_f32 receiver: upstream ResidualVectorQuantize.from_codes -> (z_q, z_p)
+  rvq_dequant_layers          mvq_rvq_dequant_layers_f32 lossy receiver: the same over the first nb_valid[b,t] books of each token
+  idx_pack_packets            mvq_idx_pack_packets_u8    lossy receiver: indices -> packet bodies uint8 [B,P,body_full] (packets.py)
+  idx_unpack_packets          mvq_idx_unpack_packets     lossy receiver: bodies + per-packet book counts -> (idx, nb_valid)
   attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
   mel_ssim_f32                mvq_mel_ssim_f32           mel ST-SIM of column-listed image pairs (PLC/PLC1_eval.py:270-333)
 
@@ -139,7 +142,8 @@ def _(z, gy, stack):
 
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
-              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes")
+              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes",
+              "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets")
 
 
 @torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
@@ -182,3 +186,36 @@ def dac_rvq_from_codes(codes: Tensor, codebook: Tensor, out_w: Tensor, out_b: Te
 def _(codes, codebook, out_w, out_b):
     B, nq, T = codes.shape
     return out_w.new_empty(B, out_w.shape[1], T), out_w.new_empty(B, nq * codebook.shape[-1], T)
+
+
+@torch.library.custom_op(f"{NS}::rvq_dequant_layers", mutates_args=())
+def rvq_dequant_layers(idx: Tensor, books: Tensor, nb_valid: Tensor, n_use: int) -> Tensor:
+    return ops.rvq_dequant_layers(idx, books, nb_valid, n_books_use=n_use)
+
+
+@rvq_dequant_layers.register_fake
+def _(idx, books, nb_valid, n_use):
+    return books.new_empty(idx.shape[1], books.shape[-1], idx.shape[2])
+
+
+@torch.library.custom_op(f"{NS}::idx_pack_packets", mutates_args=())
+def idx_pack_packets(idx: Tensor, k: int, packet_tok: int, book_dim: int) -> Tensor:
+    return ops.idx_pack_packets(idx, k, packet_tok, book_dim)
+
+
+@idx_pack_packets.register_fake
+def _(idx, k, packet_tok, book_dim):
+    from .packets import body_bytes, n_packets
+    nb, B = (idx.shape[0], idx.shape[1]) if book_dim == 0 else (idx.shape[1], idx.shape[0])
+    return idx.new_empty(B, n_packets(idx.shape[2], packet_tok), body_bytes(packet_tok, nb, k), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f"{NS}::idx_unpack_packets", mutates_args=())
+def idx_unpack_packets(bodies: Tensor, nb_recv: Tensor, k: int, nb: int, t: int, packet_tok: int) -> Tuple[Tensor, Tensor]:
+    return ops.idx_unpack_packets(bodies, nb_recv, k, nb, t, packet_tok)
+
+
+@idx_unpack_packets.register_fake
+def _(bodies, nb_recv, k, nb, t, packet_tok):
+    B = bodies.shape[0]
+    return bodies.new_empty(nb, B, t, dtype=torch.int64), bodies.new_empty(B, t, dtype=torch.uint8)
