@@ -39,7 +39,8 @@ extern "C" {
 /* ABI version.  3 (round 5): whole-stack entry points (additive since, same version: the full-sequence attention pair
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
- * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32).
+ * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
+ * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -534,6 +535,30 @@ int mvq_resample_f32(const float* x, const float* kern, float* y, int batch, int
  * A slice is clamped to its row on the device (0 <= off, off + len <= pitch) and to lout_pitch output samples. */
 int mvq_resample_ragged_f32(const float* x, const float* kern, float* y, const int32_t* off, const int32_t* len, int32_t* len_out,
                             int batch, int pitch, int lout_pitch, int orig, int newf, int width, int ks, void* stream);
+
+/* ---- streaming receiver: session state in fixed device buffers, updated in place by the kernel ----
+ * mvq_resample_stream_f32: mvq_resample_f32 fed piece by piece, for pure decimation (newf == 1 after the gcd; anything else is
+ * MVQ_EUNSUPPORTED).  `consumed` = samples of the item given to earlier calls (a multiple of orig), x_new[batch, n_new] the next
+ * piece; n_new must be a multiple of orig unless `final` (MVQ_EINVAL).  The call writes y[batch, len_out], the outputs
+ * n in [done(consumed), done(consumed + n_new)) of the whole-signal resample, done(L) = max(0, L/orig - hold),
+ * hold = ceil(width/orig): output n reads xpad[n*orig .. n*orig + ks), complete once sample n*orig + ks - width - 1 has arrived
+ * (24 kHz -> 3 kHz: orig 8, width 49, ks 106: sample 8n + 56).  final = 1 pads zeros on the right and flushes up to
+ * ceil((consumed + n_new)/orig).  len_out must equal that count (MVQ_EINVAL: the message names it).
+ * STATE LAYOUT: state[batch, S] fp32, S = hold*orig + width (105 for 24 -> 3 kHz; S <= 1024, else MVQ_EUNSUPPORTED), row b holds the
+ * last S samples of (zeros | x received so far), oldest first; a new session starts from all zeros (the `width` zeros of the
+ * left padding and hold*orig samples no output reads).  The kernel moves it up by n_new samples after the outputs are written
+ * (one block per item, a barrier between).  Every output is the fma chain of mvq_resample_f32 (k ascending, the taps that fall
+ * on padding skipped): concatenated, the pieces equal the whole-signal call bit for bit.  With consumed >= S and a fixed n_new the
+ * launch does not depend on `consumed`, so a captured steady step replays. */
+int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new, long long consumed,
+                            int final, int len_out, int orig, int newf, int width, int ks, void* stream);
+/* mvq_stream_window_f32: the decoder window of a session.  hist[batch, c, cap] (row pitch cap, the first h_in columns valid) and
+ * z_new[batch, c, n] (contiguous) -> win[batch, c, h_in + n] = [hist | z_new] (contiguous, a buffer of its own), then
+ * hist <- the last h_out columns of win, all in ONE launch: a block owns 32 (b, c) rows, reads them completely, and rewrites only
+ * them after a barrier, so the in-place update has no cross-block hazard.  MVQ_EINVAL before any launch on h_out > h_in + n,
+ * h_in or h_out > cap, a negative size, or a null pointer with a non-empty shape. */
+int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, float* win, int h_out, int cap, int batch, int c,
+                          void* stream);
 
 /* Optimiser step of the training config (torch.optim.AdamW + clip_grad_norm_, Training/compare_dacvsproposal_5.py:367,394-395):
  *   sumsq_partial : partial[n_partial] block sums of x^2 (their total is the squared gradient norm), n_partial <= 4096

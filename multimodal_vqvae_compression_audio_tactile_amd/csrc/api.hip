@@ -1183,6 +1183,47 @@ int mvq_resample_f32(const float* x, const float* kern, float* y, int batch, int
     return e == hipSuccess ? MVQ_OK : hipfail(e, "resample");
 }
 
+int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new, long long consumed,
+                            int final, int len_out, int orig, int newf, int width, int ks, void* stream)
+{
+    if (batch < 0 || n_new < 0 || consumed < 0 || len_out < 0 || orig <= 0 || newf <= 0 || width < 0 || ks != 2 * width + orig)
+        return fail(MVQ_EINVAL, "resample_stream: bad shape (ks must be 2*width + orig)");
+    if (newf != 1) return fail(MVQ_EUNSUPPORTED, "resample_stream: pure decimation only (newf = %d after the gcd)", newf);
+    const long long hold = (width + orig - 1) / orig;
+    const long long ns = hold * orig + width;
+    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "resample_stream: state of %lld samples exceeds 1024", ns);
+    if (consumed % orig) return fail(MVQ_EINVAL, "resample_stream: consumed = %lld is no multiple of orig = %d", consumed, orig);
+    if (!final && n_new % orig)
+        return fail(MVQ_EINVAL, "resample_stream: n_new = %d is no multiple of orig = %d (only the final call may be)", n_new, orig);
+    const long long q0 = consumed / orig;
+    const long long done = q0 > hold ? q0 - hold : 0;
+    const long long q1 = final ? (consumed + n_new + orig - 1) / orig : q0 + n_new / orig - hold;
+    const long long n_out = q1 > done ? q1 - done : 0;
+    if (n_out != len_out) return fail(MVQ_EINVAL, "resample_stream: len_out = %d, this call completes %lld outputs", len_out, n_out);
+    if (batch == 0) return MVQ_OK;
+    if (!kern || !state || (!x_new && n_new) || (!y && n_out)) return fail(MVQ_EINVAL, "resample_stream: null tensor");
+    const int base = (int)(q0 < hold ? (hold - q0) * orig : 0);
+    const int lead = (int)(consumed < ns ? ns - consumed : 0);
+    hipError_t e = mvq::launch_resample_stream(x_new, kern, state, y, batch, n_new, (int)n_out, orig, ks, (int)ns, base, lead, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream");
+}
+
+int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, float* win, int h_out, int cap, int batch, int c,
+                          void* stream)
+{
+    if (h_in < 0 || n < 0 || h_out < 0 || cap < 0 || batch < 0 || c < 0)
+        return fail(MVQ_EINVAL, "stream_window: negative size");
+    if (h_in > cap || h_out > cap) return fail(MVQ_EINVAL, "stream_window: h_in = %d / h_out = %d exceed the history capacity %d", h_in, h_out, cap);
+    if ((long long)h_out > (long long)h_in + n) return fail(MVQ_EINVAL, "stream_window: h_out = %d exceeds h_in + n = %d + %d", h_out, h_in, n);
+    if ((long long)h_in + n > (1 << 20)) return fail(MVQ_EINVAL, "stream_window: window of %lld columns", (long long)h_in + n);
+    const size_t rows = (size_t)batch * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (!win || (!hist && (h_in || h_out)) || (!z_new && n)) return fail(MVQ_EINVAL, "stream_window: null tensor");
+    if (rows > (size_t)0x7FFFFFFF * 32) return fail(MVQ_EINVAL, "stream_window: too many rows");
+    hipError_t e = mvq::launch_stream_window(hist, z_new, win, h_in, n, h_out, cap, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window");
+}
+
 int mvq_sumsq_partial_f32(const float* x, float* partial, int n_partial, size_t n, void* stream)
 {
     if (!partial || n_partial <= 0 || n_partial > 4096 || (!x && n)) return fail(MVQ_EINVAL, "sumsq_partial: bad argument");

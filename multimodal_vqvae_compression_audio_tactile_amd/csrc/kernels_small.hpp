@@ -127,4 +127,9 @@ hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_re
                                      int T, int K, int bits, int ptok, hipStream_t s);
 hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
                                      int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
+// stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024)
+hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
+                                hipStream_t s);
+hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, float* y, int B, int n_new, int n_out, int orig,
+                                  int ks, int S, int base, int lead, hipStream_t s);
 }  // namespace mvq

@@ -1,0 +1,107 @@
+// stream.hip -- the streaming receiver's two state kernels (include/mvq.h: mvq_stream_window_f32, mvq_resample_stream_f32).
+// Both keep their session state in a fixed device buffer that the kernel itself updates in place, so the steady step of a
+// session is the same launch sequence on the same addresses every time (a captured graph replays it).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "det_math.hpp"
+#include "kernels_small.hpp"
+
+namespace mvq {
+namespace {
+constexpr int WIN_ROWS = 32;          // (b, c) rows of one block of stream_window_kernel
+}  // namespace
+
+// win[r][0 .. h_in + n) = [hist[r][0 .. h_in) | z_new[r][0 .. n)], then hist[r][0 .. h_out) = the last h_out columns of win[r].
+// r = b*C + c; hist rows have the fixed pitch `cap`.  A block owns WIN_ROWS consecutive rows: phase 1 reads hist and z_new and
+// writes win (a buffer of its own), the barrier ends every read of the block's hist rows, phase 2 rewrites those rows from the
+// block's own part of win.  No row is touched by two blocks, so the in-place update has no cross-block hazard.
+__global__ __launch_bounds__(256) void stream_window_kernel(float* __restrict__ hist, const float* __restrict__ z_new, float* win,
+                                                            int h_in, int n, int h_out, int cap, size_t rows)
+{
+    const size_t row0 = (size_t)blockIdx.x * WIN_ROWS;
+    const int nrow = (int)(rows - row0 < (size_t)WIN_ROWS ? rows - row0 : (size_t)WIN_ROWS);
+    const int W = h_in + n;
+    const int total = nrow * W;
+    float* wb = win + row0 * (size_t)W;
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int r = e / W, j = e - r * W;
+        wb[e] = j < h_in ? hist[(row0 + r) * (size_t)cap + j] : z_new[(row0 + r) * (size_t)n + (j - h_in)];
+    }
+    __syncthreads();
+    const int skip = W - h_out;
+    const int total_h = nrow * h_out;
+    for (int e = threadIdx.x; e < total_h; e += 256) {
+        const int r = e / h_out, j = e - r * h_out;
+        hist[(row0 + r) * (size_t)cap + j] = wb[r * W + skip + j];
+    }
+}
+
+// Stateful decimation (newf == 1).  state[b][0 .. S), S = hold*orig + width with hold = ceil(width / orig), holds the last S
+// samples of (zeros | x received so far).  With v = [state | x_new] (S + n_new samples), output m of this call reads
+// v[base + m*orig + k], k < ks = 2*width + orig; `lead` leading samples of v are left padding and `S + n_new` is where the right
+// padding begins: taps outside [lead, S + n_new) are skipped, exactly the taps resample_kernel skips, so the fma chain (k
+// ascending) of an output is the one the whole-signal kernel runs.  One block per item: outputs first, then the barrier, then
+// the state moves up by n_new samples (each thread carries its elements in registers across a second barrier: a shift by less
+// than S overlaps itself).
+__global__ __launch_bounds__(256) void resample_stream_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
+                                                              float* __restrict__ state, float* __restrict__ y, int n_new, int n_out,
+                                                              int orig, int ks, int S, int base, int lead, int kern_in_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) float ksm[];
+    if (kern_in_lds) {
+        for (int e = threadIdx.x; e < ks; e += 256) ksm[e] = kern[e];
+        __syncthreads();
+    }
+    const float* kp = kern_in_lds ? ksm : kern;
+    const int b = blockIdx.x;
+    float* st = state + (size_t)b * S;
+    const float* xb = x_new + (size_t)b * n_new;
+    const int V = S + n_new;
+    for (int m = threadIdx.x; m < n_out; m += 256) {
+        const int j0 = base + m * orig;
+        const int k_lo = j0 < lead ? lead - j0 : 0;
+        int k_hi = ks; if (j0 + k_hi > V) k_hi = V - j0;
+        float acc = 0.0f;
+        for (int k = k_lo; k < k_hi; ++k) {
+            const int j = j0 + k;
+            acc = dfma(kp[k], j < S ? st[j] : xb[j - S], acc);
+        }
+        y[(size_t)b * n_out + m] = acc;
+    }
+    __syncthreads();
+    float keep[4];                                                       // S <= 1024 (checked by the entry point)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        const int j = i + n_new;
+        keep[u] = i < S ? (j < S ? st[j] : xb[j - S]) : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        if (i < S) st[i] = keep[u];
+    }
+}
+
+hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
+                                hipStream_t s)
+{
+    if (rows == 0 || h_in + n == 0) return hipSuccess;
+    const size_t blocks = (rows + WIN_ROWS - 1) / WIN_ROWS;
+    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, hist, z_new, win, h_in, n, h_out, cap, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, float* y, int B, int n_new, int n_out, int orig,
+                                  int ks, int S, int base, int lead, hipStream_t s)
+{
+    if (B == 0) return hipSuccess;
+    const size_t lds = (size_t)ks * sizeof(float);
+    const int in_lds = lds <= 48 * 1024;
+    hipLaunchKernelGGL(resample_stream_kernel, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out, orig, ks,
+                       S, base, lead, in_lds);
+    return hipGetLastError();
+}
+
+}  // namespace mvq

@@ -988,6 +988,57 @@ def resample_ragged(x, kern, off, length, orig, newf, width, lout_pitch):
     return y, lout
 
 
+def resample_stream_state(orig, width, batch, device):
+    """A new session's state for resample_stream: zeros [batch, ceil(width/orig)*orig + width] (layout: include/mvq.h)."""
+    hold = (int(width) + int(orig) - 1) // int(orig)
+    return torch.zeros(int(batch), hold * int(orig) + int(width), device=device, dtype=torch.float32)
+
+
+def resample_stream_out_len(consumed, n_new, orig, width, final=False):
+    """Outputs a resample_stream call completes after ``consumed`` samples: the count mvq_resample_stream_f32 checks."""
+    hold = (width + orig - 1) // orig
+    done = max(0, consumed // orig - hold)
+    upto = -(-(consumed + n_new) // orig) if final else (consumed + n_new) // orig - hold
+    return max(0, upto - done)
+
+
+def resample_stream(x_new, kern, state, consumed, orig, newf, width, final=False):
+    """The next piece x_new[B, n_new] of a decimated stream -> the outputs y[B, n_out] it completes (mvq_resample_stream_f32);
+    ``state`` (resample_stream_state) is updated in place, ``consumed`` = samples given to earlier calls."""
+    x_new = _dev(x_new, "x_new")
+    if x_new.dim() != 2 or state.dim() != 2 or state.shape[0] != x_new.shape[0] or state.dtype != torch.float32 \
+            or not state.is_cuda or not state.is_contiguous():
+        raise MvqError("resample_stream: x_new must be [B, n_new] and state a contiguous fp32 HIP tensor [B, S]")
+    B, n_new = x_new.shape
+    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
+    if orig <= 0 or width < 0 or state.shape[1] != (width + orig - 1) // orig * orig + width:
+        raise MvqError(f"resample_stream: state {tuple(state.shape)} does not fit orig={orig}, width={width}, B={B}")
+    if not final and n_new % orig:
+        raise MvqError(f"resample_stream: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
+    n_out = resample_stream_out_len(consumed, n_new, orig, width, final)
+    y = torch.empty(B, n_out, device=x_new.device, dtype=torch.float32)
+    check(_lib.lib().mvq_resample_stream_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, n_new, consumed,
+                                             int(bool(final)), n_out, orig, newf, width, kern.shape[1], _stream()),
+          "mvq_resample_stream_f32")
+    return y
+
+
+def stream_window(hist, h_in, z_new, h_out):
+    """win[B, C, h_in + n] = [hist[..., :h_in] | z_new[B, C, n]], then hist[..., :h_out] <- the last h_out columns of win, in one
+    launch (mvq_stream_window_f32).  hist: contiguous fp32 [B, C, cap], updated in place."""
+    z_new = _dev(z_new, "z_new")
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 3 or z_new.dim() != 3 or hist.dtype != torch.float32 or not hist.is_cuda \
+            or not hist.is_contiguous() or hist.shape[:2] != z_new.shape[:2] or hist.device != z_new.device:
+        raise MvqError("stream_window: hist must be a contiguous fp32 HIP tensor [B, C, cap] with z_new's batch and channels")
+    B, C, cap = hist.shape
+    n = z_new.shape[2]
+    h_in, h_out = int(h_in), int(h_out)
+    win = torch.empty(B, C, max(h_in, 0) + n, device=z_new.device, dtype=torch.float32)
+    check(_lib.lib().mvq_stream_window_f32(hist.data_ptr(), h_in, z_new.data_ptr(), n, win.data_ptr(), h_out, cap, B, C, _stream()),
+          "mvq_stream_window_f32")
+    return win
+
+
 # ---------------------------------------------------------------------------------- backward (row f1)
 def pack_conv1d_dgrad(w: torch.Tensor) -> torch.Tensor:
     """Conv1d weight w[Cout,Cin,ks] -> packed image of its input-gradient conv (flip + transpose)."""

@@ -162,7 +162,9 @@ def parse(packet, info: StreamInfo):
     return _parse(packet, _check(info))
 
 
-def _parse(packet, info: StreamInfo):
+def _parse(packet, info: StreamInfo, seq_base: int = 0):
+    """``seq_base``: the sequence number of ``info``'s packet 0 (a chunk of a longer stream).  A packet from before it comes back
+    as (negative seq, 0, b"") with only its magic and version checked: its chunk's shape is not ``info``'s."""
     data = bytes(packet)
     if len(data) < HEADER_BYTES:
         raise ValueError(f"packet: {len(data)} bytes, shorter than the {HEADER_BYTES}-byte header")
@@ -171,8 +173,11 @@ def _parse(packet, info: StreamInfo):
         raise ValueError(f"packet: bad magic {magic!r}")
     if version != VERSION:
         raise ValueError(f"packet: unsupported version {version}")
+    seq -= seq_base
+    if seq < 0:
+        return seq, 0, b""
     if seq >= info.P:
-        raise ValueError(f"packet: seq {seq} >= P = {info.P}")
+        raise ValueError(f"packet: seq {seq + seq_base} >= {seq_base} + P = {seq_base + info.P}")
     if ntok != info.ntok(seq):
         raise ValueError(f"packet {seq}: ntok {ntok}, the stream has {info.ntok(seq)} tokens there")
     if not 1 <= nb_sent <= info.nb:
@@ -194,16 +199,29 @@ def thin(packet, nb_keep: int, info: StreamInfo) -> bytes:
     return _HEADER.pack(MAGIC, VERSION, seq, ntok, nb_keep) + _first_books(np.frombuffer(body, np.uint8), ntok, nb_keep, info.K)
 
 
-def gather(packets: Iterable, info: StreamInfo):
+def gather(packets: Iterable, info: StreamInfo, seq_base: int = 0, late: Optional[list] = None):
     """Any iterable of received packets (missing, reordered, duplicated) -> (bodies uint8[P, body_full], nb_recv uint8[P]).
     Rows of packets that did not arrive stay zero with nb_recv = 0; of duplicates the one with more books is kept.  Raises
     ValueError on bad magic or version, seq >= P, an ntok that disagrees with ``info``, nb_sent outside 1..nb, or a body length
-    that disagrees with the header."""
+    that disagrees with the header.
+
+    ``seq_base`` (streaming, stream.py): ``info`` describes one chunk of a longer stream whose packets carry the stream's sequence
+    numbers seq_base .. seq_base + P - 1; row seq - seq_base takes the packet.  A number at or past seq_base + P raises as above.
+    One below seq_base belongs to a chunk already decoded: it is appended to ``late`` when that is a list (and otherwise
+    ignored), ValueError when ``late`` is None."""
     info = _check(info)
+    seq_base = int(seq_base)
+    if not 0 <= seq_base <= 2 ** 32 - info.P:
+        raise ValueError(f"gather: seq_base = {seq_base} with P = {info.P} packets leaves the 32-bit sequence number")
     full = body_bytes(info.packet_tok, info.nb, info.K)
     buf, got = bytearray(info.P * full), bytearray(info.P)                   # plain byte buffers: no numpy call per packet
     for pkt in packets:
-        seq, nb_sent, body = _parse(pkt, info)
+        seq, nb_sent, body = _parse(pkt, info, seq_base)
+        if seq < 0:
+            if late is None:
+                raise ValueError(f"packet: seq {seq + seq_base} < seq_base = {seq_base}")
+            late.append(pkt)
+            continue
         if nb_sent > got[seq]:                                               # a richer copy is never shorter: it covers the poorer
             buf[seq * full:seq * full + len(body)] = body
             got[seq] = nb_sent

@@ -401,7 +401,7 @@ class _ProposedBase(nn.Module):
     # ------------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
     def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
-                       conceal="predict", plc=None):
+                       conceal="predict", plc=None, z_prev=None, z_last_out=None):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -419,7 +419,15 @@ class _ProposedBase(nn.Module):
         "predict" none; "zero" lost tokens become 0 (the unconcealed baseline AllPredPLC feeds its predictor); "plc"
         where(lost, plc.predict(z_run * ~lost, qa), z_run) with ``plc`` an AllPredPLC.  The mask is never read on the host: the
         launch sequence depends on shapes and ``conceal`` only, so a captured graph replays with another loss pattern written
-        into the same nb_valid buffer."""
+        into the same nb_valid buffer.
+
+        Streaming (stream.py): a chunk depends on the ones before it through z_run[..., s-1] alone, so a sequence is decoded
+        piece by piece, each piece a whole number of 16-token chunks (the last may be shorter), with ``z_prev`` ([B, C] fp32 on the
+        device) = the LAST token of the piece before, as the recursion saw it; pass 2 then feeds it to chunk 0 where it feeds zero
+        today.  ``z_last_out`` ([B, C] fp32 on the device; may be the z_prev buffer itself) receives this piece's last token
+        BEFORE the ``conceal`` post-pass, which is what the next piece's z_prev must be ("zero" would otherwise erase a lost
+        last token that the whole-item recursion still reads).  Not with conceal="plc" (its predictor attends over the whole
+        sequence) and not with tactile_only (no recursion to carry).  Both None: today's launch sequence exactly."""
         if idx is None:
             raise MvqError("decode_latents: idx (the RVQ indices [n_books, B, T_lat]) is required")
         dev = self.proj_up.weight.device
@@ -437,6 +445,15 @@ class _ProposedBase(nn.Module):
                 raise MvqError("decode_latents: conceal='plc' needs plc (an AllPredPLC)")
             if Tlat > ops.ATTN_SEQ_MAX_T:
                 raise MvqError(f"decode_latents: conceal='plc' at T_lat={Tlat} exceeds attention_seq's {ops.ATTN_SEQ_MAX_T} tokens")
+        if z_prev is not None or z_last_out is not None:
+            if conceal == "plc":
+                raise MvqError("decode_latents: z_prev / z_last_out decode a piece of a sequence; conceal='plc' attends over the whole of it")
+            if tactile_only:
+                raise MvqError("decode_latents: z_prev / z_last_out carry the recursion; tactile_only has none")
+            for t, name in ((z_prev, "z_prev"), (z_last_out, "z_last_out")):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32
+                                          and tuple(t.shape) == (B, C) and t.is_contiguous()):
+                    raise MvqError(f"decode_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {dev}")
         if nb_valid is None:
             conceal = "predict"                                               # every token arrived whole: nothing to conceal
         else:
@@ -470,7 +487,9 @@ class _ProposedBase(nn.Module):
         qa = ops._dev(qa.to(dev), "qa")                                       # fp32, contiguous
         if qa.shape[0] != B or qa.shape[1] != C:
             raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
-        z_run = self._rx_two_pass(qa, idx, books_use, nb_valid)
+        z_run = self._rx_two_pass(qa, idx, books_use, nb_valid, z_prev)
+        if z_last_out is not None:                                            # before the post-pass: what the recursion reads
+            ops.copy_strided_(z_last_out, 0, (C, 1), z_run, Tlat - 1, (C * Tlat, Tlat), B, C, 1)
         if conceal == "predict":
             return z_run
         lost = nb_valid == 0
@@ -479,7 +498,7 @@ class _ProposedBase(nn.Module):
         zt_in, _ = ops.plc_mask_fill(z_run, None, lost)                       # what AllPredPLC's predictor is fed
         return ops.plc_mask_fill(z_run, plc.predict(zt_in, qa), lost, want_zt_in=False)[1]
 
-    def _rx_two_pass(self, qa, idx, books_use, nb_valid=None):
+    def _rx_two_pass(self, qa, idx, books_use, nb_valid=None, z_prev=None):
         """Layout: every [.., B*Tlat] tensor of the plan is token-folded and PADDED per chunk -- column (b*NC + c)*16 + i holds
         token c*16 + i of item b (NC chunks, the tail chunk's columns past its end are filler) -- so "chunk" is a batch index of
         stride 16 and every chunk with 16 queries and 16 keys is ONE attention call (chunk as batch).  The tail chunk and chunks
@@ -487,7 +506,8 @@ class _ProposedBase(nn.Module):
         results for those chunks.  Per-token kernels (LayerNorm, GEMMs) give the same bits whatever the batching.
           pass 1: every token with a zero query input (q = LN(PE[i])), z_run = proj_up(qD) + z_pred;
           pass 2: one query per chunk, input z_run[s-1], attending to its own chunk's keys; the result replaces position 0.
-        Chunk 0 takes part in pass 2 with a zero input, recomputing its position 0 exactly as pass 1 did."""
+        Chunk 0 takes part in pass 2 with a zero input, recomputing its position 0 exactly as pass 1 did -- or, when this call
+        continues a sequence, with ``z_prev`` [B, C], the last token of the piece before (pass 2 then runs for one chunk too)."""
         pr, L = self.predict, self.predict._lin
         B, C, Ta_in = qa.shape
         Tlat = idx.shape[2]
@@ -525,10 +545,13 @@ class _ProposedBase(nn.Module):
         z_pred = pr.run(zero, None, folded_batch=G, attend=lambda Q: attend(Q, CH, (CH, N), lambda c: c * CH))
         z_run_p = self._pu(qD_p, residual=z_pred)
         # pass 2: column b*NC + c <- z_run[b, :, c*16 - 1] (zero for c = 0)
-        if NC > 1:
+        if NC > 1 or z_prev is not None:
             x2 = torch.empty(1, C, G, device=dev)
             ops.copy_strided_(x2, 1, (1, G), z_run_p, CH - 1, (CH, N), G - 1, C, 1)
-            ops.copy_strided_(x2, 0, (NC, G), zero, 0, (0, 0), B, C, 1)
+            if z_prev is None:
+                ops.copy_strided_(x2, 0, (NC, G), zero, 0, (0, 0), B, C, 1)
+            else:
+                ops.copy_strided_(x2, 0, (NC, G), z_prev, 0, (C, 1), B, C, 1)
             z_pred2 = pr.run(x2, None, folded_batch=G, attend=lambda Q: attend(Q, 1, (1, G), lambda c: c))
             qD2 = torch.empty(1, CODE_DIM, G, device=dev)
             ops.copy_strided_(qD2, 0, (1, G), qD_p, 0, (CH, N), G, CODE_DIM, 1)
@@ -683,6 +706,13 @@ class ProposedEval(_ProposedBase):
         codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
         y = self.decode(codes_t, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc)
         return y, nb_valid == 0
+
+    def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False):
+        """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
+        time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit."""
+        from .stream import StreamReceiver
+        return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
+                              out_rate=out_rate, graph=graph)
 
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):

@@ -60,3 +60,45 @@ def resample_to(wav: torch.Tensor, sr_in: int, sr_out: int) -> torch.Tensor:
     if sr_in == sr_out:
         return wav
     return Resample(sr_in, sr_out).to(wav.device)(wav)
+
+
+class StreamResample:
+    """``Resample(orig_freq, new_freq)`` fed piece by piece for ``batch`` signals in lockstep (mvq_resample_stream_f32; pure
+    decimation only: new_freq must divide orig_freq).  ``push(x[B, ..., n])`` returns the outputs that piece completes -- output n
+    needs input sample n*orig + width + orig - 1 (8n + 56 for 24 kHz -> 3 kHz) -- and ``finish(x=None)`` pads on the right and
+    flushes; a pushed piece must be a multiple of ``orig`` samples long, the final one need not.  The concatenated outputs equal
+    ``Resample(orig_freq, new_freq)`` of the concatenated input bit for bit.  The state is one fixed device buffer
+    [batch, ceil(width/orig)*orig + width] that the kernel updates in place."""
+
+    def __init__(self, orig_freq: int, new_freq: int, batch: int, device=None, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        kern, self.width, self.orig, self.new = sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        if self.new != 1:
+            raise ops.MvqError(f"StreamResample: {orig_freq} -> {new_freq} Hz is no pure decimation (the streamed kernel covers new = 1)")
+        self.orig_freq, self.new_freq, self.batch = int(orig_freq), int(new_freq), int(batch)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.kernel = kern.to(device)
+        self.state = ops.resample_stream_state(self.orig, self.width, self.batch, device)
+        self.consumed, self.done, self._lead = 0, False, (self.batch,)
+
+    def _piece(self, x, final):
+        if self.done:
+            raise ops.MvqError("StreamResample: the stream is finished")
+        if x.shape[0] != self.batch or x.numel() != self.batch * x.shape[-1]:
+            raise ops.MvqError(f"StreamResample: a piece must be [B={self.batch}, ..., n], got {tuple(x.shape)}")
+        lead, n = tuple(x.shape[:-1]), x.shape[-1]
+        self._lead = lead                                                    # finish() without a piece answers in this shape
+        y = ops.resample_stream(x.reshape(self.batch, n), self.kernel, self.state, self.consumed, self.orig, self.new, self.width,
+                                final=final)
+        self.consumed += n
+        self.done = final
+        return y.reshape(lead + (y.shape[-1],))
+
+    @torch.no_grad()
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        return self._piece(x, False)
+
+    @torch.no_grad()
+    def finish(self, x: torch.Tensor = None) -> torch.Tensor:
+        if x is None:
+            x = torch.empty(self._lead + (0,), device=self.state.device)
+        return self._piece(x, True)
