@@ -40,7 +40,8 @@ extern "C" {
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
- * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32).
+ * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
+ * mvq_ar_latents_staged_carry_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -559,6 +560,17 @@ int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state,
  * h_in or h_out > cap, a negative size, or a null pointer with a non-empty shape. */
 int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, float* win, int h_out, int cap, int batch, int c,
                           void* stream);
+/* mvq_stream_samples_f32: the sample state of a streaming SENDER session.  buf[rows, cap] fp32 (row pitch
+ * cap, the first `fill` samples of every row valid; rows = the audio rows then the tactile rows, so one launch serves both
+ * modalities) and x_new[rows, n] (contiguous).  Per row, with v = [buf[0 .. fill) | x_new[0 .. n)]:
+ *   win[0 .. w) = v[0 .. w)                  win[rows, w] contiguous, a buffer of its own: what the encoder stacks read
+ *   buf[0 .. fill + n - drop) = v[drop ..)    the samples the next window still needs, moved to the front
+ * in ONE launch, one block per row: the move overlaps itself, so a block carries its row through registers tile by tile across
+ * a barrier and no row is touched by two blocks.  w = 0 and drop = 0 is the pure append.  Columns of buf at and past the new fill
+ * are left as they were.  MVQ_EINVAL before any launch on a negative argument, fill > cap, fill + n - drop > cap, w > fill + n,
+ * drop > fill + n, or a null pointer with a non-empty shape; rows = 0 (or n = w = drop = 0) returns MVQ_OK without a launch. */
+int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
+                           void* stream);
 
 /* Optimiser step of the training config (torch.optim.AdamW + clip_grad_norm_, Training/compare_dacvsproposal_5.py:367,394-395):
  *   sumsq_partial : partial[n_partial] block sums of x^2 (their total is the squared gradient norm), n_partial <= 4096
@@ -646,6 +658,12 @@ size_t mvq_ar_workspace_bytes(int batch, int t_lat);
 int mvq_ar_latents_f32(const mvq_ar_args* args, void* workspace, size_t workspace_bytes, void* stream);
 /* the same loop as stream-ordered stand-alone launches from one host call (batch <= 8; capturable; same bits) */
 int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* the staged loop on a PIECE of a longer sequence (a whole number of chunks, the last may be shorter): z_prev[batch, c_lat] (may be
+ * NULL = zero) is the last z_run token of the piece before, fed as column 0 of the first chunk's shift-by-one input; the piece's
+ * own last token is copied to z_last_out[batch, c_lat] (may be NULL, may be the z_prev buffer).  Pieces run one after the other give
+ * the bits of the whole-sequence call.  Not with tactile_only (MVQ_EINVAL). */
+int mvq_ar_latents_staged_carry_f32(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 /* synchronises `stream`, then: MVQ_OK when every grid barrier of the last call on this workspace completed */
 int mvq_ar_check(const void* workspace, void* stream);
 

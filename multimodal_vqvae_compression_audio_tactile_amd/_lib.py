@@ -123,6 +123,7 @@ EXPORTS = {
     "mvq_resample_f32": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
     "mvq_resample_stream_f32": (c_int, [c_void_p] * 4 + [c_int] * 2 + [ctypes.c_longlong] + [c_int] * 6 + [c_void_p]),
     "mvq_stream_window_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "mvq_stream_samples_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
     "mvq_sumsq_partial_f32": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "mvq_adamw_f32": (c_int, [c_void_p] * 5 + [c_size_t] + [c_float] * 5 + [c_int, c_void_p]),
     "mvq_conv1d_padded_f32": (c_int, [c_void_p] * 9 + [c_int] * 10 + [c_void_p]),
@@ -156,6 +157,7 @@ EXPORTS = {
     "mvq_ar_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mvq_ar_latents_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_size_t, c_void_p]),
     "mvq_ar_latents_staged_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_size_t, c_void_p]),
+    "mvq_ar_latents_staged_carry_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvq_ar_check": (c_int, [c_void_p, c_void_p]),
 }
 

@@ -1224,6 +1224,22 @@ int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, floa
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window");
 }
 
+int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
+                           void* stream)
+{
+    if (fill < 0 || n < 0 || w < 0 || drop < 0 || cap < 0 || rows < 0) return fail(MVQ_EINVAL, "stream_samples: negative size");
+    if (cap > (1 << 24) || n > (1 << 24)) return fail(MVQ_EINVAL, "stream_samples: cap = %d / n = %d samples per row", cap, n);
+    if (fill > cap) return fail(MVQ_EINVAL, "stream_samples: fill = %d exceeds the capacity %d", fill, cap);
+    const long long have = (long long)fill + n;
+    if (w > have) return fail(MVQ_EINVAL, "stream_samples: w = %d exceeds fill + n = %d + %d", w, fill, n);
+    if (drop > have) return fail(MVQ_EINVAL, "stream_samples: drop = %d exceeds fill + n = %d + %d", drop, fill, n);
+    if (have - drop > cap) return fail(MVQ_EINVAL, "stream_samples: %lld samples to keep exceed the capacity %d", have - drop, cap);
+    if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return MVQ_OK;
+    if (!buf || (!x_new && n) || (!win && w)) return fail(MVQ_EINVAL, "stream_samples: null tensor");
+    hipError_t e = mvq::launch_stream_samples(buf, x_new, win, fill, n, w, drop, cap, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_samples");
+}
+
 int mvq_sumsq_partial_f32(const float* x, float* partial, int n_partial, size_t n, void* stream)
 {
     if (!partial || n_partial <= 0 || n_partial > 4096 || (!x && n)) return fail(MVQ_EINVAL, "sumsq_partial: bad argument");

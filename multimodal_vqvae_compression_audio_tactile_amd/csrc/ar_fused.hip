@@ -496,7 +496,7 @@ int mvq_ar_latents_f32(const mvq_ar_args* args, void* workspace, size_t workspac
  * allocations cost as much host time as the kernels take on the device (eager encode 2.5 ms against 2.3 ms replayed as a graph);
  * from C a launch costs 2-3 us.  Same kernels, same bits as the Python loop (tests/test_gpu_ar_fused.py).  Needs every GEMM in the
  * latency form's range (batch <= 8: at most 1 024 16 x 16 tiles per launch). */
-int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t workspace_bytes, void* stream)
+static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace, size_t workspace_bytes, void* stream)
 {
     using namespace mvq;
     auto fail = [](int code, const char* msg) { set_last_error(msg); return code; };
@@ -506,6 +506,7 @@ int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t w
     const ArK& k = kt.k;
     const mvq_ar_args& a = k.a;
     if (a.batch > 8) return fail(MVQ_EUNSUPPORTED, "ar_latents_staged: batch <= 8 (beyond it the LDS-tiled GEMMs of the per-stage loop win)");
+    if ((z_prev || z_last_out) && a.tactile_only) return fail(MVQ_EINVAL, "ar_latents_staged_carry: tactile_only has no recursion to carry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int B = a.batch, Tl = a.t_lat;
     // chunk-local buffers start defined: a last chunk shorter than 16 tokens leaves columns nobody writes, and the search reads all 16
@@ -528,7 +529,11 @@ int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t w
                 case ST_LN: {
                     LnIo io = d.ln;
                     if (io.x && (d.adv & ADV_LN_X)) io.x += s;
-                    if (d.adv & ADV_LN_PREV) io.prev = s > 0 ? io.prev + (s - 1) : nullptr;
+                    if (d.adv & ADV_LN_PREV) {
+                        if (s > 0) io.prev += s - 1;
+                        else if (z_prev) { io.prev = z_prev; io.prev_sb = C_LAT; io.prev_sc = 1; }      // S1 of the first chunk: the carried token
+                        else io.prev = nullptr;
+                    }
                     if (io.sub && (d.adv & ADV_LN_SUB)) io.sub += s;
                     if (io.y1 && (d.adv & ADV_LN_Y1)) io.y1 += s;
                     e = launch_layernorm_lat_io(io, B, C_LAT, n, st);
@@ -567,8 +572,24 @@ int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t w
             }
         }
     }
+    if (e == hipSuccess && z_last_out)                                   // z_run[b, :, Tl - 1] -> z_last_out[b, :]
+        e = launch_strided3d(a.z_run + (Tl - 1), (size_t)C_LAT * Tl, (size_t)Tl, nullptr, 0, 0, z_last_out, C_LAT, 1, B, C_LAT, 1, st);
     if (e != hipSuccess) return fail(MVQ_EHIP, hipGetErrorString(e));
     return MVQ_OK;
+}
+
+int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return ar_staged(args, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+/* A piece of a longer sequence (a whole number of chunks; the last may be shorter): the same launches, with z_prev[batch, c_lat]
+ * (may be NULL: zero) as column 0 of the first chunk's shift-by-one input in stage S1, and one copy of the piece's last z_run
+ * token into z_last_out[batch, c_lat] (may be NULL; may be z_prev itself: it is read by the first chunk, written after the last). */
+int mvq_ar_latents_staged_carry_f32(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace,
+                                    size_t workspace_bytes, void* stream)
+{
+    return ar_staged(args, z_prev, z_last_out, workspace, workspace_bytes, stream);
 }
 
 /* after the stream has been synchronised: 0 = every grid barrier of the last call on this workspace completed */

@@ -132,4 +132,7 @@ hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int
                                 hipStream_t s);
 hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, float* y, int B, int n_new, int n_out, int orig,
                                   int ks, int S, int base, int lead, hipStream_t s);
+// stream.hip: the streaming sender's sample state (one block per row of buf[rows][cap])
+hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int fill, int n, int w, int drop, int cap, int rows,
+                                 hipStream_t s);
 }  // namespace mvq

@@ -1,6 +1,7 @@
-// stream.hip -- the streaming receiver's two state kernels (include/mvq.h: mvq_stream_window_f32, mvq_resample_stream_f32).
-// Both keep their session state in a fixed device buffer that the kernel itself updates in place, so the steady step of a
-// session is the same launch sequence on the same addresses every time (a captured graph replays it).
+// stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32 and
+// mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
+// the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
+// every time (a captured graph replays it).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -9,6 +10,8 @@
 namespace mvq {
 namespace {
 constexpr int WIN_ROWS = 32;          // (b, c) rows of one block of stream_window_kernel
+constexpr int SMP_THREADS = 1024;     // stream_samples_kernel: one block per row
+constexpr int SMP_PER = 4;            // elements a thread carries across the barrier: a tile is SMP_THREADS * SMP_PER samples
 }  // namespace
 
 // win[r][0 .. h_in + n) = [hist[r][0 .. h_in) | z_new[r][0 .. n)], then hist[r][0 .. h_out) = the last h_out columns of win[r].
@@ -84,6 +87,39 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __res
     }
 }
 
+// The sender's sample state.  Per row r (one block each): v = [buf[r][0 .. fill) | x_new[r][0 .. n)], win[r][0 .. w) = v[0 .. w)
+// (a buffer of its own, pitch w), then buf[r][0 .. fill + n - drop) = v[drop ..): the samples the next window still needs move to
+// the front of the row, the new ones behind them.  The move overlaps itself (drop < fill + n), so it goes tile by tile in
+// ascending order: a tile's sources lie at or past its own start, every thread holds its elements in registers across the
+// barrier, and only then are they stored -- a store of tile k lands below (k+1)*TILE, where no later tile reads.  With drop == 0
+// the old samples stay where they are and only x_new is appended.  No row is touched by two blocks.
+__global__ __launch_bounds__(SMP_THREADS) void stream_samples_kernel(float* buf, const float* __restrict__ x_new,
+                                                                     float* __restrict__ win, int fill, int n, int w, int drop, int cap)
+{
+    float* b = buf + (size_t)blockIdx.x * cap;
+    const float* x = x_new + (size_t)blockIdx.x * n;
+    float* wr = win + (size_t)blockIdx.x * w;
+    for (int i = threadIdx.x; i < w; i += SMP_THREADS) wr[i] = i < fill ? b[i] : x[i - fill];
+    __syncthreads();                                                     // every read of the window is done before the row moves
+    const int keep = fill + n - drop;
+    constexpr int TILE = SMP_THREADS * SMP_PER;
+    for (int t0 = drop ? 0 : fill; t0 < keep; t0 += TILE) {
+        float v[SMP_PER];
+#pragma unroll
+        for (int u = 0; u < SMP_PER; ++u) {
+            const int i = t0 + threadIdx.x + SMP_THREADS * u;
+            const int j = i + drop;
+            v[u] = i < keep ? (j < fill ? b[j] : x[j - fill]) : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < SMP_PER; ++u) {
+            const int i = t0 + threadIdx.x + SMP_THREADS * u;
+            if (i < keep) b[i] = v[u];
+        }
+    }
+}
+
 hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
                                 hipStream_t s)
 {
@@ -101,6 +137,14 @@ hipError_t launch_resample_stream(const float* x_new, const float* kern, float* 
     const int in_lds = lds <= 48 * 1024;
     hipLaunchKernelGGL(resample_stream_kernel, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out, orig, ks,
                        S, base, lead, in_lds);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int fill, int n, int w, int drop, int cap, int rows,
+                                 hipStream_t s)
+{
+    if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return hipSuccess;
+    hipLaunchKernelGGL(stream_samples_kernel, dim3((unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, fill, n, w, drop, cap);
     return hipGetLastError();
 }
 

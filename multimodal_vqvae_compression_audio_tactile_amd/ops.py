@@ -851,13 +851,17 @@ _AR_CHECKED = set()
 
 def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f, w1, b1, w3, b3, ln_eps, tok, tok_eps, scale,
                      wd, bd, wu, bu, books, books_use, heads, c_ff, code_dim, r_tokens=None, idx_out=None, tactile_only=False, chunk=16,
-                     staged=False):
+                     staged=False, z_prev=None, z_last_out=None):
     """The whole chunked AR loop as ONE persistent kernel (csrc/ar_fused.hip: mvq_ar_latents_f32): zt[B,C,Tlat] -> z_run[B,C,Tlat]
     (written in place), optionally r_tokens[B,96,Tlat] and idx_out[nb,B,Tlat] (int32).  ``k_all`` / ``v_all``: token-folded K / V
     of all chunks ([1,C,B*t_audio], CrossPredictor.keys_values) or None; the w* are K-major packed 1x1 weights (pack_conv1d);
     ln_q / ln_f / tok = (weight, bias).  ``staged``: the same stages as stand-alone launches issued by ONE host call
     (mvq_ar_latents_staged_f32; batch <= 8) instead of the persistent kernel.  Same bits as the Python loop either way
-    (tests/test_gpu_ar_fused.py)."""
+    (tests/test_gpu_ar_fused.py).  ``z_prev`` / ``z_last_out`` ([B, C] fp32, staged only): the token carried into and out of a
+    piece of a longer sequence (mvq_ar_latents_staged_carry_f32)."""
+    carried = z_prev is not None or z_last_out is not None
+    if carried and not staged:
+        raise MvqError("ar_latents_fused: z_prev / z_last_out need staged=True (the persistent kernel carries no token)")
     zt = _dev(zt, "zt")
     B, C, Tl = zt.shape
     nb_all, K = (books.shape[0], books.shape[1]) if books is not None else (0, 1)
@@ -874,6 +878,10 @@ def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f
     L = _lib.lib()
     nbytes = L.mvq_ar_workspace_bytes(B, Tl)
     ws = torch.empty(max(nbytes, 4), device=zt.device, dtype=torch.uint8)
+    if carried:
+        check(L.mvq_ar_latents_staged_carry_f32(ctypes.byref(a), _p(z_prev), _p(z_last_out), ws.data_ptr(), nbytes, _stream()),
+              "mvq_ar_latents_staged_carry_f32")
+        return z_run
     if staged:
         check(L.mvq_ar_latents_staged_f32(ctypes.byref(a), ws.data_ptr(), nbytes, _stream()), "mvq_ar_latents_staged_f32")
         return z_run
@@ -1036,6 +1044,23 @@ def stream_window(hist, h_in, z_new, h_out):
     win = torch.empty(B, C, max(h_in, 0) + n, device=z_new.device, dtype=torch.float32)
     check(_lib.lib().mvq_stream_window_f32(hist.data_ptr(), h_in, z_new.data_ptr(), n, win.data_ptr(), h_out, cap, B, C, _stream()),
           "mvq_stream_window_f32")
+    return win
+
+
+def stream_samples(buf, fill, x_new, w, drop):
+    """The sender's sample state in one launch (mvq_stream_samples_f32).  buf: contiguous fp32 [R, cap], the first ``fill`` samples
+    of every row valid, updated in place; x_new [R, n].  With v = [buf[:, :fill] | x_new]: -> win[R, w] = v[:, :w], and
+    buf[:, :fill + n - drop] = v[:, drop:].  w = 0 and drop = 0 is the pure append (an empty win comes back)."""
+    x_new = _dev(x_new, "x_new")
+    if not isinstance(buf, torch.Tensor) or buf.dim() != 2 or x_new.dim() != 2 or buf.dtype != torch.float32 or not buf.is_cuda \
+            or not buf.is_contiguous() or buf.shape[0] != x_new.shape[0] or buf.device != x_new.device:
+        raise MvqError("stream_samples: buf must be a contiguous fp32 HIP tensor [R, cap] with x_new's rows")
+    R, cap = buf.shape
+    n = x_new.shape[1]
+    fill, w, drop = int(fill), int(w), int(drop)
+    win = torch.empty(R, max(w, 0), device=buf.device, dtype=torch.float32)
+    check(_lib.lib().mvq_stream_samples_f32(buf.data_ptr(), fill, x_new.data_ptr(), n, win.data_ptr(), w, drop, cap, R, _stream()),
+          "mvq_stream_samples_f32")
     return win
 
 

@@ -130,9 +130,14 @@ def unpack_bodies(bodies, nb_recv, info: StreamInfo):
     return idx, nb_valid
 
 
-def frame(bodies, info: StreamInfo, nb_sent: Optional[int] = None) -> list:
-    """bodies[P, body_full] -> one ``bytes`` per packet: the header and the first ``nb_sent`` (default: all nb) books of the body."""
+def frame(bodies, info: StreamInfo, nb_sent: Optional[int] = None, seq_base: int = 0) -> list:
+    """bodies[P, body_full] -> one ``bytes`` per packet: the header and the first ``nb_sent`` (default: all nb) books of the body.
+    ``seq_base`` (streaming, stream.py): ``info`` describes one chunk of a longer stream and packet p is numbered seq_base + p,
+    the stream's sequence number, as ``gather(seq_base=)`` expects it."""
     info = _check(info)
+    seq_base = int(seq_base)
+    if not 0 <= seq_base <= 2 ** 32 - info.P:
+        raise ValueError(f"frame: seq_base = {seq_base} with P = {info.P} packets leaves the 32-bit sequence number")
     nb_sent = info.nb if nb_sent is None else int(nb_sent)
     if not 1 <= nb_sent <= info.nb:
         raise ValueError(f"frame: nb_sent={nb_sent} outside 1..{info.nb}")
@@ -143,7 +148,7 @@ def frame(bodies, info: StreamInfo, nb_sent: Optional[int] = None) -> list:
     out = []
     for p in range(info.P):
         ntok = info.ntok(p)
-        out.append(_HEADER.pack(MAGIC, VERSION, p, ntok, nb_sent) + _first_books(bodies[p], ntok, nb_sent, info.K))
+        out.append(_HEADER.pack(MAGIC, VERSION, seq_base + p, ntok, nb_sent) + _first_books(bodies[p], ntok, nb_sent, info.K))
     return out
 
 

@@ -247,10 +247,26 @@ class _ProposedBase(nn.Module):
         return min(max(self._scale_raw(), 5e-3), 0.5)
 
     @torch.no_grad()
-    def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False):
+    def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False, z_prev=None,
+                    z_last_out=None):
         """The chunked AR loop (Training/...5.py:302-320 == Evaluation/...6_latency.py:461-477).
-        ``want_indices``: also return the per-book code indices idx[n_books_use, B, Tlat] (int64)."""
+        ``want_indices``: also return the per-book code indices idx[n_books_use, B, Tlat] (int64).
+
+        Streaming (stream.StreamSender): a chunk depends on the ones before it through z_run[..., s-1] alone, so a sequence is
+        quantised piece by piece, each piece a whole number of 16-token chunks (the last may be shorter): ``z_prev`` ([B, C]
+        contiguous fp32 on the device) is the last z_run token of the piece before and becomes column 0 of the first chunk's
+        zt_prev; ``z_last_out`` (same shape; may be the z_prev buffer) receives this piece's last z_run token.  Both None:
+        today's launch sequence exactly.  The opt-in persistent kernel carries no token: such a call takes the staged form or the
+        Python loop."""
         B, C, Tlat = zt.shape
+        carried = z_prev is not None or z_last_out is not None
+        if carried:
+            if tactile_only:
+                raise MvqError("_ar_latents: z_prev / z_last_out carry the recursion; tactile_only has none")
+            for t, name in ((z_prev, "z_prev"), (z_last_out, "z_last_out")):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.device == zt.device and t.dtype == torch.float32
+                                          and tuple(t.shape) == (B, C) and t.is_contiguous()):
+                    raise MvqError(f"_ar_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {zt.device}")
         z_run = torch.zeros_like(zt)
         r_tokens = torch.empty(B, CODE_DIM, Tlat, device=zt.device, dtype=torch.float32) if want_tokens else None
         idx_all = [] if want_indices else None
@@ -266,9 +282,11 @@ class _ProposedBase(nn.Module):
             if Ta > 0:                                                        # K, V of all chunks up front (3 launches)
                 kv_all = self.predict.keys_values(ops.fold_time_slice(qa, 0, Ta), B, AR_CHUNK_TOK)
         mode = self._ar_one_call_mode(zt, books)
+        if mode == "fused" and carried:
+            mode = "staged" if zt.shape[0] <= self.AR_STAGED_MAX_BATCH and self._ar_shapes_covered(zt, books) else None
         if mode is not None:
             return self._ar_latents_fused(zt, z_run, r_tokens, kv_all, 0 if tactile_only else min(qa.shape[-1], Tlat), books, books_use,
-                                          tactile_only, want_indices, staged=(mode == "staged"))
+                                          tactile_only, want_indices, staged=(mode == "staged"), z_prev=z_prev, z_last_out=z_last_out)
         zt_prev, zp_n = None, -1      # the shift-by-one input: all zero except column 0 of each item (s > 0), so one zeroed
         for s in range(0, Tlat, AR_CHUNK_TOK):                               # buffer per chunk width serves every chunk
             e = min(Tlat, s + AR_CHUNK_TOK)
@@ -281,6 +299,8 @@ class _ProposedBase(nn.Module):
                     zt_prev, zp_n = torch.zeros(1, C, B * n, device=zt.device, dtype=torch.float32), n
                 if s > 0:                                                     # column 0 <- z_run[..., s-1]
                     ops.fold_column_into_(zt_prev, 0, z_run, s - 1, B)
+                elif z_prev is not None:                                      # ... of the piece before
+                    ops.copy_strided_(zt_prev, 0, (n, B * n), z_prev, 0, (C, 1), B, C, 1)
                 ka = min(qa.shape[-1], e) - min(qa.shape[-1], s)
                 if ka > 0:
                     z_pred = self.predict.run(zt_prev, None, folded_batch=B, kv_all=kv_all, kv_slice=(s, ka))
@@ -300,6 +320,8 @@ class _ProposedBase(nn.Module):
             ops.unfold_into_(z_run, s, z_hat, B)
             if want_tokens:
                 ops.unfold_into_(r_tokens, s, rD, B)
+        if z_last_out is not None:
+            ops.copy_strided_(z_last_out, 0, (C, 1), z_run, Tlat - 1, (C * Tlat, Tlat), B, C, 1)
         if want_indices:
             return z_run, r_tokens, torch.cat(idx_all, dim=2) if idx_all else torch.zeros(0, B, Tlat, dtype=torch.int64)
         return z_run, r_tokens
@@ -338,7 +360,8 @@ class _ProposedBase(nn.Module):
                 and zt.shape[1] == 1024 and p.h == 8 and p.ffn[1].out_features == 2048 and CODE_DIM == 96 and p.ln_q.eps == p.ffn[0].eps
                 and (books is None or (books.shape[1] <= 512 and books.shape[2] == CODE_DIM)))
 
-    def _ar_latents_fused(self, zt, z_run, r_tokens, kv_all, t_audio, books, books_use, tactile_only, want_indices, staged=False):
+    def _ar_latents_fused(self, zt, z_run, r_tokens, kv_all, t_audio, books, books_use, tactile_only, want_indices, staged=False,
+                          z_prev=None, z_last_out=None):
         B, _, Tlat = zt.shape
         p, L, ln = self.predict, self.predict._lin, self.tokennorm.ln
         nb = 0 if books is None else (books.shape[0] if books_use is None else max(0, min(int(books_use), books.shape[0])))
@@ -351,7 +374,7 @@ class _ProposedBase(nn.Module):
             w3=L["f3"].wp(), b3=det(p.ffn[3].bias), ln_eps=p.ln_q.eps, tok=(det(ln.weight), det(ln.bias)), tok_eps=ln.eps,
             scale=self._scale_value(), wd=self._pd.wp(), bd=det(self.proj_down.bias), wu=self._pu.wp(), bu=det(self.proj_up.bias),
             books=books, books_use=books_use, heads=p.h, c_ff=p.ffn[1].out_features, code_dim=CODE_DIM, r_tokens=r_tokens, idx_out=idx,
-            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged)
+            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged, z_prev=z_prev, z_last_out=z_last_out)
         if want_indices:
             return z_run, r_tokens, idx.long()
         return z_run, r_tokens
@@ -713,6 +736,13 @@ class ProposedEval(_ProposedBase):
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
                               out_rate=out_rate, graph=graph)
+
+    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False):
+        """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
+        get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output
+        equals compress_packets on the whole item byte for byte."""
+        from .stream import StreamSender
+        return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph)
 
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):

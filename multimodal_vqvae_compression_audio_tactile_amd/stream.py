@@ -1,4 +1,6 @@
-"""Streaming receiver: the tactile waveform chunk by chunk, bit-equal to the whole-item ``decompress_packets``.
+"""Streaming link, both ends.  Receiver: the tactile waveform chunk by chunk, bit-equal to the whole-item ``decompress_packets``
+(DESIGN.md section 14).  Sender: packets and audio codes chunk by chunk, byte-equal to the whole-item ``compress_packets``
+(section 15; ``sender_schedule``, ``StreamSender`` below).
 
 The whole-item receiver waits for every token of an item before the first sample leaves it.  Nothing in the model needs that:
 
@@ -14,10 +16,14 @@ tests/test_stream_cpu.py repeats the part that guards them (the schedule at halo
 tests/stream_oracle.py holds the procedure (measure_halo: 3133 at both ends of the window [20, 55) of 75 tokens, counted inside
 the window's 320*(b-a) - 8 output samples; 3141 is that extent counted from the nominal edge 320*b, and the count at the start
 moves by a sample with the data).  The schedule's margins are 3200 samples at a window start and 3192 at a window end.  The
-extents are properties of the architecture (kernel sizes, dilations, strides), not of the weights.  ENC_HALO_TOK, measured the
-same way on the encoder, is recorded for a streaming sender, which does not exist yet.
+extents are properties of the architecture (kernel sizes, dilations, strides), not of the weights.  ENC_HALO_TOK is measured the
+same way on the encoder (oracle.dac_encoder, synth.dac_state(seed=7) encoder weights): encoding the samples of tokens [20, 55)
+of a 75-token item reproduces the whole-item latents bit for bit except for the first 8 and the last 8 tokens of the window, and
+a window that starts on a multiple of 320 samples keeps every stage's stride alignment, so a true sequence edge is exact
+(tests/test_sender_cpu.py: the sender's schedule is exact at halo 8 and not at halo 7).
 
-``schedule`` is host arithmetic only; ``StreamReceiver`` is the session object (``ProposedEval.stream_receiver``).
+``schedule`` / ``sender_schedule`` are host arithmetic only; ``StreamReceiver`` / ``StreamSender`` are the session objects
+(``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).
 """
 from __future__ import annotations
 
@@ -27,8 +33,11 @@ HOP = 320                         # samples per latent token (the product of the
 DEC_TAIL = 8                      # T_DEC(z[..., :T]) has 320*T - 8 samples
 DEC_HALO_TOK = 10                 # tokens of context on each side of what a window may emit (3200 samples)
 DEC_HALO_SAMPLES = (3132, 3141)   # inexact samples at the start / end of a window that is not at the sequence's edge
-ENC_HALO_TOK = 8                  # the encoder's halo, each side (for the streaming sender: not built)
+ENC_HALO_TOK = 8                  # the encoder's halo, each side (the streaming sender's look-back and look-ahead)
 CHUNK_TOK = 16                    # proposed.AR_CHUNK_TOK, restated so that schedule() needs no torch
+PUSH_MAX_TOK = 16                 # a sender push carries 1..16 tokens of samples, so it completes at most one chunk
+SEND_CAP_TOK = 48                 # the sender's sample buffer: it never holds more than 47 tokens of samples
+ENC_RATES = (2, 4, 5, 8)          # dac.ENC_RATES, restated so that sender_schedule() needs no torch
 
 
 def schedule(T: int, chunk: int = CHUNK_TOK, halo: int = DEC_HALO_TOK) -> List[Tuple[int, int, int, int]]:
@@ -48,6 +57,268 @@ def schedule(T: int, chunk: int = CHUNK_TOK, halo: int = DEC_HALO_TOK) -> List[T
         before = n
     steps.append((max(0, before - 2 * halo), T, HOP * max(0, before - halo), max(0, HOP * T - DEC_TAIL)))
     return steps
+
+
+def enc_tokens(samples: int, rates=ENC_RATES) -> int:
+    """Latent tokens the encoder stack makes of ``samples`` samples (per stage a conv of kernel 2s, stride s, padding ceil(s/2))."""
+    n = int(samples)
+    for r in rates:
+        n = (n + 2 * ((r + 1) // 2) - 2 * r) // r + 1 if n > 0 else 0
+    return max(0, n)
+
+
+def sender_schedule(T_tokens: int, pushes, chunk: int = CHUNK_TOK, halo: int = ENC_HALO_TOK) -> List[Tuple[int, int, int, int, int]]:
+    """The steps of a sender session over an item of T_tokens tokens fed in ``pushes`` (tokens of samples per push, each
+    1..PUSH_MAX_TOK, sum <= T_tokens; whatever remains goes to ``finish``): one entry per push and then the ``finish`` entry,
+    each (win_start_tok, win_end_tok, chunk_first, chunk_end, held_tok) -- the encoder window in tokens (empty when nothing is
+    emitted), the chunks [chunk_first, chunk_end) the step emits, and the tokens of samples the session holds afterwards.
+
+    Chunk c (tokens [16c, 16c+16)) leaves with the push after which 16c + 16 + halo tokens are in hand: one chunk plus the
+    look-ahead, 213.3 + 106.7 ms.  Its window is [max(0, 16c - halo), 16c + 16 + halo): 24 tokens for chunk 0, then 32 in the
+    steady state, 2 times the tokens emitted (the receiver's decoder windows: 2.25 times).  After the emit the session keeps
+    the samples from token 16c + 16 - halo on.  A push of at most 16 tokens completes at most one chunk: before it fewer than
+    16(c+1) + halo tokens are in hand, after it fewer than 16(c+2) + halo.  ``finish`` encodes [max(0, 16c - halo), T) once and
+    emits every remaining chunk; the window's right edge is the item's, which is exact."""
+    T, chunk, halo = int(T_tokens), int(chunk), int(halo)
+    pushes = [int(m) for m in pushes]
+    if T < 0 or chunk < 1 or halo < 0 or chunk > PUSH_MAX_TOK:
+        raise ValueError(f"sender_schedule: T={T}, chunk={chunk}, halo={halo}")
+    if any(not 1 <= m <= PUSH_MAX_TOK for m in pushes) or sum(pushes) > T:
+        raise ValueError(f"sender_schedule: pushes of 1..{PUSH_MAX_TOK} tokens that sum to at most T = {T}")
+    steps, have, c, start = [], 0, 0, 0                                  # tokens in hand, next chunk, first token held
+    for m in pushes:
+        have += m
+        if have >= chunk * (c + 1) + halo:
+            steps.append((start, chunk * (c + 1) + halo, c, c + 1, have - max(0, chunk * (c + 1) - halo)))
+            c, start = c + 1, max(0, chunk * (c + 1) - halo)
+        else:
+            steps.append((start, start, c, c, have - start))
+    n_chunks = (T + chunk - 1) // chunk
+    steps.append((start, T, c, n_chunks, 0) if n_chunks > c else (start, start, c, c, 0))
+    return steps
+
+
+class StreamSender:
+    """A sender session for ``batch`` items advancing in lockstep: ``push`` the next samples of both modalities (320*m each,
+    1 <= m <= 16), get back the tactile packets and audio codes of the 16-token chunk they complete (nothing when they complete
+    none); ``finish`` takes the remaining samples (any count, none too) and flushes.
+
+    Per item the packets of all pushes and ``finish`` concatenated equal ``compress_packets``' packets byte for byte, the audio
+    codes concatenated equal the whole-item codes, and ``finish`` returns the same ``StreamInfo`` -- for ``ops.get_arith() ==
+    "f32"`` (the opt-in arithmetic modes scale per item, so a window changes their arithmetic; they are refused) and for
+    modalities of one length.  Chunk c leaves once 8 tokens past its end are in hand: the algorithmic latency is one chunk plus
+    the encoder look-ahead, 213.3 + 106.7 ms, instead of the whole item.
+
+    An emitting ``push`` runs, in order: ops.stream_samples (the sample buffer [2B, 48*320]: window out, buffer moved on, one
+    launch for both modalities) -> A_ENC and T_ENC on the window (``sender_schedule``; one or two HIP streams as
+    ``_encode_branches`` decides) -> the chunk's 16 exact tokens -> A_QUANT -> _ar_latents(want_indices=True, z_prev=carry,
+    z_last_out=carry) -> ops.idx_pack_packets -> ONE device-to-host copy of the bodies -> packets.frame(seq_base=).  A push that
+    emits nothing is the append launch alone.  All session state is in fixed device buffers (samples [2B, 15360], carry [B, C]).
+
+    ``graph=True``: the steady step (a push of exactly 16 tokens that completes a chunk after the first: the 32-token window) is
+    captured once as a graph, at the buffer fill it first occurs with, and replayed after the host has written the samples into
+    the static input buffer whenever a push has that shape again -- with 16-token pushes the fill before every push is the same
+    (16 tokens when the first push was 8, 24 when every push was 16).  Everything else runs eagerly."""
+
+    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False):
+        import torch
+        from . import ops, proposed
+        from .packets import StreamInfo, body_bytes, _check
+        packet_tok, batch = int(packet_tok), int(batch)
+        if packet_tok < 1 or CHUNK_TOK % packet_tok:
+            raise ValueError(f"StreamSender: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
+                             "(a packet must never straddle two chunks)")
+        if batch < 1:
+            raise ValueError("StreamSender: batch must be at least 1")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"StreamSender: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        assert proposed.AR_CHUNK_TOK == CHUNK_TOK
+        for enc in (net.A_ENC, net.T_ENC):
+            if tuple(enc._desc[1]) != ENC_RATES:
+                raise ValueError(f"StreamSender: encoder strides {tuple(enc._desc[1])}; the window schedule is measured for {ENC_RATES}")
+        self.K = int(net.vq.n_embed)
+        self.nb = int(net.vq.n_books) if books_use is None else max(0, min(int(books_use), int(net.vq.n_books)))
+        _check(StreamInfo(self.K, self.nb, CHUNK_TOK, packet_tok))
+        self.net, self.packet_tok, self.batch, self.books_use, self.graph = net, packet_tok, batch, books_use, bool(graph)
+        self.dev = net.proj_up.weight.device
+        self.C = net.proj_up.out_channels
+        self.full = body_bytes(packet_tok, self.nb, self.K)
+        self.n_audio_books = net.A_QUANT.n_codebooks
+        self.buf = torch.zeros(2 * batch, SEND_CAP_TOK * HOP, device=self.dev)         # audio rows, then tactile rows
+        self.carry = torch.zeros(batch, self.C, device=self.dev)                       # z_run[..., -1] of the chunk before
+        self.fill = 0                                                                  # valid samples of every buffer row
+        self.start = 0                                                                 # the token buf[:, 0] belongs to
+        self.chunk = 0                                                                 # the next chunk to emit
+        self.finished = False
+        self._g = None                                                                 # (graph, fill, x_static, bodies_static, codes_static)
+
+    @property
+    def tokens(self):
+        """Tokens of samples received so far."""
+        return self.start + self.fill // HOP
+
+    # ------------------------------------------------------------------------------------------------------------ stages
+    def _branches(self, a_w, t_w, lo, hi):
+        """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt); the audio branch
+        on a second HIP stream under the rule of ``_encode_branches``."""
+        import torch
+        from . import ops
+        net = self.net
+        if a_w.shape[0] > net.TWO_STREAM_MAX_BATCH or not a_w.is_cuda or ops.get_arith() != "f32":
+            qa, codes, *_ = net.A_QUANT(net.A_ENC(a_w)[..., lo:hi].contiguous())
+            return qa, codes, net.T_ENC(t_w)[..., lo:hi].contiguous()
+        cur = torch.cuda.current_stream()
+        side = getattr(net, "_side_stream", None)
+        if side is None or side.device != a_w.device:
+            side = torch.cuda.Stream(device=a_w.device)
+            net._side_stream = side
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            za = net.A_ENC(a_w)
+            za_c = za[..., lo:hi].contiguous()
+            qa, codes, *_ = net.A_QUANT(za_c)
+        zt = net.T_ENC(t_w)[..., lo:hi].contiguous()
+        cur.wait_stream(side)
+        for x in (za, za_c, qa, codes):
+            x.record_stream(cur)
+        return qa, codes, zt
+
+    def _device_step(self, x, fill, w, drop, lo, hi):
+        """Device: samples -> window -> latents of tokens [lo, hi) of the window -> (packet bodies uint8 [B, P, full], audio codes
+        int64 [B, 32, hi - lo]); the buffer and the carried token move on in place."""
+        from . import ops
+        B = self.batch
+        win = ops.stream_samples(self.buf, fill, x, w, drop)
+        qa, codes, zt = self._branches(win[:B].unsqueeze(1), win[B:].unsqueeze(1), lo, hi)
+        _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=self.carry, z_last_out=self.carry)
+        return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
+
+    def _samples(self, a, t, what, tail=False):
+        """The checks of a push, before any launch -> (a, t) as [B, n] fp32 on the device and n."""
+        import torch
+        a, t = torch.as_tensor(a), torch.as_tensor(t)
+        B = self.batch
+        for x, name in ((a, "a"), (t, "t")):
+            if x.dim() != 3 or x.shape[1] != 1 or not x.dtype.is_floating_point:
+                raise ValueError(f"StreamSender.{what}: {name} must be a float tensor [B, 1, samples], got {tuple(x.shape)}")
+        if a.shape[0] != B or t.shape[0] != B:
+            raise ValueError(f"StreamSender.{what}: samples of {a.shape[0]} / {t.shape[0]} items for a session of batch {B}")
+        if a.shape[2] != t.shape[2]:
+            raise ValueError(f"StreamSender.{what}: {a.shape[2]} audio and {t.shape[2]} tactile samples; the two modalities advance together")
+        n = int(a.shape[2])
+        if not tail and (n % HOP or not HOP <= n <= PUSH_MAX_TOK * HOP):
+            raise ValueError(f"StreamSender.push: {n} samples; a push is {HOP}*m samples, 1 <= m <= {PUSH_MAX_TOK} "
+                             "(anything else goes to finish)")
+        if tail and self.fill + n > (1 << 24):
+            raise ValueError(f"StreamSender.finish: {n} samples")
+        return a, t, n
+
+    def _upload(self, a, t, n):
+        import torch
+        x = torch.empty(2 * self.batch, n, device=self.dev)
+        x[:self.batch].copy_(a.reshape(self.batch, n))
+        x[self.batch:].copy_(t.reshape(self.batch, n))
+        return x
+
+    def _framed(self, bodies, codes, n_tok):
+        """ONE device-to-host copy of the bodies, then the headers with the stream's sequence numbers."""
+        from .packets import StreamInfo, frame
+        info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
+        host = bodies.cpu().numpy()
+        base = self.chunk * CHUNK_TOK // self.packet_tok
+        return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
+
+    def _nothing(self):
+        import torch
+        return [[] for _ in range(self.batch)], torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
+
+    def _open(self, what):
+        from . import ops
+        from ._lib import MvqError
+        if self.finished:
+            raise MvqError(f"StreamSender: {what} after finish")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"StreamSender: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+
+    # ------------------------------------------------------------------------------------------------------------ session
+    def push(self, a, t):
+        """``a`` / ``t`` [B, 1, 320*m], 1 <= m <= 16: the next samples of the audio and the tactile signal ->
+        (tactile_packets, audio_codes): B lists of framed packets (``bytes``) with the stream's sequence numbers
+        16c/packet_tok ... and int64 [B, 32, 16] on the device when the push completes chunk c; B empty lists and [B, 32, 0]
+        when it completes none."""
+        import torch
+        from . import ops
+        self._open("push")
+        a, t, n = self._samples(a, t, "push")
+        c = self.chunk
+        emit = self.tokens + n // HOP >= CHUNK_TOK * (c + 1) + ENC_HALO_TOK
+        with torch.no_grad():
+            if not emit:
+                ops.stream_samples(self.buf, self.fill, self._upload(a, t, n), 0, 0)
+                self.fill += n
+                return self._nothing()
+            new_start = CHUNK_TOK * (c + 1) - ENC_HALO_TOK
+            w, drop = HOP * (CHUNK_TOK * (c + 1) + ENC_HALO_TOK - self.start), HOP * (new_start - self.start)
+            lo = CHUNK_TOK * c - self.start
+            if self.graph and c > 0 and n == CHUNK_TOK * HOP and (self._g is None or self._g[1] == self.fill):   # the steady step
+                bodies, codes = self._replay(a, t, n, (self.fill, w, drop, lo, lo + CHUNK_TOK))
+            else:
+                bodies, codes = self._device_step(self._upload(a, t, n), self.fill, w, drop, lo, lo + CHUNK_TOK)
+            out = self._framed(bodies, codes, CHUNK_TOK)
+            self.fill, self.start, self.chunk = self.fill + n - drop, new_start, c + 1
+            return out
+
+    def finish(self, a=None, t=None):
+        """Flush: optionally the remaining samples ``a`` / ``t`` [B, 1, n] (any n, no multiple of 320 needed), then every
+        remaining chunk from ONE encoder window that ends at the item's true end, the token carried from chunk to chunk
+        -> (tactile_packets, audio_codes, StreamInfo(K, nb, T, packet_tok)).  Runs eagerly.  The session accepts nothing afterwards."""
+        import torch
+        from .packets import StreamInfo
+        self._open("finish")
+        if (a is None) != (t is None):
+            raise ValueError("StreamSender.finish: the remaining samples of both modalities, or of neither")
+        n = 0
+        if a is not None:
+            a, t, n = self._samples(a, t, "finish", tail=True)
+        T_w = enc_tokens(self.fill + n)
+        lo = CHUNK_TOK * self.chunk - self.start
+        with torch.no_grad():
+            if T_w <= lo:                                                # an item shorter than one token: nothing to send
+                self.finished = True
+                return self._nothing() + (StreamInfo(self.K, self.nb, self.start + max(T_w, 0), self.packet_tok),)
+            x = self._upload(a, t, n) if n else torch.empty(2 * self.batch, 0, device=self.dev)
+            bodies, codes = self._device_step(x, self.fill, self.fill + n, self.fill + n, lo, T_w)
+            out = self._framed(bodies, codes, T_w - lo)
+            T = self.start + T_w
+            self.fill, self.chunk, self.finished = 0, (T + CHUNK_TOK - 1) // CHUNK_TOK, True
+            return out + (StreamInfo(self.K, self.nb, T, self.packet_tok),)
+
+    def _replay(self, a, t, n, plan):
+        """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
+        that nothing is built during the capture), then replayed with the samples written into the static input buffer.  The
+        audio codes come back as a copy: the graph's own output buffer is overwritten by the next replay."""
+        import torch
+        B = self.batch
+        if self._g is None:
+            x_s = self._upload(a, t, n)
+            keep = (self.buf.clone(), self.carry.clone())
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(device=self.dev)
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                self._device_step(x_s, *plan)                                # warm-up at the steady shape; it moved the state on
+                self.buf.copy_(keep[0])
+                self.carry.copy_(keep[1])
+                with torch.cuda.graph(g, stream=s):
+                    bodies_s, codes_s = self._device_step(x_s, *plan)
+            torch.cuda.current_stream().wait_stream(s)
+            self._g = (g, plan[0], x_s, bodies_s, codes_s)
+        else:
+            g, _, x_s, bodies_s, codes_s = self._g
+            x_s[:B].copy_(a.reshape(B, n))
+            x_s[B:].copy_(t.reshape(B, n))
+        g.replay()
+        return bodies_s, codes_s.clone()
 
 
 class StreamReceiver:
