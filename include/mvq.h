@@ -41,7 +41,8 @@ extern "C" {
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
- * mvq_ar_latents_staged_carry_f32).
+ * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
+ * mvq_stream_rows_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -571,6 +572,27 @@ int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, floa
  * drop > fill + n, or a null pointer with a non-empty shape; rows = 0 (or n = w = drop = 0) returns MVQ_OK without a launch. */
 int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
                            void* stream);
+
+/* ---- receiver pool: the state of n_slots independent sessions in ONE set of buffers, one row block per
+ * slot -- carry[n_slots, c], hist[n_slots, c, cap], state[n_slots, S] -- and a launch serves the n_group sessions that a DEVICE
+ * list slots[n_group] (int32) names, in that order; every other tensor of a call is dense over the group.  The caller passes
+ * distinct slots inside [0, n_slots): two equal entries would make two blocks update one row.  The kernels check the range
+ * themselves as a second line: a slot outside [0, n_slots) reads as zeros and nothing is stored to the pool for it.  All three:
+ * MVQ_EINVAL before any launch on a negative size, n_group > n_slots, n_group * c beyond 2^31 - 1 or a null pointer with a
+ * non-empty shape; n_group = 0 returns MVQ_OK without a launch.
+ * mvq_stream_window_slots_f32: mvq_stream_window_f32 with row (g, ch) of z_new[n_group, c, n] and win[n_group, c, h_in + n] on
+ * hist[slots[g]][ch]; the other refusals of mvq_stream_window_f32.  Rows of unlisted slots are not touched.
+ * mvq_resample_stream_slots_f32: mvq_resample_stream_f32 with item g of x_new[n_group, n_new] and y[n_group, len_out] on
+ * state[slots[g]]; same fma chain, same refusals.  `consumed` names the group's launch class: the launch depends on it only
+ * through base = max(0, hold*orig - consumed), lead = max(0, S - consumed) and the output count, which agree for all sessions
+ * with consumed == 0 and, n_new and final given, for all with consumed >= S; a value in (0, S) is refused (MVQ_EINVAL).
+ * mvq_stream_rows_f32: rows[g][0 .. c) <- pool[slots[g]][0 .. c) (scatter == 0), or pool[slots[g]] <- rows[g] (scatter != 0). */
+int mvq_stream_window_slots_f32(float* hist, const int32_t* slots, int n_group, int n_slots, int h_in, const float* z_new, int n,
+                                float* win, int h_out, int cap, int c, void* stream);
+int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group, int n_slots,
+                                  float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
+                                  void* stream);
+int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream);
 
 /* Optimiser step of the training config (torch.optim.AdamW + clip_grad_norm_, Training/compare_dacvsproposal_5.py:367,394-395):
  *   sumsq_partial : partial[n_partial] block sums of x^2 (their total is the squared gradient norm), n_partial <= 4096

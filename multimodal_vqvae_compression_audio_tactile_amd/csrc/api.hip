@@ -1240,6 +1240,74 @@ int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, floa
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_samples");
 }
 
+// ---- the receiver pool: the three state kernels on slots[n_group] of a pool of n_slots sessions ----
+static int slots_shape_bad(const char* who, int n_group, int n_slots, long long per_session)
+{
+    if (n_group < 0 || n_slots < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
+    if (n_group > n_slots) return fail(MVQ_EINVAL, "%s: a group of %d sessions in a pool of %d slots", who, n_group, n_slots);
+    if ((long long)n_group * per_session > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: %d sessions of %lld rows", who, n_group, per_session);
+    return MVQ_OK;
+}
+
+int mvq_stream_window_slots_f32(float* hist, const int32_t* slots, int n_group, int n_slots, int h_in, const float* z_new, int n,
+                                float* win, int h_out, int cap, int c, void* stream)
+{
+    if (h_in < 0 || n < 0 || h_out < 0 || cap < 0 || c < 0) return fail(MVQ_EINVAL, "stream_window_slots: negative size");
+    if (int rc = slots_shape_bad("stream_window_slots", n_group, n_slots, c)) return rc;
+    if (h_in > cap || h_out > cap)
+        return fail(MVQ_EINVAL, "stream_window_slots: h_in = %d / h_out = %d exceed the history capacity %d", h_in, h_out, cap);
+    if ((long long)h_out > (long long)h_in + n)
+        return fail(MVQ_EINVAL, "stream_window_slots: h_out = %d exceeds h_in + n = %d + %d", h_out, h_in, n);
+    if ((long long)h_in + n > (1 << 20)) return fail(MVQ_EINVAL, "stream_window_slots: window of %lld columns", (long long)h_in + n);
+    const int rows = n_group * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (!slots || !win || (!hist && (h_in || h_out)) || (!z_new && n)) return fail(MVQ_EINVAL, "stream_window_slots: null tensor");
+    hipError_t e = mvq::launch_stream_window_slots(hist, slots, z_new, win, h_in, n, h_out, cap, c, n_slots, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window_slots");
+}
+
+int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group, int n_slots,
+                                  float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
+                                  void* stream)
+{
+    if (n_new < 0 || consumed < 0 || len_out < 0 || orig <= 0 || newf <= 0 || width < 0 || ks != 2 * width + orig)
+        return fail(MVQ_EINVAL, "resample_stream_slots: bad shape (ks must be 2*width + orig)");
+    if (int rc = slots_shape_bad("resample_stream_slots", n_group, n_slots, 1)) return rc;
+    if (newf != 1) return fail(MVQ_EUNSUPPORTED, "resample_stream_slots: pure decimation only (newf = %d after the gcd)", newf);
+    const long long hold = (width + orig - 1) / orig;
+    const long long ns = hold * orig + width;
+    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "resample_stream_slots: state of %lld samples exceeds 1024", ns);
+    if (consumed % orig) return fail(MVQ_EINVAL, "resample_stream_slots: consumed = %lld is no multiple of orig = %d", consumed, orig);
+    if (consumed && consumed < ns)
+        return fail(MVQ_EINVAL, "resample_stream_slots: consumed = %lld inside the %lld-sample state names no launch class (0, or at least %lld)",
+                    consumed, ns, ns);
+    if (!final && n_new % orig)
+        return fail(MVQ_EINVAL, "resample_stream_slots: n_new = %d is no multiple of orig = %d (only the final call may be)", n_new, orig);
+    const long long q0 = consumed / orig;
+    const long long done = q0 > hold ? q0 - hold : 0;
+    const long long q1 = final ? (consumed + n_new + orig - 1) / orig : q0 + n_new / orig - hold;
+    const long long n_out = q1 > done ? q1 - done : 0;
+    if (n_out != len_out) return fail(MVQ_EINVAL, "resample_stream_slots: len_out = %d, this call completes %lld outputs", len_out, n_out);
+    if ((long long)n_group * n_out > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "resample_stream_slots: %d x %lld outputs", n_group, n_out);
+    if (n_group == 0) return MVQ_OK;
+    if (!kern || !state || !slots || (!x_new && n_new) || (!y && n_out)) return fail(MVQ_EINVAL, "resample_stream_slots: null tensor");
+    const int base = (int)(q0 < hold ? (hold - q0) * orig : 0);
+    const int lead = (int)(consumed < ns ? ns - consumed : 0);
+    hipError_t e = mvq::launch_resample_stream_slots(x_new, kern, state, slots, y, n_group, n_new, (int)n_out, orig, ks, (int)ns, base,
+                                                     lead, n_slots, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_slots");
+}
+
+int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream)
+{
+    if (c < 0) return fail(MVQ_EINVAL, "stream_rows: negative size");
+    if (int rc = slots_shape_bad("stream_rows", n_group, n_slots, c)) return rc;
+    if (n_group == 0 || c == 0) return MVQ_OK;
+    if (!pool || !slots || !rows) return fail(MVQ_EINVAL, "stream_rows: null tensor");
+    hipError_t e = mvq::launch_stream_rows(pool, slots, rows, n_group, c, n_slots, scatter != 0, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_rows");
+}
+
 int mvq_sumsq_partial_f32(const float* x, float* partial, int n_partial, size_t n, void* stream)
 {
     if (!partial || n_partial <= 0 || n_partial > 4096 || (!x && n)) return fail(MVQ_EINVAL, "sumsq_partial: bad argument");

@@ -1,7 +1,8 @@
 // stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32 and
 // mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
 // the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
-// every time (a captured graph replays it).
+// every time (a captured graph replays it).  The *_slots kernels and stream_rows_kernel serve a POOL of sessions (DESIGN.md
+// section 16): the state buffers hold one row block per session slot and a launch works on the slots a device list names.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -120,6 +121,103 @@ __global__ __launch_bounds__(SMP_THREADS) void stream_samples_kernel(float* buf,
     }
 }
 
+// ---- the session pool: state addressed through a slot list ---------------------------------------------------------------------
+// stream_window_kernel for a group of G sessions of a pool: row r = g*C + c of win / z_new (dense) is row slots[g]*C + c of
+// hist.  Distinct slots (the host wrapper refuses a repeated one) are distinct hist rows, so a block still owns the hist rows
+// it reads and rewrites, wherever they lie in the pool.  A slot outside [0, n_slots) reads zeros and stores nothing.
+__global__ __launch_bounds__(256) void stream_window_slots_kernel(float* __restrict__ hist, const int32_t* __restrict__ slots,
+                                                                  const float* __restrict__ z_new, float* win, int h_in, int n,
+                                                                  int h_out, int cap, int C, int n_slots, int rows)
+{
+    const int row0 = blockIdx.x * WIN_ROWS;
+    const int nrow = rows - row0 < WIN_ROWS ? rows - row0 : WIN_ROWS;
+    const int W = h_in + n;
+    const int total = nrow * W;
+    float* wb = win + (size_t)row0 * W;
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int r = e / W, j = e - r * W;
+        const int row = row0 + r, g = row / C, c = row - g * C;
+        const int slot = slots[g];
+        const bool ok = slot >= 0 && slot < n_slots;
+        wb[e] = j < h_in ? (ok ? hist[((size_t)slot * C + c) * cap + j] : 0.0f) : z_new[(size_t)row * n + (j - h_in)];
+    }
+    __syncthreads();
+    const int skip = W - h_out;
+    const int total_h = nrow * h_out;
+    for (int e = threadIdx.x; e < total_h; e += 256) {
+        const int r = e / h_out, j = e - r * h_out;
+        const int row = row0 + r, g = row / C, c = row - g * C;
+        const int slot = slots[g];
+        if (slot >= 0 && slot < n_slots) hist[((size_t)slot * C + c) * cap + j] = wb[r * W + skip + j];
+    }
+}
+
+// resample_stream_kernel with block g on state[slots[g]]: the same fma chain (k ascending, padding taps skipped), x_new and y
+// dense [G, .].  base / lead / n_out are those of the group's launch class (every member has consumed == 0, or every member
+// has consumed >= S).  A slot outside [0, n_slots) reads a zero state and stores none.
+__global__ __launch_bounds__(256) void resample_stream_slots_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
+                                                                    float* __restrict__ state, const int32_t* __restrict__ slots,
+                                                                    float* __restrict__ y, int n_new, int n_out, int orig, int ks,
+                                                                    int S, int base, int lead, int n_slots, int kern_in_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) float ksm[];
+    if (kern_in_lds) {
+        for (int e = threadIdx.x; e < ks; e += 256) ksm[e] = kern[e];
+        __syncthreads();
+    }
+    const float* kp = kern_in_lds ? ksm : kern;
+    const int b = blockIdx.x;
+    const int slot = slots[b];
+    const bool ok = slot >= 0 && slot < n_slots;
+    float* st = state + (size_t)(ok ? slot : 0) * S;
+    const float* xb = x_new + (size_t)b * n_new;
+    const int V = S + n_new;
+    for (int m = threadIdx.x; m < n_out; m += 256) {
+        const int j0 = base + m * orig;
+        const int k_lo = j0 < lead ? lead - j0 : 0;
+        int k_hi = ks; if (j0 + k_hi > V) k_hi = V - j0;
+        float acc = 0.0f;
+        for (int k = k_lo; k < k_hi; ++k) {
+            const int j = j0 + k;
+            acc = dfma(kp[k], j < S ? (ok ? st[j] : 0.0f) : xb[j - S], acc);
+        }
+        y[(size_t)b * n_out + m] = acc;
+    }
+    if (!ok) return;                                                     // block-uniform: the whole block leaves before the barriers
+    __syncthreads();
+    float keep[4];                                                       // S <= 1024 (checked by the entry point)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        const int j = i + n_new;
+        keep[u] = i < S ? (j < S ? st[j] : xb[j - S]) : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        if (i < S) st[i] = keep[u];
+    }
+}
+
+// rows[g][0 .. C) <- pool[slots[g]][0 .. C) (scatter == 0) or the other way (scatter != 0): the carried token of a group, so that
+// decode_latents works on a dense [G, C] copy.  One element per thread; a slot outside [0, n_slots) gathers zeros and scatters
+// nothing.  (At 256 sessions x 1024 channels this moves 1 MB: the launch, not the traffic, is its cost.)
+__global__ __launch_bounds__(256) void stream_rows_kernel(float* __restrict__ pool, const int32_t* __restrict__ slots,
+                                                          float* __restrict__ rows, int C, int n_slots, int total, int scatter)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int g = e / C, c = e - g * C;
+    const int slot = slots[g];
+    const bool ok = slot >= 0 && slot < n_slots;
+    if (scatter) {
+        if (ok) pool[(size_t)slot * C + c] = rows[e];
+    } else {
+        rows[e] = ok ? pool[(size_t)slot * C + c] : 0.0f;
+    }
+}
+
 hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
                                 hipStream_t s)
 {
@@ -145,6 +243,36 @@ hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int
 {
     if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return hipSuccess;
     hipLaunchKernelGGL(stream_samples_kernel, dim3((unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, fill, n, w, drop, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_window_slots(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out,
+                                      int cap, int C, int n_slots, int rows, hipStream_t s)
+{
+    if (rows == 0 || h_in + n == 0) return hipSuccess;
+    const int blocks = (rows + WIN_ROWS - 1) / WIN_ROWS;
+    hipLaunchKernelGGL(stream_window_slots_kernel, dim3((unsigned)blocks), dim3(256), 0, s, hist, slots, z_new, win, h_in, n, h_out,
+                       cap, C, n_slots, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_stream_slots(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int G,
+                                        int n_new, int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s)
+{
+    if (G == 0) return hipSuccess;
+    const size_t lds = (size_t)ks * sizeof(float);
+    const int in_lds = lds <= 48 * 1024;
+    hipLaunchKernelGGL(resample_stream_slots_kernel, dim3(G), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, slots, y, n_new,
+                       n_out, orig, ks, S, base, lead, n_slots, in_lds);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_rows(float* pool, const int32_t* slots, float* rows, int G, int C, int n_slots, int scatter, hipStream_t s)
+{
+    const int total = G * C;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pool, slots, rows, C, n_slots,
+                       total, scatter);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@ autocast, Evaluation/compare_dacvsproposal_5_eval.py:441) are widened to fp32: t
 from __future__ import annotations
 
 import ctypes
+import operator
 
 import torch
 
@@ -1045,6 +1046,92 @@ def stream_window(hist, h_in, z_new, h_out):
     check(_lib.lib().mvq_stream_window_f32(hist.data_ptr(), h_in, z_new.data_ptr(), n, win.data_ptr(), h_out, cap, B, C, _stream()),
           "mvq_stream_window_f32")
     return win
+
+
+# ---------------------------------------------------------------------------------- receiver pool
+def _slot_list(who, slots, pool, dims, slots_dev):
+    """The slot list of a group as HOST integers: refused here, before anything else is looked at, when one is out of range or
+    repeated, so no unchecked index reaches the device.  -> (G, int32 device tensor [G]); ``slots_dev`` is that tensor when the
+    caller uploaded the list already (StreamReceiverPool sends the lists of a whole tick with its packet bodies), else it is
+    uploaded here.  ``pool``: the state buffer, [n_slots, ...] of ``dims`` dimensions."""
+    if not isinstance(pool, torch.Tensor) or pool.dim() != dims:
+        raise MvqError(f"{who}: the pool buffer must be a tensor of {dims} dimensions")
+    try:
+        if isinstance(slots, torch.Tensor):
+            raise TypeError
+        host = [operator.index(v) for v in slots]
+    except TypeError:
+        raise MvqError(f"{who}: slots must be a sequence of host integers") from None
+    n_slots = pool.shape[0]
+    bad = [v for v in host if not 0 <= v < n_slots]
+    if bad:
+        raise MvqError(f"{who}: slot {bad[0]} outside the pool's [0, {n_slots})")
+    if len(set(host)) != len(host):
+        raise MvqError(f"{who}: a slot is listed twice in {host} (two blocks would update one row)")
+    if pool.dtype != torch.float32 or not pool.is_cuda or not pool.is_contiguous():
+        raise MvqError(f"{who}: the pool buffer must be a contiguous fp32 HIP tensor")
+    if slots_dev is None:
+        slots_dev = torch.tensor(host, dtype=torch.int32).to(pool.device)
+    elif not isinstance(slots_dev, torch.Tensor) or slots_dev.dtype != torch.int32 or slots_dev.device != pool.device \
+            or tuple(slots_dev.shape) != (len(host),) or not slots_dev.is_contiguous():
+        raise MvqError(f"{who}: slots_dev must be the contiguous int32 tensor [{len(host)}] of the list on {pool.device}")
+    return len(host), slots_dev
+
+
+def stream_rows(pool, slots, rows=None, slots_dev=None):
+    """The carried token of a group (mvq_stream_rows_f32).  ``rows`` None: gather, -> rows[G, C] = pool[slots]; ``rows`` [G, C]:
+    scatter, pool[slots] = rows (-> pool).  pool: contiguous fp32 [S, C] on the device, ``slots`` host integers."""
+    G, sd = _slot_list("stream_rows", slots, pool, 2, slots_dev)
+    S, C = pool.shape
+    scatter = rows is not None
+    if scatter:
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or not rows.is_contiguous() \
+                or tuple(rows.shape) != (G, C) or rows.device != pool.device:
+            raise MvqError(f"stream_rows: rows must be a contiguous fp32 tensor [G={G}, C={C}] on the pool's device")
+    else:
+        rows = torch.empty(G, C, device=pool.device, dtype=torch.float32)
+    check(_lib.lib().mvq_stream_rows_f32(pool.data_ptr(), sd.data_ptr(), G, S, rows.data_ptr(), C, int(scatter), _stream()),
+          "mvq_stream_rows_f32")
+    return pool if scatter else rows
+
+
+def stream_window_slots(hist, slots, h_in, z_new, h_out, slots_dev=None):
+    """stream_window for the sessions ``slots`` (host integers) of a pool: win[G, C, h_in + n] = [hist[slots][..., :h_in] | z_new],
+    then hist[slots][..., :h_out] <- the last h_out columns of win, in one launch (mvq_stream_window_slots_f32).  hist: contiguous
+    fp32 [S, C, cap], updated in place in the listed slots only."""
+    G, sd = _slot_list("stream_window_slots", slots, hist, 3, slots_dev)
+    z_new = _dev(z_new, "z_new")
+    S, C, cap = hist.shape
+    if z_new.dim() != 3 or tuple(z_new.shape[:2]) != (G, C) or z_new.device != hist.device:
+        raise MvqError(f"stream_window_slots: z_new {tuple(z_new.shape)} for [G={G}, C={C}, n] on the pool's device")
+    n = z_new.shape[2]
+    h_in, h_out = int(h_in), int(h_out)
+    win = torch.empty(G, C, max(h_in, 0) + n, device=hist.device, dtype=torch.float32)
+    check(_lib.lib().mvq_stream_window_slots_f32(hist.data_ptr(), sd.data_ptr(), G, S, h_in, z_new.data_ptr(), n, win.data_ptr(), h_out,
+                                                 cap, C, _stream()), "mvq_stream_window_slots_f32")
+    return win
+
+
+def resample_stream_slots(x_new, kern, state, slots, consumed, orig, newf, width, final=False, slots_dev=None):
+    """resample_stream for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots] moved on
+    in place (mvq_resample_stream_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of ``orig`` of at
+    least the state's length that one member has consumed (include/mvq.h)."""
+    G, sd = _slot_list("resample_stream_slots", slots, state, 2, slots_dev)
+    x_new = _dev(x_new, "x_new")
+    if x_new.dim() != 2 or x_new.shape[0] != G or x_new.device != state.device:
+        raise MvqError(f"resample_stream_slots: x_new {tuple(x_new.shape)} for [G={G}, n_new] on the pool's device")
+    n_new = x_new.shape[1]
+    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
+    if orig <= 0 or width < 0 or state.shape[1] != (width + orig - 1) // orig * orig + width:
+        raise MvqError(f"resample_stream_slots: state {tuple(state.shape)} does not fit orig={orig}, width={width}")
+    if not final and n_new % orig:
+        raise MvqError(f"resample_stream_slots: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
+    n_out = resample_stream_out_len(consumed, n_new, orig, width, final)
+    y = torch.empty(G, n_out, device=x_new.device, dtype=torch.float32)
+    check(_lib.lib().mvq_resample_stream_slots_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), G, state.shape[0],
+                                                   y.data_ptr(), n_new, consumed, int(bool(final)), n_out, orig, newf, width,
+                                                   kern.shape[1], _stream()), "mvq_resample_stream_slots_f32")
+    return y
 
 
 def stream_samples(buf, fill, x_new, w, drop):

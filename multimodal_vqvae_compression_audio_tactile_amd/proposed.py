@@ -737,6 +737,14 @@ class ProposedEval(_ProposedBase):
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
                               out_rate=out_rate, graph=graph)
 
+    def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
+        """A pool of up to ``slots`` independent receiver sessions on this model (stream.StreamReceiverPool): ``open`` a
+        session, ``step`` once per tick with the chunks that are ready (and the sessions that end); each session gets what a
+        stream_receiver(batch=1) of its own would return, and the sessions of a tick share batched launches."""
+        from .stream import StreamReceiverPool
+        return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
+                                  out_rate=out_rate)
+
     def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False):
         """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
         get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output

@@ -23,11 +23,13 @@ a window that starts on a multiple of 320 samples keeps every stage's stride ali
 (tests/test_sender_cpu.py: the sender's schedule is exact at halo 8 and not at halo 7).
 
 ``schedule`` / ``sender_schedule`` are host arithmetic only; ``StreamReceiver`` / ``StreamSender`` are the session objects
-(``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).
+(``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).  ``StreamReceiverPool`` (``ProposedEval.stream_receiver_pool``)
+serves receiver sessions that join, run and leave independently: their state lies in slots of one set of device buffers and a
+tick batches whichever sessions have a chunk ready, grouped by ``pool_groups``.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 HOP = 320                         # samples per latent token (the product of the decoder rates)
 DEC_TAIL = 8                      # T_DEC(z[..., :T]) has 320*T - 8 samples
@@ -38,6 +40,7 @@ CHUNK_TOK = 16                    # proposed.AR_CHUNK_TOK, restated so that sche
 PUSH_MAX_TOK = 16                 # a sender push carries 1..16 tokens of samples, so it completes at most one chunk
 SEND_CAP_TOK = 48                 # the sender's sample buffer: it never holds more than 47 tokens of samples
 ENC_RATES = (2, 4, 5, 8)          # dac.ENC_RATES, restated so that sender_schedule() needs no torch
+RS_ORIG, RS_WIDTH = 8, 49         # resample.sinc_resample_kernel(24000, 3000): decimation and filter half-width, restated likewise
 
 
 def schedule(T: int, chunk: int = CHUNK_TOK, halo: int = DEC_HALO_TOK) -> List[Tuple[int, int, int, int]]:
@@ -96,6 +99,58 @@ def sender_schedule(T_tokens: int, pushes, chunk: int = CHUNK_TOK, halo: int = E
     n_chunks = (T + chunk - 1) // chunk
     steps.append((start, T, c, n_chunks, 0) if n_chunks > c else (start, start, c, c, 0))
     return steps
+
+
+def _window_plan(before: int, n: int, last: bool) -> Tuple[int, int, int, int]:
+    """(h_in, h_out, e0, e1) of the step that takes n new tokens after ``before``: schedule()'s step in window-local samples."""
+    a = max(0, before - 2 * DEC_HALO_TOK)
+    h = before - a
+    g0 = HOP * max(0, before - DEC_HALO_TOK)
+    g1 = max(0, HOP * (before + n) - DEC_TAIL) if last else HOP * max(0, before + n - DEC_HALO_TOK)
+    return h, min(2 * DEC_HALO_TOK, h + n), g0 - HOP * a, g1 - HOP * a
+
+
+class PoolGroup(NamedTuple):
+    """Sessions of one tick that share a launch sequence: ``key`` = (min(tokens_before, 32), n, last); ``sids`` ascending;
+    ``plan`` = StreamReceiver._plan's (h_in, h_out, e0, e1) of every member; ``consumed`` = the resampler's launch class (the
+    samples a member at the key's token count has emitted) and ``n_out`` the outputs its piece of e1 - e0 samples completes."""
+    key: Tuple[int, int, bool]
+    sids: Tuple[int, ...]
+    plan: Tuple[int, int, int, int]
+    consumed: int
+    n_out: int
+
+
+def pool_groups(sessions, orig: int = RS_ORIG, width: int = RS_WIDTH) -> List[PoolGroup]:
+    """``sessions``: (sid, tokens_before, n, last) of every session that takes a step this tick -- a push has n = 16 and last
+    False, a finish 0 <= n <= 15 and last True; tokens_before is a multiple of 16.  -> the groups, ordered by key.
+
+    Sessions may share a launch sequence only when their launch parameters agree: the window plan (h_in, h_out, e0, e1) and the
+    resampler's base, lead and output count.  All of them depend on tokens_before only through min(tokens_before, 32): the plan is
+    that of 0, 16 or "32 and more" tokens (a full 20-token history, the emit range a fixed offset into the window), and the
+    resampler has consumed 0 samples, 1920 or at least 7040 -- zero or beyond its 105-sample state, where base = 0 and lead = 0
+    and the output count depends on the piece alone.  Nothing coarser is sound: sessions of different phases are never merged by
+    padding, a zero-latent history is not the sequence edge."""
+    seen, by_key = set(), {}
+    for sid, before, n, last in sessions:
+        before, n, last = int(before), int(n), bool(last)
+        if sid in seen:
+            raise ValueError(f"pool_groups: session {sid} is listed twice")
+        seen.add(sid)
+        if before < 0 or before % CHUNK_TOK or (n != CHUNK_TOK if not last else not 0 <= n < CHUNK_TOK):
+            raise ValueError(f"pool_groups: session {sid}: tokens_before = {before}, n = {n}, last = {last}")
+        by_key.setdefault((min(before, 2 * CHUNK_TOK), n, last), []).append(sid)
+    hold = (width + orig - 1) // orig
+    out = []
+    for key in sorted(by_key):
+        before, n, last = key
+        plan = _window_plan(before, n, last)
+        consumed = HOP * max(0, before - DEC_HALO_TOK)
+        n_new = plan[3] - plan[2]
+        done = max(0, consumed // orig - hold)
+        upto = -(-(consumed + n_new) // orig) if last else (consumed + n_new) // orig - hold
+        out.append(PoolGroup(key, tuple(sorted(by_key[key])), plan, consumed, max(0, upto - done)))
+    return out
 
 
 class StreamSender:
@@ -321,6 +376,27 @@ class StreamSender:
         return bodies_s, codes_s.clone()
 
 
+def _receiver_args(who, net, K, nb, packet_tok, conceal, out_rate):
+    """What a receiver session refuses at construction, StreamReceiver and StreamReceiverPool alike."""
+    from . import proposed
+    from .packets import StreamInfo, _check
+    if conceal == "plc":
+        raise ValueError(f"{who}: conceal='plc' attends over the whole sequence and cannot run on a chunk")
+    if conceal not in ("predict", "zero"):
+        raise ValueError(f"{who}: conceal must be 'predict' or 'zero', not {conceal!r}")
+    if packet_tok < 1 or CHUNK_TOK % packet_tok:
+        raise ValueError(f"{who}: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
+                         "(a packet must never straddle two chunks)")
+    if K != net.vq.n_embed:
+        raise ValueError(f"{who}: the stream has K = {K}, the model's codebook has {net.vq.n_embed}")
+    if not 0 <= nb <= net.vq.n_books:
+        raise ValueError(f"{who}: nb = {nb} books, the model has {net.vq.n_books}")
+    if int(out_rate) not in (proposed.EVAL_SR, proposed.ORIG_3K):
+        raise ValueError(f"{who}: out_rate must be {proposed.EVAL_SR} or {proposed.ORIG_3K}, not {out_rate}")
+    assert proposed.AR_CHUNK_TOK == CHUNK_TOK
+    _check(StreamInfo(K, nb, CHUNK_TOK, packet_tok))
+
+
 class StreamReceiver:
     """A receiver session for ``batch`` items advancing in lockstep: ``push`` one 16-token chunk at a time (whatever tactile
     packets of it arrived, and its audio codes), get back the samples that chunk completes; ``finish`` flushes.
@@ -343,25 +419,11 @@ class StreamReceiver:
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False):
         import torch
         from . import proposed
-        from .packets import StreamInfo, body_bytes, _check
+        from .packets import body_bytes
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
-        if conceal == "plc":
-            raise ValueError("StreamReceiver: conceal='plc' attends over the whole sequence and cannot run on a chunk")
-        if conceal not in ("predict", "zero"):
-            raise ValueError(f"StreamReceiver: conceal must be 'predict' or 'zero', not {conceal!r}")
-        if packet_tok < 1 or CHUNK_TOK % packet_tok:
-            raise ValueError(f"StreamReceiver: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
-                             "(a packet must never straddle two chunks)")
-        if K != net.vq.n_embed:
-            raise ValueError(f"StreamReceiver: the stream has K = {K}, the model's codebook has {net.vq.n_embed}")
-        if not 0 <= nb <= net.vq.n_books:
-            raise ValueError(f"StreamReceiver: nb = {nb} books, the model has {net.vq.n_books}")
+        _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
             raise ValueError("StreamReceiver: batch must be at least 1")
-        if int(out_rate) not in (proposed.EVAL_SR, proposed.ORIG_3K):
-            raise ValueError(f"StreamReceiver: out_rate must be {proposed.EVAL_SR} or {proposed.ORIG_3K}, not {out_rate}")
-        assert proposed.AR_CHUNK_TOK == CHUNK_TOK
-        _check(StreamInfo(K, nb, CHUNK_TOK, packet_tok))
         self.net, self.K, self.nb, self.packet_tok, self.batch = net, K, nb, packet_tok, batch
         self.books_use, self.conceal, self.out_rate, self.graph = books_use, conceal, int(out_rate), bool(graph)
         self.dev = net.proj_up.weight.device
@@ -417,12 +479,8 @@ class StreamReceiver:
 
     def _plan(self, n, last):
         """(h_in, h_out, e0, e1) of the step that takes n new tokens: schedule()'s step in window-local samples."""
-        before, after = self.tokens, self.tokens + n
-        a = max(0, before - 2 * DEC_HALO_TOK)
-        assert self.h == before - a
-        g0 = HOP * max(0, before - DEC_HALO_TOK)
-        g1 = max(0, HOP * after - DEC_TAIL) if last else HOP * max(0, after - DEC_HALO_TOK)
-        return self.h, min(2 * DEC_HALO_TOK, self.h + n), g0 - HOP * a, g1 - HOP * a
+        assert self.h == min(self.tokens, 2 * DEC_HALO_TOK)
+        return _window_plan(self.tokens, n, last)
 
     def _codes(self, audio_codes, n_lo, n_hi):
         import torch
@@ -524,3 +582,227 @@ class StreamReceiver:
             codes_s.copy_(codes)
         g.replay()
         return y_s
+
+
+class StreamReceiverPool:
+    """Receiver sessions that join, run for different lengths and leave independently, served together: ``open`` takes a
+    session slot, ``step`` is one tick that advances whichever sessions have a chunk ready (and flushes the ones that end),
+    ``close`` abandons one.  Every session gets back exactly what a ``StreamReceiver(batch=1)`` fed the same data returns from
+    ``push`` / ``finish``, bit for bit (``ops.get_arith() == "f32"`` only, as there).
+
+    The state of all ``slots`` sessions lies in one set of device buffers allocated once -- carry [S, C], hist [S, C, 20] and, for
+    out_rate=3000, the resampler's [S, 105] -- and a session is a row block of each (its slot).  A tick runs, in order:
+      host   every session's input checked and gathered (packets.gather against ITS seq_base, the audio codes' shape, the sids);
+             an error leaves every session as it was, the late counters too;
+             pool_groups: the sessions that share a launch sequence -- at most three groups of pushes (first, second, steady
+             chunk), one more per kind of finisher;
+      copy   ONE upload of all groups' slot lists, packet bodies and counts, ONE of all audio codes;
+      device per group of G sessions: ops.idx_unpack_packets -> ops.stream_rows (the carried tokens, pool -> dense [G, C]) ->
+             decode_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.stream_window_slots -> T_DEC on [G, C, window]
+             -> the emit slice (-> ops.resample_stream_slots).
+    ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick."""
+
+    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
+        import torch
+        from . import ops, proposed
+        from .packets import body_bytes
+        K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
+        _receiver_args("StreamReceiverPool", net, K, nb, packet_tok, conceal, out_rate)
+        if slots < 1:
+            raise ValueError("StreamReceiverPool: slots must be at least 1")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"StreamReceiverPool: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        self.net, self.K, self.nb, self.packet_tok, self.slots = net, K, nb, packet_tok, slots
+        self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
+        self.dev = net.proj_up.weight.device
+        self.C = net.proj_up.out_channels
+        self.full = body_bytes(packet_tok, nb, K)
+        self.n_audio_books = net.A_QUANT.n_codebooks
+        self.carry = torch.zeros(slots, self.C, device=self.dev)                       # per slot: z_run[..., -1] of the chunk before
+        self.hist = torch.zeros(slots, self.C, 2 * DEC_HALO_TOK, device=self.dev)      # per slot: the last <= 20 latent tokens
+        self.rs_state = self.rs_kernel = None
+        if self.out_rate != proposed.EVAL_SR:
+            from .resample import sinc_resample_kernel
+            kern, width, orig, new = sinc_resample_kernel(proposed.EVAL_SR, self.out_rate)
+            assert (orig, width, new) == (RS_ORIG, RS_WIDTH, 1)
+            self.rs_kernel = kern.to(self.dev)
+            self.rs_state = ops.resample_stream_state(orig, width, slots, self.dev)
+        self._free = list(range(slots))                                                # ascending: open() takes the lowest
+        self._sess = {}                                                                # sid -> [slot, tokens, late]
+        self._next_sid = 0
+
+    # ----------------------------------------------------------------------------------------------------------- sessions
+    @property
+    def active(self):
+        """The sids of the open sessions, ascending."""
+        return tuple(sorted(self._sess))
+
+    @property
+    def free(self):
+        """Slots no session holds."""
+        return len(self._free)
+
+    def _get(self, sid, what):
+        from ._lib import MvqError
+        try:
+            return self._sess[sid]
+        except (KeyError, TypeError):
+            raise MvqError(f"StreamReceiverPool: {what}: no open session {sid!r} (never opened, finished or closed)") from None
+
+    def tokens(self, sid):
+        """Tokens session ``sid`` has received."""
+        return self._get(sid, "tokens")[1]
+
+    def late(self, sid):
+        """Packets of chunks already decoded that session ``sid`` was handed (counted and ignored)."""
+        return self._get(sid, "late")[2]
+
+    def open(self):
+        """A new session -> its sid (never reused).  Takes the lowest free slot and resets it: the carried token and the
+        resampler state to zero on the device, the history count (the session's tokens) to zero."""
+        from ._lib import MvqError
+        if not self._free:
+            raise MvqError(f"StreamReceiverPool: all {self.slots} slots hold a session")
+        slot = self._free.pop(0)
+        self.carry[slot].zero_()
+        if self.rs_state is not None:
+            self.rs_state[slot].zero_()
+        sid, self._next_sid = self._next_sid, self._next_sid + 1
+        self._sess[sid] = [slot, 0, 0]
+        return sid
+
+    def close(self, sid):
+        """Abandon session ``sid`` without flushing it; its slot is free again."""
+        import bisect
+        slot = self._get(sid, "close")[0]
+        del self._sess[sid]
+        bisect.insort(self._free, slot)
+
+    # --------------------------------------------------------------------------------------------------------------- tick
+    def _codes(self, sid, audio_codes, n_lo, n_hi):
+        import torch
+        codes = torch.as_tensor(audio_codes)
+        if codes.dim() == 3 and codes.shape[0] == 1:
+            codes = codes[0]
+        if codes.dim() != 2 or codes.dtype.is_floating_point or codes.dtype == torch.bool:
+            raise ValueError(f"StreamReceiverPool: session {sid}: audio_codes must be int [n_codebooks, tokens] or [1, n_codebooks, "
+                             f"tokens], got {codes.dtype} {tuple(torch.as_tensor(audio_codes).shape)}")
+        if codes.shape[0] != self.n_audio_books:
+            raise ValueError(f"StreamReceiverPool: session {sid}: {codes.shape[0]} audio code rows, the model's quantiser has "
+                             f"{self.n_audio_books}")
+        if not n_lo <= codes.shape[1] <= n_hi:
+            want = f"{n_lo}" if n_lo == n_hi else f"{n_lo}..{n_hi}"
+            raise ValueError(f"StreamReceiverPool: session {sid}: {codes.shape[1]} audio tokens for a chunk of {want} tokens")
+        return codes
+
+    def _inputs(self, pushes, finishes):
+        """Host: every session's input of this tick, checked and gathered; raises before anything has changed.
+        -> {sid: (n, last, bodies uint8 [P, full] or None, counts uint8 [P] or None, codes [32, n] or None, late packets)}"""
+        from .packets import StreamInfo, gather
+        work = {}
+        for sid in pushes:
+            if sid in finishes:
+                raise ValueError(f"StreamReceiverPool: session {sid!r} is both pushed and finished in one tick")
+        for last, items in ((False, pushes), (True, finishes)):
+            for sid, item in items.items():
+                tokens = self._get(sid, "finish" if last else "push")[1]
+                if item is None:
+                    if not last:
+                        raise ValueError(f"StreamReceiverPool: session {sid}: a push needs (packets, audio_codes)")
+                    work[sid] = (0, True, None, None, None, 0)
+                    continue
+                try:
+                    pkts, audio_codes = item
+                except (TypeError, ValueError):
+                    raise ValueError(f"StreamReceiverPool: session {sid}: (packets, audio_codes) expected") from None
+                codes = self._codes(sid, audio_codes, 1, CHUNK_TOK - 1) if last else self._codes(sid, audio_codes, CHUNK_TOK, CHUNK_TOK)
+                n, late = int(codes.shape[1]), []
+                bodies, counts = gather(pkts, StreamInfo(self.K, self.nb, n, self.packet_tok), seq_base=tokens // self.packet_tok, late=late)
+                work[sid] = (n, last, bodies, counts, codes, len(late))
+        return work
+
+    def step(self, pushes, finishes=None):
+        """One tick.  ``pushes``: {sid: (packets of its current chunk that arrived, audio_codes int [32, 16] or [1, 32, 16])};
+        ``finishes``: {sid: (packets, audio_codes [32, n]) with 1 <= n <= 15, or None} for the sessions that end with this tick.
+        -> {sid: y [1, 1, n_emit]}: per session what StreamReceiver(batch=1).push / .finish returns (views of the group's
+        output).  A finished session's slot is freed.  ValueError / MvqError for any one session (a packet of a later chunk, a
+        wrong code shape, an unknown sid, a sid in both maps) comes before the first device call and leaves every session as it
+        was."""
+        import numpy as np
+        import torch
+        from . import ops
+        pushes, finishes = dict(pushes or {}), dict(finishes or {})
+        if ops.get_arith() != "f32":
+            raise ValueError(f"StreamReceiverPool: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        work = self._inputs(pushes, finishes)
+        if not work:
+            return {}
+        groups = pool_groups((sid, self._sess[sid][1], w[0], w[1]) for sid, w in work.items())
+        # ONE host array: the slot lists of all groups (int32, first: aligned), then per group its bodies and its counts
+        n_sess = sum(len(g.sids) for g in groups)
+        size, where = 4 * n_sess, []
+        for g in groups:
+            G, n = len(g.sids), g.key[1]
+            P = (n + self.packet_tok - 1) // self.packet_tok
+            where.append((size, size + G * P * self.full, P))
+            size += G * P * (self.full + 1)
+        host = np.empty(size, np.uint8)
+        slot_lists = [[self._sess[sid][0] for sid in g.sids] for g in groups]
+        host[:4 * n_sess] = np.asarray([s for sl in slot_lists for s in sl], np.int32).view(np.uint8)
+        flat_codes = []
+        for g, (o_b, o_c, P) in zip(groups, where):
+            G = len(g.sids)
+            if P:
+                hb, hc = host[o_b:o_c].reshape(G, P, self.full), host[o_c:o_c + G * P].reshape(G, P)
+                for i, sid in enumerate(g.sids):
+                    hb[i], hc[i] = work[sid][2], work[sid][3]
+                    flat_codes.append(work[sid][4].reshape(-1))
+        out = {}
+        with torch.no_grad():
+            up = torch.from_numpy(host).to(self.dev)
+            if flat_codes:
+                if any(c.is_cuda for c in flat_codes):
+                    codes_all = torch.cat([c.to(self.dev, torch.int64) for c in flat_codes])
+                else:
+                    codes_all = torch.cat([c.to(torch.int64) for c in flat_codes]).to(self.dev)
+            slots_all = up[:4 * n_sess].view(torch.int32)
+            s0 = c0 = 0
+            for g, sl, (o_b, o_c, P) in zip(groups, slot_lists, where):
+                G, n = len(g.sids), g.key[1]
+                codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n) if n else None
+                y = self._group(g, sl, slots_all[s0:s0 + G], up[o_b:o_c].view(G, P, self.full), up[o_c:o_c + G * P].view(G, P), codes)
+                s0, c0 = s0 + G, c0 + G * self.n_audio_books * n
+                for i, sid in enumerate(g.sids):
+                    out[sid] = y[i:i + 1]
+        for sid, w in work.items():
+            if w[1]:
+                self.close(sid)
+            else:
+                self._sess[sid][1] += w[0]
+                self._sess[sid][2] += w[5]
+        return out
+
+    def _group(self, g, slots, slots_dev, bodies, counts, codes):
+        """Device: one group's launch sequence -> y [G, 1, n_emit]; the listed slots of carry / hist / resampler state move on."""
+        import torch
+        from . import ops
+        G, (_, n, last), (h_in, h_out, e0, e1) = len(slots), g.key, g.plan
+        if n:
+            idx, nbv = ops.idx_unpack_packets(bodies, counts, self.K, self.nb, n, self.packet_tok)
+            carry = ops.stream_rows(self.carry, slots, slots_dev=slots_dev)
+            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry)
+            if not last:                                          # a finished session's slot is reset by the next open()
+                ops.stream_rows(self.carry, slots, rows=carry, slots_dev=slots_dev)
+            if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
+                z = ops.plc_mask_fill(z, None, nbv == 0)[0]
+        else:
+            z = torch.empty(G, self.C, 0, device=self.dev)
+        if h_in + n:
+            y = self.net.T_DEC(ops.stream_window_slots(self.hist, slots, h_in, z, h_out, slots_dev=slots_dev))[..., e0:e1]
+        else:
+            y = torch.empty(G, 1, 0, device=self.dev)
+        if self.rs_state is None or e1 == e0:                     # an empty piece is the finish of a session without a token
+            return y
+        y3 = ops.resample_stream_slots(y.reshape(G, e1 - e0), self.rs_kernel, self.rs_state, slots, g.consumed, RS_ORIG, 1, RS_WIDTH,
+                                       final=last, slots_dev=slots_dev)
+        return y3.reshape(G, 1, g.n_out)
