@@ -579,7 +579,8 @@ int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, floa
  * distinct slots inside [0, n_slots): two equal entries would make two blocks update one row.  The kernels check the range
  * themselves as a second line: a slot outside [0, n_slots) reads as zeros and nothing is stored to the pool for it.  All three:
  * MVQ_EINVAL before any launch on a negative size, n_group > n_slots, n_group * c beyond 2^31 - 1 or a null pointer with a
- * non-empty shape; n_group = 0 returns MVQ_OK without a launch.
+ * non-empty shape; n_group = 0 returns MVQ_OK without a launch.  The window and the resampler run the kernel body of their dense
+ * entry point under this addressing (one template, two instantiations), behind the same argument check.
  * mvq_stream_window_slots_f32: mvq_stream_window_f32 with row (g, ch) of z_new[n_group, c, n] and win[n_group, c, h_in + n] on
  * hist[slots[g]][ch]; the other refusals of mvq_stream_window_f32.  Rows of unlisted slots are not touched.
  * mvq_resample_stream_slots_f32: mvq_resample_stream_f32 with item g of x_new[n_group, n_new] and y[n_group, len_out] on

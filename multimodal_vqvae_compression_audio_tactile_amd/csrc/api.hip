@@ -1183,45 +1183,102 @@ int mvq_resample_f32(const float* x, const float* kern, float* y, int batch, int
     return e == hipSuccess ? MVQ_OK : hipfail(e, "resample");
 }
 
-int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new, long long consumed,
-                            int final, int len_out, int orig, int newf, int width, int ks, void* stream)
+// ---- the streaming state kernels: dense sessions, and slots[n_group] of a pool of n_slots sessions ----
+static int slots_shape_bad(const char* who, int n_group, int n_slots, long long per_session)
+{
+    if (n_group < 0 || n_slots < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
+    if (n_group > n_slots) return fail(MVQ_EINVAL, "%s: a group of %d sessions in a pool of %d slots", who, n_group, n_slots);
+    if ((long long)n_group * per_session > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: %d sessions of %lld rows", who, n_group, per_session);
+    return MVQ_OK;
+}
+
+// The one argument check of the streamed resampler (`who`: the entry point) -> the launch's state length, output count, base, lead.
+struct ResampleStreamPlan { int ns, n_out, base, lead; };
+static int resample_stream_plan(const char* who, int batch, int n_new, long long consumed, int final, int len_out, int orig, int newf,
+                                int width, int ks, ResampleStreamPlan* p)
 {
     if (batch < 0 || n_new < 0 || consumed < 0 || len_out < 0 || orig <= 0 || newf <= 0 || width < 0 || ks != 2 * width + orig)
-        return fail(MVQ_EINVAL, "resample_stream: bad shape (ks must be 2*width + orig)");
-    if (newf != 1) return fail(MVQ_EUNSUPPORTED, "resample_stream: pure decimation only (newf = %d after the gcd)", newf);
+        return fail(MVQ_EINVAL, "%s: bad shape (ks must be 2*width + orig)", who);
+    if (newf != 1) return fail(MVQ_EUNSUPPORTED, "%s: pure decimation only (newf = %d after the gcd)", who, newf);
     const long long hold = (width + orig - 1) / orig;
     const long long ns = hold * orig + width;
-    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "resample_stream: state of %lld samples exceeds 1024", ns);
-    if (consumed % orig) return fail(MVQ_EINVAL, "resample_stream: consumed = %lld is no multiple of orig = %d", consumed, orig);
+    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "%s: state of %lld samples exceeds 1024", who, ns);
+    if (consumed % orig) return fail(MVQ_EINVAL, "%s: consumed = %lld is no multiple of orig = %d", who, consumed, orig);
     if (!final && n_new % orig)
-        return fail(MVQ_EINVAL, "resample_stream: n_new = %d is no multiple of orig = %d (only the final call may be)", n_new, orig);
+        return fail(MVQ_EINVAL, "%s: n_new = %d is no multiple of orig = %d (only the final call may be)", who, n_new, orig);
     const long long q0 = consumed / orig;
     const long long done = q0 > hold ? q0 - hold : 0;
     const long long q1 = final ? (consumed + n_new + orig - 1) / orig : q0 + n_new / orig - hold;
     const long long n_out = q1 > done ? q1 - done : 0;
-    if (n_out != len_out) return fail(MVQ_EINVAL, "resample_stream: len_out = %d, this call completes %lld outputs", len_out, n_out);
-    if (batch == 0) return MVQ_OK;
-    if (!kern || !state || (!x_new && n_new) || (!y && n_out)) return fail(MVQ_EINVAL, "resample_stream: null tensor");
+    if (n_out != len_out) return fail(MVQ_EINVAL, "%s: len_out = %d, this call completes %lld outputs", who, len_out, n_out);
     const int base = (int)(q0 < hold ? (hold - q0) * orig : 0);
     const int lead = (int)(consumed < ns ? ns - consumed : 0);
-    hipError_t e = mvq::launch_resample_stream(x_new, kern, state, y, batch, n_new, (int)n_out, orig, ks, (int)ns, base, lead, S(stream));
+    *p = {(int)ns, (int)n_out, base, lead};
+    return MVQ_OK;
+}
+
+int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new, long long consumed,
+                            int final, int len_out, int orig, int newf, int width, int ks, void* stream)
+{
+    ResampleStreamPlan p;
+    if (int rc = resample_stream_plan("resample_stream", batch, n_new, consumed, final, len_out, orig, newf, width, ks, &p)) return rc;
+    if (batch == 0) return MVQ_OK;
+    if (!kern || !state || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "resample_stream: null tensor");
+    hipError_t e = mvq::launch_resample_stream(x_new, kern, state, nullptr, y, batch, n_new, p.n_out, orig, ks, p.ns, p.base, p.lead, 0,
+                                               S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream");
+}
+
+int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group, int n_slots,
+                                  float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
+                                  void* stream)
+{
+    if (int rc = slots_shape_bad("resample_stream_slots", n_group, n_slots, 1)) return rc;
+    ResampleStreamPlan p;
+    if (int rc = resample_stream_plan("resample_stream_slots", n_group, n_new, consumed, final, len_out, orig, newf, width, ks, &p)) return rc;
+    if (consumed && consumed < p.ns)
+        return fail(MVQ_EINVAL, "resample_stream_slots: consumed = %lld inside the %d-sample state names no launch class (0, or at least %d)",
+                    consumed, p.ns, p.ns);
+    if ((long long)n_group * p.n_out > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "resample_stream_slots: %d x %d outputs", n_group, p.n_out);
+    if (n_group == 0) return MVQ_OK;
+    if (!kern || !state || !slots || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "resample_stream_slots: null tensor");
+    hipError_t e = mvq::launch_resample_stream(x_new, kern, state, slots, y, n_group, n_new, p.n_out, orig, ks, p.ns, p.base, p.lead,
+                                               n_slots, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_slots");
+}
+
+// The size checks of the history window, `who` the entry point's name; `sessions` = batch or n_group.
+static int stream_window_sizes_bad(const char* who, int sessions, int h_in, int n, int h_out, int cap, int c)
+{
+    if (h_in < 0 || n < 0 || h_out < 0 || cap < 0 || sessions < 0 || c < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
+    if (h_in > cap || h_out > cap) return fail(MVQ_EINVAL, "%s: h_in = %d / h_out = %d exceed the history capacity %d", who, h_in, h_out, cap);
+    if ((long long)h_out > (long long)h_in + n) return fail(MVQ_EINVAL, "%s: h_out = %d exceeds h_in + n = %d + %d", who, h_out, h_in, n);
+    if ((long long)h_in + n > (1 << 20)) return fail(MVQ_EINVAL, "%s: window of %lld columns", who, (long long)h_in + n);
+    return MVQ_OK;
 }
 
 int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, float* win, int h_out, int cap, int batch, int c,
                           void* stream)
 {
-    if (h_in < 0 || n < 0 || h_out < 0 || cap < 0 || batch < 0 || c < 0)
-        return fail(MVQ_EINVAL, "stream_window: negative size");
-    if (h_in > cap || h_out > cap) return fail(MVQ_EINVAL, "stream_window: h_in = %d / h_out = %d exceed the history capacity %d", h_in, h_out, cap);
-    if ((long long)h_out > (long long)h_in + n) return fail(MVQ_EINVAL, "stream_window: h_out = %d exceeds h_in + n = %d + %d", h_out, h_in, n);
-    if ((long long)h_in + n > (1 << 20)) return fail(MVQ_EINVAL, "stream_window: window of %lld columns", (long long)h_in + n);
+    if (int rc = stream_window_sizes_bad("stream_window", batch, h_in, n, h_out, cap, c)) return rc;
     const size_t rows = (size_t)batch * c;
     if (rows == 0 || h_in + n == 0) return MVQ_OK;
     if (!win || (!hist && (h_in || h_out)) || (!z_new && n)) return fail(MVQ_EINVAL, "stream_window: null tensor");
     if (rows > (size_t)0x7FFFFFFF * 32) return fail(MVQ_EINVAL, "stream_window: too many rows");
-    hipError_t e = mvq::launch_stream_window(hist, z_new, win, h_in, n, h_out, cap, rows, S(stream));
+    hipError_t e = mvq::launch_stream_window(hist, nullptr, z_new, win, h_in, n, h_out, cap, c, 0, rows, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window");
+}
+
+int mvq_stream_window_slots_f32(float* hist, const int32_t* slots, int n_group, int n_slots, int h_in, const float* z_new, int n,
+                                float* win, int h_out, int cap, int c, void* stream)
+{
+    if (int rc = stream_window_sizes_bad("stream_window_slots", n_group, h_in, n, h_out, cap, c)) return rc;
+    if (int rc = slots_shape_bad("stream_window_slots", n_group, n_slots, c)) return rc;
+    const size_t rows = (size_t)n_group * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (!slots || !win || (!hist && (h_in || h_out)) || (!z_new && n)) return fail(MVQ_EINVAL, "stream_window_slots: null tensor");
+    hipError_t e = mvq::launch_stream_window(hist, slots, z_new, win, h_in, n, h_out, cap, c, n_slots, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window_slots");
 }
 
 int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
@@ -1238,64 +1295,6 @@ int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, floa
     if (!buf || (!x_new && n) || (!win && w)) return fail(MVQ_EINVAL, "stream_samples: null tensor");
     hipError_t e = mvq::launch_stream_samples(buf, x_new, win, fill, n, w, drop, cap, rows, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_samples");
-}
-
-// ---- the receiver pool: the three state kernels on slots[n_group] of a pool of n_slots sessions ----
-static int slots_shape_bad(const char* who, int n_group, int n_slots, long long per_session)
-{
-    if (n_group < 0 || n_slots < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
-    if (n_group > n_slots) return fail(MVQ_EINVAL, "%s: a group of %d sessions in a pool of %d slots", who, n_group, n_slots);
-    if ((long long)n_group * per_session > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: %d sessions of %lld rows", who, n_group, per_session);
-    return MVQ_OK;
-}
-
-int mvq_stream_window_slots_f32(float* hist, const int32_t* slots, int n_group, int n_slots, int h_in, const float* z_new, int n,
-                                float* win, int h_out, int cap, int c, void* stream)
-{
-    if (h_in < 0 || n < 0 || h_out < 0 || cap < 0 || c < 0) return fail(MVQ_EINVAL, "stream_window_slots: negative size");
-    if (int rc = slots_shape_bad("stream_window_slots", n_group, n_slots, c)) return rc;
-    if (h_in > cap || h_out > cap)
-        return fail(MVQ_EINVAL, "stream_window_slots: h_in = %d / h_out = %d exceed the history capacity %d", h_in, h_out, cap);
-    if ((long long)h_out > (long long)h_in + n)
-        return fail(MVQ_EINVAL, "stream_window_slots: h_out = %d exceeds h_in + n = %d + %d", h_out, h_in, n);
-    if ((long long)h_in + n > (1 << 20)) return fail(MVQ_EINVAL, "stream_window_slots: window of %lld columns", (long long)h_in + n);
-    const int rows = n_group * c;
-    if (rows == 0 || h_in + n == 0) return MVQ_OK;
-    if (!slots || !win || (!hist && (h_in || h_out)) || (!z_new && n)) return fail(MVQ_EINVAL, "stream_window_slots: null tensor");
-    hipError_t e = mvq::launch_stream_window_slots(hist, slots, z_new, win, h_in, n, h_out, cap, c, n_slots, rows, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window_slots");
-}
-
-int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group, int n_slots,
-                                  float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
-                                  void* stream)
-{
-    if (n_new < 0 || consumed < 0 || len_out < 0 || orig <= 0 || newf <= 0 || width < 0 || ks != 2 * width + orig)
-        return fail(MVQ_EINVAL, "resample_stream_slots: bad shape (ks must be 2*width + orig)");
-    if (int rc = slots_shape_bad("resample_stream_slots", n_group, n_slots, 1)) return rc;
-    if (newf != 1) return fail(MVQ_EUNSUPPORTED, "resample_stream_slots: pure decimation only (newf = %d after the gcd)", newf);
-    const long long hold = (width + orig - 1) / orig;
-    const long long ns = hold * orig + width;
-    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "resample_stream_slots: state of %lld samples exceeds 1024", ns);
-    if (consumed % orig) return fail(MVQ_EINVAL, "resample_stream_slots: consumed = %lld is no multiple of orig = %d", consumed, orig);
-    if (consumed && consumed < ns)
-        return fail(MVQ_EINVAL, "resample_stream_slots: consumed = %lld inside the %lld-sample state names no launch class (0, or at least %lld)",
-                    consumed, ns, ns);
-    if (!final && n_new % orig)
-        return fail(MVQ_EINVAL, "resample_stream_slots: n_new = %d is no multiple of orig = %d (only the final call may be)", n_new, orig);
-    const long long q0 = consumed / orig;
-    const long long done = q0 > hold ? q0 - hold : 0;
-    const long long q1 = final ? (consumed + n_new + orig - 1) / orig : q0 + n_new / orig - hold;
-    const long long n_out = q1 > done ? q1 - done : 0;
-    if (n_out != len_out) return fail(MVQ_EINVAL, "resample_stream_slots: len_out = %d, this call completes %lld outputs", len_out, n_out);
-    if ((long long)n_group * n_out > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "resample_stream_slots: %d x %lld outputs", n_group, n_out);
-    if (n_group == 0) return MVQ_OK;
-    if (!kern || !state || !slots || (!x_new && n_new) || (!y && n_out)) return fail(MVQ_EINVAL, "resample_stream_slots: null tensor");
-    const int base = (int)(q0 < hold ? (hold - q0) * orig : 0);
-    const int lead = (int)(consumed < ns ? ns - consumed : 0);
-    hipError_t e = mvq::launch_resample_stream_slots(x_new, kern, state, slots, y, n_group, n_new, (int)n_out, orig, ks, (int)ns, base,
-                                                     lead, n_slots, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_slots");
 }
 
 int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream)

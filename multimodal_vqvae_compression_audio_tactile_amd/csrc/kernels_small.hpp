@@ -127,17 +127,13 @@ hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_re
                                      int T, int K, int bits, int ptok, hipStream_t s);
 hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
                                      int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
-// stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024)
-hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
-                                hipStream_t s);
-hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, float* y, int B, int n_new, int n_out, int orig,
-                                  int ks, int S, int base, int lead, hipStream_t s);
-// stream.hip: the receiver pool's state kernels (G sessions of a pool of n_slots, addressed through the device list slots[G];
-// rows = G*C <= INT_MAX)
-hipError_t launch_stream_window_slots(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out,
-                                      int cap, int C, int n_slots, int rows, hipStream_t s);
-hipError_t launch_resample_stream_slots(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int G,
-                                        int n_new, int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s);
+// stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024).  slots ==
+// nullptr: every session of the buffers, densely; else the G sessions slots[G] (a device list) of a pool of n_slots, C rows per
+// session and rows = G*C <= INT_MAX
+hipError_t launch_stream_window(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out, int cap,
+                                int C, int n_slots, size_t rows, hipStream_t s);
+hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B, int n_new,
+                                  int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s);
 hipError_t launch_stream_rows(float* pool, const int32_t* slots, float* rows, int G, int C, int n_slots, int scatter, hipStream_t s);
 // stream.hip: the streaming sender's sample state (one block per row of buf[rows][cap])
 hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int fill, int n, int w, int drop, int cap, int rows,

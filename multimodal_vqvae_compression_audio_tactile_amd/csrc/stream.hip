@@ -1,8 +1,10 @@
 // stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32 and
 // mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
 // the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
-// every time (a captured graph replays it).  The *_slots kernels and stream_rows_kernel serve a POOL of sessions (DESIGN.md
-// section 16): the state buffers hold one row block per session slot and a launch works on the slots a device list names.
+// every time (a captured graph replays it).  A POOL of sessions keeps one row block per session slot in
+// the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
+// instantiated for the dense addressing and for the slot list (Sessions<SLOTS> below), and stream_rows_kernel moves the carried
+// tokens.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -15,12 +17,43 @@ constexpr int SMP_THREADS = 1024;     // stream_samples_kernel: one block per ro
 constexpr int SMP_PER = 4;            // elements a thread carries across the barrier: a tile is SMP_THREADS * SMP_PER samples
 }  // namespace
 
-// win[r][0 .. h_in + n) = [hist[r][0 .. h_in) | z_new[r][0 .. n)], then hist[r][0 .. h_out) = the last h_out columns of win[r].
-// r = b*C + c; hist rows have the fixed pitch `cap`.  A block owns WIN_ROWS consecutive rows: phase 1 reads hist and z_new and
-// writes win (a buffer of its own), the barrier ends every read of the block's hist rows, phase 2 rewrites those rows from the
-// block's own part of win.  No row is touched by two blocks, so the in-place update has no cross-block hazard.
+// Which session of the state buffer a kernel's session g works on, fixed at compile time.  Dense (a lockstep session object):
+// session g itself, always valid -- nothing is loaded and every guard folds away.  Slots (a group of a pool): slots[g], valid
+// inside [0, n_slots); the host wrapper refuses a repeated slot, so two sessions of a launch never share state rows.
+template <bool SLOTS> struct Sessions;
+template <> struct Sessions<false> {
+    __device__ bool session(int g, size_t& s) const { s = (size_t)g; return true; }
+    __device__ bool row(size_t r, size_t& at) const { at = r; return true; }
+};
+template <> struct Sessions<true> {
+    const int32_t* slots;
+    int n_slots;
+    int C;                                                               // rows per session (stream_window; rows <= INT_MAX)
+    __device__ bool session(int g, size_t& s) const
+    {
+        const int slot = slots[g];
+        s = (size_t)slot;
+        return slot >= 0 && slot < n_slots;
+    }
+    __device__ bool row(size_t r, size_t& at) const                      // row g*C + c of the group -> row slots[g]*C + c of the pool
+    {
+        const int g = (int)r / C, c = (int)r - g * C;
+        size_t s;
+        const bool ok = session(g, s);
+        at = s * C + c;
+        return ok;
+    }
+};
+
+// win[r][0 .. h_in + n) = [hist[r'][0 .. h_in) | z_new[r][0 .. n)], then hist[r'][0 .. h_out) = the last h_out columns of win[r].
+// r = b*C + c; z_new and win are dense, r' = ses.row(r) is the session's row of hist (pitch `cap`): r itself, or the row of the
+// slot.  A block owns WIN_ROWS consecutive rows r: phase 1 reads hist and z_new and writes win (a buffer of its own), the barrier
+// ends every read of the block's hist rows, phase 2 rewrites those rows from the block's own part of win.  Distinct r are
+// distinct r' (distinct slots), so no hist row is touched by two blocks and the in-place update has no cross-block hazard,
+// wherever the rows lie in a pool.  A slot outside [0, n_slots) reads zeros and stores nothing.
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void stream_window_kernel(float* __restrict__ hist, const float* __restrict__ z_new, float* win,
-                                                            int h_in, int n, int h_out, int cap, size_t rows)
+                                                            int h_in, int n, int h_out, int cap, size_t rows, Sessions<SLOTS> ses)
 {
     const size_t row0 = (size_t)blockIdx.x * WIN_ROWS;
     const int nrow = (int)(rows - row0 < (size_t)WIN_ROWS ? rows - row0 : (size_t)WIN_ROWS);
@@ -29,27 +62,34 @@ __global__ __launch_bounds__(256) void stream_window_kernel(float* __restrict__ 
     float* wb = win + row0 * (size_t)W;
     for (int e = threadIdx.x; e < total; e += 256) {
         const int r = e / W, j = e - r * W;
-        wb[e] = j < h_in ? hist[(row0 + r) * (size_t)cap + j] : z_new[(row0 + r) * (size_t)n + (j - h_in)];
+        size_t at;
+        const bool ok = ses.row(row0 + r, at);
+        wb[e] = j < h_in ? (ok ? hist[at * (size_t)cap + j] : 0.0f) : z_new[(row0 + r) * (size_t)n + (j - h_in)];
     }
     __syncthreads();
     const int skip = W - h_out;
     const int total_h = nrow * h_out;
     for (int e = threadIdx.x; e < total_h; e += 256) {
         const int r = e / h_out, j = e - r * h_out;
-        hist[(row0 + r) * (size_t)cap + j] = wb[r * W + skip + j];
+        size_t at;
+        if (ses.row(row0 + r, at)) hist[at * (size_t)cap + j] = wb[r * W + skip + j];
     }
 }
 
-// Stateful decimation (newf == 1).  state[b][0 .. S), S = hold*orig + width with hold = ceil(width / orig), holds the last S
-// samples of (zeros | x received so far).  With v = [state | x_new] (S + n_new samples), output m of this call reads
-// v[base + m*orig + k], k < ks = 2*width + orig; `lead` leading samples of v are left padding and `S + n_new` is where the right
-// padding begins: taps outside [lead, S + n_new) are skipped, exactly the taps resample_kernel skips, so the fma chain (k
-// ascending) of an output is the one the whole-signal kernel runs.  One block per item: outputs first, then the barrier, then
-// the state moves up by n_new samples (each thread carries its elements in registers across a second barrier: a shift by less
-// than S overlaps itself).
+// Stateful decimation (newf == 1).  state[s][0 .. S), S = hold*orig + width with hold = ceil(width / orig), holds the last S
+// samples of (zeros | x received so far) of session s = ses.session(b): b itself, or slots[b]; x_new and y are dense [B, .].
+// With v = [state | x_new] (S + n_new samples), output m of this call reads v[base + m*orig + k], k < ks = 2*width + orig;
+// `lead` leading samples of v are left padding and `S + n_new` is where the right padding begins: taps outside [lead, S + n_new)
+// are skipped, exactly the taps resample_kernel skips, so the fma chain (k ascending) of an output is the one the whole-signal
+// kernel runs.  base / lead / n_out are one launch's: a group of a pool shares a launch class (every member has consumed == 0,
+// or every member has consumed >= S).  One block per item: outputs first, then the barrier, then the state moves up by n_new
+// samples (each thread carries its elements in registers across a second barrier: a shift by less than S overlaps itself).
+// A slot outside [0, n_slots) reads a zero state and stores none.
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
                                                               float* __restrict__ state, float* __restrict__ y, int n_new, int n_out,
-                                                              int orig, int ks, int S, int base, int lead, int kern_in_lds)
+                                                              int orig, int ks, int S, int base, int lead, int kern_in_lds,
+                                                              Sessions<SLOTS> ses)
 {
     extern __shared__ __attribute__((aligned(16))) float ksm[];
     if (kern_in_lds) {
@@ -58,7 +98,9 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __res
     }
     const float* kp = kern_in_lds ? ksm : kern;
     const int b = blockIdx.x;
-    float* st = state + (size_t)b * S;
+    size_t at;
+    const bool ok = ses.session(b, at);
+    float* st = state + (ok ? at : 0) * S;
     const float* xb = x_new + (size_t)b * n_new;
     const int V = S + n_new;
     for (int m = threadIdx.x; m < n_out; m += 256) {
@@ -68,10 +110,11 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __res
         float acc = 0.0f;
         for (int k = k_lo; k < k_hi; ++k) {
             const int j = j0 + k;
-            acc = dfma(kp[k], j < S ? st[j] : xb[j - S], acc);
+            acc = dfma(kp[k], j < S ? (ok ? st[j] : 0.0f) : xb[j - S], acc);
         }
         y[(size_t)b * n_out + m] = acc;
     }
+    if (!ok) return;                                                     // block-uniform: the whole block leaves before the barriers
     __syncthreads();
     float keep[4];                                                       // S <= 1024 (checked by the entry point)
 #pragma unroll
@@ -121,85 +164,7 @@ __global__ __launch_bounds__(SMP_THREADS) void stream_samples_kernel(float* buf,
     }
 }
 
-// ---- the session pool: state addressed through a slot list ---------------------------------------------------------------------
-// stream_window_kernel for a group of G sessions of a pool: row r = g*C + c of win / z_new (dense) is row slots[g]*C + c of
-// hist.  Distinct slots (the host wrapper refuses a repeated one) are distinct hist rows, so a block still owns the hist rows
-// it reads and rewrites, wherever they lie in the pool.  A slot outside [0, n_slots) reads zeros and stores nothing.
-__global__ __launch_bounds__(256) void stream_window_slots_kernel(float* __restrict__ hist, const int32_t* __restrict__ slots,
-                                                                  const float* __restrict__ z_new, float* win, int h_in, int n,
-                                                                  int h_out, int cap, int C, int n_slots, int rows)
-{
-    const int row0 = blockIdx.x * WIN_ROWS;
-    const int nrow = rows - row0 < WIN_ROWS ? rows - row0 : WIN_ROWS;
-    const int W = h_in + n;
-    const int total = nrow * W;
-    float* wb = win + (size_t)row0 * W;
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int r = e / W, j = e - r * W;
-        const int row = row0 + r, g = row / C, c = row - g * C;
-        const int slot = slots[g];
-        const bool ok = slot >= 0 && slot < n_slots;
-        wb[e] = j < h_in ? (ok ? hist[((size_t)slot * C + c) * cap + j] : 0.0f) : z_new[(size_t)row * n + (j - h_in)];
-    }
-    __syncthreads();
-    const int skip = W - h_out;
-    const int total_h = nrow * h_out;
-    for (int e = threadIdx.x; e < total_h; e += 256) {
-        const int r = e / h_out, j = e - r * h_out;
-        const int row = row0 + r, g = row / C, c = row - g * C;
-        const int slot = slots[g];
-        if (slot >= 0 && slot < n_slots) hist[((size_t)slot * C + c) * cap + j] = wb[r * W + skip + j];
-    }
-}
-
-// resample_stream_kernel with block g on state[slots[g]]: the same fma chain (k ascending, padding taps skipped), x_new and y
-// dense [G, .].  base / lead / n_out are those of the group's launch class (every member has consumed == 0, or every member
-// has consumed >= S).  A slot outside [0, n_slots) reads a zero state and stores none.
-__global__ __launch_bounds__(256) void resample_stream_slots_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
-                                                                    float* __restrict__ state, const int32_t* __restrict__ slots,
-                                                                    float* __restrict__ y, int n_new, int n_out, int orig, int ks,
-                                                                    int S, int base, int lead, int n_slots, int kern_in_lds)
-{
-    extern __shared__ __attribute__((aligned(16))) float ksm[];
-    if (kern_in_lds) {
-        for (int e = threadIdx.x; e < ks; e += 256) ksm[e] = kern[e];
-        __syncthreads();
-    }
-    const float* kp = kern_in_lds ? ksm : kern;
-    const int b = blockIdx.x;
-    const int slot = slots[b];
-    const bool ok = slot >= 0 && slot < n_slots;
-    float* st = state + (size_t)(ok ? slot : 0) * S;
-    const float* xb = x_new + (size_t)b * n_new;
-    const int V = S + n_new;
-    for (int m = threadIdx.x; m < n_out; m += 256) {
-        const int j0 = base + m * orig;
-        const int k_lo = j0 < lead ? lead - j0 : 0;
-        int k_hi = ks; if (j0 + k_hi > V) k_hi = V - j0;
-        float acc = 0.0f;
-        for (int k = k_lo; k < k_hi; ++k) {
-            const int j = j0 + k;
-            acc = dfma(kp[k], j < S ? (ok ? st[j] : 0.0f) : xb[j - S], acc);
-        }
-        y[(size_t)b * n_out + m] = acc;
-    }
-    if (!ok) return;                                                     // block-uniform: the whole block leaves before the barriers
-    __syncthreads();
-    float keep[4];                                                       // S <= 1024 (checked by the entry point)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int i = threadIdx.x + 256 * u;
-        const int j = i + n_new;
-        keep[u] = i < S ? (j < S ? st[j] : xb[j - S]) : 0.0f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int i = threadIdx.x + 256 * u;
-        if (i < S) st[i] = keep[u];
-    }
-}
-
+// ---- the session pool: the carried tokens ----------------------------------------------------------------------------------------
 // rows[g][0 .. C) <- pool[slots[g]][0 .. C) (scatter == 0) or the other way (scatter != 0): the carried token of a group, so that
 // decode_latents works on a dense [G, C] copy.  One element per thread; a slot outside [0, n_slots) gathers zeros and scatters
 // nothing.  (At 256 sessions x 1024 channels this moves 1 MB: the launch, not the traffic, is its cost.)
@@ -218,23 +183,33 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(float* __restrict__ po
     }
 }
 
-hipError_t launch_stream_window(float* hist, const float* z_new, float* win, int h_in, int n, int h_out, int cap, size_t rows,
-                                hipStream_t s)
+// slots == nullptr: the dense instantiation; else the group slots[rows / C] (slots[B]) of a pool of n_slots sessions.
+hipError_t launch_stream_window(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out, int cap,
+                                int C, int n_slots, size_t rows, hipStream_t s)
 {
     if (rows == 0 || h_in + n == 0) return hipSuccess;
-    const size_t blocks = (rows + WIN_ROWS - 1) / WIN_ROWS;
-    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, hist, z_new, win, h_in, n, h_out, cap, rows);
+    const dim3 grid((unsigned)((rows + WIN_ROWS - 1) / WIN_ROWS)), block(256);
+    if (slots)
+        hipLaunchKernelGGL(stream_window_kernel<true>, grid, block, 0, s, hist, z_new, win, h_in, n, h_out, cap, rows,
+                           Sessions<true>{slots, n_slots, C});
+    else
+        hipLaunchKernelGGL(stream_window_kernel<false>, grid, block, 0, s, hist, z_new, win, h_in, n, h_out, cap, rows,
+                           Sessions<false>{});
     return hipGetLastError();
 }
 
-hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, float* y, int B, int n_new, int n_out, int orig,
-                                  int ks, int S, int base, int lead, hipStream_t s)
+hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B, int n_new,
+                                  int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s)
 {
     if (B == 0) return hipSuccess;
     const size_t lds = (size_t)ks * sizeof(float);
     const int in_lds = lds <= 48 * 1024;
-    hipLaunchKernelGGL(resample_stream_kernel, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out, orig, ks,
-                       S, base, lead, in_lds);
+    if (slots)
+        hipLaunchKernelGGL(resample_stream_kernel<true>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out,
+                           orig, ks, S, base, lead, in_lds, Sessions<true>{slots, n_slots, 1});
+    else
+        hipLaunchKernelGGL(resample_stream_kernel<false>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out,
+                           orig, ks, S, base, lead, in_lds, Sessions<false>{});
     return hipGetLastError();
 }
 
@@ -243,27 +218,6 @@ hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int
 {
     if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return hipSuccess;
     hipLaunchKernelGGL(stream_samples_kernel, dim3((unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, fill, n, w, drop, cap);
-    return hipGetLastError();
-}
-
-hipError_t launch_stream_window_slots(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out,
-                                      int cap, int C, int n_slots, int rows, hipStream_t s)
-{
-    if (rows == 0 || h_in + n == 0) return hipSuccess;
-    const int blocks = (rows + WIN_ROWS - 1) / WIN_ROWS;
-    hipLaunchKernelGGL(stream_window_slots_kernel, dim3((unsigned)blocks), dim3(256), 0, s, hist, slots, z_new, win, h_in, n, h_out,
-                       cap, C, n_slots, rows);
-    return hipGetLastError();
-}
-
-hipError_t launch_resample_stream_slots(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int G,
-                                        int n_new, int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s)
-{
-    if (G == 0) return hipSuccess;
-    const size_t lds = (size_t)ks * sizeof(float);
-    const int in_lds = lds <= 48 * 1024;
-    hipLaunchKernelGGL(resample_stream_slots_kernel, dim3(G), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, slots, y, n_new,
-                       n_out, orig, ks, S, base, lead, n_slots, in_lds);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import MvqError, check
+from .stream import resample_stream_out_len  # noqa: F401  (host arithmetic, kept where no torch is needed)
 
 
 def _stream():
@@ -1003,49 +1004,64 @@ def resample_stream_state(orig, width, batch, device):
     return torch.zeros(int(batch), hold * int(orig) + int(width), device=device, dtype=torch.float32)
 
 
-def resample_stream_out_len(consumed, n_new, orig, width, final=False):
-    """Outputs a resample_stream call completes after ``consumed`` samples: the count mvq_resample_stream_f32 checks."""
-    hold = (width + orig - 1) // orig
-    done = max(0, consumed // orig - hold)
-    upto = -(-(consumed + n_new) // orig) if final else (consumed + n_new) // orig - hold
-    return max(0, upto - done)
+def _resample_stream(who, x_new, kern, state, sd, consumed, orig, newf, width, final):
+    """resample_stream and resample_stream_slots: ``sd`` None for the dense sessions state[B, S], else the group's device slot
+    list (_slot_list has checked ``state`` then)."""
+    x_new = _dev(x_new, "x_new")
+    if state.dim() != 2 or state.dtype != torch.float32 or not state.is_cuda or not state.is_contiguous() or x_new.dim() != 2 \
+            or x_new.shape[0] != (state.shape[0] if sd is None else sd.shape[0]) or x_new.device != state.device:
+        raise MvqError(f"{who}: x_new must be [B, n_new], one row per session, on the device of state, a contiguous fp32 HIP tensor "
+                       f"[sessions, S]; got {tuple(x_new.shape)} and {tuple(state.shape)}")
+    B, n_new = x_new.shape
+    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
+    if orig <= 0 or width < 0 or state.shape[1] != (width + orig - 1) // orig * orig + width:
+        raise MvqError(f"{who}: state {tuple(state.shape)} does not fit orig={orig}, width={width}")
+    if not final and n_new % orig:
+        raise MvqError(f"{who}: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
+    n_out = resample_stream_out_len(consumed, n_new, orig, width, final)
+    y = torch.empty(B, n_out, device=x_new.device, dtype=torch.float32)
+    tail = (n_new, consumed, int(bool(final)), n_out, orig, newf, width, kern.shape[1], _stream())
+    if sd is None:
+        check(_lib.lib().mvq_resample_stream_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, *tail),
+              "mvq_resample_stream_f32")
+    else:
+        check(_lib.lib().mvq_resample_stream_slots_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), B,
+                                                       state.shape[0], y.data_ptr(), *tail), "mvq_resample_stream_slots_f32")
+    return y
 
 
 def resample_stream(x_new, kern, state, consumed, orig, newf, width, final=False):
     """The next piece x_new[B, n_new] of a decimated stream -> the outputs y[B, n_out] it completes (mvq_resample_stream_f32);
     ``state`` (resample_stream_state) is updated in place, ``consumed`` = samples given to earlier calls."""
-    x_new = _dev(x_new, "x_new")
-    if x_new.dim() != 2 or state.dim() != 2 or state.shape[0] != x_new.shape[0] or state.dtype != torch.float32 \
-            or not state.is_cuda or not state.is_contiguous():
-        raise MvqError("resample_stream: x_new must be [B, n_new] and state a contiguous fp32 HIP tensor [B, S]")
-    B, n_new = x_new.shape
-    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
-    if orig <= 0 or width < 0 or state.shape[1] != (width + orig - 1) // orig * orig + width:
-        raise MvqError(f"resample_stream: state {tuple(state.shape)} does not fit orig={orig}, width={width}, B={B}")
-    if not final and n_new % orig:
-        raise MvqError(f"resample_stream: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
-    n_out = resample_stream_out_len(consumed, n_new, orig, width, final)
-    y = torch.empty(B, n_out, device=x_new.device, dtype=torch.float32)
-    check(_lib.lib().mvq_resample_stream_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, n_new, consumed,
-                                             int(bool(final)), n_out, orig, newf, width, kern.shape[1], _stream()),
-          "mvq_resample_stream_f32")
-    return y
+    return _resample_stream("resample_stream", x_new, kern, state, None, consumed, orig, newf, width, final)
+
+
+def _stream_window(who, hist, h_in, z_new, h_out, sd):
+    """stream_window and stream_window_slots: ``sd`` None for the dense sessions hist[B, C, cap], else the group's device slot
+    list."""
+    z_new = _dev(z_new, "z_new")
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 3 or z_new.dim() != 3 or hist.dtype != torch.float32 or not hist.is_cuda \
+            or not hist.is_contiguous() or hist.device != z_new.device \
+            or tuple(z_new.shape[:2]) != (hist.shape[0] if sd is None else sd.shape[0], hist.shape[1]):
+        raise MvqError(f"{who}: hist must be a contiguous fp32 HIP tensor [sessions, C, cap] and z_new [B, C, n] on its device, one "
+                       "block of C rows per session")
+    S, C, cap = hist.shape
+    B, _, n = z_new.shape
+    h_in, h_out = int(h_in), int(h_out)
+    win = torch.empty(B, C, max(h_in, 0) + n, device=z_new.device, dtype=torch.float32)
+    if sd is None:
+        check(_lib.lib().mvq_stream_window_f32(hist.data_ptr(), h_in, z_new.data_ptr(), n, win.data_ptr(), h_out, cap, B, C, _stream()),
+              "mvq_stream_window_f32")
+    else:
+        check(_lib.lib().mvq_stream_window_slots_f32(hist.data_ptr(), sd.data_ptr(), B, S, h_in, z_new.data_ptr(), n, win.data_ptr(),
+                                                     h_out, cap, C, _stream()), "mvq_stream_window_slots_f32")
+    return win
 
 
 def stream_window(hist, h_in, z_new, h_out):
     """win[B, C, h_in + n] = [hist[..., :h_in] | z_new[B, C, n]], then hist[..., :h_out] <- the last h_out columns of win, in one
     launch (mvq_stream_window_f32).  hist: contiguous fp32 [B, C, cap], updated in place."""
-    z_new = _dev(z_new, "z_new")
-    if not isinstance(hist, torch.Tensor) or hist.dim() != 3 or z_new.dim() != 3 or hist.dtype != torch.float32 or not hist.is_cuda \
-            or not hist.is_contiguous() or hist.shape[:2] != z_new.shape[:2] or hist.device != z_new.device:
-        raise MvqError("stream_window: hist must be a contiguous fp32 HIP tensor [B, C, cap] with z_new's batch and channels")
-    B, C, cap = hist.shape
-    n = z_new.shape[2]
-    h_in, h_out = int(h_in), int(h_out)
-    win = torch.empty(B, C, max(h_in, 0) + n, device=z_new.device, dtype=torch.float32)
-    check(_lib.lib().mvq_stream_window_f32(hist.data_ptr(), h_in, z_new.data_ptr(), n, win.data_ptr(), h_out, cap, B, C, _stream()),
-          "mvq_stream_window_f32")
-    return win
+    return _stream_window("stream_window", hist, h_in, z_new, h_out, None)
 
 
 # ---------------------------------------------------------------------------------- receiver pool (DESIGN.md section 16)
@@ -1099,39 +1115,16 @@ def stream_window_slots(hist, slots, h_in, z_new, h_out, slots_dev=None):
     """stream_window for the sessions ``slots`` (host integers) of a pool: win[G, C, h_in + n] = [hist[slots][..., :h_in] | z_new],
     then hist[slots][..., :h_out] <- the last h_out columns of win, in one launch (mvq_stream_window_slots_f32).  hist: contiguous
     fp32 [S, C, cap], updated in place in the listed slots only."""
-    G, sd = _slot_list("stream_window_slots", slots, hist, 3, slots_dev)
-    z_new = _dev(z_new, "z_new")
-    S, C, cap = hist.shape
-    if z_new.dim() != 3 or tuple(z_new.shape[:2]) != (G, C) or z_new.device != hist.device:
-        raise MvqError(f"stream_window_slots: z_new {tuple(z_new.shape)} for [G={G}, C={C}, n] on the pool's device")
-    n = z_new.shape[2]
-    h_in, h_out = int(h_in), int(h_out)
-    win = torch.empty(G, C, max(h_in, 0) + n, device=hist.device, dtype=torch.float32)
-    check(_lib.lib().mvq_stream_window_slots_f32(hist.data_ptr(), sd.data_ptr(), G, S, h_in, z_new.data_ptr(), n, win.data_ptr(), h_out,
-                                                 cap, C, _stream()), "mvq_stream_window_slots_f32")
-    return win
+    _, sd = _slot_list("stream_window_slots", slots, hist, 3, slots_dev)
+    return _stream_window("stream_window_slots", hist, h_in, z_new, h_out, sd)
 
 
 def resample_stream_slots(x_new, kern, state, slots, consumed, orig, newf, width, final=False, slots_dev=None):
     """resample_stream for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots] moved on
     in place (mvq_resample_stream_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of ``orig`` of at
     least the state's length that one member has consumed (include/mvq.h)."""
-    G, sd = _slot_list("resample_stream_slots", slots, state, 2, slots_dev)
-    x_new = _dev(x_new, "x_new")
-    if x_new.dim() != 2 or x_new.shape[0] != G or x_new.device != state.device:
-        raise MvqError(f"resample_stream_slots: x_new {tuple(x_new.shape)} for [G={G}, n_new] on the pool's device")
-    n_new = x_new.shape[1]
-    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
-    if orig <= 0 or width < 0 or state.shape[1] != (width + orig - 1) // orig * orig + width:
-        raise MvqError(f"resample_stream_slots: state {tuple(state.shape)} does not fit orig={orig}, width={width}")
-    if not final and n_new % orig:
-        raise MvqError(f"resample_stream_slots: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
-    n_out = resample_stream_out_len(consumed, n_new, orig, width, final)
-    y = torch.empty(G, n_out, device=x_new.device, dtype=torch.float32)
-    check(_lib.lib().mvq_resample_stream_slots_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), G, state.shape[0],
-                                                   y.data_ptr(), n_new, consumed, int(bool(final)), n_out, orig, newf, width,
-                                                   kern.shape[1], _stream()), "mvq_resample_stream_slots_f32")
-    return y
+    _, sd = _slot_list("resample_stream_slots", slots, state, 2, slots_dev)
+    return _resample_stream("resample_stream_slots", x_new, kern, state, sd, consumed, orig, newf, width, final)
 
 
 def stream_samples(buf, fill, x_new, w, drop):

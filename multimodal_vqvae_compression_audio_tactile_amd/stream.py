@@ -110,6 +110,14 @@ def _window_plan(before: int, n: int, last: bool) -> Tuple[int, int, int, int]:
     return h, min(2 * DEC_HALO_TOK, h + n), g0 - HOP * a, g1 - HOP * a
 
 
+def resample_stream_out_len(consumed: int, n_new: int, orig: int, width: int, final: bool = False) -> int:
+    """Outputs a resample_stream call completes after ``consumed`` samples: the count mvq_resample_stream_f32 checks."""
+    hold = (width + orig - 1) // orig
+    done = max(0, consumed // orig - hold)
+    upto = -(-(consumed + n_new) // orig) if final else (consumed + n_new) // orig - hold
+    return max(0, upto - done)
+
+
 class PoolGroup(NamedTuple):
     """Sessions of one tick that share a launch sequence: ``key`` = (min(tokens_before, 32), n, last); ``sids`` ascending;
     ``plan`` = StreamReceiver._plan's (h_in, h_out, e0, e1) of every member; ``consumed`` = the resampler's launch class (the
@@ -140,17 +148,41 @@ def pool_groups(sessions, orig: int = RS_ORIG, width: int = RS_WIDTH) -> List[Po
         if before < 0 or before % CHUNK_TOK or (n != CHUNK_TOK if not last else not 0 <= n < CHUNK_TOK):
             raise ValueError(f"pool_groups: session {sid}: tokens_before = {before}, n = {n}, last = {last}")
         by_key.setdefault((min(before, 2 * CHUNK_TOK), n, last), []).append(sid)
-    hold = (width + orig - 1) // orig
     out = []
     for key in sorted(by_key):
         before, n, last = key
         plan = _window_plan(before, n, last)
         consumed = HOP * max(0, before - DEC_HALO_TOK)
-        n_new = plan[3] - plan[2]
-        done = max(0, consumed // orig - hold)
-        upto = -(-(consumed + n_new) // orig) if last else (consumed + n_new) // orig - hold
-        out.append(PoolGroup(key, tuple(sorted(by_key[key])), plan, consumed, max(0, upto - done)))
+        n_out = resample_stream_out_len(consumed, plan[3] - plan[2], orig, width, last)
+        out.append(PoolGroup(key, tuple(sorted(by_key[key])), plan, consumed, n_out))
     return out
+
+
+def _f32_only(who):
+    """The sessions that claim an equality chunk by chunk refuse the opt-in arithmetic modes: they scale per item, so a window
+    changes their arithmetic."""
+    from . import ops
+    if ops.get_arith() != "f32":
+        raise ValueError(f"{who}: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+
+
+def _capture(dev, state, step):
+    """A session's steady step as a graph -> (CUDAGraph, what ``step()`` returned inside the capture).  ``step`` runs once
+    eagerly first, at the steady shape, so that nothing is built during the capture; it moves the session on, so the ``state``
+    tensors are saved before and restored after it."""
+    import torch
+    keep = [t.clone() for t in state]
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+        for t, k in zip(state, keep):
+            t.copy_(k)
+        with torch.cuda.graph(g, stream=s):
+            out = step()
+    torch.cuda.current_stream().wait_stream(s)
+    return g, out
 
 
 class StreamSender:
@@ -177,7 +209,7 @@ class StreamSender:
 
     def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False):
         import torch
-        from . import ops, proposed
+        from . import proposed
         from .packets import StreamInfo, body_bytes, _check
         packet_tok, batch = int(packet_tok), int(batch)
         if packet_tok < 1 or CHUNK_TOK % packet_tok:
@@ -185,8 +217,7 @@ class StreamSender:
                              "(a packet must never straddle two chunks)")
         if batch < 1:
             raise ValueError("StreamSender: batch must be at least 1")
-        if ops.get_arith() != "f32":
-            raise ValueError(f"StreamSender: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        _f32_only("StreamSender")
         assert proposed.AR_CHUNK_TOK == CHUNK_TOK
         for enc in (net.A_ENC, net.T_ENC):
             if tuple(enc._desc[1]) != ENC_RATES:
@@ -288,12 +319,10 @@ class StreamSender:
         return [[] for _ in range(self.batch)], torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
 
     def _open(self, what):
-        from . import ops
         from ._lib import MvqError
         if self.finished:
             raise MvqError(f"StreamSender: {what} after finish")
-        if ops.get_arith() != "f32":
-            raise ValueError(f"StreamSender: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        _f32_only("StreamSender")
 
     # ------------------------------------------------------------------------------------------------------------ session
     def push(self, a, t):
@@ -352,21 +381,10 @@ class StreamSender:
         """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
         that nothing is built during the capture), then replayed with the samples written into the static input buffer.  The
         audio codes come back as a copy: the graph's own output buffer is overwritten by the next replay."""
-        import torch
         B = self.batch
         if self._g is None:
             x_s = self._upload(a, t, n)
-            keep = (self.buf.clone(), self.carry.clone())
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.dev)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._device_step(x_s, *plan)                                # warm-up at the steady shape; it moved the state on
-                self.buf.copy_(keep[0])
-                self.carry.copy_(keep[1])
-                with torch.cuda.graph(g, stream=s):
-                    bodies_s, codes_s = self._device_step(x_s, *plan)
-            torch.cuda.current_stream().wait_stream(s)
+            g, (bodies_s, codes_s) = _capture(self.dev, (self.buf, self.carry), lambda: self._device_step(x_s, *plan))
             self._g = (g, plan[0], x_s, bodies_s, codes_s)
         else:
             g, _, x_s, bodies_s, codes_s = self._g
@@ -397,7 +415,109 @@ def _receiver_args(who, net, K, nb, packet_tok, conceal, out_rate):
     _check(StreamInfo(K, nb, CHUNK_TOK, packet_tok))
 
 
-class StreamReceiver:
+class _ReceiverCore:
+    """What StreamReceiver and StreamReceiverPool share: the configuration, the state buffers -- one row block per session,
+    ``rows`` of them: carry [rows, C], hist [rows, C, 20] and, for out_rate=3000, the resampler's rs_state [rows, 105] -- the
+    check of a chunk's audio codes, and THE device sequence of a step, written once.  With ``sl`` None a step works on every
+    session of the buffers (the lockstep receiver); with ``sl`` = (slots, slots_dev), the host list of a group's slots and its
+    int32 device copy, on those sessions of a pool: the same launches under another addressing (csrc/stream.hip), which is why a
+    pool session computes what a solo one does."""
+
+    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate):
+        import torch
+        from . import ops, proposed
+        from .packets import body_bytes
+        self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
+        self.dev = net.proj_up.weight.device
+        self.C = net.proj_up.out_channels
+        self.full = body_bytes(packet_tok, nb, K)
+        self.n_audio_books = net.A_QUANT.n_codebooks
+        self.carry = torch.zeros(rows, self.C, device=self.dev)                        # per session: z_run[..., -1] of the chunk before
+        self.hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)       # per session: the last <= 20 latent tokens
+        self.rs_state = self.rs_kernel = None
+        if self.out_rate != proposed.EVAL_SR:
+            from .resample import sinc_resample_kernel
+            kern, width, orig, new = sinc_resample_kernel(proposed.EVAL_SR, self.out_rate)
+            assert (orig, width, new) == (RS_ORIG, RS_WIDTH, 1)
+            self.rs_kernel = kern.to(self.dev)
+            self.rs_state = ops.resample_stream_state(orig, width, rows, self.dev)
+
+    def _codes(self, audio_codes, n_lo, n_hi, sid=None):
+        """A chunk's audio codes, checked: int [B, n_codebooks, n] for the lockstep receiver (``sid`` None), [n_codebooks, n] or
+        [1, n_codebooks, n] (-> [n_codebooks, n]) for session ``sid`` of a pool; n_lo <= n <= n_hi."""
+        import torch
+        codes = torch.as_tensor(audio_codes)
+        if sid is None:
+            who, want = "StreamReceiver", f"[B={self.carry.shape[0]}, n_codebooks, tokens]"
+            shape_ok = codes.dim() == 3 and codes.shape[0] == self.carry.shape[0]
+        else:
+            who, want = f"StreamReceiverPool: session {sid}", "[n_codebooks, tokens] or [1, n_codebooks, tokens]"
+            if codes.dim() == 3 and codes.shape[0] == 1:
+                codes = codes[0]
+            shape_ok = codes.dim() == 2
+        if not shape_ok or codes.dtype.is_floating_point or codes.dtype == torch.bool:
+            raise ValueError(f"{who}: audio_codes must be int {want}, got {codes.dtype} {tuple(torch.as_tensor(audio_codes).shape)}")
+        if codes.shape[-2] != self.n_audio_books:
+            raise ValueError(f"{who}: {codes.shape[-2]} audio code rows, the model's quantiser has {self.n_audio_books}")
+        if not n_lo <= codes.shape[-1] <= n_hi:
+            want = f"{n_lo}" if n_lo == n_hi else f"{n_lo}..{n_hi}"
+            raise ValueError(f"{who}: {codes.shape[-1]} audio tokens for a chunk of {want} tokens")
+        return codes
+
+    # ------------------------------------------------------------------------------------------------ the device sequence
+    def _latents(self, up, codes, n, sl=None, last=False):
+        """Device: upload (the G*P packet bodies, then their G*P counts) and codes [G, 32, n] -> indices -> latents [G, C, n].  The carried
+        token moves on in place; for slots through a dense [G, C] copy, not written back for sessions that end (``last``: the
+        next open() resets the slot)."""
+        from . import ops
+        G, full = codes.shape[0], self.full
+        P = (n + self.packet_tok - 1) // self.packet_tok
+        idx, nbv = ops.idx_unpack_packets(up[:G * P * full].view(G, P, full), up[G * P * full:].view(G, P), self.K, self.nb, n,
+                                          self.packet_tok)
+        carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
+        z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry)
+        if sl is not None and not last:
+            ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
+        if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
+            z = ops.plc_mask_fill(z, None, nbv == 0)[0]
+        return z
+
+    def _window_decode(self, z, h_in, h_out, e0, e1, sl=None):
+        """Device: window = [history | z] (history updated in place), T_DEC on it, samples [e0, e1) of the window's output."""
+        from . import ops
+        if sl is None:
+            win = ops.stream_window(self.hist, h_in, z, h_out)
+        else:
+            win = ops.stream_window_slots(self.hist, sl[0], h_in, z, h_out, slots_dev=sl[1])
+        return self.net.T_DEC(win)[..., e0:e1]
+
+    def _device_step(self, up, codes, n, h_in, h_out, e0, e1, sl=None, last=False):
+        """A step up to the emit slice -> y [G, 1, e1 - e0].  n = 0 (a finish without a partial chunk) decodes the history alone;
+        without a history either (a session that never got a token) nothing runs."""
+        import torch
+        G = self.carry.shape[0] if sl is None else len(sl[0])
+        if h_in + n == 0:
+            return torch.empty(G, 1, 0, device=self.dev)
+        z = self._latents(up, codes, n, sl, last) if n else torch.empty(G, self.C, 0, device=self.dev)
+        return self._window_decode(z, h_in, h_out, e0, e1, sl)
+
+    def _decimate(self, y, consumed, last, sl=None):
+        """out_rate=3000: the emitted piece through the streamed resampler, ``consumed`` = the samples the sessions emitted before
+        (a pool group's launch class).  An empty piece -- the finish of a session without a token -- launches nothing."""
+        from . import ops
+        G, n = y.shape[0], y.shape[-1]
+        if self.rs_state is None or n == 0:
+            return y
+        if sl is None:
+            y3 = ops.resample_stream(y.reshape(G, n), self.rs_kernel, self.rs_state, consumed, RS_ORIG, 1, RS_WIDTH, final=last)
+        else:
+            y3 = ops.resample_stream_slots(y.reshape(G, n), self.rs_kernel, self.rs_state, sl[0], consumed, RS_ORIG, 1, RS_WIDTH,
+                                           final=last, slots_dev=sl[1])
+        return y3.unsqueeze(1)
+
+
+class StreamReceiver(_ReceiverCore):
     """A receiver session for ``batch`` items advancing in lockstep: ``push`` one 16-token chunk at a time (whatever tactile
     packets of it arrived, and its audio codes), get back the samples that chunk completes; ``finish`` flushes.
 
@@ -408,8 +528,8 @@ class StreamReceiver:
 
     ``push`` runs, in order: packets.gather(seq_base=) per item -> ONE upload of the packet bodies and counts ->
     ops.idx_unpack_packets -> decode_latents(nb_valid=, z_prev=carry, z_last_out=carry) -> ops.stream_window (window = history
-    | new latents; history updated in place) -> T_DEC on the window -> the emit slice (-> StreamResample for out_rate=3000).
-    All session state is in fixed device buffers (carry [B, C], history [B, C, 20], the resampler's [B, 105]).
+    | new latents; history updated in place) -> T_DEC on the window -> the emit slice (-> ops.resample_stream for out_rate=3000):
+    _ReceiverCore's sequence.  All session state is in fixed device buffers (carry [B, C], history [B, C, 20], rs_state [B, 105]).
 
     ``graph=True``: the steady step (36-token window, from the third push on) is captured once as a graph on one stream and
     replayed for every later chunk after the host has written the packet bodies and audio codes into the static upload buffers;
@@ -417,28 +537,16 @@ class StreamReceiver:
     THE GRAPH'S OUTPUT BUFFER: it is valid until the next push (clone it to keep it)."""
 
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False):
-        import torch
-        from . import proposed
-        from .packets import body_bytes
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
             raise ValueError("StreamReceiver: batch must be at least 1")
-        self.net, self.K, self.nb, self.packet_tok, self.batch = net, K, nb, packet_tok, batch
-        self.books_use, self.conceal, self.out_rate, self.graph = books_use, conceal, int(out_rate), bool(graph)
-        self.dev = net.proj_up.weight.device
-        self.C = net.proj_up.out_channels
-        self.full = body_bytes(packet_tok, nb, K)
-        self.carry = torch.zeros(batch, self.C, device=self.dev)                       # z_run[..., -1] of the chunk before
-        self.hist = torch.zeros(batch, self.C, 2 * DEC_HALO_TOK, device=self.dev)      # the last <= 20 latent tokens
+        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate)
+        self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
         self.late = 0                                                                  # packets of chunks already decoded
         self.finished = False
-        self.rs = None
-        if self.out_rate != proposed.EVAL_SR:
-            from .resample import StreamResample
-            self.rs = StreamResample(proposed.EVAL_SR, self.out_rate, batch, device=self.dev)
         self._g = None                                                                 # (graph, up_static, codes_static, y_static)
 
     # ------------------------------------------------------------------------------------------------------------ stages
@@ -456,54 +564,16 @@ class StreamReceiver:
         self.late += len(late)
         return host
 
-    def _latents(self, up, codes, n):
-        """Device: upload -> indices -> this chunk's latents [B, C, n]; the carried token moves on in place."""
-        from . import ops
-        B, full = self.batch, self.full
-        P = (n + self.packet_tok - 1) // self.packet_tok
-        idx, nbv = ops.idx_unpack_packets(up[:B * P * full].view(B, P, full), up[B * P * full:].view(B, P), self.K, self.nb, n,
-                                          self.packet_tok)
-        z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=self.carry, z_last_out=self.carry)
-        if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
-            z = ops.plc_mask_fill(z, None, nbv == 0)[0]
-        return z
-
-    def _window_decode(self, z, h_in, h_out, e0, e1):
-        """Device: window = [history | z] (history updated in place), T_DEC on it, samples [e0, e1) of the window's output."""
-        from . import ops
-        win = ops.stream_window(self.hist, h_in, z, h_out)
-        return self.net.T_DEC(win)[..., e0:e1]
-
-    def _device_step(self, up, codes, n, h_in, h_out, e0, e1):
-        return self._window_decode(self._latents(up, codes, n), h_in, h_out, e0, e1)
-
     def _plan(self, n, last):
         """(h_in, h_out, e0, e1) of the step that takes n new tokens: schedule()'s step in window-local samples."""
         assert self.h == min(self.tokens, 2 * DEC_HALO_TOK)
         return _window_plan(self.tokens, n, last)
-
-    def _codes(self, audio_codes, n_lo, n_hi):
-        import torch
-        codes = torch.as_tensor(audio_codes)
-        if codes.dim() != 3 or codes.shape[0] != self.batch or codes.dtype.is_floating_point or codes.dtype == torch.bool:
-            raise ValueError(f"StreamReceiver: audio_codes must be int [B={self.batch}, n_codebooks, tokens], got {tuple(codes.shape)}")
-        if codes.shape[1] != self.net.A_QUANT.n_codebooks:
-            raise ValueError(f"StreamReceiver: {codes.shape[1]} audio code rows, the model's quantiser has {self.net.A_QUANT.n_codebooks}")
-        if not n_lo <= codes.shape[2] <= n_hi:
-            want = f"{n_lo}" if n_lo == n_hi else f"{n_lo}..{n_hi}"
-            raise ValueError(f"StreamReceiver: {codes.shape[2]} audio tokens for a chunk of {want} tokens")
-        return codes
 
     def _packets_ok(self, tactile_packets):
         tactile_packets = list(tactile_packets)
         if len(tactile_packets) != self.batch:
             raise ValueError(f"StreamReceiver: packets of {len(tactile_packets)} items for a session of batch {self.batch}")
         return tactile_packets
-
-    def _out(self, y, last):
-        if self.rs is None:
-            return y
-        return self.rs.finish(y) if last else self.rs.push(y)
 
     # ------------------------------------------------------------------------------------------------------------ session
     def push(self, tactile_packets, audio_codes):
@@ -521,13 +591,14 @@ class StreamReceiver:
         n = CHUNK_TOK
         host = self._gather(tactile_packets, n)
         plan = self._plan(n, False)
+        consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)                   # the samples emitted so far
         with torch.no_grad():
             if self.graph and plan[0] == 2 * DEC_HALO_TOK:                    # the steady step: a full history
                 y = self._replay(host, codes, n, plan)
             else:
                 y = self._device_step(torch.from_numpy(host).to(self.dev), codes.to(self.dev), n, *plan)
             self.h, self.tokens = plan[1], self.tokens + n
-            return self._out(y, False)
+            return self._decimate(y, consumed, False)
 
     def finish(self, tactile_packets=None, audio_codes=None):
         """Flush: optionally a last partial chunk of 1..15 tokens (its packets and audio_codes [B, 32, n]), then every remaining
@@ -538,24 +609,20 @@ class StreamReceiver:
             raise MvqError("StreamReceiver: finish after finish")
         if (tactile_packets is None) != (audio_codes is None):
             raise ValueError("StreamReceiver.finish: the last chunk needs both its packets and its audio codes")
-        n, host, codes = 0, None, None
+        n, up, codes = 0, None, None
         if audio_codes is not None:
             tactile_packets = self._packets_ok(tactile_packets)
             codes = self._codes(audio_codes, 1, CHUNK_TOK - 1)
             n = int(codes.shape[2])
             host = self._gather(tactile_packets, n)
         plan = self._plan(n, True)
+        consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)
         with torch.no_grad():
             if n:
-                z = self._latents(torch.from_numpy(host).to(self.dev), codes.to(self.dev), n)
-            else:
-                z = torch.empty(self.batch, self.C, 0, device=self.dev)
-            if self.h + n:
-                y = self._window_decode(z, *plan)
-            else:
-                y = torch.empty(self.batch, 1, 0, device=self.dev)
+                up, codes = torch.from_numpy(host).to(self.dev), codes.to(self.dev)
+            y = self._device_step(up, codes, n, *plan, last=True)
             self.h, self.tokens, self.finished = plan[1], self.tokens + n, True
-            return self._out(y, True)
+            return self._decimate(y, consumed, True)
 
     def _replay(self, host, codes, n, plan):
         """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
@@ -564,17 +631,7 @@ class StreamReceiver:
         if self._g is None:
             up_s = torch.from_numpy(host).to(self.dev)
             codes_s = codes.to(self.dev).long().clone()
-            keep = (self.hist.clone(), self.carry.clone())
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.dev)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._device_step(up_s, codes_s, n, *plan)                   # warm-up at the steady shape; it moved the state on
-                self.hist.copy_(keep[0])
-                self.carry.copy_(keep[1])
-                with torch.cuda.graph(g, stream=s):
-                    y_s = self._device_step(up_s, codes_s, n, *plan)
-            torch.cuda.current_stream().wait_stream(s)
+            g, y_s = _capture(self.dev, (self.hist, self.carry), lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
         else:
             g, up_s, codes_s, y_s = self._g
@@ -584,7 +641,7 @@ class StreamReceiver:
         return y_s
 
 
-class StreamReceiverPool:
+class StreamReceiverPool(_ReceiverCore):
     """Receiver sessions that join, run for different lengths and leave independently, served together: ``open`` takes a
     session slot, ``step`` is one tick that advances whichever sessions have a chunk ready (and flushes the ones that end),
     ``close`` abandons one.  Every session gets back exactly what a ``StreamReceiver(batch=1)`` fed the same data returns from
@@ -599,34 +656,17 @@ class StreamReceiverPool:
       copy   ONE upload of all groups' slot lists, packet bodies and counts, ONE of all audio codes;
       device per group of G sessions: ops.idx_unpack_packets -> ops.stream_rows (the carried tokens, pool -> dense [G, C]) ->
              decode_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.stream_window_slots -> T_DEC on [G, C, window]
-             -> the emit slice (-> ops.resample_stream_slots).
+             -> the emit slice (-> ops.resample_stream_slots): _ReceiverCore's sequence on the group's slots.
     ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick."""
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
-        import torch
-        from . import ops, proposed
-        from .packets import body_bytes
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
         _receiver_args("StreamReceiverPool", net, K, nb, packet_tok, conceal, out_rate)
         if slots < 1:
             raise ValueError("StreamReceiverPool: slots must be at least 1")
-        if ops.get_arith() != "f32":
-            raise ValueError(f"StreamReceiverPool: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
-        self.net, self.K, self.nb, self.packet_tok, self.slots = net, K, nb, packet_tok, slots
-        self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
-        self.dev = net.proj_up.weight.device
-        self.C = net.proj_up.out_channels
-        self.full = body_bytes(packet_tok, nb, K)
-        self.n_audio_books = net.A_QUANT.n_codebooks
-        self.carry = torch.zeros(slots, self.C, device=self.dev)                       # per slot: z_run[..., -1] of the chunk before
-        self.hist = torch.zeros(slots, self.C, 2 * DEC_HALO_TOK, device=self.dev)      # per slot: the last <= 20 latent tokens
-        self.rs_state = self.rs_kernel = None
-        if self.out_rate != proposed.EVAL_SR:
-            from .resample import sinc_resample_kernel
-            kern, width, orig, new = sinc_resample_kernel(proposed.EVAL_SR, self.out_rate)
-            assert (orig, width, new) == (RS_ORIG, RS_WIDTH, 1)
-            self.rs_kernel = kern.to(self.dev)
-            self.rs_state = ops.resample_stream_state(orig, width, slots, self.dev)
+        _f32_only("StreamReceiverPool")
+        super().__init__(net, K, nb, packet_tok, slots, books_use, conceal, out_rate)
+        self.slots = slots
         self._free = list(range(slots))                                                # ascending: open() takes the lowest
         self._sess = {}                                                                # sid -> [slot, tokens, late]
         self._next_sid = 0
@@ -679,22 +719,6 @@ class StreamReceiverPool:
         bisect.insort(self._free, slot)
 
     # --------------------------------------------------------------------------------------------------------------- tick
-    def _codes(self, sid, audio_codes, n_lo, n_hi):
-        import torch
-        codes = torch.as_tensor(audio_codes)
-        if codes.dim() == 3 and codes.shape[0] == 1:
-            codes = codes[0]
-        if codes.dim() != 2 or codes.dtype.is_floating_point or codes.dtype == torch.bool:
-            raise ValueError(f"StreamReceiverPool: session {sid}: audio_codes must be int [n_codebooks, tokens] or [1, n_codebooks, "
-                             f"tokens], got {codes.dtype} {tuple(torch.as_tensor(audio_codes).shape)}")
-        if codes.shape[0] != self.n_audio_books:
-            raise ValueError(f"StreamReceiverPool: session {sid}: {codes.shape[0]} audio code rows, the model's quantiser has "
-                             f"{self.n_audio_books}")
-        if not n_lo <= codes.shape[1] <= n_hi:
-            want = f"{n_lo}" if n_lo == n_hi else f"{n_lo}..{n_hi}"
-            raise ValueError(f"StreamReceiverPool: session {sid}: {codes.shape[1]} audio tokens for a chunk of {want} tokens")
-        return codes
-
     def _inputs(self, pushes, finishes):
         """Host: every session's input of this tick, checked and gathered; raises before anything has changed.
         -> {sid: (n, last, bodies uint8 [P, full] or None, counts uint8 [P] or None, codes [32, n] or None, late packets)}"""
@@ -715,7 +739,7 @@ class StreamReceiverPool:
                     pkts, audio_codes = item
                 except (TypeError, ValueError):
                     raise ValueError(f"StreamReceiverPool: session {sid}: (packets, audio_codes) expected") from None
-                codes = self._codes(sid, audio_codes, 1, CHUNK_TOK - 1) if last else self._codes(sid, audio_codes, CHUNK_TOK, CHUNK_TOK)
+                codes = self._codes(audio_codes, 1, CHUNK_TOK - 1, sid) if last else self._codes(audio_codes, CHUNK_TOK, CHUNK_TOK, sid)
                 n, late = int(codes.shape[1]), []
                 bodies, counts = gather(pkts, StreamInfo(self.K, self.nb, n, self.packet_tok), seq_base=tokens // self.packet_tok, late=late)
                 work[sid] = (n, last, bodies, counts, codes, len(late))
@@ -730,10 +754,8 @@ class StreamReceiverPool:
         was."""
         import numpy as np
         import torch
-        from . import ops
         pushes, finishes = dict(pushes or {}), dict(finishes or {})
-        if ops.get_arith() != "f32":
-            raise ValueError(f"StreamReceiverPool: arithmetic mode {ops.get_arith()!r} scales per item; only 'f32' is equal chunk by chunk")
+        _f32_only("StreamReceiverPool")
         work = self._inputs(pushes, finishes)
         if not work:
             return {}
@@ -767,10 +789,11 @@ class StreamReceiverPool:
                     codes_all = torch.cat([c.to(torch.int64) for c in flat_codes]).to(self.dev)
             slots_all = up[:4 * n_sess].view(torch.int32)
             s0 = c0 = 0
-            for g, sl, (o_b, o_c, P) in zip(groups, slot_lists, where):
-                G, n = len(g.sids), g.key[1]
+            for g, slots, (o_b, o_c, P) in zip(groups, slot_lists, where):
+                G, (_, n, last) = len(g.sids), g.key
+                sl = (slots, slots_all[s0:s0 + G])
                 codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n) if n else None
-                y = self._group(g, sl, slots_all[s0:s0 + G], up[o_b:o_c].view(G, P, self.full), up[o_c:o_c + G * P].view(G, P), codes)
+                y = self._decimate(self._device_step(up[o_b:o_c + G * P], codes, n, *g.plan, sl=sl, last=last), g.consumed, last, sl)
                 s0, c0 = s0 + G, c0 + G * self.n_audio_books * n
                 for i, sid in enumerate(g.sids):
                     out[sid] = y[i:i + 1]
@@ -781,28 +804,3 @@ class StreamReceiverPool:
                 self._sess[sid][1] += w[0]
                 self._sess[sid][2] += w[5]
         return out
-
-    def _group(self, g, slots, slots_dev, bodies, counts, codes):
-        """Device: one group's launch sequence -> y [G, 1, n_emit]; the listed slots of carry / hist / resampler state move on."""
-        import torch
-        from . import ops
-        G, (_, n, last), (h_in, h_out, e0, e1) = len(slots), g.key, g.plan
-        if n:
-            idx, nbv = ops.idx_unpack_packets(bodies, counts, self.K, self.nb, n, self.packet_tok)
-            carry = ops.stream_rows(self.carry, slots, slots_dev=slots_dev)
-            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry)
-            if not last:                                          # a finished session's slot is reset by the next open()
-                ops.stream_rows(self.carry, slots, rows=carry, slots_dev=slots_dev)
-            if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
-                z = ops.plc_mask_fill(z, None, nbv == 0)[0]
-        else:
-            z = torch.empty(G, self.C, 0, device=self.dev)
-        if h_in + n:
-            y = self.net.T_DEC(ops.stream_window_slots(self.hist, slots, h_in, z, h_out, slots_dev=slots_dev))[..., e0:e1]
-        else:
-            y = torch.empty(G, 1, 0, device=self.dev)
-        if self.rs_state is None or e1 == e0:                     # an empty piece is the finish of a session without a token
-            return y
-        y3 = ops.resample_stream_slots(y.reshape(G, e1 - e0), self.rs_kernel, self.rs_state, slots, g.consumed, RS_ORIG, 1, RS_WIDTH,
-                                       final=last, slots_dev=slots_dev)
-        return y3.reshape(G, 1, g.n_out)
