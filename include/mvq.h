@@ -42,7 +42,7 @@ extern "C" {
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
- * mvq_stream_rows_f32).
+ * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -594,6 +594,21 @@ int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* 
                                   float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
                                   void* stream);
 int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream);
+/* mvq_stream_samples_slots_f32: the sample state of a group of SENDER sessions of a pool: the kernel body of
+ * mvq_stream_samples_f32 under the slot addressing, with fill, n and drop PER SESSION.  buf[n_slots, 2, cap] fp32: slot s owns row 2s
+ * (audio) and row 2s + 1 (tactile).  desc[n_group][5] int32 on the DEVICE, per session (slot, fill, n, drop, x_off): its n new audio
+ * samples lie at x_new[x_off], its n new tactile samples at x_new[x_off + n]; x_new is ONE packed array of x_total floats (the
+ * caller lays the sessions out one after the other: x_off = the exclusive prefix sum of 2n).  win[2, n_group, w] contiguous, a
+ * buffer of its own: the audio rows of all sessions, then the tactile rows; w is one value per launch.  Per session and modality,
+ * exactly what mvq_stream_samples_f32 does for a row: win = the first w samples of [buf | new], buf <- [buf | new] from drop on.
+ * ONE launch of 2 * n_group blocks, one per row; rows of unlisted slots are not touched, nor the columns past a row's new fill.
+ * w = 0 with every drop = 0 is the pure append.  The caller passes distinct slots and, per session, values mvq_stream_samples_f32
+ * accepts for that w; the kernel checks them itself as a second line: for a descriptor with a slot outside [0, n_slots), a
+ * negative value, n > 2^24, fill > cap, drop > fill + n, fill + n - drop > cap, w > fill + n or x_off + 2n > x_total both window
+ * rows of the session are written as zeros and nothing is stored to the pool.  MVQ_EINVAL before any launch on a negative size,
+ * cap > 2^24, n_group > n_slots or a null pointer with a non-empty shape; n_group = 0 returns MVQ_OK without a launch. */
+int mvq_stream_samples_slots_f32(float* buf, const int32_t* desc, int n_group, int n_slots, const float* x_new, int x_total, float* win,
+                                 int w, int cap, void* stream);
 
 /* Optimiser step of the training config (torch.optim.AdamW + clip_grad_norm_, Training/compare_dacvsproposal_5.py:367,394-395):
  *   sumsq_partial : partial[n_partial] block sums of x^2 (their total is the squared gradient norm), n_partial <= 4096

@@ -20,13 +20,14 @@ Drop-in surface:
     ``decode(nb_valid=..., conceal=...)`` with ``packets`` -- the packet format (thinning, gathering what arrived); chunk by
     chunk ``ProposedEval.stream_receiver`` / ``StreamReceiver`` (``stream``: window schedule) and ``StreamResample``, for
     sessions that come and go ``ProposedEval.stream_receiver_pool`` / ``StreamReceiverPool`` (one batched step per tick), and
-    the sending half ``ProposedEval.stream_sender`` / ``StreamSender`` (packets chunk by chunk, byte-equal to the whole item);
+    the sending half ``ProposedEval.stream_sender`` / ``StreamSender`` (packets chunk by chunk, byte-equal to the whole item)
+    and ``ProposedEval.stream_sender_pool`` / ``StreamSenderPool`` (sender sessions that come and go, one batched encode per tick);
   * ``ops`` -- tensor-level wrappers over the C ABI (include/mvq.h), ``synth`` -- seeded weights / signals.
 All compute runs in libmvq_hip.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
 from . import bitstream, ops, optim, packets, stream, synth, train  # noqa: F401
 from .resample import Resample, StreamResample, resample_to  # noqa: F401
-from .stream import StreamReceiver, StreamReceiverPool, StreamSender  # noqa: F401
+from .stream import StreamReceiver, StreamReceiverPool, StreamSender, StreamSenderPool  # noqa: F401
 from .losses import MelCosineLoss, MultiResSTFTLoss, TrainingLoss, safe_l1, stsim_batch  # noqa: F401
 from ._lib import MvqError, build, lib  # noqa: F401
 from .dac import plan_overrides  # noqa: F401

@@ -1293,8 +1293,20 @@ int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, floa
     if (have - drop > cap) return fail(MVQ_EINVAL, "stream_samples: %lld samples to keep exceed the capacity %d", have - drop, cap);
     if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return MVQ_OK;
     if (!buf || (!x_new && n) || (!win && w)) return fail(MVQ_EINVAL, "stream_samples: null tensor");
-    hipError_t e = mvq::launch_stream_samples(buf, x_new, win, fill, n, w, drop, cap, rows, S(stream));
+    hipError_t e = mvq::launch_stream_samples(buf, nullptr, x_new, win, fill, n, w, drop, cap, rows, 0, 0, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_samples");
+}
+
+int mvq_stream_samples_slots_f32(float* buf, const int32_t* desc, int n_group, int n_slots, const float* x_new, int x_total, float* win,
+                                 int w, int cap, void* stream)
+{
+    if (x_total < 0 || w < 0 || cap < 0) return fail(MVQ_EINVAL, "stream_samples_slots: negative size");
+    if (int rc = slots_shape_bad("stream_samples_slots", n_group, n_slots, 2)) return rc;
+    if (cap > (1 << 24) || w > (1 << 25)) return fail(MVQ_EINVAL, "stream_samples_slots: cap = %d / w = %d samples per row", cap, w);
+    if (n_group == 0) return MVQ_OK;
+    if (!buf || !desc || (!x_new && x_total) || (!win && w)) return fail(MVQ_EINVAL, "stream_samples_slots: null tensor");
+    hipError_t e = mvq::launch_stream_samples(buf, desc, x_new, win, 0, 0, w, 0, cap, n_group, n_slots, x_total, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_samples_slots");
 }
 
 int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream)

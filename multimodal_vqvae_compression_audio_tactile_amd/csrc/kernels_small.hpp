@@ -136,6 +136,6 @@ hipError_t launch_resample_stream(const float* x_new, const float* kern, float* 
                                   int n_out, int orig, int ks, int S, int base, int lead, int n_slots, hipStream_t s);
 hipError_t launch_stream_rows(float* pool, const int32_t* slots, float* rows, int G, int C, int n_slots, int scatter, hipStream_t s);
 // stream.hip: the streaming sender's sample state (one block per row of buf[rows][cap])
-hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int fill, int n, int w, int drop, int cap, int rows,
-                                 hipStream_t s);
+hipError_t launch_stream_samples(float* buf, const int32_t* desc, const float* x_new, float* win, int fill, int n, int w, int drop,
+                                 int cap, int rows, int n_slots, int x_total, hipStream_t s);
 }  // namespace mvq

@@ -3,8 +3,9 @@
 // the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
 // every time (a captured graph replays it).  A POOL of sessions keeps one row block per session slot in
 // the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
-// instantiated for the dense addressing and for the slot list (Sessions<SLOTS> below), and stream_rows_kernel moves the carried
-// tokens.
+// instantiated for the dense addressing and for the slot list (Sessions<SLOTS> below), the sample-state kernel likewise
+// (SampleRows<SLOTS>: a pool's sender sessions also bring their own fill / n / drop, section 17), and stream_rows_kernel moves
+// the carried tokens.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -131,18 +132,68 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __res
     }
 }
 
-// The sender's sample state.  Per row r (one block each): v = [buf[r][0 .. fill) | x_new[r][0 .. n)], win[r][0 .. w) = v[0 .. w)
-// (a buffer of its own, pitch w), then buf[r][0 .. fill + n - drop) = v[drop ..): the samples the next window still needs move to
-// the front of the row, the new ones behind them.  The move overlaps itself (drop < fill + n), so it goes tile by tile in
-// ascending order: a tile's sources lie at or past its own start, every thread holds its elements in registers across the
-// barrier, and only then are they stored -- a store of tile k lands below (k+1)*TILE, where no later tile reads.  With drop == 0
-// the old samples stay where they are and only x_new is appended.  No row is touched by two blocks.
+// Which row of the sender's sample state block `blk` of stream_samples_kernel works on and with which parameters, fixed at
+// compile time.  Dense (a lockstep StreamSender): row blk of buf[rows, cap], x_new[rows, n] and win[rows, w], with the ONE
+// (fill, n, drop) of the launch -- nothing is loaded and the check folds away (the entry point has made it).  Slots (a group of G
+// sessions of a pool): block m*G + g is modality m of session g, whose descriptor desc[g] = (slot, fill,
+// n, drop, x_off) names ITS parameters: row 2*slot + m of buf[n_slots, 2, cap], its n new samples at x_new[x_off + m*n], row
+// m*G + g of win[2, G, w].  The kernel checks a descriptor itself as a second line behind the host wrapper: the slot inside
+// [0, n_slots), every value what mvq_stream_samples_f32 accepts, the samples inside x_new[0 .. x_total).  All threads of a block
+// read the same five words, so the verdict is block-uniform.
+struct SampleRow {
+    size_t buf_row;                                                      // row of buf
+    size_t x_at;                                                         // offset of the row's new samples in x_new
+    int fill, n, drop;
+};
+template <bool SLOTS> struct SampleRows;
+template <> struct SampleRows<false> {
+    int fill, n, drop;
+    __device__ bool row(int blk, int, int, SampleRow& r) const
+    {
+        r.buf_row = (size_t)blk;
+        r.x_at = (size_t)blk * n;
+        r.fill = fill, r.n = n, r.drop = drop;
+        return true;
+    }
+};
+template <> struct SampleRows<true> {
+    const int32_t* desc;                                                 // [G][5]
+    int G, n_slots, x_total;
+    __device__ bool row(int blk, int w, int cap, SampleRow& r) const
+    {
+        const int m = blk / G, g = blk - m * G;
+        const int32_t* d = desc + (size_t)g * 5;
+        const int slot = d[0], fill = d[1], n = d[2], drop = d[3], x_off = d[4];
+        r.buf_row = (size_t)(slot < 0 ? 0 : slot) * 2 + m;
+        r.x_at = (size_t)(x_off < 0 ? 0 : x_off) + (size_t)m * (n < 0 ? 0 : n);
+        r.fill = fill, r.n = n, r.drop = drop;
+        const long long have = (long long)fill + n;
+        return slot >= 0 && slot < n_slots && fill >= 0 && n >= 0 && drop >= 0 && x_off >= 0 && n <= (1 << 24) && fill <= cap &&
+               drop <= have && have - drop <= cap && w <= have && (long long)x_off + 2LL * n <= x_total;
+    }
+};
+
+// The sender's sample state.  Per row (one block each; rows.row() says which and with what fill, n and drop): v = [buf[0 .. fill)
+// | x_new[0 .. n)], win[0 .. w) = v[0 .. w) (a buffer of its own, pitch w), then buf[0 .. fill + n - drop) = v[drop ..): the
+// samples the next window still needs move to the front of the row, the new ones behind them.  The move overlaps itself
+// (drop < fill + n), so it goes tile by tile in ascending order: a tile's sources lie at or past its own start, every thread holds
+// its elements in registers across the barrier, and only then are they stored -- a store of tile k lands below (k+1)*TILE, where
+// no later tile reads.  With drop == 0 the old samples stay where they are and only x_new is appended.  No row is touched by two
+// blocks (distinct slots are distinct rows), and the trip counts are one row's, so block-uniform, whatever the other blocks of
+// the launch hold.  A block whose descriptor fails the check writes zeros to its window row and leaves, before any barrier.
+template <bool SLOTS>
 __global__ __launch_bounds__(SMP_THREADS) void stream_samples_kernel(float* buf, const float* __restrict__ x_new,
-                                                                     float* __restrict__ win, int fill, int n, int w, int drop, int cap)
+                                                                     float* __restrict__ win, int w, int cap, SampleRows<SLOTS> rows)
 {
-    float* b = buf + (size_t)blockIdx.x * cap;
-    const float* x = x_new + (size_t)blockIdx.x * n;
     float* wr = win + (size_t)blockIdx.x * w;
+    SampleRow r;
+    if (!rows.row(blockIdx.x, w, cap, r)) {
+        for (int i = threadIdx.x; i < w; i += SMP_THREADS) wr[i] = 0.0f;
+        return;
+    }
+    const int fill = r.fill, n = r.n, drop = r.drop;
+    float* b = buf + r.buf_row * (size_t)cap;
+    const float* x = x_new + r.x_at;
     for (int i = threadIdx.x; i < w; i += SMP_THREADS) wr[i] = i < fill ? b[i] : x[i - fill];
     __syncthreads();                                                     // every read of the window is done before the row moves
     const int keep = fill + n - drop;
@@ -213,11 +264,20 @@ hipError_t launch_resample_stream(const float* x_new, const float* kern, float* 
     return hipGetLastError();
 }
 
-hipError_t launch_stream_samples(float* buf, const float* x_new, float* win, int fill, int n, int w, int drop, int cap, int rows,
-                                 hipStream_t s)
+// desc == nullptr: the dense instantiation on `rows` rows with the one (fill, n, drop); else the group desc[G][5] of a pool of
+// n_slots sessions, 2*G blocks (fill / n / drop unused).
+hipError_t launch_stream_samples(float* buf, const int32_t* desc, const float* x_new, float* win, int fill, int n, int w, int drop,
+                                 int cap, int rows, int n_slots, int x_total, hipStream_t s)
 {
-    if (rows == 0 || (n == 0 && w == 0 && drop == 0)) return hipSuccess;
-    hipLaunchKernelGGL(stream_samples_kernel, dim3((unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, fill, n, w, drop, cap);
+    if (rows == 0) return hipSuccess;
+    if (desc) {
+        hipLaunchKernelGGL(stream_samples_kernel<true>, dim3(2u * (unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, w, cap,
+                           SampleRows<true>{desc, rows, n_slots, x_total});
+        return hipGetLastError();
+    }
+    if (n == 0 && w == 0 && drop == 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_samples_kernel<false>, dim3((unsigned)rows), dim3(SMP_THREADS), 0, s, buf, x_new, win, w, cap,
+                       SampleRows<false>{fill, n, drop});
     return hipGetLastError();
 }
 

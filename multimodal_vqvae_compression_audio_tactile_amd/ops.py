@@ -1065,11 +1065,10 @@ def stream_window(hist, h_in, z_new, h_out):
 
 
 # ---------------------------------------------------------------------------------- receiver pool
-def _slot_list(who, slots, pool, dims, slots_dev):
-    """The slot list of a group as HOST integers: refused here, before anything else is looked at, when one is out of range or
-    repeated, so no unchecked index reaches the device.  -> (G, int32 device tensor [G]); ``slots_dev`` is that tensor when the
-    caller uploaded the list already (StreamReceiverPool sends the lists of a whole tick with its packet bodies), else it is
-    uploaded here.  ``pool``: the state buffer, [n_slots, ...] of ``dims`` dimensions."""
+def _slot_host(who, slots, pool, dims):
+    """The slot rule of every pool call: ``slots`` as HOST integers, refused here, before anything else is looked at, when one is
+    out of range or repeated, so no unchecked index reaches the device.  -> the list.  ``pool``: the state buffer, [n_slots, ...]
+    of ``dims`` dimensions."""
     if not isinstance(pool, torch.Tensor) or pool.dim() != dims:
         raise MvqError(f"{who}: the pool buffer must be a tensor of {dims} dimensions")
     try:
@@ -1086,6 +1085,13 @@ def _slot_list(who, slots, pool, dims, slots_dev):
         raise MvqError(f"{who}: a slot is listed twice in {host} (two blocks would update one row)")
     if pool.dtype != torch.float32 or not pool.is_cuda or not pool.is_contiguous():
         raise MvqError(f"{who}: the pool buffer must be a contiguous fp32 HIP tensor")
+    return host
+
+
+def _slot_list(who, slots, pool, dims, slots_dev):
+    """_slot_host -> (G, int32 device tensor [G]); ``slots_dev`` is that tensor when the caller uploaded the list already
+    (StreamReceiverPool sends the lists of a whole tick with its packet bodies), else it is uploaded here."""
+    host = _slot_host(who, slots, pool, dims)
     if slots_dev is None:
         slots_dev = torch.tensor(host, dtype=torch.int32).to(pool.device)
     elif not isinstance(slots_dev, torch.Tensor) or slots_dev.dtype != torch.int32 or slots_dev.device != pool.device \
@@ -1141,6 +1147,67 @@ def stream_samples(buf, fill, x_new, w, drop):
     win = torch.empty(R, max(w, 0), device=buf.device, dtype=torch.float32)
     check(_lib.lib().mvq_stream_samples_f32(buf.data_ptr(), fill, x_new.data_ptr(), n, win.data_ptr(), w, drop, cap, R, _stream()),
           "mvq_stream_samples_f32")
+    return win
+
+
+def stream_samples_desc(sessions, w, cap, who="stream_samples_slots"):
+    """Host only: the descriptor table of a group of pool sessions for mvq_stream_samples_slots_f32.  ``sessions``: host-integer
+    tuples (slot, fill, n, drop); -> (rows [slot, fill, n, drop, x_off], x_total) with x_off the exclusive prefix sum of 2n, the
+    packed layout of x_new.  Refuses every entry mvq_stream_samples_f32 would refuse for that ``w`` and ``cap`` (the slots are
+    _slot_host's to check)."""
+    rows, x_off = [], 0
+    w, cap = int(w), int(cap)
+    if w < 0 or not 0 <= cap <= 1 << 24:
+        raise MvqError(f"{who}: w = {w}, cap = {cap}")
+    for s in sessions:
+        try:
+            if isinstance(s, torch.Tensor) or len(s) != 4:
+                raise TypeError
+            slot, fill, n, drop = (operator.index(v) for v in s)
+        except TypeError:
+            raise MvqError(f"{who}: a session is four host integers (slot, fill, n, drop)") from None
+        if fill < 0 or n < 0 or drop < 0 or n > 1 << 24:
+            raise MvqError(f"{who}: slot {slot}: fill = {fill}, n = {n}, drop = {drop}")
+        if fill > cap or fill + n - drop > cap:
+            raise MvqError(f"{who}: slot {slot}: fill = {fill}, or the {fill + n - drop} samples to keep, exceed the capacity {cap}")
+        if w > fill + n or drop > fill + n:
+            raise MvqError(f"{who}: slot {slot}: w = {w} / drop = {drop} exceed fill + n = {fill} + {n}")
+        rows.append([slot, fill, n, drop, x_off])
+        x_off += 2 * n
+    if x_off > 0x7FFFFFFF:
+        raise MvqError(f"{who}: {x_off} new samples in one launch")
+    return rows, x_off
+
+
+def stream_samples_slots(buf, sessions, x_new, w, desc_dev=None):
+    """stream_samples for a group of sessions of a sender pool, each with ITS fill, n and drop, in one launch
+    (mvq_stream_samples_slots_f32).  buf: contiguous fp32 [S, 2, cap], slot s = the audio and the tactile row of one session,
+    updated in place in the listed slots only.  ``sessions``: host-integer tuples (slot, fill, n, drop).  x_new: contiguous fp32,
+    sum(2n) floats, per session its n new audio samples and then its n new tactile samples, in the order of ``sessions``.
+    -> win[2, G, w]: the first w samples of [buf[slot, m, :fill] | new] of every session, audio rows then tactile rows (one w per
+    launch; w = 0 with every drop 0 is the pure append).  ``desc_dev``: the int32 table [G, 5] of stream_samples_desc when the
+    caller uploaded it already.  Everything is refused on the host, before anything is uploaded: a repeated or out-of-range slot,
+    an entry stream_samples would refuse, an x_new of another size."""
+    who = "stream_samples_slots"
+    sessions = list(sessions) if not isinstance(sessions, torch.Tensor) else sessions
+    pool_ok = isinstance(buf, torch.Tensor) and buf.dim() == 3 and buf.shape[1] == 2
+    if not pool_ok:
+        raise MvqError(f"{who}: buf must be a contiguous fp32 HIP tensor [slots, 2, cap]")
+    rows, x_total = stream_samples_desc(sessions, w, buf.shape[2], who)
+    _slot_host(who, [r[0] for r in rows], buf, 3)
+    S, _, cap = buf.shape
+    G, w = len(rows), int(w)
+    if not isinstance(x_new, torch.Tensor) or x_new.dtype != torch.float32 or x_new.device != buf.device or not x_new.is_contiguous() \
+            or x_new.numel() != x_total:
+        raise MvqError(f"{who}: x_new must be a contiguous fp32 tensor of sum(2n) = {x_total} floats on {buf.device}")
+    if desc_dev is None:
+        desc_dev = torch.tensor(rows, dtype=torch.int32).reshape(G, 5).to(buf.device)
+    elif not isinstance(desc_dev, torch.Tensor) or desc_dev.dtype != torch.int32 or desc_dev.device != buf.device \
+            or tuple(desc_dev.shape) != (G, 5) or not desc_dev.is_contiguous():
+        raise MvqError(f"{who}: desc_dev must be the contiguous int32 tensor [{G}, 5] of the table on {buf.device}")
+    win = torch.empty(2, G, w, device=buf.device, dtype=torch.float32)
+    check(_lib.lib().mvq_stream_samples_slots_f32(buf.data_ptr(), desc_dev.data_ptr(), G, S, x_new.data_ptr(), x_total, win.data_ptr(),
+                                                  w, cap, _stream()), "mvq_stream_samples_slots_f32")
     return win
 
 

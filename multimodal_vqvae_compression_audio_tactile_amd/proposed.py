@@ -752,6 +752,13 @@ class ProposedEval(_ProposedBase):
         from .stream import StreamSender
         return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph)
 
+    def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None):
+        """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,
+        ``step`` once per tick with the samples that arrived (1..16 tokens per session, and the sessions that end); each
+        session gets what a stream_sender(batch=1) of its own would return, and the sessions of a tick share batched encodes."""
+        from .stream import StreamSenderPool
+        return StreamSenderPool(self, packet_tok=packet_tok, slots=slots, books_use=books_use)
+
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):
         idx, k = bitstream.unpack_indices(payload)

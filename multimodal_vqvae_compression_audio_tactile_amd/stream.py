@@ -25,7 +25,9 @@ a window that starts on a multiple of 320 samples keeps every stage's stride ali
 ``schedule`` / ``sender_schedule`` are host arithmetic only; ``StreamReceiver`` / ``StreamSender`` are the session objects
 (``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).  ``StreamReceiverPool`` (``ProposedEval.stream_receiver_pool``)
 serves receiver sessions that join, run and leave independently: their state lies in slots of one set of device buffers and a
-tick batches whichever sessions have a chunk ready, grouped by ``pool_groups``.
+tick batches whichever sessions have a chunk ready, grouped by ``pool_groups``.  ``StreamSenderPool``
+(``ProposedEval.stream_sender_pool``) is the same for sender sessions, which push 1..16 tokens of samples at a time: ``sender_step``
+is a session's host arithmetic, ``sender_pool_groups`` the sessions of a tick that share an encode.
 """
 from __future__ import annotations
 
@@ -158,6 +160,93 @@ def pool_groups(sessions, orig: int = RS_ORIG, width: int = RS_WIDTH) -> List[Po
     return out
 
 
+class SenderStep(NamedTuple):
+    """What one ``push`` / ``finish`` of a sender session does: ``emit`` -- whether an encoder window runs; then the window's ``w``
+    samples, the ``drop`` samples the buffer loses, the tokens [lo, hi) of the window that are emitted (``finish`` without an
+    emit: hi = the tokens the samples in hand make, for its StreamInfo); and the session afterwards: ``fill`` samples held,
+    ``start`` the token buf[0] belongs to, ``chunk`` the next chunk to emit."""
+    emit: bool
+    w: int
+    drop: int
+    lo: int
+    hi: int
+    fill: int
+    start: int
+    chunk: int
+
+
+def sender_step(fill: int, start: int, chunk: int, n: int, last: bool = False) -> SenderStep:
+    """The host arithmetic of a sender session (StreamSender and StreamSenderPool both call it; ``sender_schedule`` says the same
+    in tokens): the step that takes ``n`` new samples with ``fill`` samples held from token ``start`` on and ``chunk`` the next
+    chunk to emit.  A push (n = 320*m, 1 <= m <= 16) emits chunk c once 16c + 16 + 8 tokens are in hand: the window is every
+    sample from ``start`` up to that token, and the samples before token 16c + 16 - 8 are dropped.  ``finish`` (``last``, any n)
+    encodes all fill + n samples once and keeps nothing; it emits unless no token lies past ``lo`` (an item shorter than a token)."""
+    fill, start, c, n, last = int(fill), int(start), int(chunk), int(n), bool(last)
+    if fill < 0 or start < 0 or c < 0 or n < 0 or fill % HOP and not last:
+        raise ValueError(f"sender_step: fill = {fill}, start = {start}, chunk = {c}, n = {n}")
+    lo = CHUNK_TOK * c - start
+    if last:
+        T_w = enc_tokens(fill + n)
+        if T_w <= lo:
+            return SenderStep(False, 0, 0, lo, T_w, 0, start, c)
+        return SenderStep(True, fill + n, fill + n, lo, T_w, 0, start, (start + T_w + CHUNK_TOK - 1) // CHUNK_TOK)
+    if n % HOP or not HOP <= n <= PUSH_MAX_TOK * HOP:
+        raise ValueError(f"sender_step: a push of {n} samples")
+    end = CHUNK_TOK * (c + 1) + ENC_HALO_TOK                              # the first token the window of chunk c does not need
+    if start + (fill + n) // HOP < end:
+        return SenderStep(False, 0, 0, 0, 0, fill + n, start, c)
+    new_start = CHUNK_TOK * (c + 1) - ENC_HALO_TOK
+    drop = HOP * (new_start - start)
+    return SenderStep(True, HOP * (end - start), drop, lo, lo + CHUNK_TOK, fill + n - drop, new_start, c + 1)
+
+
+class SenderGroup(NamedTuple):
+    """Sender sessions of one tick that share a launch sequence: ``key`` = ("append",), ("emit", min(chunk, 1)) or
+    ("finish", fill + n, lo); ``sids`` ascending; ``w`` the window in samples and [lo, hi) the tokens of it that are emitted
+    (all zero for the append group); ``steps`` the SenderStep of every member, in the order of ``sids``."""
+    key: tuple
+    sids: Tuple[int, ...]
+    w: int
+    lo: int
+    hi: int
+    steps: Tuple[SenderStep, ...]
+
+
+def sender_pool_groups(sessions) -> List[SenderGroup]:
+    """``sessions``: (sid, fill, start, chunk, n, last) of every session that takes a step this tick (``sender_step``'s
+    arguments).  -> the groups that do device work, ordered by key.
+
+    Sessions may share a launch sequence only when their launch parameters agree.  The sample-state kernel takes fill, n and drop
+    per session, so what must agree is what the encoders and everything after them see: the window length and the emitted tokens.
+      * pushes that emit nothing need the sample-state launch alone: ONE group, ("append",), w = 0;
+      * a push that emits chunk 0 runs the 24-token window with lo = 0, one that emits any later chunk the 32-token window with
+        lo = 8, whatever it holds and whatever it pushed: ("emit", 0) and ("emit", 1);
+      * a finisher's window is all it holds, fill + n samples, emitted from lo on: ("finish", fill + n, lo).  One whose window
+        holds no token past lo does no device work and is in no group.
+    Nothing coarser is sound: windows of different lengths are never merged by padding, only a true edge is exact."""
+    seen, by_key, step_of = set(), {}, {}
+    for sid, fill, start, chunk, n, last in sessions:
+        if sid in seen:
+            raise ValueError(f"sender_pool_groups: session {sid} is listed twice")
+        seen.add(sid)
+        st = sender_step(fill, start, chunk, n, last)
+        if last:
+            if not st.emit:
+                continue
+            key = ("finish", st.w, st.lo)
+        else:
+            key = ("emit", min(int(chunk), 1)) if st.emit else ("append",)
+        by_key.setdefault(key, []).append(sid)
+        step_of[sid] = st
+    out = []
+    for key in sorted(by_key):
+        sids = tuple(sorted(by_key[key]))
+        first = step_of[sids[0]]
+        assert all((step_of[s].w, step_of[s].lo, step_of[s].hi) == (first.w, first.lo, first.hi) for s in sids)
+        out.append(SenderGroup(key, sids, first.w, first.lo, first.hi, tuple(step_of[s] for s in sids)))
+    return out
+
+
 def _f32_only(who):
     """The sessions that claim an equality chunk by chunk refuse the opt-in arithmetic modes: they scale per item, so a window
     changes their arithmetic."""
@@ -185,65 +274,59 @@ def _capture(dev, state, step):
     return g, out
 
 
-class StreamSender:
-    """A sender session for ``batch`` items advancing in lockstep: ``push`` the next samples of both modalities (320*m each,
-    1 <= m <= 16), get back the tactile packets and audio codes of the 16-token chunk they complete (nothing when they complete
-    none); ``finish`` takes the remaining samples (any count, none too) and flushes.
+def _sender_samples(who, what, a, t, B, fill, tail=False):
+    """The checks of a sender's samples, before any launch -> (a, t, n): ``a`` / ``t`` float tensors [B, 1, n] of one length; a
+    push carries 320*m samples, 1 <= m <= 16, ``finish`` (``tail``) any count."""
+    import torch
+    a, t = torch.as_tensor(a), torch.as_tensor(t)
+    for x, name in ((a, "a"), (t, "t")):
+        if x.dim() != 3 or x.shape[1] != 1 or not x.dtype.is_floating_point:
+            raise ValueError(f"{who}.{what}: {name} must be a float tensor [B, 1, samples], got {tuple(x.shape)}")
+    if a.shape[0] != B or t.shape[0] != B:
+        raise ValueError(f"{who}.{what}: samples of {a.shape[0]} / {t.shape[0]} items for a session of batch {B}")
+    if a.shape[2] != t.shape[2]:
+        raise ValueError(f"{who}.{what}: {a.shape[2]} audio and {t.shape[2]} tactile samples; the two modalities advance together")
+    n = int(a.shape[2])
+    if not tail and (n % HOP or not HOP <= n <= PUSH_MAX_TOK * HOP):
+        raise ValueError(f"{who}.push: {n} samples; a push is {HOP}*m samples, 1 <= m <= {PUSH_MAX_TOK} "
+                         "(anything else goes to finish)")
+    if tail and fill + n > (1 << 24):
+        raise ValueError(f"{who}.finish: {n} samples")
+    return a, t, n
 
-    Per item the packets of all pushes and ``finish`` concatenated equal ``compress_packets``' packets byte for byte, the audio
-    codes concatenated equal the whole-item codes, and ``finish`` returns the same ``StreamInfo`` -- for ``ops.get_arith() ==
-    "f32"`` (the opt-in arithmetic modes scale per item, so a window changes their arithmetic; they are refused) and for
-    modalities of one length.  Chunk c leaves once 8 tokens past its end are in hand: the algorithmic latency is one chunk plus
-    the encoder look-ahead, 213.3 + 106.7 ms, instead of the whole item.
 
-    An emitting ``push`` runs, in order: ops.stream_samples (the sample buffer [2B, 48*320]: window out, buffer moved on, one
-    launch for both modalities) -> A_ENC and T_ENC on the window (``sender_schedule``; one or two HIP streams as
-    ``_encode_branches`` decides) -> the chunk's 16 exact tokens -> A_QUANT -> _ar_latents(want_indices=True, z_prev=carry,
-    z_last_out=carry) -> ops.idx_pack_packets -> ONE device-to-host copy of the bodies -> packets.frame(seq_base=).  A push that
-    emits nothing is the append launch alone.  All session state is in fixed device buffers (samples [2B, 15360], carry [B, C]).
+class _SenderCore:
+    """What StreamSender and StreamSenderPool share: the configuration, the state buffers -- per session two rows of ``buf``
+    (audio, tactile; 48*320 samples each) and a row of ``carry`` [sessions, C] -- and THE device sequence from an encoder window
+    to packet bodies, written once.  With ``sl`` None it works on every session of the buffers (the lockstep sender); with ``sl``
+    = (slots, slots_dev), the host list of a group's slots and its int32 device copy, on those sessions of a pool: the carried
+    tokens go through a dense [G, C] copy (ops.stream_rows), everything else is the same launches on the group's window."""
 
-    ``graph=True``: the steady step (a push of exactly 16 tokens that completes a chunk after the first: the 32-token window) is
-    captured once as a graph, at the buffer fill it first occurs with, and replayed after the host has written the samples into
-    the static input buffer whenever a push has that shape again -- with 16-token pushes the fill before every push is the same
-    (16 tokens when the first push was 8, 24 when every push was 16).  Everything else runs eagerly."""
-
-    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False):
+    def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape):
         import torch
         from . import proposed
         from .packets import StreamInfo, body_bytes, _check
-        packet_tok, batch = int(packet_tok), int(batch)
         if packet_tok < 1 or CHUNK_TOK % packet_tok:
-            raise ValueError(f"StreamSender: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
+            raise ValueError(f"{who}: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
                              "(a packet must never straddle two chunks)")
-        if batch < 1:
-            raise ValueError("StreamSender: batch must be at least 1")
-        _f32_only("StreamSender")
+        if sessions < 1:
+            raise ValueError(f"{who}: {'batch' if who == 'StreamSender' else 'slots'} must be at least 1")
+        _f32_only(who)
         assert proposed.AR_CHUNK_TOK == CHUNK_TOK
         for enc in (net.A_ENC, net.T_ENC):
             if tuple(enc._desc[1]) != ENC_RATES:
-                raise ValueError(f"StreamSender: encoder strides {tuple(enc._desc[1])}; the window schedule is measured for {ENC_RATES}")
+                raise ValueError(f"{who}: encoder strides {tuple(enc._desc[1])}; the window schedule is measured for {ENC_RATES}")
         self.K = int(net.vq.n_embed)
         self.nb = int(net.vq.n_books) if books_use is None else max(0, min(int(books_use), int(net.vq.n_books)))
         _check(StreamInfo(self.K, self.nb, CHUNK_TOK, packet_tok))
-        self.net, self.packet_tok, self.batch, self.books_use, self.graph = net, packet_tok, batch, books_use, bool(graph)
+        self.net, self.packet_tok, self.books_use = net, packet_tok, books_use
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
         self.full = body_bytes(packet_tok, self.nb, self.K)
         self.n_audio_books = net.A_QUANT.n_codebooks
-        self.buf = torch.zeros(2 * batch, SEND_CAP_TOK * HOP, device=self.dev)         # audio rows, then tactile rows
-        self.carry = torch.zeros(batch, self.C, device=self.dev)                       # z_run[..., -1] of the chunk before
-        self.fill = 0                                                                  # valid samples of every buffer row
-        self.start = 0                                                                 # the token buf[:, 0] belongs to
-        self.chunk = 0                                                                 # the next chunk to emit
-        self.finished = False
-        self._g = None                                                                 # (graph, fill, x_static, bodies_static, codes_static)
+        self.buf = torch.zeros(*buf_shape, device=self.dev)                            # per session: an audio and a tactile row
+        self.carry = torch.zeros(sessions, self.C, device=self.dev)                    # per session: z_run[..., -1] of the chunk before
 
-    @property
-    def tokens(self):
-        """Tokens of samples received so far."""
-        return self.start + self.fill // HOP
-
-    # ------------------------------------------------------------------------------------------------------------ stages
     def _branches(self, a_w, t_w, lo, hi):
         """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt); the audio branch
         on a second HIP stream under the rule of ``_encode_branches``."""
@@ -269,35 +352,65 @@ class StreamSender:
             x.record_stream(cur)
         return qa, codes, zt
 
+    def _encode(self, win, lo, hi, sl=None):
+        """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
+        uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place."""
+        from . import ops
+        qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
+        carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
+        _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=carry, z_last_out=carry)
+        if sl is not None:
+            ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
+        return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
+
+
+class StreamSender(_SenderCore):
+    """A sender session for ``batch`` items advancing in lockstep: ``push`` the next samples of both modalities (320*m each,
+    1 <= m <= 16), get back the tactile packets and audio codes of the 16-token chunk they complete (nothing when they complete
+    none); ``finish`` takes the remaining samples (any count, none too) and flushes.
+
+    Per item the packets of all pushes and ``finish`` concatenated equal ``compress_packets``' packets byte for byte, the audio
+    codes concatenated equal the whole-item codes, and ``finish`` returns the same ``StreamInfo`` -- for ``ops.get_arith() ==
+    "f32"`` (the opt-in arithmetic modes scale per item, so a window changes their arithmetic; they are refused) and for
+    modalities of one length.  Chunk c leaves once 8 tokens past its end are in hand: the algorithmic latency is one chunk plus
+    the encoder look-ahead, 213.3 + 106.7 ms, instead of the whole item.
+
+    An emitting ``push`` runs, in order: ops.stream_samples (the sample buffer [2B, 48*320]: window out, buffer moved on, one
+    launch for both modalities) -> A_ENC and T_ENC on the window (``sender_schedule``; one or two HIP streams as
+    ``_encode_branches`` decides) -> the chunk's 16 exact tokens -> A_QUANT -> _ar_latents(want_indices=True, z_prev=carry,
+    z_last_out=carry) -> ops.idx_pack_packets -> ONE device-to-host copy of the bodies -> packets.frame(seq_base=).  A push that
+    emits nothing is the append launch alone.  All session state is in fixed device buffers (samples [2B, 15360], carry [B, C]).
+
+    ``graph=True``: the steady step (a push of exactly 16 tokens that completes a chunk after the first: the 32-token window) is
+    captured once as a graph, at the buffer fill it first occurs with, and replayed after the host has written the samples into
+    the static input buffer whenever a push has that shape again -- with 16-token pushes the fill before every push is the same
+    (16 tokens when the first push was 8, 24 when every push was 16).  Everything else runs eagerly."""
+
+    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False):
+        packet_tok, batch = int(packet_tok), int(batch)
+        super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP))   # audio rows, then tactile rows
+        self.batch, self.graph = batch, bool(graph)
+        self.fill = 0                                                                  # valid samples of every buffer row
+        self.start = 0                                                                 # the token buf[:, 0] belongs to
+        self.chunk = 0                                                                 # the next chunk to emit
+        self.finished = False
+        self._g = None                                                                 # (graph, fill, x_static, bodies_static, codes_static)
+
+    @property
+    def tokens(self):
+        """Tokens of samples received so far."""
+        return self.start + self.fill // HOP
+
+    # ------------------------------------------------------------------------------------------------------------ stages
     def _device_step(self, x, fill, w, drop, lo, hi):
         """Device: samples -> window -> latents of tokens [lo, hi) of the window -> (packet bodies uint8 [B, P, full], audio codes
         int64 [B, 32, hi - lo]); the buffer and the carried token move on in place."""
         from . import ops
-        B = self.batch
-        win = ops.stream_samples(self.buf, fill, x, w, drop)
-        qa, codes, zt = self._branches(win[:B].unsqueeze(1), win[B:].unsqueeze(1), lo, hi)
-        _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=self.carry, z_last_out=self.carry)
-        return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
+        return self._encode(ops.stream_samples(self.buf, fill, x, w, drop).view(2, self.batch, w), lo, hi)
 
     def _samples(self, a, t, what, tail=False):
-        """The checks of a push, before any launch -> (a, t) as [B, n] fp32 on the device and n."""
-        import torch
-        a, t = torch.as_tensor(a), torch.as_tensor(t)
-        B = self.batch
-        for x, name in ((a, "a"), (t, "t")):
-            if x.dim() != 3 or x.shape[1] != 1 or not x.dtype.is_floating_point:
-                raise ValueError(f"StreamSender.{what}: {name} must be a float tensor [B, 1, samples], got {tuple(x.shape)}")
-        if a.shape[0] != B or t.shape[0] != B:
-            raise ValueError(f"StreamSender.{what}: samples of {a.shape[0]} / {t.shape[0]} items for a session of batch {B}")
-        if a.shape[2] != t.shape[2]:
-            raise ValueError(f"StreamSender.{what}: {a.shape[2]} audio and {t.shape[2]} tactile samples; the two modalities advance together")
-        n = int(a.shape[2])
-        if not tail and (n % HOP or not HOP <= n <= PUSH_MAX_TOK * HOP):
-            raise ValueError(f"StreamSender.push: {n} samples; a push is {HOP}*m samples, 1 <= m <= {PUSH_MAX_TOK} "
-                             "(anything else goes to finish)")
-        if tail and self.fill + n > (1 << 24):
-            raise ValueError(f"StreamSender.finish: {n} samples")
-        return a, t, n
+        """The checks of a push, before any launch -> (a, t) and n."""
+        return _sender_samples("StreamSender", what, a, t, self.batch, self.fill, tail)
 
     def _upload(self, a, t, n):
         import torch
@@ -334,22 +447,19 @@ class StreamSender:
         from . import ops
         self._open("push")
         a, t, n = self._samples(a, t, "push")
-        c = self.chunk
-        emit = self.tokens + n // HOP >= CHUNK_TOK * (c + 1) + ENC_HALO_TOK
+        st = sender_step(self.fill, self.start, self.chunk, n)
         with torch.no_grad():
-            if not emit:
+            if not st.emit:
                 ops.stream_samples(self.buf, self.fill, self._upload(a, t, n), 0, 0)
-                self.fill += n
+                self.fill = st.fill
                 return self._nothing()
-            new_start = CHUNK_TOK * (c + 1) - ENC_HALO_TOK
-            w, drop = HOP * (CHUNK_TOK * (c + 1) + ENC_HALO_TOK - self.start), HOP * (new_start - self.start)
-            lo = CHUNK_TOK * c - self.start
-            if self.graph and c > 0 and n == CHUNK_TOK * HOP and (self._g is None or self._g[1] == self.fill):   # the steady step
-                bodies, codes = self._replay(a, t, n, (self.fill, w, drop, lo, lo + CHUNK_TOK))
+            plan = (self.fill, st.w, st.drop, st.lo, st.hi)
+            if self.graph and self.chunk > 0 and n == CHUNK_TOK * HOP and (self._g is None or self._g[1] == self.fill):   # the steady step
+                bodies, codes = self._replay(a, t, n, plan)
             else:
-                bodies, codes = self._device_step(self._upload(a, t, n), self.fill, w, drop, lo, lo + CHUNK_TOK)
+                bodies, codes = self._device_step(self._upload(a, t, n), *plan)
             out = self._framed(bodies, codes, CHUNK_TOK)
-            self.fill, self.start, self.chunk = self.fill + n - drop, new_start, c + 1
+            self.fill, self.start, self.chunk = st.fill, st.start, st.chunk
             return out
 
     def finish(self, a=None, t=None):
@@ -364,18 +474,16 @@ class StreamSender:
         n = 0
         if a is not None:
             a, t, n = self._samples(a, t, "finish", tail=True)
-        T_w = enc_tokens(self.fill + n)
-        lo = CHUNK_TOK * self.chunk - self.start
+        st = sender_step(self.fill, self.start, self.chunk, n, last=True)
         with torch.no_grad():
-            if T_w <= lo:                                                # an item shorter than one token: nothing to send
+            if not st.emit:                                              # an item shorter than one token: nothing to send
                 self.finished = True
-                return self._nothing() + (StreamInfo(self.K, self.nb, self.start + max(T_w, 0), self.packet_tok),)
+                return self._nothing() + (StreamInfo(self.K, self.nb, self.start + max(st.hi, 0), self.packet_tok),)
             x = self._upload(a, t, n) if n else torch.empty(2 * self.batch, 0, device=self.dev)
-            bodies, codes = self._device_step(x, self.fill, self.fill + n, self.fill + n, lo, T_w)
-            out = self._framed(bodies, codes, T_w - lo)
-            T = self.start + T_w
-            self.fill, self.chunk, self.finished = 0, (T + CHUNK_TOK - 1) // CHUNK_TOK, True
-            return out + (StreamInfo(self.K, self.nb, T, self.packet_tok),)
+            bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi)
+            out = self._framed(bodies, codes, st.hi - st.lo)
+            self.fill, self.chunk, self.finished = st.fill, st.chunk, True
+            return out + (StreamInfo(self.K, self.nb, self.start + st.hi, self.packet_tok),)
 
     def _replay(self, a, t, n, plan):
         """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
@@ -803,4 +911,175 @@ class StreamReceiverPool(_ReceiverCore):
             else:
                 self._sess[sid][1] += w[0]
                 self._sess[sid][2] += w[5]
+        return out
+
+
+class StreamSenderPool(_SenderCore):
+    """Sender sessions that join at any time, push 1..16 tokens of samples at a time and end after different lengths, served
+    together: ``open`` takes a session slot, ``step`` is one tick that takes the samples of whichever sessions have some (and
+    flushes the ones that end), ``close`` abandons one.  Every session gets back exactly what a ``StreamSender(batch=1)`` fed
+    the same samples returns from ``push`` / ``finish`` (``ops.get_arith() == "f32"`` only, as there), so per session the
+    packets concatenated equal ``compress_packets``' of that item alone byte for byte.
+
+    The state of all ``slots`` sessions lies in device buffers allocated once -- buf [S, 2, 48*320] (a session's audio and tactile
+    row) and carry [S, C] -- and a session is a row block of each (its slot); its (fill, start, chunk) are host integers.  A tick
+    runs, in order:
+      host   every session's samples checked (StreamSender's checks, the sids); an error leaves every session as it was;
+             sender_step per session, sender_pool_groups: ONE group of the pushes that emit nothing, at most two of the pushes
+             that emit (chunk 0: the 24-token window; later: the 32-token window), one more per kind of finisher -- inside a
+             group every session has its own fill, n and drop;
+      copy   ONE upload of all groups' descriptor tables and slot lists, ONE of all new samples (host tensors; samples already
+             on the device are concatenated there);
+      device per group of G sessions: ops.stream_samples_slots (per-session fill / n / drop, window [2, G, w] out, buffers moved
+             on) -> A_ENC, T_ENC on [G, 1, w] -> tokens [lo, hi) -> A_QUANT -> ops.stream_rows (the carried tokens, pool -> dense
+             [G, C]) -> _ar_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.idx_pack_packets: _SenderCore's
+             sequence on the group's slots.  The append group is the sample-state launch alone;
+      copy   ONE device-to-host copy of all groups' packet bodies, then packets.frame(seq_base=) per session with ITS chunk.
+    Nothing is captured as a graph: the group sizes change from tick to tick."""
+
+    def __init__(self, net, packet_tok=2, slots=64, books_use=None):
+        packet_tok, slots = int(packet_tok), int(slots)
+        super().__init__("StreamSenderPool", net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP))
+        self.slots = slots
+        self._free = list(range(slots))                                                # ascending: open() takes the lowest
+        self._sess = {}                                                                # sid -> [slot, fill, start, chunk]
+        self._next_sid = 0
+        self.last_groups = ()                                                          # the SenderGroups of the last tick
+
+    # ----------------------------------------------------------------------------------------------------------- sessions
+    @property
+    def active(self):
+        """The sids of the open sessions, ascending."""
+        return tuple(sorted(self._sess))
+
+    @property
+    def free(self):
+        """Slots no session holds."""
+        return len(self._free)
+
+    def _get(self, sid, what):
+        from ._lib import MvqError
+        try:
+            return self._sess[sid]
+        except (KeyError, TypeError):
+            raise MvqError(f"StreamSenderPool: {what}: no open session {sid!r} (never opened, finished or closed)") from None
+
+    def tokens(self, sid):
+        """Tokens of samples session ``sid`` has received."""
+        _, fill, start, _ = self._get(sid, "tokens")
+        return start + fill // HOP
+
+    def open(self):
+        """A new session -> its sid (never reused).  Takes the lowest free slot and resets it: the carried token to zero on the
+        device, the fill to zero on the host (which makes whatever the slot's buffer rows hold irrelevant)."""
+        from ._lib import MvqError
+        if not self._free:
+            raise MvqError(f"StreamSenderPool: all {self.slots} slots hold a session")
+        slot = self._free.pop(0)
+        self.carry[slot].zero_()
+        sid, self._next_sid = self._next_sid, self._next_sid + 1
+        self._sess[sid] = [slot, 0, 0, 0]
+        return sid
+
+    def close(self, sid):
+        """Abandon session ``sid`` without flushing it; its slot is free again."""
+        import bisect
+        slot = self._get(sid, "close")[0]
+        del self._sess[sid]
+        bisect.insort(self._free, slot)
+
+    # --------------------------------------------------------------------------------------------------------------- tick
+    def _inputs(self, pushes, finishes):
+        """Host: every session's samples of this tick, checked; raises before anything has changed.
+        -> {sid: (a [1, 1, n] or None, t or None, n, last)}"""
+        work = {}
+        for sid in pushes:
+            if sid in finishes:
+                raise ValueError(f"StreamSenderPool: session {sid!r} is both pushed and finished in one tick")
+        for last, items in ((False, pushes), (True, finishes)):
+            for sid, item in items.items():
+                fill = self._get(sid, "finish" if last else "push")[1]
+                if item is None:
+                    if not last:
+                        raise ValueError(f"StreamSenderPool: session {sid}: a push needs its samples (a, t)")
+                    work[sid] = (None, None, 0, True)
+                    continue
+                try:
+                    a, t = item
+                except (TypeError, ValueError):
+                    raise ValueError(f"StreamSenderPool: session {sid}: the samples (a, t) of both modalities expected") from None
+                a, t, n = _sender_samples(f"StreamSenderPool: session {sid}", "finish" if last else "push", a, t, 1, fill, tail=last)
+                work[sid] = (a, t, n, last)
+        return work
+
+    def step(self, pushes, finishes=None):
+        """One tick.  ``pushes``: {sid: (a, t)}, the next samples [1, 1, 320*m] of both modalities, 1 <= m <= 16, m per session;
+        ``finishes``: {sid: (a, t) of any length, or None} for the sessions that end with this tick.
+        -> {sid: (packets, audio_codes)} for the pushes and {sid: (packets, audio_codes, StreamInfo)} for the finishes: the
+        session's framed packets (a list of ``bytes``, numbered with ITS stream's sequence numbers) and int64 [1, 32, n] on the
+        device -- what StreamSender(batch=1).push / .finish returns for its one item; an empty list and [1, 32, 0] when the
+        push completes no chunk.  A finished session's slot is freed.  ValueError / MvqError for any one session (a push that is
+        no 320*m samples, modalities of different length, an unknown sid, a sid in both maps) comes before the first device call
+        and leaves every session as it was."""
+        import numpy as np
+        import torch
+        from . import ops
+        from .packets import StreamInfo, frame
+        pushes, finishes = dict(pushes or {}), dict(finishes or {})
+        _f32_only("StreamSenderPool")
+        work = self._inputs(pushes, finishes)
+        if not work:
+            return {}
+        groups = sender_pool_groups((sid, *self._sess[sid][1:], w[2], w[3]) for sid, w in work.items())
+        steps = {sid: st for g in groups for sid, st in zip(g.sids, g.steps)}
+        for sid, w in work.items():                                      # the finishers without a token: no device work
+            if sid not in steps:
+                steps[sid] = sender_step(*self._sess[sid][1:], w[2], w[3])
+        cap = self.buf.shape[2]
+        # ONE host array: the descriptor tables of all groups (int32 [5] per session), then their slot lists
+        tables = [ops.stream_samples_desc([(self._sess[sid][0], self._sess[sid][1], work[sid][2], st.drop)
+                                           for sid, st in zip(g.sids, g.steps)], g.w, cap, "StreamSenderPool") for g in groups]
+        n_sess = sum(len(g.sids) for g in groups)
+        host = np.asarray([r for rows, _ in tables for r in rows], np.int32).reshape(n_sess, 5)
+        host = np.concatenate([host.reshape(-1), host[:, 0]])
+        pieces = [x.reshape(-1) for g in groups for sid in g.sids if work[sid][2] for x in work[sid][:2]]
+        empty = torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
+        out, bodies_all, framing = {}, [], []
+        with torch.no_grad():
+            if groups:
+                up = torch.from_numpy(host).to(self.dev)
+                desc_all, slots_all = up[:5 * n_sess].view(n_sess, 5), up[5 * n_sess:]
+                if not pieces:
+                    x_all = torch.empty(0, device=self.dev)
+                elif any(p.is_cuda for p in pieces):
+                    x_all = torch.cat([p.to(self.dev, torch.float32) for p in pieces])
+                else:
+                    x_all = torch.cat([p.to(torch.float32) for p in pieces]).to(self.dev)
+            s0 = x0 = b0 = 0
+            for g, (rows, x_total) in zip(groups, tables):
+                G = len(g.sids)
+                win = ops.stream_samples_slots(self.buf, [r[:4] for r in rows], x_all[x0:x0 + x_total], g.w, desc_dev=desc_all[s0:s0 + G])
+                if g.hi > g.lo:
+                    bodies, codes = self._encode(win, g.lo, g.hi, sl=([r[0] for r in rows], slots_all[s0:s0 + G]))
+                    bodies_all.append(bodies.reshape(-1))
+                    per = bodies.numel() // G
+                    for i, sid in enumerate(g.sids):
+                        framing.append((sid, b0 + i * per, per, g.hi - g.lo, codes[i:i + 1]))
+                    b0 += G * per
+                s0, x0 = s0 + G, x0 + x_total
+            if bodies_all:                                                # ONE device-to-host copy of the tick's packet bodies
+                host_b = (bodies_all[0] if len(bodies_all) == 1 else torch.cat(bodies_all)).cpu().numpy()
+        for sid, at, per, n_tok, codes in framing:
+            base = self._sess[sid][3] * CHUNK_TOK // self.packet_tok
+            out[sid] = (frame(host_b[at:at + per], StreamInfo(self.K, self.nb, n_tok, self.packet_tok), seq_base=base), codes)
+        for sid, w in work.items():
+            st = steps[sid]
+            if sid not in out:
+                out[sid] = ([], empty)
+            if w[3]:
+                out[sid] += (StreamInfo(self.K, self.nb, self._sess[sid][2] + max(st.hi, 0), self.packet_tok),)
+                self.close(sid)
+            else:
+                self._sess[sid][1:] = [st.fill, st.start, st.chunk]
+        self.last_groups = tuple(groups)
         return out
