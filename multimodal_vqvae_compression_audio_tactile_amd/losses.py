@@ -186,6 +186,7 @@ def _evaluate(y, tgt, w_l1, w_stft, w_mel, ffts=(256, 512, 1024), hops=(64, 128,
         for sp in spectra.values():
             ca, cb = sp.coefs
             sp.backward_into_(dy, ca, cb, getattr(sp, "extra", None))
+        dy.mul_(torch.isfinite(x))                    # nan_to_num's autograd: gradient 0 at a non-finite prediction sample
     total = sum(w * parts[k] for k, w in (("l1", w_l1), ("stft", w_stft), ("mel", w_mel)) if w)
     if want:
         total = _WithGrad.apply(y, total, dy)
