@@ -1112,7 +1112,7 @@ int mvq_transpose2d_f32(const float* in, float* out, int rows, int cols, void* s
 int mvq_rowsum_f32(const float* in, float* out, int rows, int cols, int accumulate, void* stream)
 {
     if (rows < 0 || cols < 0) return fail(MVQ_EINVAL, "rowsum: bad shape");
-    if ((!in || !out) && rows) return fail(MVQ_EINVAL, "rowsum: null tensor");
+    if ((!in && rows && cols) || (!out && rows)) return fail(MVQ_EINVAL, "rowsum: null tensor");   /* cols == 0: nothing is read, out = 0 */
     hipError_t e = mvq::launch_rowsum(in, out, rows, cols, accumulate, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "rowsum");
 }

@@ -57,6 +57,21 @@ class AdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, clip_coef=None):
         loss = closure() if closure is not None else None
+        # The kernel walks p, exp_avg and exp_avg_sq as flat fp32 arrays of p.numel() elements.  Every parameter is checked
+        # before the first launch, so a refused step has changed nothing: another dtype is refused (a bf16 tensor is half as
+        # long in bytes as the kernel would write); a non-contiguous fp32 parameter is updated in a contiguous copy and copied
+        # back, its state being kept in the same (logical, row-major) element order.
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.dtype != torch.float32:
+                    raise ops.MvqError(f"AdamW: parameter of shape {tuple(p.shape)} is {p.dtype}; the fused update takes "
+                                       "torch.float32 parameters only")
+                if p.device.type != "cuda":
+                    raise ops.MvqError(f"AdamW: parameter is on {p.device}; the MI355X path has no CPU fallback")
+                if p.grad.shape != p.shape:
+                    raise ops.MvqError(f"AdamW: gradient of shape {tuple(p.grad.shape)} for a parameter of shape {tuple(p.shape)}")
         f = _lib.lib().mvq_adamw_f32
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -70,9 +85,12 @@ class AdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] += 1
                 g = ops._dev(p.grad.contiguous(), "grad")
-                ops._dev(p.data, "param")
-                ops.check(f(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                            ops._p(clip_coef), p.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                pd = p.data
+                pc = pd if pd.is_contiguous() else pd.contiguous()
+                ops.check(f(pc.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                            ops._p(clip_coef), pc.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                             float(group["weight_decay"]), int(st["step"]), ops._stream()), "mvq_adamw_f32")
+                if pc is not pd:
+                    pd.copy_(pc)
                 torch.autograd.graph.increment_version(p)        # written through the raw pointer: packed-weight caches must refresh
         return loss
