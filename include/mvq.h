@@ -42,7 +42,8 @@ extern "C" {
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
- * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32).
+ * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
+ * mvq_ar_latents_staged_rate_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -241,6 +242,35 @@ int mvq_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_
  * writes +0 (RVQ is successively refinable: a partly delivered token is a lower-rate token).  Same strided output. */
 int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,
                                int t, int nb_use, int k, size_t out_sb, size_t out_sd, void* stream);
+
+/* Closed-loop sender rate control (additive, same ABI version; no reference counterpart).  After the search of a chunk the SENDER
+ * decides how many books each packet carries and forms, from exactly those books, the sum the receiver will form
+ * (mvq_rvq_dequant_layers_f32's arithmetic), so that the AR history of both ends is the same bits at any rate.
+ * Per item the t tokens fall into groups of group_tok (the AR chunk, 16; the last may be shorter) and packets of packet_tok
+ * (packet_tok divides group_tok).  Per token, with r_0 = z(b, :, t) and the indices the search returned:
+ *   r_{m+1}[d] = r_m[d] - e_m[idx_m][d];   E_m = (...((+0 + r_m[0]*r_m[0]) + r_m[1]*r_m[1]) + ...), d ascending, the multiply and
+ *   the add rounded separately (no fma), m = 0 .. nb_use.
+ * MVQ_RATE_FULL: every packet carries nb_use books.  MVQ_RATE_TOL2 (constant quality): need(token) = the smallest m in
+ * [min_books, nb_use] with E_m <= tol2 * E_0 (one fp32 multiply; nb_use when there is none: a NaN compares false), a packet
+ * carries the max over its tokens.  MVQ_RATE_BUDGET (constant rate): the packets of a group share `budget` books
+ * (a group of g < P_c = group_tok / packet_tok packets: max(g*min_books, budget*g / P_c)); every packet starts at min_books, then
+ * book by book the packet with the largest gain = (...(+0 + (E_m[j] - E_{m+1}[j])) + ...) over its tokens j gets its next one --
+ * candidates (packets below nb_use) in ascending order, the first is the incumbent, a later one replaces it only when its gain
+ * compares strictly greater -- until the budget is spent or every packet has nb_use.
+ * z (b, d, t) is read at b*z_sb + d*z_sd + t, index (book i, item b, token t) at idx[i*idx_sbook + b*idx_sitem + t] (int32 as the
+ * search writes it, clamped to [0, K)); a stride pair of 0 means contiguous.  Writes EVERY element of q_out (strided like
+ * mvq_rvq_dequant_f32's: the sum over the first nb_valid books), nb_valid[b*nbv_sb + t] (the count of the token's packet),
+ * nb_sent[b*nbs_sb + p] (packet p of the item; P = ceil(t / packet_tok)) and, unless NULL, energy[nb_use + 1, batch*t].
+ * nb_use == 0 writes zeros and counts of 0.  Covered: D % 4 == 0, D <= 128, nb_use <= 32, group_tok <= 16 (else MVQ_EUNSUPPORTED);
+ * 1 <= min_books <= nb_use, a finite tol2 > 0, P_c*min_books <= budget <= P_c*nb_use, packet_tok | group_tok (else MVQ_EINVAL):
+ * all before any launch.  One block per (item, group); no atomics. */
+#define MVQ_RATE_FULL 0
+#define MVQ_RATE_TOL2 1
+#define MVQ_RATE_BUDGET 2
+int mvq_rvq_rate_f32(const float* z, size_t z_sb, size_t z_sd, const int32_t* idx, size_t idx_sbook, size_t idx_sitem,
+                     const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
+                     uint8_t* nb_sent, size_t nbs_sb, float* energy, int batch, int dim, int t, int nb_use, int k,
+                     int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget, void* stream);
 
 /* ---- predictor / glue primitives (CrossPredictor, TokenNorm, PosEnc1D) --------------------------- */
 
@@ -702,6 +732,14 @@ int mvq_ar_latents_staged_f32(const mvq_ar_args* args, void* workspace, size_t w
  * the bits of the whole-sequence call.  Not with tactile_only (MVQ_EINVAL). */
 int mvq_ar_latents_staged_carry_f32(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace,
                                     size_t workspace_bytes, void* stream);
+/* mvq_ar_latents_staged_carry_f32 with closed-loop rate control (mvq_rvq_rate_f32's rule and argument checks, group = the 16-token
+ * chunk): one rate launch per chunk after the search; z_run is built from the books each packet carries, in the receiver's
+ * arithmetic, and so equals the receiver's bit for bit.  Also writes nb_valid_out[batch, t_lat] and nb_sent_out[batch,
+ * ceil(t_lat / packet_tok)].  args->idx_out is required; z_prev / z_last_out as in the carry form (both may be NULL).  Same bits
+ * as the launch-per-stage loop with mvq_rvq_rate_f32 after each search. */
+int mvq_ar_latents_staged_rate_f32(const mvq_ar_args* args, int packet_tok, int min_books, int mode, float tol2, int budget,
+                                   const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 /* synchronises `stream`, then: MVQ_OK when every grid barrier of the last call on this workspace completed */
 int mvq_ar_check(const void* workspace, void* stream);
 

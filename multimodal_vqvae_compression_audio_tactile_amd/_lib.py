@@ -85,6 +85,8 @@ EXPORTS = {
     "mvq_idx_pack_packets_u8": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_idx_unpack_packets": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "mvq_rvq_dequant_layers_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
+    "mvq_rvq_rate_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                 c_size_t, c_void_p, c_size_t, c_void_p] + [c_int] * 9 + [c_float, c_int, c_void_p]),
     "mvq_layernorm_c_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_float, c_int, c_float, c_void_p]),
     "mvq_attention_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_align_xcorr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -162,6 +164,7 @@ EXPORTS = {
     "mvq_ar_latents_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_size_t, c_void_p]),
     "mvq_ar_latents_staged_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_size_t, c_void_p]),
     "mvq_ar_latents_staged_carry_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvq_ar_latents_staged_rate_f32": (c_int, [ctypes.POINTER(ArArgs)] + [c_int] * 3 + [c_float, c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mvq_ar_check": (c_int, [c_void_p, c_void_p]),
 }
 

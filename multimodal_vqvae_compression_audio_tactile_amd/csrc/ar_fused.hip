@@ -496,10 +496,20 @@ int mvq_ar_latents_f32(const mvq_ar_args* args, void* workspace, size_t workspac
  * allocations cost as much host time as the kernels take on the device (eager encode 2.5 ms against 2.3 ms replayed as a graph);
  * from C a launch costs 2-3 us.  Same kernels, same bits as the Python loop (tests/test_gpu_ar_fused.py).  Needs every GEMM in the
  * latency form's range (batch <= 8: at most 1 024 16 x 16 tiles per launch). */
-static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace, size_t workspace_bytes, void* stream)
+struct ArRate { int packet_tok, min_books, mode, budget; float tol2; uint8_t *nb_valid, *nb_sent; };      // the rate form's extras
+
+static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace, size_t workspace_bytes, void* stream,
+                     const ArRate* rate = nullptr)
 {
     using namespace mvq;
     auto fail = [](int code, const char* msg) { set_last_error(msg); return code; };
+    // The rate rule's own argument checks come first, so that a bad packet_tok / min_books / tol2 / budget is named as such whatever else
+    // is wrong with the call (tests/test_rate_cpu.py reaches them without a device).  Shapes rvq_rate_check itself would call bad
+    // (books_use < 0, K <= 0) are left to ar_prepare below, which refuses them with the loop's own text: one rule, one place each.
+    if (rate && args && args->books_use >= 0 && args->rvq_k > 0)
+        if (const int rc = rvq_rate_check(D_CODE, args->books_use, args->rvq_k, rate->packet_tok, CHUNK, rate->min_books, rate->mode, rate->tol2, rate->budget);
+            rc != MVQ_OK)
+            return rc;
     ArKT kt;
     bool done = false;
     if (const int rc = ar_prepare(args, workspace, workspace_bytes, kt, done); rc != MVQ_OK || done) return rc;
@@ -507,6 +517,8 @@ static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last
     const mvq_ar_args& a = k.a;
     if (a.batch > 8) return fail(MVQ_EUNSUPPORTED, "ar_latents_staged: batch <= 8 (beyond it the LDS-tiled GEMMs of the per-stage loop win)");
     if ((z_prev || z_last_out) && a.tactile_only) return fail(MVQ_EINVAL, "ar_latents_staged_carry: tactile_only has no recursion to carry");
+    if (rate && (!rate->nb_valid || !rate->nb_sent || !a.idx_out))
+        return fail(MVQ_EINVAL, "ar_latents_staged_rate: nb_valid_out, nb_sent_out and args->idx_out are required");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int B = a.batch, Tl = a.t_lat;
     // chunk-local buffers start defined: a last chunk shorter than 16 tokens leaves columns nobody writes, and the search reads all 16
@@ -562,6 +574,11 @@ static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last
                         hipLaunchKernelGGL(ar_zero_kernel, dim3(8), dim3(256), 0, st, reinterpret_cast<float4*>(k.qD16), (size_t)D_CODE * B * CHUNK / 4);
                         e = hipGetLastError();
                     }
+                    if (e == hipSuccess && rate)      // the books each packet carries, and qD16 <- what the receiver sums from them
+                        e = launch_rvq_rate(k.rD16, (size_t)D_CODE * CHUNK, CHUNK, idx_tmp, (size_t)B * CHUNK, CHUNK, a.books, k.qD16, (size_t)D_CODE * CHUNK,
+                                            CHUNK, rate->nb_valid + s, (size_t)Tl, rate->nb_sent + s / rate->packet_tok,
+                                            (size_t)((Tl + rate->packet_tok - 1) / rate->packet_tok), nullptr, B, D_CODE, n, a.books_use, a.rvq_k,
+                                            rate->packet_tok, CHUNK, rate->min_books, rate->mode, rate->tol2, rate->budget, st);
                     if (e == hipSuccess && a.idx_out && a.books_use > 0)      // [books * B][16] -> idx_out[books * B][Tlat] at s (4-byte moves)
                         e = launch_strided3d(reinterpret_cast<const float*>(idx_tmp), CHUNK, 0, nullptr, 0, 0,
                                              reinterpret_cast<float*>(a.idx_out) + s, (size_t)Tl, 0, a.books_use * B, 1, n, st);
@@ -590,6 +607,16 @@ int mvq_ar_latents_staged_carry_f32(const mvq_ar_args* args, const float* z_prev
                                     size_t workspace_bytes, void* stream)
 {
     return ar_staged(args, z_prev, z_last_out, workspace, workspace_bytes, stream);
+}
+
+/* The staged loop with the sender's closed-loop rate control: one mvq_rvq_rate_f32 launch per chunk after the search decides the
+ * books of each packet and replaces the straight-through qD16 by the receiver's sum over them, so z_run is the receiver's. */
+int mvq_ar_latents_staged_rate_f32(const mvq_ar_args* args, int packet_tok, int min_books, int mode, float tol2, int budget,
+                                   const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out, void* workspace,
+                                   size_t workspace_bytes, void* stream)
+{
+    const ArRate r{packet_tok, min_books, mode, budget, tol2, nb_valid_out, nb_sent_out};
+    return ar_staged(args, z_prev, z_last_out, workspace, workspace_bytes, stream, &r);
 }
 
 /* after the stream has been synchronised: 0 = every grid barrier of the last call on this workspace completed */

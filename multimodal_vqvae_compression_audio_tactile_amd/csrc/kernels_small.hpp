@@ -127,6 +127,12 @@ hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_re
                                      int T, int K, int bits, int ptok, hipStream_t s);
 hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
                                      int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
+// rate.hip: closed-loop sender rate control (mvq_rvq_rate_f32); rvq_rate_check returns an MVQ_* code, its text through set_last_error
+int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget);
+hipError_t launch_rvq_rate(const float* z, size_t z_sb, size_t z_sd, const int32_t* idx, size_t idx_sbook, size_t idx_sitem,
+                           const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
+                           uint8_t* nb_sent, size_t nbs_sb, float* energy, int B, int D, int T, int nb, int K, int ptok, int gtok,
+                           int min_books, int mode, float tol2, int budget, hipStream_t s);
 // stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024).  slots ==
 // nullptr: every session of the buffers, densely; else the G sessions slots[G] (a device list) of a pool of n_slots, C rows per
 // session and rows = G*C <= INT_MAX

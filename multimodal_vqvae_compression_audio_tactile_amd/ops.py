@@ -398,7 +398,8 @@ def conv_transpose1d_packed_rows(xp, wp, cout, stride, pad, seg_per_row, seg_per
 
 
 def rvq_ema_forward(z, books, n_books_use=None, return_indices=False):
-    """ResidualVQEMA.forward.  z[B,D,T]; books[nb,K,D] (stacked).  -> q[B,D,T] (, idx[nb_use, B*T] int64)."""
+    """ResidualVQEMA.forward.  z[B,D,T]; books[nb,K,D] (stacked).  -> q[B,D,T] (, idx[nb_use, B*T] int64; ``return_indices="int32"``:
+    as the kernel wrote them, not widened -- what ops.rvq_rate reads)."""
     z = _dev(z, "z"); books = _dev(books, "books")
     B, D, T = z.shape
     nb_all, K, D2 = books.shape
@@ -410,7 +411,7 @@ def rvq_ema_forward(z, books, n_books_use=None, return_indices=False):
     check(_lib.lib().mvq_rvq_ema_forward_f32(z.data_ptr(), books.data_ptr(), q.data_ptr(), _p(idx), B, D, T, nb, K,
                                              _stream()), "mvq_rvq_ema_forward_f32")
     if return_indices:
-        return q, idx.long()
+        return q, (idx if return_indices == "int32" else idx.long())
     return q
 
 
@@ -526,6 +527,57 @@ def rvq_dequant_layers(idx, books, nb_valid, n_books_use=None, out=None, out_str
     check(_lib.lib().mvq_rvq_dequant_layers_f32(idx.data_ptr(), books.data_ptr(), nbv.data_ptr(), out.data_ptr(), B, D, T, nb, K,
                                                 sb, sd, _stream()), "mvq_rvq_dequant_layers_f32")
     return out
+
+
+def rvq_rate(z, idx, books, rate, packet_tok, n_books_use=None, folded_batch=None, nb_valid_out=None, nb_sent_out=None, col=0,
+             want_energy=False, group_tok=16):
+    """Closed-loop sender rate control on the search's result (mvq_rvq_rate_f32): decide how many books each packet carries and
+    sum exactly those, in the receiver's arithmetic.  z[B, D, T] (or token-folded [1, D, B*T] with ``folded_batch`` = B), idx
+    [nb, B, T] / [nb, B*T] (int32 as the search writes it, or int64) of rvq_ema_forward on that z, books[nb_all, K, D]; ``rate`` a
+    packets.Rate.  Groups of ``group_tok`` tokens start at token 0 of each item.  -> (q shaped and laid out like z, nb_valid uint8
+    [B, T], nb_sent uint8 [B, P]) and energy fp32 [nb + 1, B*T] with ``want_energy``.  ``nb_valid_out`` [B, W] / ``nb_sent_out``
+    [B, Wp] (uint8, contiguous): write the counts there instead, tokens from column ``col`` and packets from col // packet_tok
+    (a chunk of a longer item); they are returned as given."""
+    z = _dev(z, "z"); books = _dev(books, "books")
+    if z.dim() != 3 or books.dim() != 3 or books.device != z.device or books.shape[2] != z.shape[1]:
+        raise MvqError(f"rvq_rate: z {tuple(z.shape)} and books {tuple(books.shape)} must be [B, D, T] and [n_books, K, D] on one device")
+    D = z.shape[1]
+    if folded_batch is None:
+        B, T = z.shape[0], z.shape[2]
+        z_sb, z_sd = D * T, T
+    else:
+        B = int(folded_batch)
+        if z.shape[0] != 1 or B < 1 or z.shape[2] % B:
+            raise MvqError(f"rvq_rate: z {tuple(z.shape)} is not token-folded [1, D, {B}*T]")
+        T = z.shape[2] // B
+        z_sb, z_sd = T, B * T
+    nb_all, K, _ = books.shape
+    if not isinstance(idx, torch.Tensor) or idx.device != z.device or idx.dtype not in (torch.int32, torch.int64):
+        raise MvqError("rvq_rate: idx must be an int32 or int64 tensor on z's device")
+    if idx.dim() not in (2, 3) or idx.numel() != idx.shape[0] * B * T:
+        raise MvqError(f"rvq_rate: idx {tuple(idx.shape)} for [n_books, B={B}, T={T}]")
+    nb = min(idx.shape[0], nb_all) if n_books_use is None else max(0, min(int(n_books_use), idx.shape[0], nb_all))
+    idx = idx.to(torch.int32).contiguous()
+    packet_tok, col = int(packet_tok), int(col)
+    min_books, mode, tol2, budget = rate.resolve(nb, packet_tok, group_tok)
+    if col < 0 or col % int(group_tok):
+        raise MvqError(f"rvq_rate: col = {col} is not the start of a {group_tok}-token group")
+    P = (T + packet_tok - 1) // packet_tok
+    outs = []
+    for t, name, n, c in ((nb_valid_out, "nb_valid_out", T, col), (nb_sent_out, "nb_sent_out", P, col // packet_tok)):
+        if t is None:
+            t, c = torch.empty(B, n, device=z.device, dtype=torch.uint8), 0
+        elif (not isinstance(t, torch.Tensor) or t.device != z.device or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != B
+              or not t.is_contiguous() or c + n > t.shape[1]):
+            raise MvqError(f"rvq_rate: {name} must be a contiguous uint8 tensor [B={B}, >= {c + n}] on z's device")
+        outs.append((t, c))
+    (nbv, cv), (nbs, cs) = outs
+    q = torch.empty_like(z)
+    energy = torch.empty(nb + 1, B * T, device=z.device, dtype=torch.float32) if want_energy else None
+    check(_lib.lib().mvq_rvq_rate_f32(z.data_ptr(), z_sb, z_sd, idx.data_ptr(), B * T, T, books.data_ptr(), q.data_ptr(), z_sb, z_sd,
+                                      nbv.data_ptr() + cv, nbv.shape[1], nbs.data_ptr() + cs, nbs.shape[1], _p(energy), B, D, T, nb, K,
+                                      packet_tok, int(group_tok), min_books, mode, tol2, budget, _stream()), "mvq_rvq_rate_f32")
+    return (q, nbv, nbs, energy) if want_energy else (q, nbv, nbs)
 
 
 PACKET_MAX_BITS = 24           # the packet kernels cover ceil(log2 K) <= 24, nb and packet_tok <= 255 (include/mvq.h)
@@ -853,15 +905,19 @@ _AR_CHECKED = set()
 
 def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f, w1, b1, w3, b3, ln_eps, tok, tok_eps, scale,
                      wd, bd, wu, bu, books, books_use, heads, c_ff, code_dim, r_tokens=None, idx_out=None, tactile_only=False, chunk=16,
-                     staged=False, z_prev=None, z_last_out=None):
+                     staged=False, z_prev=None, z_last_out=None, rate=None):
     """The whole chunked AR loop as ONE persistent kernel (csrc/ar_fused.hip: mvq_ar_latents_f32): zt[B,C,Tlat] -> z_run[B,C,Tlat]
     (written in place), optionally r_tokens[B,96,Tlat] and idx_out[nb,B,Tlat] (int32).  ``k_all`` / ``v_all``: token-folded K / V
     of all chunks ([1,C,B*t_audio], CrossPredictor.keys_values) or None; the w* are K-major packed 1x1 weights (pack_conv1d);
     ln_q / ln_f / tok = (weight, bias).  ``staged``: the same stages as stand-alone launches issued by ONE host call
     (mvq_ar_latents_staged_f32; batch <= 8) instead of the persistent kernel.  Same bits as the Python loop either way
     (tests/test_gpu_ar_fused.py).  ``z_prev`` / ``z_last_out`` ([B, C] fp32, staged only): the token carried into and out of a
-    piece of a longer sequence (mvq_ar_latents_staged_carry_f32)."""
+    piece of a longer sequence (mvq_ar_latents_staged_carry_f32).  ``rate`` (staged only) = (packet_tok, min_books, mode, tol2,
+    budget, nb_valid_out uint8 [B, Tlat], nb_sent_out uint8 [B, P]): closed-loop rate control, one mvq_rvq_rate_f32 launch per chunk
+    (mvq_ar_latents_staged_rate_f32); needs idx_out."""
     carried = z_prev is not None or z_last_out is not None
+    if rate is not None and (not staged or idx_out is None):
+        raise MvqError("ar_latents_fused: rate needs staged=True and idx_out (the persistent kernel has no rate stage)")
     if carried and not staged:
         raise MvqError("ar_latents_fused: z_prev / z_last_out need staged=True (the persistent kernel carries no token)")
     zt = _dev(zt, "zt")
@@ -880,6 +936,12 @@ def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f
     L = _lib.lib()
     nbytes = L.mvq_ar_workspace_bytes(B, Tl)
     ws = torch.empty(max(nbytes, 4), device=zt.device, dtype=torch.uint8)
+    if rate is not None:
+        packet_tok, min_books, mode, tol2, budget, nbv, nbs = rate
+        check(L.mvq_ar_latents_staged_rate_f32(ctypes.byref(a), int(packet_tok), int(min_books), int(mode), float(tol2), int(budget),
+                                               _p(z_prev), _p(z_last_out), nbv.data_ptr(), nbs.data_ptr(), ws.data_ptr(), nbytes,
+                                               _stream()), "mvq_ar_latents_staged_rate_f32")
+        return z_run
     if carried:
         check(L.mvq_ar_latents_staged_carry_f32(ctypes.byref(a), _p(z_prev), _p(z_last_out), ws.data_ptr(), nbytes, _stream()),
               "mvq_ar_latents_staged_carry_f32")

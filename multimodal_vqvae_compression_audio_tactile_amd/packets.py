@@ -22,6 +22,7 @@ the shorter tail packet and every thinned packet are zero-padded to the full wid
 """
 from __future__ import annotations
 
+import dataclasses
 import struct
 from typing import Iterable, NamedTuple, Optional
 
@@ -50,6 +51,68 @@ class StreamInfo(NamedTuple):
     def ntok(self, p: int) -> int:
         """Tokens packet p carries."""
         return max(0, min(self.packet_tok, self.T - p * self.packet_tok))
+
+
+@dataclasses.dataclass(frozen=True)
+class Rate:
+    """Sender-side rate control (closed loop: the sender builds its AR history from exactly the books it sends, in the receiver's
+    arithmetic; include/mvq.h, mvq_rvq_rate_f32).  Every packet carries at least ``min_books`` books.
+      * neither ``tol2`` nor ``budget``: every packet carries all books in use;
+      * ``tol2`` (fp32 > 0), constant quality: a token needs the fewest books m >= min_books that leave a residual energy
+        E_m <= tol2 * E_0 (all of them when none does); a packet carries the max over its tokens;
+      * ``budget`` (int), constant rate: the books of the 16 / packet_tok packets of a 16-token chunk sum to ``budget``, given out
+        one at a time to the packet whose next book removes most residual energy (a shorter tail group of g packets gets
+        max(g*min_books, budget*g // P_c)).
+    ``tol2`` and ``budget`` are mutually exclusive (ValueError).  ``resolve`` checks the values against a stream's shape."""
+    min_books: int = 1
+    tol2: Optional[float] = None
+    budget: Optional[int] = None
+
+    def __post_init__(self):
+        if self.tol2 is not None and self.budget is not None:
+            raise ValueError("Rate: tol2 (constant quality) and budget (constant rate) are mutually exclusive")
+        for name in ("min_books", "budget"):
+            v = getattr(self, name)
+            if v is not None and (isinstance(v, bool) or int(v) != v):
+                raise ValueError(f"Rate: {name} = {v!r} is not an integer")
+        if self.min_books < 1:
+            raise ValueError(f"Rate: min_books = {self.min_books} (at least one book per packet: the format has no empty packet)")
+        if self.tol2 is not None and not (np.float32(self.tol2) > 0 and np.isfinite(np.float32(self.tol2))):
+            raise ValueError(f"Rate: tol2 = {self.tol2!r} must be a finite positive fp32 value")
+
+    def resolve(self, nb_use: int, packet_tok: int, group_tok: int = 16):
+        """-> (min_books, mode, tol2, budget) as mvq_rvq_rate_f32 takes them (mode 0 full, 1 tol2, 2 budget); ValueError on a
+        packet_tok that does not divide the chunk, min_books > nb_use, or a budget outside P_c*min_books .. P_c*nb_use."""
+        nb_use, packet_tok, group_tok, min_books = int(nb_use), int(packet_tok), int(group_tok), int(self.min_books)
+        if packet_tok < 1 or group_tok % packet_tok:
+            raise ValueError(f"Rate: packet_tok = {packet_tok} does not divide the {group_tok}-token chunk")
+        if nb_use > 0 and min_books > nb_use:
+            raise ValueError(f"Rate: min_books = {min_books} outside 1..{nb_use} (the books in use)")
+        if self.tol2 is not None:
+            return min_books, 1, float(np.float32(self.tol2)), 0
+        if self.budget is not None:
+            budget, pc = int(self.budget), group_tok // packet_tok
+            if nb_use > 0 and not pc * min_books <= budget <= pc * nb_use:
+                raise ValueError(f"Rate: budget = {budget} outside {pc * min_books}..{pc * nb_use} "
+                                 f"({pc} packets per chunk, {min_books}..{nb_use} books each)")
+            return min_books, 2, 0.0, budget
+        return min_books, 0, 0.0, 0
+
+
+def sent_bits(nb_sent, info: StreamInfo, headers: bool = True) -> int:
+    """Bits on the wire of one item whose packet p carries nb_sent[p] books (an int: every packet): the bodies as framed (whole
+    bytes per packet), plus the 9-byte headers when ``headers``."""
+    info = _check(info)
+    counts = [int(nb_sent)] * info.P if np.ndim(nb_sent) == 0 else [int(v) for v in np.asarray(nb_sent).reshape(-1)]
+    if len(counts) != info.P:
+        raise ValueError(f"sent_bits: {len(counts)} counts for P={info.P} packets")
+    return 8 * sum(body_bytes(info.ntok(p), counts[p], info.K) + (HEADER_BYTES if headers else 0) for p in range(info.P))
+
+
+def sent_kbps(nb_sent, info: StreamInfo, headers: bool = True, token_rate: float = 75.0) -> float:
+    """The realised rate of ``sent_bits`` in kbit/s at ``token_rate`` tokens per second (75: 24 kHz / 320)."""
+    info = _check(info)
+    return sent_bits(nb_sent, info, headers) * float(token_rate) / (1000.0 * info.T) if info.T else 0.0
 
 
 def n_packets(t: int, packet_tok: int) -> int:
@@ -130,17 +193,25 @@ def unpack_bodies(bodies, nb_recv, info: StreamInfo):
     return idx, nb_valid
 
 
-def frame(bodies, info: StreamInfo, nb_sent: Optional[int] = None, seq_base: int = 0) -> list:
+def frame(bodies, info: StreamInfo, nb_sent=None, seq_base: int = 0) -> list:
     """bodies[P, body_full] -> one ``bytes`` per packet: the header and the first ``nb_sent`` (default: all nb) books of the body.
+    ``nb_sent`` is one count for every packet or a sequence of P counts, one per packet (sender rate control): packet p then
+    equals ``thin`` of the full packet to nb_sent[p] books.
     ``seq_base`` (streaming, stream.py): ``info`` describes one chunk of a longer stream and packet p is numbered seq_base + p,
     the stream's sequence number, as ``gather(seq_base=)`` expects it."""
     info = _check(info)
     seq_base = int(seq_base)
     if not 0 <= seq_base <= 2 ** 32 - info.P:
         raise ValueError(f"frame: seq_base = {seq_base} with P = {info.P} packets leaves the 32-bit sequence number")
-    nb_sent = info.nb if nb_sent is None else int(nb_sent)
-    if not 1 <= nb_sent <= info.nb:
-        raise ValueError(f"frame: nb_sent={nb_sent} outside 1..{info.nb}")
+    if nb_sent is None or np.ndim(nb_sent) == 0:
+        counts = [info.nb if nb_sent is None else int(nb_sent)] * max(info.P, 1)
+    else:
+        counts = [int(v) for v in np.asarray(nb_sent).reshape(-1)]
+        if len(counts) != info.P:
+            raise ValueError(f"frame: {len(counts)} book counts for P={info.P} packets")
+    for c in counts:
+        if not 1 <= c <= info.nb:
+            raise ValueError(f"frame: nb_sent={c} outside 1..{info.nb}")
     full = body_bytes(info.packet_tok, info.nb, info.K)
     bodies = np.asarray(bodies, np.uint8).reshape(-1, full) if full else np.zeros((info.P, 0), np.uint8)
     if bodies.shape[0] != info.P:
@@ -148,7 +219,7 @@ def frame(bodies, info: StreamInfo, nb_sent: Optional[int] = None, seq_base: int
     out = []
     for p in range(info.P):
         ntok = info.ntok(p)
-        out.append(_HEADER.pack(MAGIC, VERSION, seq_base + p, ntok, nb_sent) + _first_books(bodies[p], ntok, nb_sent, info.K))
+        out.append(_HEADER.pack(MAGIC, VERSION, seq_base + p, ntok, counts[p]) + _first_books(bodies[p], ntok, counts[p], info.K))
     return out
 
 

@@ -246,9 +246,22 @@ class _ProposedBase(nn.Module):
         """clamp(scale, 5e-3, 0.5)   (Training/compare_dacvsproposal_5.py:314)."""
         return min(max(self._scale_raw(), 5e-3), 0.5)
 
+    def _rate_resolve(self, rate, books_use, packet_tok):
+        """The refusals of sender rate control, before any launch -> (packet_tok, (min_books, mode, tol2, budget))."""
+        from . import packets
+        if not isinstance(rate, packets.Rate):
+            raise ValueError(f"rate must be a packets.Rate, not {type(rate).__name__}")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"rate control claims bit-equality with the receiver; arithmetic mode {ops.get_arith()!r} makes no "
+                             "parity claim")
+        packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
+        n_books = len(self.vq.books)
+        nb_use = n_books if books_use is None else max(0, min(int(books_use), n_books))
+        return packet_tok, rate.resolve(nb_use, packet_tok, AR_CHUNK_TOK)
+
     @torch.no_grad()
     def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False, z_prev=None,
-                    z_last_out=None):
+                    z_last_out=None, rate=None, packet_tok=None):
         """The chunked AR loop (Training/...5.py:302-320 == Evaluation/...6_latency.py:461-477).
         ``want_indices``: also return the per-book code indices idx[n_books_use, B, Tlat] (int64).
 
@@ -257,8 +270,19 @@ class _ProposedBase(nn.Module):
         contiguous fp32 on the device) is the last z_run token of the piece before and becomes column 0 of the first chunk's
         zt_prev; ``z_last_out`` (same shape; may be the z_prev buffer) receives this piece's last z_run token.  Both None:
         today's launch sequence exactly.  The opt-in persistent kernel carries no token: such a call takes the staged form or the
-        Python loop."""
+        Python loop.
+
+        ``rate`` (a packets.Rate; packets of ``packet_tok`` tokens, default packets.PACKET_TOK): closed-loop sender rate control.
+        After each chunk's search one ops.rvq_rate launch decides on the device how many books each packet carries and replaces the
+        straight-through qD by the sum the receiver will form from exactly those books, so z_run -- and through z_run[..., s-1]
+        every later chunk -- is what decode_latents(nb_valid=) reconstructs, bit for bit (given ``qa`` from the codes).  Implies
+        ``want_indices`` and returns (z_run, r_tokens, idx, nb_valid uint8 [B, Tlat], nb_sent uint8 [B, P]).  Only in "f32"
+        arithmetic; the persistent kernel is never taken.  None: today's launches exactly."""
         B, C, Tlat = zt.shape
+        rate_args = None
+        if rate is not None:
+            packet_tok, rate_args = self._rate_resolve(rate, books_use, packet_tok)
+            want_indices = True
         carried = z_prev is not None or z_last_out is not None
         if carried:
             if tactile_only:
@@ -271,8 +295,16 @@ class _ProposedBase(nn.Module):
         r_tokens = torch.empty(B, CODE_DIM, Tlat, device=zt.device, dtype=torch.float32) if want_tokens else None
         idx_all = [] if want_indices else None
         if B == 0 or Tlat == 0:                                               # empty batch / clip shorter than a token
+            if rate is not None:
+                return (z_run, r_tokens, torch.zeros(0, B, Tlat, dtype=torch.int64, device=zt.device),
+                        torch.zeros(B, Tlat, dtype=torch.uint8, device=zt.device), torch.zeros(B, 0, dtype=torch.uint8, device=zt.device))
             return (z_run, r_tokens, torch.zeros(0, B, Tlat, dtype=torch.int64, device=zt.device)) if want_indices \
                 else (z_run, r_tokens)
+        nb_valid = nb_sent = None
+        if rate is not None:                                                  # the rate kernel writes every element (no books: zeros)
+            mk = torch.empty if len(self.vq.books) else torch.zeros
+            nb_valid = mk(B, Tlat, dtype=torch.uint8, device=zt.device)
+            nb_sent = mk(B, (Tlat + packet_tok - 1) // packet_tok, dtype=torch.uint8, device=zt.device)
         scale = self._scale_value()
         ln = self.tokennorm.ln
         books = self.vq.stacked() if len(self.vq.books) else None             # ONE stack per call, not one per chunk
@@ -282,11 +314,14 @@ class _ProposedBase(nn.Module):
             if Ta > 0:                                                        # K, V of all chunks up front (3 launches)
                 kv_all = self.predict.keys_values(ops.fold_time_slice(qa, 0, Ta), B, AR_CHUNK_TOK)
         mode = self._ar_one_call_mode(zt, books)
-        if mode == "fused" and carried:
+        if rate is not None and books is None:
+            mode = None                                                       # no books: nothing to search or rate; the loop below writes zeros
+        if mode == "fused" and (carried or rate is not None):
             mode = "staged" if zt.shape[0] <= self.AR_STAGED_MAX_BATCH and self._ar_shapes_covered(zt, books) else None
         if mode is not None:
             return self._ar_latents_fused(zt, z_run, r_tokens, kv_all, 0 if tactile_only else min(qa.shape[-1], Tlat), books, books_use,
-                                          tactile_only, want_indices, staged=(mode == "staged"), z_prev=z_prev, z_last_out=z_last_out)
+                                          tactile_only, want_indices, staged=(mode == "staged"), z_prev=z_prev, z_last_out=z_last_out,
+                                          rate=None if rate is None else (packet_tok,) + rate_args + (nb_valid, nb_sent))
         zt_prev, zp_n = None, -1      # the shift-by-one input: all zero except column 0 of each item (s > 0), so one zeroed
         for s in range(0, Tlat, AR_CHUNK_TOK):                               # buffer per chunk width serves every chunk
             e = min(Tlat, s + AR_CHUNK_TOK)
@@ -311,6 +346,11 @@ class _ProposedBase(nn.Module):
             rD = self._pd(rN)                                                 # [1,96,B*n]
             if books is None:
                 qD = torch.zeros_like(rD)
+            elif rate is not None:      # the search's int32 indices go to the rate kernel as they are: the receiver's sum over the books sent
+                _, idx = ops.rvq_ema_forward(rD, books, books_use, return_indices="int32")
+                idx_all.append(idx.reshape(idx.shape[0], B, n))
+                qD = ops.rvq_rate(rD, idx, books, rate, packet_tok, books_use, folded_batch=B, nb_valid_out=nb_valid,
+                                  nb_sent_out=nb_sent, col=s)[0]
             elif want_indices:
                 qD, idx = ops.rvq_ema_forward(rD, books, books_use, return_indices=True)
                 idx_all.append(idx.reshape(idx.shape[0], B, n))
@@ -323,7 +363,8 @@ class _ProposedBase(nn.Module):
         if z_last_out is not None:
             ops.copy_strided_(z_last_out, 0, (C, 1), z_run, Tlat - 1, (C * Tlat, Tlat), B, C, 1)
         if want_indices:
-            return z_run, r_tokens, torch.cat(idx_all, dim=2) if idx_all else torch.zeros(0, B, Tlat, dtype=torch.int64)
+            idx = torch.cat(idx_all, dim=2).long() if idx_all else torch.zeros(0, B, Tlat, dtype=torch.int64)
+            return (z_run, r_tokens, idx) if rate is None else (z_run, r_tokens, idx, nb_valid, nb_sent)
         return z_run, r_tokens
 
     # The loop as ONE persistent kernel (csrc/ar_fused.hip: eleven stages per chunk between grid-wide barriers), for up to this many
@@ -361,7 +402,7 @@ class _ProposedBase(nn.Module):
                 and (books is None or (books.shape[1] <= 512 and books.shape[2] == CODE_DIM)))
 
     def _ar_latents_fused(self, zt, z_run, r_tokens, kv_all, t_audio, books, books_use, tactile_only, want_indices, staged=False,
-                          z_prev=None, z_last_out=None):
+                          z_prev=None, z_last_out=None, rate=None):
         B, _, Tlat = zt.shape
         p, L, ln = self.predict, self.predict._lin, self.tokennorm.ln
         nb = 0 if books is None else (books.shape[0] if books_use is None else max(0, min(int(books_use), books.shape[0])))
@@ -374,7 +415,9 @@ class _ProposedBase(nn.Module):
             w3=L["f3"].wp(), b3=det(p.ffn[3].bias), ln_eps=p.ln_q.eps, tok=(det(ln.weight), det(ln.bias)), tok_eps=ln.eps,
             scale=self._scale_value(), wd=self._pd.wp(), bd=det(self.proj_down.bias), wu=self._pu.wp(), bu=det(self.proj_up.bias),
             books=books, books_use=books_use, heads=p.h, c_ff=p.ffn[1].out_features, code_dim=CODE_DIM, r_tokens=r_tokens, idx_out=idx,
-            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged, z_prev=z_prev, z_last_out=z_last_out)
+            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged, z_prev=z_prev, z_last_out=z_last_out, rate=rate)
+        if rate is not None:
+            return z_run, r_tokens, idx.long(), rate[5], rate[6]
         if want_indices:
             return z_run, r_tokens, idx.long()
         return z_run, r_tokens
@@ -414,10 +457,22 @@ class _ProposedBase(nn.Module):
         return qa, zt
 
     @torch.no_grad()
-    def encode_latents_with_indices(self, a_1T, t_1T, books_use=None):
-        """encode_latents plus what a transmitter would send: -> (z_run, audio codes[B,32,Ta] of A_QUANT, RVQ idx[n_books_use,B,Tlat])."""
+    def encode_latents_with_indices(self, a_1T, t_1T, books_use=None, rate=None, packet_tok=None):
+        """encode_latents plus what a transmitter would send: -> (z_run, audio codes[B,32,Ta] of A_QUANT, RVQ idx[n_books_use,B,Tlat]).
+
+        ``rate`` (packets.Rate; packets of ``packet_tok`` tokens, default packets.PACKET_TOK): closed-loop sender rate control
+        (_ar_latents) -> (z_run, codes, idx, nb_sent uint8 [B, P]): packet p of item b carries the first nb_sent[b, p] books of
+        its tokens' rows of idx, and z_run is bit for bit what decode_latents(codes, idx, nb_valid=<nb_sent per token>) gives: the
+        loop runs on the books sent and on qa = A_QUANT.from_codes(codes), the receiver's audio latent, not the straight-through
+        one."""
+        if rate is not None:
+            self._rate_resolve(rate, books_use, packet_tok)                   # refusals before any launch
         za = self.A_ENC(a_1T)
         qa, codes, *_ = self.A_QUANT(za)
+        if rate is not None:
+            z_run, _, idx, _, nb_sent = self._ar_latents(self.A_QUANT.from_codes(codes)[0], self.T_ENC(t_1T), books_use, rate=rate,
+                                                         packet_tok=packet_tok)
+            return z_run, codes, idx, nb_sent
         z_run, _, idx = self._ar_latents(qa, self.T_ENC(t_1T), books_use, want_indices=True)
         return z_run, codes, idx
 
@@ -684,20 +739,35 @@ class ProposedEval(_ProposedBase):
         return self.decode(codes_t, idx_t, books_use=books_use)
 
     @torch.no_grad()
-    def compress_packets(self, a_1T, t_1T, books_use=None, packet_tok=None):
+    def compress_packets(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None):
         """-> (infos, tactile_packets, audio_payloads) for a lossy channel: per item the session parameters
         packets.StreamInfo(K, nb, T_lat, packet_tok) (sent reliably out of band), the list of framed packets (``bytes``, packets.py)
         of its RVQ indices, and the audio codes as a v1 payload (the audio stream is assumed delivered, as the reference's PLC
-        model does).  The packet bodies of the batch are packed on the device and come back in one device->host copy."""
+        model does).  The packet bodies of the batch are packed on the device and come back in one device->host copy.
+
+        ``rate`` (packets.Rate): the sender chooses each packet's book count on the device, closed loop
+        (encode_latents_with_indices); the counts ride back behind the bodies in the same copy and every packet is cut to its
+        count (packets.frame).  StreamInfo.nb stays the books in use; decompress_packets needs no change and returns
+        T_DEC(the sender's z_run) exactly."""
         from . import bitstream, packets
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
-        _, codes, idx = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use)
+        nb_sent = None
+        if rate is None:
+            _, codes, idx = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use)
+        else:
+            _, codes, idx, nb_sent = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use, rate=rate, packet_tok=packet_tok)
         nb, B, T = idx.shape
         info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
-        bodies = ops.idx_pack_packets(idx, info.K, packet_tok).cpu().numpy()
+        bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
+        if nb_sent is None:
+            bodies, counts = bodies.cpu().numpy(), [None] * B
+        else:
+            full = bodies.shape[2]
+            host = torch.cat([bodies.reshape(B, info.P * full), nb_sent], dim=1).cpu().numpy()
+            bodies, counts = host[:, :info.P * full].reshape(B, info.P, full), host[:, info.P * full:]
         codes = codes.cpu().numpy()
         k_audio = self.A_QUANT.codebook_size
-        return ([info] * B, [packets.frame(bodies[b], info) for b in range(B)],
+        return ([info] * B, [packets.frame(bodies[b], info, nb_sent=counts[b]) for b in range(B)],
                 [bitstream.pack_indices(codes[b], k_audio) for b in range(B)])
 
     @torch.no_grad()
@@ -745,12 +815,12 @@ class ProposedEval(_ProposedBase):
         return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
                                   out_rate=out_rate)
 
-    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False):
+    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None):
         """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
         get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output
-        equals compress_packets on the whole item byte for byte."""
+        equals compress_packets on the whole item byte for byte (with ``rate``, a packets.Rate: compress_packets(rate=))."""
         from .stream import StreamSender
-        return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph)
+        return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate)
 
     def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None):
         """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,

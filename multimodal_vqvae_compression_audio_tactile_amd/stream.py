@@ -302,7 +302,7 @@ class _SenderCore:
     = (slots, slots_dev), the host list of a group's slots and its int32 device copy, on those sessions of a pool: the carried
     tokens go through a dense [G, C] copy (ops.stream_rows), everything else is the same launches on the group's window."""
 
-    def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape):
+    def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape, rate=None):
         import torch
         from . import proposed
         from .packets import StreamInfo, body_bytes, _check
@@ -320,6 +320,9 @@ class _SenderCore:
         self.nb = int(net.vq.n_books) if books_use is None else max(0, min(int(books_use), int(net.vq.n_books)))
         _check(StreamInfo(self.K, self.nb, CHUNK_TOK, packet_tok))
         self.net, self.packet_tok, self.books_use = net, packet_tok, books_use
+        if rate is not None:
+            net._rate_resolve(rate, books_use, packet_tok)                             # ValueError before any session state exists
+        self.rate = rate
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
         self.full = body_bytes(packet_tok, self.nb, self.K)
@@ -354,10 +357,20 @@ class _SenderCore:
 
     def _encode(self, win, lo, hi, sl=None):
         """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
-        uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place."""
+        uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place.  With ``self.rate`` the loop
+        runs closed (on the books each packet carries and on qa from the codes, as the receiver will) and the bodies come back as
+        uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back."""
+        import torch
         from . import ops
         qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
+        if self.rate is not None:
+            assert sl is None                                                          # the pools take no rate
+            qa = self.net.A_QUANT.from_codes(codes)[0]
+            _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
+                                                         packet_tok=self.packet_tok)
+            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
+            return torch.cat([bodies.reshape(bodies.shape[0], -1), nb_sent], dim=1), codes
         _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=carry, z_last_out=carry)
         if sl is not None:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
@@ -384,11 +397,15 @@ class StreamSender(_SenderCore):
     ``graph=True``: the steady step (a push of exactly 16 tokens that completes a chunk after the first: the 32-token window) is
     captured once as a graph, at the buffer fill it first occurs with, and replayed after the host has written the samples into
     the static input buffer whenever a push has that shape again -- with 16-token pushes the fill before every push is the same
-    (16 tokens when the first push was 8, 24 when every push was 16).  Everything else runs eagerly."""
+    (16 tokens when the first push was 8, 24 when every push was 16).  Everything else runs eagerly.
 
-    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False):
+    ``rate`` (packets.Rate): closed-loop sender rate control, the session's output then equals compress_packets(rate=).  The book
+    count of each packet is decided on the device and comes back behind the bodies in the push's one read-back; it never reaches
+    the host before that, so the captured steady step replays with other decisions."""
+
+    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None):
         packet_tok, batch = int(packet_tok), int(batch)
-        super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP))   # audio rows, then tactile rows
+        super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP), rate=rate)   # audio rows, then tactile rows
         self.batch, self.graph = batch, bool(graph)
         self.fill = 0                                                                  # valid samples of every buffer row
         self.start = 0                                                                 # the token buf[:, 0] belongs to
@@ -425,7 +442,10 @@ class StreamSender(_SenderCore):
         info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
         host = bodies.cpu().numpy()
         base = self.chunk * CHUNK_TOK // self.packet_tok
-        return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
+        if self.rate is None:
+            return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
+        cut = host.shape[1] - info.P                                                   # bodies, then the book count of each packet
+        return [frame(host[b, :cut], info, nb_sent=host[b, cut:], seq_base=base) for b in range(self.batch)], codes
 
     def _nothing(self):
         import torch
