@@ -43,7 +43,8 @@ extern "C" {
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
- * mvq_ar_latents_staged_rate_f32).
+ * mvq_ar_latents_staged_rate_f32; audio transport: mvq_dac_rvq_from_codes_layers_f32, mvq_dac_rvq_rate_f32,
+ * mvq_dac_rvq_rate_workspace_bytes).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -271,6 +272,42 @@ int mvq_rvq_rate_f32(const float* z, size_t z_sb, size_t z_sd, const int32_t* id
                      const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
                      uint8_t* nb_sent, size_t nbs_sb, float* energy, int batch, int dim, int t, int nb_use, int k,
                      int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget, void* stream);
+
+/* Audio transport (additive, same ABI version; no reference counterpart).  The DAC quantiser is a residual VQ, so the first m stages
+ * of a token's codes are a valid lower-rate code: the audio codes travel in the layered packets of the tactile stream
+ * (mvq_idx_pack_packets_u8 with the codes[B,nq,T] strides) and the receiver sums what arrived.
+ *
+ * mvq_dac_rvq_from_codes_f32 with a per-token stage count nq_valid[B*T] (uint8, token b*T+t): token (b, t) sums only its first
+ * min(nq_use, nq_valid[b*T+t]) stages, in mvq_dac_rvq_from_codes_f32's arithmetic (the same chain cut short); a count of 0 writes
+ * +0 for every channel, no bias.  Item b's code rows start at codes + b*codes_sb (0 = nq_use*t, contiguous; larger: the first
+ * nq_use rows of a taller tensor, read in place).  z_p (NULL = not written) holds the raw rows of all nq_use stages whatever the
+ * count.  nq_valid = NULL with contiguous codes IS mvq_dac_rvq_from_codes_f32 (the same launch); every code read is clamped to
+ * [0, K); every element of zq is written.  C % 64 == 0, nq_use <= 32, Dc = 8. */
+int mvq_dac_rvq_from_codes_layers_f32(const int64_t* codes, size_t codes_sb, const float* codebook, const float* out_w, const float* out_b,
+                                      const uint8_t* nq_valid, float* zq, float* z_p, int batch, int c, int t, int nq_use, int k, int dc,
+                                      void* stream);
+/* Closed-loop audio rate control: after the DAC quantiser has produced codes[B, >= na_use, T] for z[B,C,T] (the fp32 encoder output it
+ * quantised), the SENDER decides how many stages each audio packet carries and forms, from exactly those stages, the qa the receiver
+ * will form (mvq_dac_rvq_from_codes_layers_f32 on the counts this call writes).  Per token, with S_0(c) = +0 and
+ *   S_{m+1}(c) = S_m(c) + zq_m(c)   (from_codes's own running sum),   d_m(c) = z(c) - S_m(c),   p_m(c) = fl(d_m(c) * d_m(c)),
+ *   E_m = sum of p_m over the C channels, m = 0 .. na_use, every multiply and add a separate fp32 operation (no fma), in this
+ * FIXED order, a function of the channel alone (not of B, T, the grid or where the token sits):
+ *   t(s, g) = (((+0 + p(64s + g)) + p(64s + g + 16)) + p(64s + g + 32)) + p(64s + g + 48)     s = 0 .. C/64 - 1, g = 0 .. 15
+ *   P(s)    = (...((+0 + t(s, 0)) + t(s, 1)) + ...) + t(s, 15)
+ *   E_m     = (...((+0 + P(0)) + P(1)) + ...) + P(C/64 - 1).
+ * The decision is mvq_rvq_rate_f32's rule (one device function serves both), with books = stages, nb_use = na_use, group_tok = 16
+ * tokens from token 0 of each item (the last group may be shorter) and the same mode / min_books / tol2 / budget arguments.
+ * Writes EVERY element of qa_out[B,C,T], na_valid[B*T] (the count of the token's packet), na_sent[B, P = ceil(t / packet_tok)] and,
+ * unless NULL, energy[na_use + 1, B*T].  workspace: mvq_dac_rvq_rate_workspace_bytes(batch, c, t, na_use) bytes of device memory
+ * (the per-slab partial energies; written and read by this call only).  Three launches: partial energies over (16 tokens x 64
+ * channels) blocks, one block per (item, group) that adds the partials in slab order and decides, then the layered look-up.  No
+ * atomics.  Refused before any launch: C % 64 != 0, Dc != 8, na_use outside 1..32 (MVQ_EUNSUPPORTED / MVQ_EINVAL), packet_tok not a
+ * divisor of 16 and a rate outside mvq_rvq_rate_f32's ranges (MVQ_EINVAL). */
+size_t mvq_dac_rvq_rate_workspace_bytes(int batch, int c, int t, int na_use);
+int mvq_dac_rvq_rate_f32(const float* z, const int64_t* codes, size_t codes_sb, const float* codebook, const float* out_w,
+                         const float* out_b, float* qa_out, uint8_t* na_valid, uint8_t* na_sent, float* energy, float* workspace,
+                         size_t workspace_bytes, int batch, int c, int t, int na_use, int k, int dc, int packet_tok, int min_books,
+                         int mode, float tol2, int budget, void* stream);
 
 /* ---- predictor / glue primitives (CrossPredictor, TokenNorm, PosEnc1D) --------------------------- */
 

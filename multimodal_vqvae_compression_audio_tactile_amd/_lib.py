@@ -87,6 +87,9 @@ EXPORTS = {
     "mvq_rvq_dequant_layers_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_rvq_rate_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                  c_size_t, c_void_p, c_size_t, c_void_p] + [c_int] * 9 + [c_float, c_int, c_void_p]),
+    "mvq_dac_rvq_from_codes_layers_f32": (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    "mvq_dac_rvq_rate_workspace_bytes": (c_size_t, [c_int] * 4),
+    "mvq_dac_rvq_rate_f32": (c_int, [c_void_p, c_void_p, c_size_t] + [c_void_p] * 8 + [c_size_t] + [c_int] * 9 + [c_float, c_int, c_void_p]),
     "mvq_layernorm_c_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_float, c_int, c_float, c_void_p]),
     "mvq_attention_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_align_xcorr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -718,6 +718,27 @@ int mvq_dac_rvq_from_codes_f32(const int64_t* codes, const float* codebook, cons
     return e == hipSuccess ? MVQ_OK : hipfail(e, "dac_rvq_from_codes");
 }
 
+int mvq_dac_rvq_from_codes_layers_f32(const int64_t* codes, size_t codes_sb, const float* codebook, const float* out_w, const float* out_b,
+                                      const uint8_t* nq_valid, float* zq, float* z_p, int batch, int c, int t, int nq_use, int k, int dc,
+                                      void* stream)
+{
+    if (!nq_valid && (codes_sb == 0 || codes_sb == (size_t)(nq_use > 0 ? nq_use : 0) * (size_t)(t > 0 ? t : 0)))
+        return mvq_dac_rvq_from_codes_f32(codes, codebook, out_w, out_b, zq, z_p, batch, c, t, nq_use, k, dc, stream);
+    if (batch < 0 || t < 0 || c <= 0 || c % 64 != 0 || nq_use <= 0 || nq_use > 32 || k <= 0 || dc != 8)
+        return fail(MVQ_EINVAL, "dac_rvq_from_codes_layers: bad shape B=%d C=%d T=%d nq=%d K=%d Dc=%d (C %% 64 == 0, nq <= 32, Dc = 8)",
+                    batch, c, t, nq_use, k, dc);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!nq_valid) return fail(MVQ_EINVAL, "dac_rvq_from_codes_layers: strided codes need nq_valid");
+    if (!codes || !codebook || !out_w || !out_b || !zq) return fail(MVQ_EINVAL, "dac_rvq_from_codes_layers: null tensor");
+    if ((reinterpret_cast<uintptr_t>(codebook) | reinterpret_cast<uintptr_t>(out_w)) & 15)
+        return fail(MVQ_EINVAL, "dac_rvq_from_codes_layers: codebook and out_w must be 16-byte aligned");
+    if (codes_sb == 0) codes_sb = (size_t)nq_use * t;
+    if (codes_sb < (size_t)nq_use * t) return fail(MVQ_EINVAL, "dac_rvq_from_codes_layers: codes_sb is smaller than nq_use * T");
+    hipError_t e = mvq::launch_dac_rvq_from_codes_layers(codes, codes_sb, codebook, out_w, out_b, nq_valid, zq, z_p, batch, c, t, nq_use, k,
+                                                         dc, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "dac_rvq_from_codes_layers");
+}
+
 // ---- the lossy-channel receiver (kernels in packets.hip) ----
 namespace {
 // ceil(log2 K) when the packet kernels cover the shape (1..255 books and tokens per packet as the header holds them, at most 24

@@ -120,6 +120,9 @@ hipError_t launch_rvq_dequant(const int64_t* idx, const float* books, float* q, 
                               size_t out_sb, size_t out_sd, hipStream_t s);
 hipError_t launch_dac_rvq_from_codes(const int64_t* codes, const float* cb, const float* out_w, const float* out_b, float* zq,
                                      float* z_p, int B, int C, int T, int nq, int K, int Dc, hipStream_t s);
+hipError_t launch_dac_rvq_from_codes_layers(const int64_t* codes, size_t codes_sb, const float* cb, const float* out_w, const float* out_b,
+                                            const uint8_t* nq_valid, float* zq, float* z_p, int B, int C, int T, int nq, int K, int Dc,
+                                            hipStream_t s);
 // packets.hip: the lossy-channel receiver (bits = ceil(log2 K) <= 24, ptok >= 1)
 hipError_t launch_idx_pack_packets(const int64_t* idx, uint8_t* bodies, int B, int nb, int T, int K, int bits, int ptok,
                                    size_t s_book, size_t s_item, hipStream_t s);
@@ -128,7 +131,8 @@ hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_re
 hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
                                      int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
 // rate.hip: closed-loop sender rate control (mvq_rvq_rate_f32); rvq_rate_check returns an MVQ_* code, its text through set_last_error
-int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget);
+int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget,
+                   const char* who = "rvq_rate");     // ``who`` prefixes the message (the audio rate control passes its own name)
 hipError_t launch_rvq_rate(const float* z, size_t z_sb, size_t z_sd, const int32_t* idx, size_t idx_sbook, size_t idx_sitem,
                            const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
                            uint8_t* nb_sent, size_t nbs_sb, float* energy, int B, int D, int T, int nb, int K, int ptok, int gtok,

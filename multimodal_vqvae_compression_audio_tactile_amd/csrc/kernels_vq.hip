@@ -18,6 +18,7 @@
 #include <type_traits>
 #include "det_math.hpp"
 #include "kernels_small.hpp"
+#include "dac_stage.hpp"
 
 namespace mvq {
 
@@ -1271,11 +1272,16 @@ hipError_t launch_rvq_dequant(const int64_t* idx, const float* books, float* q, 
 // ([nq][FC_TOK][8], 16 KiB at 32 stages) are gathered into LDS once; then lane (token, channel group) runs the stages in order
 // for its four channels: zq_i = fma chain over the 8 code dims from +0, + out_b; z_q = ((0 + zq_0) + zq_1) + ...
 // Blocks of the first channel tile also write z_p (the raw rows, [B, nq*8, T]).
+// LAYERS (mvq_dac_rvq_from_codes_layers_f32): token n stops after its first min(nq, nq_valid[n]) stages -- the same chain cut
+// short, so a count of nq or more is the plain kernel's bits and a count of 0 leaves the +0 the chain starts from (no bias); item
+// b's code rows start at codes + b*codes_sb (the plain kernel: nq*T).  z_p still holds the raw rows of all nq stages.
 constexpr int FC_TOK = 16, FC_CH = 64, FC_DC = 8, FC_MAX_NQ = 32;
 
+template <bool LAYERS>
 __global__ __launch_bounds__(256) void dac_rvq_from_codes_kernel(
     const int64_t* __restrict__ codes, const float* __restrict__ cb, const float* __restrict__ out_w,
-    const float* __restrict__ out_b, float* __restrict__ zq, float* __restrict__ z_p, int B, int C, int T, int nq, int K)
+    const float* __restrict__ out_b, float* __restrict__ zq, float* __restrict__ z_p, int B, int C, int T, int nq, int K,
+    const uint8_t* __restrict__ nq_valid, size_t codes_sb)
 {
     typedef float v4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float p_s[FC_MAX_NQ][FC_TOK][FC_DC];
@@ -1289,7 +1295,7 @@ __global__ __launch_bounds__(256) void dac_rvq_from_codes_kernel(
         v4 r = {0.0f, 0.0f, 0.0f, 0.0f};
         if (n < N) {
             const int b = (int)(n / T), t = (int)(n % T);
-            const int id = clamp_code(codes[((size_t)b * nq + st) * T + t], K);
+            const int id = clamp_code(LAYERS ? codes[(size_t)b * codes_sb + (size_t)st * T + t] : codes[((size_t)b * nq + st) * T + t], K);
             r = *reinterpret_cast<const v4*>(cb + ((size_t)st * K + id) * FC_DC + 4 * h);
             if (write_zp) {
                 float* o = z_p + ((size_t)b * nq * FC_DC + (size_t)st * FC_DC + 4 * h) * T + t;
@@ -1305,21 +1311,11 @@ __global__ __launch_bounds__(256) void dac_rvq_from_codes_kernel(
     const int b = (int)(n / T), t = (int)(n % T);
     const int c0 = blockIdx.y * FC_CH + cg;
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int st = 0; st < nq; ++st) {
+    const int ns = LAYERS ? min(nq, (int)nq_valid[n]) : nq;
+    for (int st = 0; st < ns; ++st) {
         const v4 pa = *reinterpret_cast<const v4*>(&p_s[st][tk][0]);
         const v4 pb = *reinterpret_cast<const v4*>(&p_s[st][tk][4]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = c0 + 16 * u;
-            const float* wr = out_w + ((size_t)st * C + c) * FC_DC;
-            const v4 wa = *reinterpret_cast<const v4*>(wr);
-            const v4 wb = *reinterpret_cast<const v4*>(wr + 4);
-            float a = 0.0f;
-            a = dfma(wa.x, pa.x, a); a = dfma(wa.y, pa.y, a); a = dfma(wa.z, pa.z, a); a = dfma(wa.w, pa.w, a);
-            a = dfma(wb.x, pb.x, a); a = dfma(wb.y, pb.y, a); a = dfma(wb.z, pb.z, a); a = dfma(wb.w, pb.w, a);
-            const float zqi = a + out_b[(size_t)st * C + c];
-            acc[u] = acc[u] + zqi;
-        }
+        dac_stage_accumulate(acc, pa, pb, out_w, out_b, st, C, c0);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) zq[((size_t)b * C + c0 + 16 * u) * T + t] = acc[u];
@@ -1331,8 +1327,24 @@ hipError_t launch_dac_rvq_from_codes(const int64_t* codes, const float* cb, cons
     const size_t N = (size_t)B * T;
     if (N == 0) return hipSuccess;
     if (Dc != FC_DC || C % FC_CH || nq <= 0 || nq > FC_MAX_NQ) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dac_rvq_from_codes_kernel, dim3((unsigned)((N + FC_TOK - 1) / FC_TOK), (unsigned)(C / FC_CH)), dim3(256), 0, s,
-                       codes, cb, out_w, out_b, zq, z_p, B, C, T, nq, K);
+    hipLaunchKernelGGL(dac_rvq_from_codes_kernel<false>, dim3((unsigned)((N + FC_TOK - 1) / FC_TOK), (unsigned)(C / FC_CH)), dim3(256), 0, s,
+                       codes, cb, out_w, out_b, zq, z_p, B, C, T, nq, K, (const uint8_t*)nullptr, (size_t)0);
+    return hipGetLastError();
+}
+
+hipError_t launch_dac_rvq_from_codes_layers(const int64_t* codes, size_t codes_sb, const float* cb, const float* out_w, const float* out_b,
+                                            const uint8_t* nq_valid, float* zq, float* z_p, int B, int C, int T, int nq, int K, int Dc,
+                                            hipStream_t s)
+{
+    const size_t N = (size_t)B * T;
+    if (N == 0) return hipSuccess;
+    if (Dc != FC_DC || C % FC_CH || nq <= 0 || nq > FC_MAX_NQ || !nq_valid || codes_sb < (size_t)nq * T) return hipErrorInvalidValue;
+    const size_t tiles = (N + FC_TOK - 1) / FC_TOK;
+    if (tiles > 0x7fffffffULL) return hipErrorInvalidValue;
+    const int pi = prof_enabled() ? prof_begin("dac_rvq_from_codes_layers_kernel", (double)N * C * nq * 18.0, s) : -1;
+    hipLaunchKernelGGL(dac_rvq_from_codes_kernel<true>, dim3((unsigned)tiles, (unsigned)(C / FC_CH)), dim3(256), 0, s,
+                       codes, cb, out_w, out_b, zq, z_p, B, C, T, nq, K, nq_valid, codes_sb);
+    prof_end(pi, s);
     return hipGetLastError();
 }
 

@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include "../../include/mvq.h"
 #include "kernels_small.hpp"
+#include "rate_decide.hpp"
 
 namespace mvq {
 void set_last_error(const char* msg);
@@ -27,8 +28,6 @@ void set_last_error(const char* msg);
 namespace {
 
 constexpr int RATE_THR = 256;
-constexpr int RATE_GROUP_MAX = 16;          // tokens of a group (and so packets of a group)
-constexpr int RATE_NB_MAX = 32;
 constexpr size_t RATE_LDS_BUDGET = 64 * 1024;
 
 struct RateArgs {
@@ -101,49 +100,10 @@ __global__ __launch_bounds__(RATE_THR) void rvq_rate_kernel(const RateArgs a)
         __syncthreads();
     }
 
-    // ---- phase 2: the decision (first wave; lane p = packet p of the group)
+    // ---- phase 2: the decision (first wave; lane p = packet p of the group; the rule itself: rate_decide.hpp)
     if (tid < 64) {
         const int lane = tid;
-        const int pt0 = lane * a.ptok;                                     // first token of this lane's packet
-        const int pnt = lane < npk ? min(a.ptok, ntok - pt0) : 0;
-        int m = nb < a.min_books ? nb : a.min_books;                       // nb == 0: counts of 0
-        if (a.mode == MVQ_RATE_FULL) {
-            m = nb;
-        } else if (a.mode == MVQ_RATE_TOL2) {
-            int need_max = m;
-            for (int jt = 0; jt < pnt; ++jt) {
-                const int i = pt0 + jt;
-                const float thr = a.tol2 * Es[i];
-                int need = nb;
-                for (int mm = nb - 1; mm >= m; --mm)                       // the smallest mm with E_mm <= thr (a NaN comparison is false)
-                    if (Es[mm * RATE_GROUP_MAX + i] <= thr) need = mm;
-                need_max = need > need_max ? need : need_max;
-            }
-            m = need_max;
-        } else if (nb > 0) {                                               // MVQ_RATE_BUDGET
-            auto gain = [&](int mm) {
-                float s = 0.0f;
-                for (int jt = 0; jt < pnt; ++jt)
-                    s = s + (Es[mm * RATE_GROUP_MAX + pt0 + jt] - Es[(mm + 1) * RATE_GROUP_MAX + pt0 + jt]);
-                return s;
-            };
-            const int share = (int)(((long long)a.budget * npk) / pc);
-            int left = (share > npk * m ? share : npk * m) - npk * m;
-            float gn = (lane < npk && m < nb) ? gain(m) : 0.0f;
-            while (left > 0) {
-                int win = -1;
-                float gw = 0.0f;
-#pragma unroll
-                for (int p = 0; p < RATE_GROUP_MAX; ++p) {
-                    const int mp = __builtin_amdgcn_readlane(m, p);
-                    const float gp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gn), p));
-                    if (p < npk && mp < nb && (win < 0 || gp > gw)) { win = p; gw = gp; }
-                }
-                if (win < 0) break;                                        // every packet has all books
-                if (lane == win) { m += 1; gn = m < nb ? gain(m) : 0.0f; }
-                left -= 1;
-            }
-        }
+        const int m = rate_decide(Es, lane, nb, ntok, npk, pc, a.ptok, a.min_books, a.mode, a.tol2, a.budget);
         if (lane < npk) {
             cnt[lane] = m;
             a.nb_sent[(size_t)b * a.s_sb + (size_t)(g * pc + lane)] = (uint8_t)m;
@@ -174,11 +134,11 @@ __global__ __launch_bounds__(RATE_THR) void rvq_rate_kernel(const RateArgs a)
 
 // The argument rules of the rate decision, shared by mvq_rvq_rate_f32 and mvq_ar_latents_staged_rate_f32; MVQ_OK or the code, the
 // text through set_last_error.  Nothing is launched.
-int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget)
+int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget, const char* who)
 {
     static thread_local char msg[256];
     auto fail = [&](int code, const char* why) {
-        snprintf(msg, sizeof(msg), "rvq_rate: %s (D=%d nb=%d K=%d packet_tok=%d group_tok=%d min_books=%d mode=%d tol2=%g budget=%d)", why, dim,
+        snprintf(msg, sizeof(msg), "%s: %s (D=%d nb=%d K=%d packet_tok=%d group_tok=%d min_books=%d mode=%d tol2=%g budget=%d)", who, why, dim,
                  nb_use, k, packet_tok, group_tok, min_books, mode, (double)tol2, budget);
         set_last_error(msg);
         return code;

@@ -660,14 +660,23 @@ class ResidualVectorQuantize(nn.Module):
 
 
     @torch.no_grad()
-    def from_codes(self, codes):
+    def from_codes(self, codes, *, nq_valid=None):
         """upstream ``ResidualVectorQuantize.from_codes``: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T], codes).
-        z_p holds the raw codebook rows, z_q the sum of out_proj_i(z_p_i) in stage order (mvq_dac_rvq_from_codes_f32)."""
+        z_p holds the raw codebook rows, z_q the sum of out_proj_i(z_p_i) in stage order (mvq_dac_rvq_from_codes_f32).
+        ``nq_valid`` (uint8 [B, T] on the device): token (b, t) sums only its first nq_valid[b, t] stages -- what arrived of a
+        layered audio stream; 0 gives a zero vector (mvq_dac_rvq_from_codes_layers_f32).  None: today's launch."""
         _, _, cb, out_w, out_b, _ = self._weights()
         if codes.dim() != 3 or codes.shape[1] > self.n_codebooks:
             raise MvqError(f"from_codes: codes must be [B, nq <= {self.n_codebooks}, T], got {tuple(codes.shape)}")
-        z_q, z_p = ops.dac_rvq_from_codes(codes.to(cb.device), cb, out_w, out_b)
+        z_q, z_p = ops.dac_rvq_from_codes(codes.to(cb.device), cb, out_w, out_b, nq_valid=nq_valid)
         return z_q, z_p, codes
+
+    @torch.no_grad()
+    def rate(self, z, codes, rate, packet_tok, na_use=None):
+        """Closed-loop audio rate control (ops.dac_rvq_rate): ``z`` the encoder output this quantiser searched, ``codes`` what it
+        returned -> (qa as from_codes(codes, nq_valid=na_valid) gives it, na_valid uint8 [B, T], na_sent uint8 [B, P])."""
+        _, _, cb, out_w, out_b, _ = self._weights()
+        return ops.dac_rvq_rate(z, codes.to(cb.device), cb, out_w, out_b, rate, packet_tok, na_use=na_use)
 
 
 class DAC(nn.Module):

@@ -493,11 +493,11 @@ def rvq_dequant(idx, books, n_books_use=None, out=None, out_strides=None):
     return out
 
 
-def _nb_valid_u8(nb_valid, B, T, device, name):
+def _nb_valid_u8(nb_valid, B, T, device, name, arg="nb_valid", of="idx"):
     if not isinstance(nb_valid, torch.Tensor) or nb_valid.device != device:
-        raise MvqError(f"{name}: nb_valid must be a tensor on the device of idx")
+        raise MvqError(f"{name}: {arg} must be a tensor on the device of {of}")
     if nb_valid.dtype != torch.uint8 or tuple(nb_valid.shape) != (B, T):
-        raise MvqError(f"{name}: nb_valid must be uint8 [B={B}, T={T}], got {nb_valid.dtype} {tuple(nb_valid.shape)}")
+        raise MvqError(f"{name}: {arg} must be uint8 [B={B}, T={T}], got {nb_valid.dtype} {tuple(nb_valid.shape)}")
     return nb_valid.contiguous()
 
 
@@ -635,9 +635,12 @@ def idx_unpack_packets(bodies, nb_recv, k, nb, T, packet_tok):
     return idx, nb_valid
 
 
-def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True):
+def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True, nq_valid=None):
     """upstream ResidualVectorQuantize.from_codes: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T] or None).
-    z_q = sum over stages of out_proj_i(codebook_i[code_i]) in stage order; the first nq stages of the stacked weights."""
+    z_q = sum over stages of out_proj_i(codebook_i[code_i]) in stage order; the first nq stages of the stacked weights.
+    ``nq_valid`` (uint8 [B, T] on the device; None = every stage, today's launch): token (b, t) sums only its first
+    min(nq, nq_valid[b, t]) stages -- what arrived of a layered audio packet; 0 gives +0 in every channel
+    (mvq_dac_rvq_from_codes_layers_f32).  z_p holds the raw rows of all nq stages either way."""
     codes = _codes_i64(codes, "codes"); codebook = _dev(codebook, "codebook")
     out_w = _dev(out_w, "out_w"); out_b = _dev(out_b, "out_b")
     if codes.dim() != 3 or codebook.dim() != 3 or out_w.dim() != 3 or out_b.dim() != 2:
@@ -657,9 +660,59 @@ def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True):
     if nq == 0:
         zq.zero_()
         return zq, z_p
+    if nq_valid is not None:
+        nqv = _nb_valid_u8(nq_valid, B, T, codes.device, "dac_rvq_from_codes", arg="nq_valid", of="codes")
+        check(_lib.lib().mvq_dac_rvq_from_codes_layers_f32(codes.data_ptr(), nq * T, codebook.data_ptr(), out_w.data_ptr(),
+                                                           out_b.data_ptr(), nqv.data_ptr(), zq.data_ptr(), _p(z_p), B, C, T, nq, K, Dc,
+                                                           _stream()), "mvq_dac_rvq_from_codes_layers_f32")
+        return zq, z_p
     check(_lib.lib().mvq_dac_rvq_from_codes_f32(codes.data_ptr(), codebook.data_ptr(), out_w.data_ptr(), out_b.data_ptr(),
                                                 zq.data_ptr(), _p(z_p), B, C, T, nq, K, Dc, _stream()), "mvq_dac_rvq_from_codes_f32")
     return zq, z_p
+
+
+def dac_rvq_rate(z, codes, codebook, out_w, out_b, rate, packet_tok, na_use=None, want_energy=False):
+    """Closed-loop audio rate control on the DAC quantiser's result (mvq_dac_rvq_rate_f32): decide how many stages each audio packet
+    carries and sum exactly those, in the receiver's arithmetic (dac_rvq_from_codes(nq_valid=)).  z[B, C, T] fp32 (the encoder
+    output the quantiser searched), codes[B, nq, T] int64 of dac_rvq on that z (the first ``na_use`` rows are read in place),
+    the stacked weights as dac_rvq_from_codes takes them; ``rate`` a packets.Rate.  Groups of 16 tokens start at token 0 of each
+    item.  -> (qa [B, C, T], na_valid uint8 [B, T], na_sent uint8 [B, P]) and energy fp32 [na_use + 1, B*T] with ``want_energy``."""
+    from .packets import Rate
+    if not isinstance(rate, Rate):
+        raise ValueError(f"dac_rvq_rate: rate must be a packets.Rate, not {type(rate).__name__}")
+    z = _dev(z, "z"); codes = _codes_i64(codes, "codes"); codebook = _dev(codebook, "codebook")
+    out_w = _dev(out_w, "out_w"); out_b = _dev(out_b, "out_b")
+    if z.dim() != 3 or codes.dim() != 3 or codebook.dim() != 3 or out_w.dim() != 3 or out_b.dim() != 2:
+        raise MvqError("dac_rvq_rate: z [B,C,T], codes [B,nq,T], codebook [nq,K,Dc], out_w [nq,C,Dc], out_b [nq,C] expected")
+    if len({z.device, codes.device, codebook.device, out_w.device, out_b.device}) != 1:
+        raise MvqError("dac_rvq_rate: all tensors must be on one device")
+    B, C, T = z.shape
+    _, K, Dc = codebook.shape
+    stages = min(codes.shape[1], codebook.shape[0], out_w.shape[0], out_b.shape[0])
+    na = stages if na_use is None else int(na_use)
+    if codes.shape[0] != B or codes.shape[2] != T or out_w.shape[1] != C or out_w.shape[2] != Dc or out_b.shape[1] != C:
+        raise MvqError(f"dac_rvq_rate: z {tuple(z.shape)}, codes {tuple(codes.shape)}, out_w {tuple(out_w.shape)}, out_b "
+                       f"{tuple(out_b.shape)} do not describe one [B, C, T] with Dc={Dc}")
+    if not 1 <= na <= stages:
+        raise MvqError(f"dac_rvq_rate: na_use = {na} outside 1..{stages} (the stages the codes and weights have)")
+    if C % 64 or Dc != 8 or na > 32:
+        raise MvqError(f"dac_rvq_rate: C={C}, Dc={Dc}, na_use={na} outside the kernels (C % 64 == 0, Dc = 8, na_use <= 32)")
+    packet_tok = int(packet_tok)
+    min_books, mode, tol2, budget = rate.resolve(na, packet_tok, 16)
+    P = (T + packet_tok - 1) // packet_tok
+    dev = z.device
+    qa = torch.empty(B, C, T, device=dev, dtype=torch.float32)
+    na_valid = torch.empty(B, T, device=dev, dtype=torch.uint8)
+    na_sent = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    energy = torch.empty(na + 1, B * T, device=dev, dtype=torch.float32) if want_energy else None
+    if B and T:
+        nbytes = _lib.lib().mvq_dac_rvq_rate_workspace_bytes(B, C, T, na)
+        work = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        check(_lib.lib().mvq_dac_rvq_rate_f32(z.data_ptr(), codes.data_ptr(), codes.shape[1] * T, codebook.data_ptr(), out_w.data_ptr(),
+                                              out_b.data_ptr(), qa.data_ptr(), na_valid.data_ptr(), na_sent.data_ptr(), _p(energy),
+                                              work.data_ptr(), work.numel() * 4, B, C, T, na, K, Dc, packet_tok, min_books, mode, tol2,
+                                              budget, _stream()), "mvq_dac_rvq_rate_f32")
+    return (qa, na_valid, na_sent, energy) if want_energy else (qa, na_valid, na_sent)
 
 
 def layernorm_c(x, gamma, beta, pe=None, eps=1e-5, do_tanh=False, post_scale=1.0, folded_batch=None, sub=None):

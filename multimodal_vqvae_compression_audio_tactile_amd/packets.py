@@ -19,6 +19,11 @@ K = 512 x 2 tokens a body is 18 bytes.
 ``pack_bodies`` / ``unpack_bodies`` are the definition of the body layout; the device kernels (ops.idx_pack_packets /
 ops.idx_unpack_packets) equal them bit for bit.  Bodies of one item form a regular array uint8[P, body_bytes(packet_tok, nb, K)]:
 the shorter tail packet and every thinned packet are zero-padded to the full width.
+
+The AUDIO codes travel in the same format (ProposedEval.compress_packets_av): StreamInfo(K = the DAC codebook size, nb = the stages
+carried, T = the audio tokens, packet_tok), "books" being the stages of the DAC residual VQ, whose first m are a valid lower-rate
+code.  Both streams share the magic ``MP`` and are told apart by the list they travel in; the format and ``VERSION`` do not change
+(there is no stream-kind field).
 """
 from __future__ import annotations
 

@@ -259,6 +259,26 @@ class _ProposedBase(nn.Module):
         nb_use = n_books if books_use is None else max(0, min(int(books_use), n_books))
         return packet_tok, rate.resolve(nb_use, packet_tok, AR_CHUNK_TOK)
 
+    def _audio_rate_resolve(self, audio_rate, audio_books, packet_tok):
+        """The refusals of audio rate control, before any launch -> (audio_rate, na_use, packet_tok)."""
+        from . import packets
+        audio_rate = packets.Rate() if audio_rate is None else audio_rate
+        if not isinstance(audio_rate, packets.Rate):
+            raise ValueError(f"audio_rate must be a packets.Rate, not {type(audio_rate).__name__}")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"audio rate control claims bit-equality with the receiver; arithmetic mode {ops.get_arith()!r} makes no "
+                             "parity claim")
+        stages = self.A_QUANT.n_codebooks
+        if audio_books is None:
+            na_use = stages
+        else:
+            if isinstance(audio_books, bool) or int(audio_books) != audio_books or not 1 <= int(audio_books) <= stages:
+                raise ValueError(f"audio_books = {audio_books!r} outside 1..{stages} (the quantiser's stages)")
+            na_use = int(audio_books)
+        packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
+        audio_rate.resolve(na_use, packet_tok, AR_CHUNK_TOK)
+        return audio_rate, na_use, packet_tok
+
     @torch.no_grad()
     def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False, z_prev=None,
                     z_last_out=None, rate=None, packet_tok=None):
@@ -457,18 +477,35 @@ class _ProposedBase(nn.Module):
         return qa, zt
 
     @torch.no_grad()
-    def encode_latents_with_indices(self, a_1T, t_1T, books_use=None, rate=None, packet_tok=None):
+    def encode_latents_with_indices(self, a_1T, t_1T, books_use=None, rate=None, packet_tok=None, audio_books=None, audio_rate=None):
         """encode_latents plus what a transmitter would send: -> (z_run, audio codes[B,32,Ta] of A_QUANT, RVQ idx[n_books_use,B,Tlat]).
 
         ``rate`` (packets.Rate; packets of ``packet_tok`` tokens, default packets.PACKET_TOK): closed-loop sender rate control
         (_ar_latents) -> (z_run, codes, idx, nb_sent uint8 [B, P]): packet p of item b carries the first nb_sent[b, p] books of
         its tokens' rows of idx, and z_run is bit for bit what decode_latents(codes, idx, nb_valid=<nb_sent per token>) gives: the
         loop runs on the books sent and on qa = A_QUANT.from_codes(codes), the receiver's audio latent, not the straight-through
-        one."""
+        one.
+
+        ``audio_books`` (1..32: the stages of A_QUANT the audio stream carries, default all) / ``audio_rate`` (packets.Rate, default
+        Rate(): every packet carries ``audio_books`` stages): the audio codes travel in layered packets too.  When either is
+        given the loop runs closed on BOTH streams (``rate`` None is Rate()): ops.dac_rvq_rate decides on the device how many stages
+        each audio packet carries and forms qa from exactly those, and the AR loop runs on that qa.
+        -> (z_run, codes, idx, nb_sent uint8 [B, P], na_sent uint8 [B, Pa]): audio packet p of item b carries the first
+        na_sent[b, p] rows of its tokens' columns of codes (all 32 rows are returned as A_QUANT made them), and z_run is bit for bit
+        decode_latents(codes, idx, nb_valid=<nb_sent per token>, na_valid=<na_sent per token>)."""
+        audio = audio_books is not None or audio_rate is not None
+        if audio:
+            from . import packets
+            audio_rate, na_use, packet_tok = self._audio_rate_resolve(audio_rate, audio_books, packet_tok)
+            rate = packets.Rate() if rate is None else rate
         if rate is not None:
             self._rate_resolve(rate, books_use, packet_tok)                   # refusals before any launch
         za = self.A_ENC(a_1T)
         qa, codes, *_ = self.A_QUANT(za)
+        if audio:
+            qa_rx, _, na_sent = self.A_QUANT.rate(za, codes, audio_rate, packet_tok, na_use)
+            z_run, _, idx, _, nb_sent = self._ar_latents(qa_rx, self.T_ENC(t_1T), books_use, rate=rate, packet_tok=packet_tok)
+            return z_run, codes, idx, nb_sent, na_sent
         if rate is not None:
             z_run, _, idx, _, nb_sent = self._ar_latents(self.A_QUANT.from_codes(codes)[0], self.T_ENC(t_1T), books_use, rate=rate,
                                                          packet_tok=packet_tok)
@@ -479,7 +516,7 @@ class _ProposedBase(nn.Module):
     # ------------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
     def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
-                       conceal="predict", plc=None, z_prev=None, z_last_out=None):
+                       conceal="predict", plc=None, z_prev=None, z_last_out=None, na_valid=None):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -498,6 +535,13 @@ class _ProposedBase(nn.Module):
         where(lost, plc.predict(z_run * ~lost, qa), z_run) with ``plc`` an AllPredPLC.  The mask is never read on the host: the
         launch sequence depends on shapes and ``conceal`` only, so a captured graph replays with another loss pattern written
         into the same nb_valid buffer.
+
+        Lossy AUDIO stream: ``na_valid`` ([B, Ta] uint8 on the device: the stages of each audio token that arrived; bool: all or
+        none; None = all, today's path launch for launch).  qa = A_QUANT.from_codes(codes, nq_valid=na_valid): a token sums only
+        the stages it has, and an audio token of which NOTHING arrived is +0 in every channel -- the predictor attends over it as it
+        would over silence.  That is the unconcealed baseline; audio concealment (a key mask, holding the last token) is not built.
+        ``conceal`` acts on the tactile tokens only; "plc" is handed the same qa.  Needs ``audio_codes`` (not ``qa``); never read
+        on the host.
 
         Streaming (stream.py): a chunk depends on the ones before it through z_run[..., s-1] alone, so a sequence is decoded
         piece by piece, each piece a whole number of 16-token chunks (the last may be shorter), with ``z_prev`` ([B, C] fp32 on the
@@ -551,8 +595,19 @@ class _ProposedBase(nn.Module):
             Ta = (audio_codes if qa is None else qa).shape[2]
             if conceal == "plc" and not 0 < Ta <= ops.ATTN_SEQ_MAX_T:
                 raise MvqError(f"decode_latents: conceal='plc' needs 1..{ops.ATTN_SEQ_MAX_T} audio tokens, got {Ta}")
+        if na_valid is not None:
+            if tactile_only or qa is not None:
+                raise MvqError("decode_latents: na_valid counts the stages of audio_codes; it goes with neither qa nor tactile_only")
+            if not isinstance(na_valid, torch.Tensor) or na_valid.dtype not in (torch.uint8, torch.bool):
+                raise MvqError("decode_latents: na_valid must be a uint8 or bool tensor [B, Ta]")
+            if tuple(na_valid.shape) != (B, audio_codes.shape[2]):
+                raise MvqError(f"decode_latents: na_valid {tuple(na_valid.shape)} does not match the codes' [B={B}, Ta={audio_codes.shape[2]}]")
         if B == 0 or Tlat == 0:
             return torch.zeros(B, C, Tlat, device=dev)
+        if na_valid is not None:
+            na_valid = na_valid.to(dev).contiguous()
+            if na_valid.dtype == torch.bool:                                  # all or none: 255 caps at the stages there are
+                na_valid = na_valid.view(torch.uint8) * 255
         if nb_valid is not None:
             nb_valid = nb_valid.to(dev).contiguous()
             if nb_valid.dtype == torch.bool:                                  # all or none: 255 caps at the books there are
@@ -561,7 +616,7 @@ class _ProposedBase(nn.Module):
             z_run = self._pu(self.vq.from_indices(idx, books_use, nb_valid=nb_valid))
             return z_run if conceal == "predict" else ops.plc_mask_fill(z_run, None, nb_valid == 0)[0]
         if qa is None:
-            qa = self.A_QUANT.from_codes(audio_codes.to(dev))[0]
+            qa = self.A_QUANT.from_codes(audio_codes.to(dev), nq_valid=na_valid)[0]
         qa = ops._dev(qa.to(dev), "qa")                                       # fp32, contiguous
         if qa.shape[0] != B or qa.shape[1] != C:
             raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
@@ -701,10 +756,11 @@ class ProposedEval(_ProposedBase):
 
     # ---------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
-    def decode(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None):
+    def decode(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None, na_valid=None):
         """Receiver: T_DEC(decode_latents(audio_codes, idx)) -- the waveform from the transmitted codes alone.  ``nb_valid`` /
-        ``conceal`` / ``plc``: the lossy-channel arguments of decode_latents."""
-        return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc))
+        ``conceal`` / ``plc`` / ``na_valid``: the lossy-channel arguments of decode_latents."""
+        return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc,
+                                              na_valid=na_valid))
 
     @torch.no_grad()
     def decode_latents_tactile_only(self, idx, books_use=None, nb_valid=None, conceal="predict"):
@@ -800,12 +856,83 @@ class ProposedEval(_ProposedBase):
         y = self.decode(codes_t, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc)
         return y, nb_valid == 0
 
-    def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False):
+    @torch.no_grad()
+    def compress_packets_av(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None, audio_books=None, audio_rate=None):
+        """compress_packets with the audio codes in layered packets too -> (infos, tactile_packets, audio_infos, audio_packets).
+        The audio stream uses the tactile stream's format unchanged: per item StreamInfo(K = A_QUANT.codebook_size,
+        nb = audio_books, Ta, packet_tok) and the framed packets of codes[b, :audio_books] (stage-major bodies: dropping the later
+        stages of an audio packet is a truncation).  One ``packet_tok`` serves both streams; they are told apart by the list they
+        travel in.  The sender runs closed on both streams (encode_latents_with_indices; ``rate`` / ``audio_rate`` None = every
+        packet whole).  Both sets of bodies are packed on the device and come back with both sets of counts in ONE device->host
+        copy; packets.frame cuts each packet to its count.  decompress_packets_av with nothing lost returns T_DEC(the sender's
+        z_run) exactly."""
+        from . import packets
+        audio_rate, na_use, packet_tok = self._audio_rate_resolve(audio_rate, audio_books, packet_tok)
+        _, codes, idx, nb_sent, na_sent = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use, rate=rate, packet_tok=packet_tok,
+                                                                           audio_books=na_use, audio_rate=audio_rate)
+        nb, B, T = idx.shape
+        info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
+        ainfo = packets.StreamInfo(self.A_QUANT.codebook_size, na_use, codes.shape[2], packet_tok)
+        bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
+        abodies = ops.idx_pack_packets(codes[:, :na_use], ainfo.K, packet_tok, book_dim=1)
+        full, afull = bodies.shape[2], abodies.shape[2]
+        cuts = np.cumsum([0, info.P * full, info.P, ainfo.P * afull, ainfo.P])
+        host = torch.cat([bodies.reshape(B, -1), nb_sent, abodies.reshape(B, -1), na_sent], dim=1).cpu().numpy()
+        hb, hc, ab, ac = (host[:, cuts[i]:cuts[i + 1]] for i in range(4))
+        hb, ab = hb.reshape(B, info.P, full), ab.reshape(B, ainfo.P, afull)
+        return ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b]) for b in range(B)],
+                [ainfo] * B, [packets.frame(ab[b], ainfo, nb_sent=ac[b]) for b in range(B)])
+
+    @torch.no_grad()
+    def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None):
+        """-> (y [B,1,T], lost [B,T_lat] bool, audio_lost [B,Ta] bool) from whatever packets of BOTH streams arrived (missing,
+        reordered, duplicated, thinned; items of one StreamInfo per stream): packets.gather per item and stream on the host, ONE
+        upload of both streams' bodies and per-packet counts, the bit unpacking of both on the device (the audio indices are
+        transposed to codes[B, nq, Ta] there), then decode(nb_valid=, na_valid=).  ``audio_lost``: the audio tokens no stage of
+        which arrived; they are +0 to the predictor (decode_latents)."""
+        from . import packets
+        if not (len(infos) == len(tactile_packets) == len(audio_infos) == len(audio_packets)):
+            raise MvqError("decompress_packets_av: one StreamInfo and one packet list per item and stream")
+        dev = self.proj_up.weight.device
+        B = len(infos)
+        if B == 0:
+            raise MvqError("decompress_packets_av: no items")
+        info, ainfo = packets.StreamInfo(*infos[0]), packets.StreamInfo(*audio_infos[0])
+        if any(tuple(i) != tuple(info) for i in infos) or any(tuple(i) != tuple(ainfo) for i in audio_infos):
+            raise ValueError("decompress_packets_av: the items of a batch must share one StreamInfo per stream")
+        if info.K != self.vq.n_embed:
+            raise ValueError(f"decompress_packets_av: the tactile stream has K = {info.K}, the model's codebook has {self.vq.n_embed}")
+        if ainfo.K != self.A_QUANT.codebook_size or not 1 <= ainfo.nb <= self.A_QUANT.n_codebooks:
+            raise ValueError(f"decompress_packets_av: the audio stream has K = {ainfo.K}, nb = {ainfo.nb}; the model's audio quantiser "
+                             f"has K = {self.A_QUANT.codebook_size} and {self.A_QUANT.n_codebooks} stages")
+        if ainfo.packet_tok != info.packet_tok:
+            raise ValueError(f"decompress_packets_av: one packet_tok serves both streams, got {info.packet_tok} and {ainfo.packet_tok}")
+        if ainfo.T != info.T:
+            raise ValueError(f"decompress_packets_av: the audio stream has T = {ainfo.T} tokens, the tactile stream {info.T}; the two "
+                             "modalities advance together")
+        P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
+        Pa, afull = ainfo.P, packets.body_bytes(ainfo.packet_tok, ainfo.nb, ainfo.K)
+        cuts = np.cumsum([0, B * P * full, B * P, B * Pa * afull, B * Pa])
+        host = np.empty(cuts[-1], np.uint8)                                   # both streams' bodies and counts: one upload
+        hb, hr, ab, ar = (host[cuts[i]:cuts[i + 1]] for i in range(4))
+        hb, hr, ab, ar = hb.reshape(B, P, full), hr.reshape(B, P), ab.reshape(B, Pa, afull), ar.reshape(B, Pa)
+        for b in range(B):
+            hb[b], hr[b] = packets.gather(tactile_packets[b], info)
+            ab[b], ar[b] = packets.gather(audio_packets[b], ainfo)
+        up = torch.from_numpy(host).to(dev)
+        ub, ur, uab, uar = (up[cuts[i]:cuts[i + 1]] for i in range(4))
+        idx, nb_valid = ops.idx_unpack_packets(ub.view(B, P, full), ur.view(B, P), info.K, info.nb, info.T, info.packet_tok)
+        aidx, na_valid = ops.idx_unpack_packets(uab.view(B, Pa, afull), uar.view(B, Pa), ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
+        codes = aidx.permute(1, 0, 2).contiguous()                            # [nq, B, Ta] -> [B, nq, Ta], on the device
+        y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid)
+        return y, nb_valid == 0, na_valid == 0
+
+    def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
         time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
-                              out_rate=out_rate, graph=graph)
+                              out_rate=out_rate, graph=graph, audio=audio)
 
     def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
         """A pool of up to ``slots`` independent receiver sessions on this model (stream.StreamReceiverPool): ``open`` a
@@ -815,12 +942,13 @@ class ProposedEval(_ProposedBase):
         return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
                                   out_rate=out_rate)
 
-    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None):
+    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None):
         """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
         get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output
         equals compress_packets on the whole item byte for byte (with ``rate``, a packets.Rate: compress_packets(rate=))."""
         from .stream import StreamSender
-        return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate)
+        return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate, audio=audio,
+                            audio_books=audio_books, audio_rate=audio_rate)
 
     def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None):
         """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,

@@ -302,7 +302,8 @@ class _SenderCore:
     = (slots, slots_dev), the host list of a group's slots and its int32 device copy, on those sessions of a pool: the carried
     tokens go through a dense [G, C] copy (ops.stream_rows), everything else is the same launches on the group's window."""
 
-    def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape, rate=None):
+    def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape, rate=None, audio="codes", audio_books=None,
+                 audio_rate=None):
         import torch
         from . import proposed
         from .packets import StreamInfo, body_bytes, _check
@@ -320,6 +321,18 @@ class _SenderCore:
         self.nb = int(net.vq.n_books) if books_use is None else max(0, min(int(books_use), int(net.vq.n_books)))
         _check(StreamInfo(self.K, self.nb, CHUNK_TOK, packet_tok))
         self.net, self.packet_tok, self.books_use = net, packet_tok, books_use
+        if audio not in ("codes", "packets"):
+            raise ValueError(f"{who}: audio must be 'codes' or 'packets', not {audio!r}")
+        if audio == "codes" and (audio_books is not None or audio_rate is not None):
+            raise ValueError(f"{who}: audio_books / audio_rate go with audio='packets'")
+        self.audio_packets = audio == "packets"
+        self.audio_rate = self.na = self.afull = None
+        if self.audio_packets:                                                         # both loops run closed (proposed.encode_latents_with_indices)
+            from .packets import Rate
+            self.audio_rate, self.na, _ = net._audio_rate_resolve(audio_rate, audio_books, packet_tok)
+            self.K_audio = int(net.A_QUANT.codebook_size)
+            self.afull = body_bytes(packet_tok, self.na, self.K_audio)
+            rate = Rate() if rate is None else rate
         if rate is not None:
             net._rate_resolve(rate, books_use, packet_tok)                             # ValueError before any session state exists
         self.rate = rate
@@ -330,15 +343,18 @@ class _SenderCore:
         self.buf = torch.zeros(*buf_shape, device=self.dev)                            # per session: an audio and a tactile row
         self.carry = torch.zeros(sessions, self.C, device=self.dev)                    # per session: z_run[..., -1] of the chunk before
 
-    def _branches(self, a_w, t_w, lo, hi):
-        """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt); the audio branch
-        on a second HIP stream under the rule of ``_encode_branches``."""
+    def _branches(self, a_w, t_w, lo, hi, want_za=False):
+        """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt) and, with
+        ``want_za``, the encoder output the quantiser searched; the audio branch on a second HIP stream under the rule of
+        ``_encode_branches``."""
         import torch
         from . import ops
         net = self.net
         if a_w.shape[0] > net.TWO_STREAM_MAX_BATCH or not a_w.is_cuda or ops.get_arith() != "f32":
-            qa, codes, *_ = net.A_QUANT(net.A_ENC(a_w)[..., lo:hi].contiguous())
-            return qa, codes, net.T_ENC(t_w)[..., lo:hi].contiguous()
+            za_c = net.A_ENC(a_w)[..., lo:hi].contiguous()
+            qa, codes, *_ = net.A_QUANT(za_c)
+            zt = net.T_ENC(t_w)[..., lo:hi].contiguous()
+            return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
         cur = torch.cuda.current_stream()
         side = getattr(net, "_side_stream", None)
         if side is None or side.device != a_w.device:
@@ -353,7 +369,7 @@ class _SenderCore:
         cur.wait_stream(side)
         for x in (za, za_c, qa, codes):
             x.record_stream(cur)
-        return qa, codes, zt
+        return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
 
     def _encode(self, win, lo, hi, sl=None):
         """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
@@ -362,6 +378,16 @@ class _SenderCore:
         uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back."""
         import torch
         from . import ops
+        if self.audio_packets:      # uint8 [G, P*full + P + P*afull + P]: tactile bodies, counts, audio bodies, counts: one read-back
+            assert sl is None                                                          # the pools take no audio packets
+            _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
+            qa, _, na_sent = self.net.A_QUANT.rate(za, codes, self.audio_rate, self.packet_tok, self.na)
+            _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=self.carry, z_last_out=self.carry, rate=self.rate,
+                                                         packet_tok=self.packet_tok)
+            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
+            abodies = ops.idx_pack_packets(codes[:, :self.na], self.K_audio, self.packet_tok, book_dim=1)
+            G = bodies.shape[0]
+            return torch.cat([bodies.reshape(G, -1), nb_sent, abodies.reshape(G, -1), na_sent], dim=1), codes
         qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
         if self.rate is not None:
@@ -401,11 +427,19 @@ class StreamSender(_SenderCore):
 
     ``rate`` (packets.Rate): closed-loop sender rate control, the session's output then equals compress_packets(rate=).  The book
     count of each packet is decided on the device and comes back behind the bodies in the push's one read-back; it never reaches
-    the host before that, so the captured steady step replays with other decisions."""
+    the host before that, so the captured steady step replays with other decisions.
 
-    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None):
+    ``audio="packets"`` (with ``audio_books`` / ``audio_rate``, as compress_packets_av takes them): the audio codes leave in layered
+    packets too.  ``push`` then returns (tactile_packets, audio_packets), both with the stream's sequence numbers, and ``finish``
+    (tactile_packets, audio_packets, StreamInfo, audio StreamInfo); per item their concatenation equals compress_packets_av byte
+    for byte.  Both loops run closed (``rate`` None is Rate()); both streams' bodies and counts come back in the push's ONE
+    read-back, so ``graph=True`` keeps working.  The default ``audio="codes"`` is the behaviour above exactly."""
+
+    def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None,
+                 audio_rate=None):
         packet_tok, batch = int(packet_tok), int(batch)
-        super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP), rate=rate)   # audio rows, then tactile rows
+        super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP), rate=rate, audio=audio,
+                         audio_books=audio_books, audio_rate=audio_rate)               # buffer: audio rows, then tactile rows
         self.batch, self.graph = batch, bool(graph)
         self.fill = 0                                                                  # valid samples of every buffer row
         self.start = 0                                                                 # the token buf[:, 0] belongs to
@@ -442,6 +476,13 @@ class StreamSender(_SenderCore):
         info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
         host = bodies.cpu().numpy()
         base = self.chunk * CHUNK_TOK // self.packet_tok
+        if self.audio_packets:
+            import numpy as np
+            ainfo = StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok)
+            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P])
+            hb, hc, ab, ac = (host[:, cuts[i]:cuts[i + 1]] for i in range(4))
+            return ([frame(hb[b], info, nb_sent=hc[b], seq_base=base) for b in range(self.batch)],
+                    [frame(ab[b], ainfo, nb_sent=ac[b], seq_base=base) for b in range(self.batch)])
         if self.rate is None:
             return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
         cut = host.shape[1] - info.P                                                   # bodies, then the book count of each packet
@@ -449,6 +490,8 @@ class StreamSender(_SenderCore):
 
     def _nothing(self):
         import torch
+        if self.audio_packets:
+            return [[] for _ in range(self.batch)], [[] for _ in range(self.batch)]
         return [[] for _ in range(self.batch)], torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
 
     def _open(self, what):
@@ -498,12 +541,17 @@ class StreamSender(_SenderCore):
         with torch.no_grad():
             if not st.emit:                                              # an item shorter than one token: nothing to send
                 self.finished = True
-                return self._nothing() + (StreamInfo(self.K, self.nb, self.start + max(st.hi, 0), self.packet_tok),)
+                return self._nothing() + self._infos(self.start + max(st.hi, 0))
             x = self._upload(a, t, n) if n else torch.empty(2 * self.batch, 0, device=self.dev)
             bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi)
             out = self._framed(bodies, codes, st.hi - st.lo)
             self.fill, self.chunk, self.finished = st.fill, st.chunk, True
-            return out + (StreamInfo(self.K, self.nb, self.start + st.hi, self.packet_tok),)
+            return out + self._infos(self.start + st.hi)
+
+    def _infos(self, T):
+        from .packets import StreamInfo
+        info = (StreamInfo(self.K, self.nb, T, self.packet_tok),)
+        return info + (StreamInfo(self.K_audio, self.na, T, self.packet_tok),) if self.audio_packets else info
 
     def _replay(self, a, t, n, plan):
         """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
@@ -551,11 +599,20 @@ class _ReceiverCore:
     int32 device copy, on those sessions of a pool: the same launches under another addressing (csrc/stream.hip), which is why a
     pool session computes what a solo one does."""
 
-    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate):
+    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None):
         import torch
         from . import ops, proposed
-        from .packets import body_bytes
+        from .packets import StreamInfo, _check, body_bytes
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        self.audio = None                                                              # (K_a, na): the audio codes arrive as packets
+        if audio is not None:
+            _f32_only("StreamReceiver")
+            K_a, na = (int(v) for v in audio)
+            if K_a != net.A_QUANT.codebook_size or not 1 <= na <= net.A_QUANT.n_codebooks:
+                raise ValueError(f"StreamReceiver: the audio stream has K = {K_a}, nb = {na}; the model's audio quantiser has "
+                                 f"K = {net.A_QUANT.codebook_size} and {net.A_QUANT.n_codebooks} stages")
+            _check(StreamInfo(K_a, na, CHUNK_TOK, packet_tok))
+            self.audio, self.afull = (K_a, na), body_bytes(packet_tok, na, K_a)
         self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
@@ -599,12 +656,19 @@ class _ReceiverCore:
         token moves on in place; for slots through a dense [G, C] copy, not written back for sessions that end (``last``: the
         next open() resets the slot)."""
         from . import ops
-        G, full = codes.shape[0], self.full
+        G, full = (self.carry.shape[0] if codes is None else codes.shape[0]), self.full
         P = (n + self.packet_tok - 1) // self.packet_tok
-        idx, nbv = ops.idx_unpack_packets(up[:G * P * full].view(G, P, full), up[G * P * full:].view(G, P), self.K, self.nb, n,
-                                          self.packet_tok)
+        idx, nbv = ops.idx_unpack_packets(up[:G * P * full].view(G, P, full), up[G * P * full:G * P * (full + 1)].view(G, P), self.K, self.nb,
+                                          n, self.packet_tok)
+        nav = None
+        if self.audio is not None:                            # behind the tactile arrays: the audio bodies, then their counts
+            assert sl is None and codes is None
+            o, afull = G * P * (full + 1), self.afull
+            aidx, nav = ops.idx_unpack_packets(up[o:o + G * P * afull].view(G, P, afull), up[o + G * P * afull:].view(G, P), self.audio[0],
+                                               self.audio[1], n, self.packet_tok)
+            codes = aidx.permute(1, 0, 2).contiguous()                                 # [na, G, n] -> [G, na, n], on the device
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
-        z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry)
+        z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav)
         if sl is not None and not last:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
         if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
@@ -662,14 +726,21 @@ class StreamReceiver(_ReceiverCore):
     ``graph=True``: the steady step (36-token window, from the third push on) is captured once as a graph on one stream and
     replayed for every later chunk after the host has written the packet bodies and audio codes into the static upload buffers;
     the first two pushes and ``finish`` run eagerly, and so does the resampler launch.  THE TENSOR A PUSH RETURNS IS THEN A VIEW OF
-    THE GRAPH'S OUTPUT BUFFER: it is valid until the next push (clone it to keep it)."""
+    THE GRAPH'S OUTPUT BUFFER: it is valid until the next push (clone it to keep it).
 
-    def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False):
+    ``audio=(K_a, na)``: the audio codes arrive as layered packets too (StreamSender(audio="packets"), compress_packets_av):
+    ``push(tactile_packets, audio_packets=...)`` and ``finish(tactile_packets, audio_packets=..., tokens=n)`` (the second
+    positional argument means the same) gather both streams, both go
+    up in the ONE upload, both are unpacked on the device and the per-token stage counts go into the chunk's from_codes
+    (decode_latents(na_valid=)); the steady step stays one captured graph with static body and count buffers.  The concatenated
+    output equals decompress_packets_av on the same packets.  ``audio=None``: today's behaviour exactly."""
+
+    def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
             raise ValueError("StreamReceiver: batch must be at least 1")
-        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate)
+        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -678,17 +749,25 @@ class StreamReceiver(_ReceiverCore):
         self._g = None                                                                 # (graph, up_static, codes_static, y_static)
 
     # ------------------------------------------------------------------------------------------------------------ stages
-    def _gather(self, tactile_packets, n):
-        """Host: per item whatever packets of this chunk arrived -> one uint8 array, bodies then counts."""
+    def _gather(self, tactile_packets, n, audio_packets=None):
+        """Host: per item whatever packets of this chunk arrived -> one uint8 array, bodies then counts (then, with audio
+        packets, the audio bodies and their counts)."""
         import numpy as np
         from .packets import StreamInfo, gather
         info = StreamInfo(self.K, self.nb, n, self.packet_tok)
         B, P, full = self.batch, info.P, self.full
-        host = np.empty(B * P * (full + 1), np.uint8)
-        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:].reshape(B, P)
+        afull = self.afull if self.audio is not None else 0
+        n_audio = B * P * (afull + 1) if self.audio is not None else 0        # the audio bodies and their counts
+        host = np.empty(B * P * (full + 1) + n_audio, np.uint8)
+        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
         base, late = self.tokens // self.packet_tok, []
         for b in range(B):
             hb[b], hr[b] = gather(tactile_packets[b], info, seq_base=base, late=late)
+        if self.audio is not None:
+            ainfo, o = StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), B * P * (full + 1)
+            ab, ar = host[o:o + B * P * afull].reshape(B, P, afull), host[o + B * P * afull:].reshape(B, P)
+            for b in range(B):
+                ab[b], ar[b] = gather(audio_packets[b], ainfo, seq_base=base, late=late)
         self.late += len(late)
         return host
 
@@ -704,7 +783,7 @@ class StreamReceiver(_ReceiverCore):
         return tactile_packets
 
     # ------------------------------------------------------------------------------------------------------------ session
-    def push(self, tactile_packets, audio_codes):
+    def push(self, tactile_packets, audio_codes=None, *, audio_packets=None):
         """One chunk: ``tactile_packets`` = ``batch`` iterables of the packets of chunk c that arrived (the stream's sequence
         numbers [c*16/packet_tok, (c+1)*16/packet_tok); missing, reordered, duplicated or thinned), ``audio_codes`` int [B, 32, 16].
         -> y [B, 1, n_emit] (1920 samples for the first push, then 5120; a third of that at out_rate=3000, less the resampler's
@@ -714,31 +793,58 @@ class StreamReceiver(_ReceiverCore):
         from ._lib import MvqError
         if self.finished:
             raise MvqError("StreamReceiver: push after finish")
+        audio_codes = self._audio_arg("push", audio_codes, audio_packets)
+        if audio_codes is None:
+            raise ValueError("StreamReceiver.push: a chunk needs its audio " + ("packets" if self.audio is not None else "codes"))
         tactile_packets = self._packets_ok(tactile_packets)
-        codes = self._codes(audio_codes, CHUNK_TOK, CHUNK_TOK)
         n = CHUNK_TOK
-        host = self._gather(tactile_packets, n)
+        if self.audio is not None:                                            # the chunk's audio PACKETS
+            host, codes = self._gather(tactile_packets, n, self._packets_ok(audio_codes)), None
+        else:
+            codes = self._codes(audio_codes, CHUNK_TOK, CHUNK_TOK)
+            host = self._gather(tactile_packets, n)
         plan = self._plan(n, False)
         consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)                   # the samples emitted so far
         with torch.no_grad():
             if self.graph and plan[0] == 2 * DEC_HALO_TOK:                    # the steady step: a full history
                 y = self._replay(host, codes, n, plan)
             else:
-                y = self._device_step(torch.from_numpy(host).to(self.dev), codes.to(self.dev), n, *plan)
+                y = self._device_step(torch.from_numpy(host).to(self.dev), None if codes is None else codes.to(self.dev), n, *plan)
             self.h, self.tokens = plan[1], self.tokens + n
             return self._decimate(y, consumed, False)
 
-    def finish(self, tactile_packets=None, audio_codes=None):
-        """Flush: optionally a last partial chunk of 1..15 tokens (its packets and audio_codes [B, 32, n]), then every remaining
-        sample up to 320*T - 8.  Runs eagerly.  The session accepts nothing afterwards."""
+    def _audio_arg(self, what, audio_codes, audio_packets):
+        """The audio side of a chunk: ``audio_codes`` (a tensor; sessions with audio=None) or ``audio_packets`` (per item the
+        packets that arrived; sessions with audio=(K_a, na), where the second positional argument means the same)."""
+        if audio_packets is None:
+            return audio_codes
+        if self.audio is None:
+            raise ValueError(f"StreamReceiver.{what}: audio_packets needs a session opened with audio=(K_a, na)")
+        if audio_codes is not None:
+            raise ValueError(f"StreamReceiver.{what}: audio_packets or audio_codes, not both")
+        return audio_packets
+
+    def finish(self, tactile_packets=None, audio_codes=None, tokens=None, *, audio_packets=None):
+        """Flush: optionally a last partial chunk of 1..15 tokens (its packets and audio_codes [B, 32, n]; with audio=(K_a, na)
+        its packets of both streams and ``tokens`` = n, which no lost packet can tell), then every remaining sample up to
+        320*T - 8.  Runs eagerly.  The session accepts nothing afterwards."""
         import torch
         from ._lib import MvqError
         if self.finished:
             raise MvqError("StreamReceiver: finish after finish")
+        audio_codes = self._audio_arg("finish", audio_codes, audio_packets)
         if (tactile_packets is None) != (audio_codes is None):
             raise ValueError("StreamReceiver.finish: the last chunk needs both its packets and its audio codes")
+        if tokens is not None and (self.audio is None or audio_codes is None):
+            raise ValueError("StreamReceiver.finish: tokens= counts a last chunk of audio PACKETS (a session with audio=(K_a, na)); "
+                             "audio codes carry their own length")
         n, up, codes = 0, None, None
-        if audio_codes is not None:
+        if audio_codes is not None and self.audio is not None:
+            if tokens is None or not 1 <= int(tokens) <= CHUNK_TOK - 1:
+                raise ValueError(f"StreamReceiver.finish: tokens = {tokens!r}; a last chunk of audio packets has 1..{CHUNK_TOK - 1} tokens")
+            n = int(tokens)
+            host = self._gather(self._packets_ok(tactile_packets), n, self._packets_ok(audio_codes))
+        elif audio_codes is not None:
             tactile_packets = self._packets_ok(tactile_packets)
             codes = self._codes(audio_codes, 1, CHUNK_TOK - 1)
             n = int(codes.shape[2])
@@ -747,7 +853,7 @@ class StreamReceiver(_ReceiverCore):
         consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)
         with torch.no_grad():
             if n:
-                up, codes = torch.from_numpy(host).to(self.dev), codes.to(self.dev)
+                up, codes = torch.from_numpy(host).to(self.dev), None if codes is None else codes.to(self.dev)
             y = self._device_step(up, codes, n, *plan, last=True)
             self.h, self.tokens, self.finished = plan[1], self.tokens + n, True
             return self._decimate(y, consumed, True)
@@ -758,13 +864,14 @@ class StreamReceiver(_ReceiverCore):
         import torch
         if self._g is None:
             up_s = torch.from_numpy(host).to(self.dev)
-            codes_s = codes.to(self.dev).long().clone()
+            codes_s = None if codes is None else codes.to(self.dev).long().clone()
             g, y_s = _capture(self.dev, (self.hist, self.carry), lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
         else:
             g, up_s, codes_s, y_s = self._g
             up_s.copy_(torch.from_numpy(host))
-            codes_s.copy_(codes)
+            if codes_s is not None:
+                codes_s.copy_(codes)
         g.replay()
         return y_s
 

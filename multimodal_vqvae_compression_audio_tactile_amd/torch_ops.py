@@ -16,6 +16,7 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   decoder_bwd_input           mvq_decoder_fwd_saving_f32 + mvq_decoder_bwd_input_f32: dL/dz of T_DEC, ...5.py:393
   rvq_dequant                 mvq_rvq_dequant_f32        receiver: ResidualVQEMA indices -> summed code vectors [B,D,T]
   dac_rvq_from_codes          mvq_dac_rvq_from_codes_f32 receiver: upstream ResidualVectorQuantize.from_codes -> (z_q, z_p)
+  dac_rvq_from_codes_layers   mvq_dac_rvq_from_codes_layers_f32 lossy audio receiver: the same over the first nq_valid[b,t] stages of each token
   rvq_dequant_layers          mvq_rvq_dequant_layers_f32 lossy receiver: the same over the first nb_valid[b,t] books of each token
   idx_pack_packets            mvq_idx_pack_packets_u8    lossy receiver: indices -> packet bodies uint8 [B,P,body_full] (packets.py)
   idx_unpack_packets          mvq_idx_unpack_packets     lossy receiver: bodies + per-packet book counts -> (idx, nb_valid)
@@ -143,7 +144,7 @@ def _(z, gy, stack):
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
               "ema_update_f32", "attention_seq_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes",
-              "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets")
+              "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets", "dac_rvq_from_codes_layers")
 
 
 @torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
@@ -196,6 +197,17 @@ def rvq_dequant_layers(idx: Tensor, books: Tensor, nb_valid: Tensor, n_use: int)
 @rvq_dequant_layers.register_fake
 def _(idx, books, nb_valid, n_use):
     return books.new_empty(idx.shape[1], books.shape[-1], idx.shape[2])
+
+
+@torch.library.custom_op(f"{NS}::dac_rvq_from_codes_layers", mutates_args=())
+def dac_rvq_from_codes_layers(codes: Tensor, codebook: Tensor, out_w: Tensor, out_b: Tensor, nq_valid: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.dac_rvq_from_codes(codes, codebook, out_w, out_b, nq_valid=nq_valid)
+
+
+@dac_rvq_from_codes_layers.register_fake
+def _(codes, codebook, out_w, out_b, nq_valid):
+    B, nq, T = codes.shape
+    return out_w.new_empty(B, out_w.shape[1], T), out_w.new_empty(B, nq * codebook.shape[-1], T)
 
 
 @torch.library.custom_op(f"{NS}::idx_pack_packets", mutates_args=())
