@@ -40,6 +40,7 @@ extern "C" {
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
+ * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
@@ -272,6 +273,32 @@ int mvq_rvq_rate_f32(const float* z, size_t z_sb, size_t z_sd, const int32_t* id
                      const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
                      uint8_t* nb_sent, size_t nbs_sb, float* energy, int batch, int dim, int t, int nb_use, int k,
                      int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget, void* stream);
+
+/* Forward error correction (additive, same ABI version; no reference counterpart, and the format is not derived from anything the
+ * reference contains).  Bodies are book-major, so the first m books of a body are a valid lower-rate body: one XOR parity row over
+ * the first m = books books of every group = g consecutive packets is unequal error protection whose repaired packet is a packet
+ * thinned to m books -- mvq_idx_unpack_packets and the layered look-ups treat it as any lower-rate token.  Parity group j of an item
+ * covers packets [j*g, min(P, (j+1)*g)), G = ceil(P / g) groups; packet p is protected to c_p = min(m, nb_sent[p]) books;
+ * prefix(p) = the first ceil(c_p*ntok_p*bits / 8) bytes of body row p, the bits of book c_p and above cleared in the last one,
+ * zero-extended to W = ceil(m*packet_tok*bits / 8).  Row j of rows[B, G, g + W]: bytes 0..g-1 = c_p of the group's packets (0 in the
+ * slots of a short tail group), bytes g..g+W-1 = the XOR of the group's prefixes.  packets.py (fec_rows / fec_recover) is the numpy
+ * definition these kernels equal bit for bit.  Refused before any launch (MVQ_EINVAL "bad shape"): group outside 1..16, books
+ * outside 1..nb, and the shapes mvq_idx_pack_packets_u8 refuses; batch == 0 or t == 0 is a no-op.
+ *
+ * Parity: bodies[B, P, body_full], nb_sent[B, P] (NULL = every packet carries nb books) -> rows_out.  One thread owns one output
+ * byte and XORs the at most 16 masked body bytes that fall into it; writes EVERY byte of rows_out; no atomics. */
+int mvq_fec_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k, int packet_tok,
+                      int group, int books, void* stream);
+/* Recovery, in place on bodies[B, P, body_full] and nb_recv[B, P] (what mvq_idx_unpack_packets reads), from rows[B, G, g + W] and
+ * got[B, G] (0 = the group's parity did not arrive).  For a group with got != 0 and c_p = min(count byte, m, nb) -- clamped, so a
+ * corrupt parity packet cannot make a read leave its row -- packet p is deficient when nb_recv[p] < c_p (lost, or thinned below its
+ * protected count).  When EXACTLY ONE packet q of the group is deficient: row q = (XOR bytes) ^ XOR_{p != q} prefix(p) over its
+ * first ceil(c_q*ntok_q*bits / 8) bytes and zero past them, nb_recv[q] = c_q, recovered[q] = 1.  In every other case the group is
+ * left exactly as it arrived.  One block per (item, group); only the deficient row and its count are written, the count behind a
+ * barrier after every thread of the block has made its decision; recovered[B, P] (NULL = not written) has every element written.
+ * No atomics. */
+int mvq_fec_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch, int nb,
+                       int t, int k, int packet_tok, int group, int books, void* stream);
 
 /* Audio transport (additive, same ABI version; no reference counterpart).  The DAC quantiser is a residual VQ, so the first m stages
  * of a token's codes are a valid lower-rate code: the audio codes travel in the layered packets of the tactile stream

@@ -779,6 +779,52 @@ int mvq_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_
     return e == hipSuccess ? MVQ_OK : hipfail(e, "idx_unpack_packets");
 }
 
+// ---- forward error correction over the packet bodies (kernels in fec.hip) ----
+namespace {
+// The shape checks of both FEC entry points: ceil(log2 K), or -1 with the message set.
+inline int fec_bits(const char* who, int batch, int nb, int t, int k, int packet_tok, int group, int books)
+{
+    const int bits = packet_bits(batch, nb, t, k, packet_tok);
+    if (bits < 0) {
+        fail(MVQ_EINVAL, "%s: bad shape B=%d nb=%d T=%d K=%d packet_tok=%d (nb, packet_tok <= 255, ceil(log2 K) <= 24)", who, batch, nb, t, k,
+             packet_tok);
+        return -1;
+    }
+    if (group < 1 || group > 16 || books < 1 || books > nb) {
+        fail(MVQ_EINVAL, "%s: bad shape group=%d (1..16) books=%d (1..nb=%d)", who, group, books, nb);
+        return -1;
+    }
+    const long long P = ((long long)t + packet_tok - 1) / packet_tok;
+    if ((long long)batch * ((P + group - 1) / group) > 2147483647LL) {
+        fail(MVQ_EINVAL, "%s: bad shape B=%d x %lld parity groups exceed the grid", who, batch, (P + group - 1) / group);
+        return -1;
+    }
+    return bits;
+}
+}  // namespace
+
+int mvq_fec_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k, int packet_tok,
+                      int group, int books, void* stream)
+{
+    const int bits = fec_bits("fec_parity", batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!rows_out || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_parity: null tensor");
+    hipError_t e = mvq::launch_fec_parity(bodies, nb_sent, rows_out, batch, nb, t, bits, packet_tok, group, books, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_parity");
+}
+
+int mvq_fec_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch, int nb,
+                       int t, int k, int packet_tok, int group, int books, void* stream)
+{
+    const int bits = fec_bits("fec_recover", batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!nb_recv || !rows || !got || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_recover: null tensor");
+    hipError_t e = mvq::launch_fec_recover(bodies, nb_recv, rows, got, recovered, batch, nb, t, bits, packet_tok, group, books, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_recover");
+}
+
 int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,
                                int t, int nb_use, int k, size_t out_sb, size_t out_sd, void* stream)
 {

@@ -635,6 +635,62 @@ def idx_unpack_packets(bodies, nb_recv, k, nb, T, packet_tok):
     return idx, nb_valid
 
 
+def _fec_shape(name, info, fec):
+    """(K, nb, T, packet_tok, P, body_full, g, m, G, W) after the checks the C ABI repeats."""
+    from .packets import StreamInfo
+    try:
+        info = StreamInfo(*(int(v) for v in info))
+        g, m = int(fec.group), int(fec.books)
+    except (TypeError, ValueError, AttributeError) as e:
+        raise MvqError(f"{name}: info must be a packets.StreamInfo and fec a packets.Fec ({e})") from None
+    P, full = _packet_shape(name, info.K, info.nb, info.T, info.packet_tok)
+    if not 1 <= g <= 16 or not 1 <= m <= info.nb:
+        raise MvqError(f"{name}: Fec(group={g}, books={m}) outside group 1..16, books 1..nb = {info.nb}")
+    from .packets import body_bytes
+    return info.K, info.nb, info.T, info.packet_tok, P, full, g, m, (P + g - 1) // g, body_bytes(info.packet_tok, m, info.K)
+
+
+def _fec_u8(name, what, t, shape, dev=None, contiguous=False):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.uint8:
+        raise MvqError(f"{name}: {what} must be a uint8 tensor on a HIP device")
+    if (dev is not None and t.device != dev) or t.dim() != len(shape) or any(w is not None and int(v) != w for v, w in zip(t.shape, shape)):
+        raise MvqError(f"{name}: {what} {tuple(t.shape)} for {list(shape)} on the device of bodies")
+    if contiguous and not t.is_contiguous():
+        raise MvqError(f"{name}: {what} is written in place and must be contiguous")
+    return t if contiguous else t.contiguous()
+
+
+def fec_parity(bodies, nb_sent, info, fec):
+    """bodies uint8 [B, P, body_full] and nb_sent uint8 [B, P] (None: every packet carries info.nb books) -> the parity rows uint8
+    [B, G, g + W]: packets.fec_rows per item, bit for bit (mvq_fec_parity_u8)."""
+    K, nb, T, ptok, P, full, g, m, G, W = _fec_shape("fec_parity", info, fec)
+    bodies = _fec_u8("fec_parity", "bodies", bodies, (None, P, full))
+    B = bodies.shape[0]
+    if nb_sent is not None:
+        nb_sent = _fec_u8("fec_parity", "nb_sent", nb_sent, (B, P), bodies.device)
+    rows = torch.empty(B, G, g + W, device=bodies.device, dtype=torch.uint8)
+    check(_lib.lib().mvq_fec_parity_u8(bodies.data_ptr(), _p(nb_sent), rows.data_ptr(), B, nb, T, K, ptok, g, m, _stream()),
+          "mvq_fec_parity_u8")
+    return rows
+
+
+def fec_recover(bodies, nb_recv, rows, got, info, fec, want_recovered=False):
+    """packets.fec_recover per item on the device, IN PLACE on bodies uint8 [B, P, body_full] and nb_recv uint8 [B, P] (both
+    contiguous), from the parity rows uint8 [B, G, g + W] and got uint8 [B, G] (0 = the group's parity did not arrive): where
+    exactly one packet of a group is deficient it is rebuilt to its protected books (mvq_fec_recover_u8).
+    -> (bodies, nb_recv), with ``want_recovered`` also recovered uint8 [B, P]."""
+    K, nb, T, ptok, P, full, g, m, G, W = _fec_shape("fec_recover", info, fec)
+    bodies = _fec_u8("fec_recover", "bodies", bodies, (None, P, full), contiguous=True)
+    B = bodies.shape[0]
+    nb_recv = _fec_u8("fec_recover", "nb_recv", nb_recv, (B, P), bodies.device, contiguous=True)
+    rows = _fec_u8("fec_recover", "rows", rows, (B, G, g + W), bodies.device)
+    got = _fec_u8("fec_recover", "got", got, (B, G), bodies.device)
+    recovered = torch.empty(B, P, device=bodies.device, dtype=torch.uint8) if want_recovered else None
+    check(_lib.lib().mvq_fec_recover_u8(bodies.data_ptr(), nb_recv.data_ptr(), rows.data_ptr(), got.data_ptr(), _p(recovered), B, nb, T, K,
+                                        ptok, g, m, _stream()), "mvq_fec_recover_u8")
+    return (bodies, nb_recv, recovered) if want_recovered else (bodies, nb_recv)
+
+
 def dac_rvq_from_codes(codes, codebook, out_w, out_b, want_z_p=True, nq_valid=None):
     """upstream ResidualVectorQuantize.from_codes: codes[B, nq, T] (int) -> (z_q [B,C,T], z_p [B,nq*Dc,T] or None).
     z_q = sum over stages of out_proj_i(codebook_i[code_i]) in stage order; the first nq stages of the stacked weights.

@@ -24,6 +24,12 @@ The AUDIO codes travel in the same format (ProposedEval.compress_packets_av): St
 carried, T = the audio tokens, packet_tok), "books" being the stages of the DAC residual VQ, whose first m are a valid lower-rate
 code.  Both streams share the magic ``MP`` and are told apart by the list they travel in; the format and ``VERSION`` do not change
 (there is no stream-kind field).
+
+FORWARD ERROR CORRECTION (``Fec``, fec_rows / frame_fec / gather_fec / fec_recover): one XOR parity packet, magic ``MF``, over the
+first m books of every group of g data packets.  A body's first m books are a valid lower-rate body, so a packet rebuilt from the
+parity is a packet thinned to m books: nothing downstream of ``fec_recover`` knows about it.  Parity packets travel in a list of
+their own; the data packets, ``gather``, ``thin``, ``frame`` and ``VERSION`` are unchanged.  ``fec_rows`` / ``fec_recover`` are the
+definition the device kernels (ops.fec_parity / ops.fec_recover) equal bit for bit.
 """
 from __future__ import annotations
 
@@ -36,6 +42,8 @@ import numpy as np
 from .bitstream import index_bits
 
 MAGIC = b"MP"
+FEC_MAGIC = b"MF"                           # a parity packet (frame_fec); ``gather`` refuses it by its magic
+FEC_MAX_GROUP = 16
 VERSION = 1
 _HEADER = struct.Struct("<2sBIBB")
 HEADER_BYTES = _HEADER.size                 # 9
@@ -307,3 +315,210 @@ def gather(packets: Iterable, info: StreamInfo, seq_base: int = 0, late: Optiona
             buf[seq * full:seq * full + len(body)] = body
             got[seq] = nb_sent
     return np.frombuffer(buf, np.uint8).reshape(info.P, full), np.frombuffer(got, np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ forward error correction
+@dataclasses.dataclass(frozen=True)
+class Fec:
+    """XOR parity over the first ``books`` books of every ``group`` consecutive packets; both ends know it out of band, like
+    StreamInfo.  Parity group j covers packets [j*group, min(P, (j+1)*group)): G = ceil(P / group) groups per item.  Packet p,
+    sent with nb_sent[p] books, is protected to c_p = min(books, nb_sent[p]) books: unequal error protection, the base books only.
+    ``resolve`` checks the values against a stream's shape."""
+    group: int
+    books: int
+
+    def __post_init__(self):
+        for name in ("group", "books"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Fec: {name} = {v!r} is not an integer")
+
+    def resolve(self, info: StreamInfo, chunk_tok: Optional[int] = None):
+        """-> (g, m, G, W): the group size, the protected books, the groups per item and the width of the XOR field,
+        body_bytes(packet_tok, m, K).  ValueError on group outside 1..16, books outside 1..nb, K < 2 (bodies of no bits), and,
+        with ``chunk_tok`` (the model's 16-token chunk), a group that does not divide the chunk_tok // packet_tok packets of a
+        chunk: a group never straddles a chunk."""
+        info = _check(info)
+        g, m = int(self.group), int(self.books)
+        if not 1 <= g <= FEC_MAX_GROUP:
+            raise ValueError(f"Fec: group = {g} outside 1..{FEC_MAX_GROUP}")
+        if not 1 <= m <= info.nb:
+            raise ValueError(f"Fec: books = {m} outside 1..{info.nb} (the stream's books)")
+        if info.K < 2:
+            raise ValueError(f"Fec: K = {info.K}: bodies of no bits have nothing to protect")
+        if chunk_tok is not None:
+            chunk_tok = int(chunk_tok)
+            if chunk_tok < 1 or chunk_tok % info.packet_tok or (chunk_tok // info.packet_tok) % g:
+                raise ValueError(f"Fec: group = {g} does not divide the {chunk_tok} // {info.packet_tok} packets of a chunk")
+        return g, m, (info.P + g - 1) // g, body_bytes(info.packet_tok, m, info.K)
+
+
+def _fec_counts(nb_sent, info: StreamInfo, what: str) -> np.ndarray:
+    if nb_sent is None or np.ndim(nb_sent) == 0:
+        return np.full(info.P, info.nb if nb_sent is None else int(nb_sent), np.int64)
+    counts = np.asarray(nb_sent).reshape(-1).astype(np.int64)
+    if counts.shape[0] != info.P:
+        raise ValueError(f"{what}: {counts.shape[0]} book counts for P={info.P} packets")
+    return counts
+
+
+def _fec_bodies(bodies, info: StreamInfo, what: str) -> np.ndarray:
+    full = body_bytes(info.packet_tok, info.nb, info.K)
+    bodies = np.asarray(bodies, np.uint8).reshape(-1, full) if full else np.zeros((info.P, 0), np.uint8)
+    if bodies.shape[0] != info.P:
+        raise ValueError(f"{what}: {bodies.shape[0]} bodies for P={info.P} packets")
+    return bodies
+
+
+def _prefix(row, ntok: int, c: int, k: int, width: int) -> np.ndarray:
+    """prefix(p): the body of the first c books (``_first_books``: what ``thin`` to c books carries), zero-extended to width."""
+    out = np.zeros(width, np.uint8)
+    body = _first_books(row, ntok, c, k)
+    out[:len(body)] = np.frombuffer(body, np.uint8)
+    return out
+
+
+def fec_rows(bodies, nb_sent, info: StreamInfo, fec: Fec) -> np.ndarray:
+    """bodies[P, body_full], nb_sent (None or a scalar: every packet; or P counts) -> the item's parity uint8[G, g + W].
+    Bytes 0..g-1 of row j: c_p = min(m, nb_sent[p]) of the group's packets (0 in the slots of a short tail group); bytes g..g+W-1:
+    the XOR over the group's packets of prefix(p), the first body_bytes(ntok_p, c_p, K) bytes of row p with the bits of book c_p
+    and above cleared in the last one, zero-extended to W."""
+    info = _check(info)
+    g, m, G, W = fec.resolve(info)
+    bodies, counts = _fec_bodies(bodies, info, "fec_rows"), _fec_counts(nb_sent, info, "fec_rows")
+    if counts.size and (counts.min() < 0 or counts.max() > 255):
+        raise ValueError("fec_rows: a book count outside 0..255")
+    rows = np.zeros((G, g + W), np.uint8)
+    for p in range(info.P):
+        j, c = p // g, min(m, int(counts[p]))
+        rows[j, p - j * g] = c
+        rows[j, g:] ^= _prefix(bodies[p], info.ntok(p), c, info.K, W)
+    return rows
+
+
+def _fec_group(info: StreamInfo, g: int, j: int) -> range:
+    return range(j * g, min(info.P, (j + 1) * g))
+
+
+def frame_fec(rows, info: StreamInfo, fec: Fec, seq_base: int = 0) -> list:
+    """rows[G, g + W] (fec_rows) -> one ``bytes`` per group: the 9-byte header of the data packets with magic b"MF",
+    seq = seq_base + j, the ``ntok`` byte holding the packets of the group g_j and the ``nb_sent`` byte max_p c_p; then the g_j count
+    bytes; then the XOR bytes cut to max_p body_bytes(ntok_p, c_p, K) (everything past that is zero by construction).
+    ``seq_base`` (streaming): ``info`` describes one chunk and group j is numbered seq_base + j, the stream's group number."""
+    info = _check(info)
+    g, m, G, W = fec.resolve(info)
+    seq_base = int(seq_base)
+    if not 0 <= seq_base <= 2 ** 32 - G:
+        raise ValueError(f"frame_fec: seq_base = {seq_base} with G = {G} groups leaves the 32-bit sequence number")
+    rows = np.asarray(rows, np.uint8).reshape(-1, g + W)
+    if rows.shape[0] != G:
+        raise ValueError(f"frame_fec: {rows.shape[0]} parity rows for G={G} groups")
+    out = []
+    for j in range(G):
+        grp = _fec_group(info, g, j)
+        counts = [int(v) for v in rows[j, :len(grp)]]
+        if any(not 1 <= c <= m for c in counts):
+            raise ValueError(f"frame_fec: group {j}: a count outside 1..{m}")
+        n = max(body_bytes(info.ntok(p), c, info.K) for p, c in zip(grp, counts))
+        out.append(_HEADER.pack(FEC_MAGIC, VERSION, seq_base + j, len(grp), max(counts)) + rows[j, :len(grp)].tobytes()
+                   + rows[j, g:g + n].tobytes())
+    return out
+
+
+def gather_fec(fec_packets: Iterable, info: StreamInfo, fec: Fec, seq_base: int = 0, late: Optional[list] = None):
+    """Any iterable of received parity packets -> (rows uint8[G, g + W], got uint8[G]).  Rows of groups whose parity did not arrive
+    stay zero with got = 0; duplicates are harmless.  Raises ValueError as ``gather`` does: bad magic or version, a group number
+    at or past seq_base + G, a g_j or a count that disagrees with ``info`` / ``fec``, a length that disagrees with the header and
+    the counts.  ``seq_base`` / ``late`` as in ``gather``, in group numbers."""
+    info = _check(info)
+    g, m, G, W = fec.resolve(info)
+    seq_base = int(seq_base)
+    if not 0 <= seq_base <= 2 ** 32 - G:
+        raise ValueError(f"gather_fec: seq_base = {seq_base} with G = {G} groups leaves the 32-bit sequence number")
+    rows, got = np.zeros((G, g + W), np.uint8), np.zeros(G, np.uint8)
+    for pkt in fec_packets:
+        data = bytes(pkt)
+        if len(data) < HEADER_BYTES:
+            raise ValueError(f"parity packet: {len(data)} bytes, shorter than the {HEADER_BYTES}-byte header")
+        magic, version, seq, gj, cmax = _HEADER.unpack_from(data, 0)
+        if magic != FEC_MAGIC:
+            raise ValueError(f"parity packet: bad magic {magic!r}")
+        if version != VERSION:
+            raise ValueError(f"parity packet: unsupported version {version}")
+        j = seq - seq_base
+        if j < 0:
+            if late is None:
+                raise ValueError(f"parity packet: seq {seq} < seq_base = {seq_base}")
+            late.append(pkt)
+            continue
+        if j >= G:
+            raise ValueError(f"parity packet: seq {seq} >= {seq_base} + G = {seq_base + G}")
+        grp = _fec_group(info, g, j)
+        if gj != len(grp):
+            raise ValueError(f"parity packet {j}: covers {gj} packets, the stream has {len(grp)} there")
+        if len(data) < HEADER_BYTES + gj:
+            raise ValueError(f"parity packet {j}: {len(data)} bytes, shorter than its {gj} count bytes")
+        counts = list(data[HEADER_BYTES:HEADER_BYTES + gj])
+        if any(not 1 <= c <= m for c in counts) or max(counts) != cmax:
+            raise ValueError(f"parity packet {j}: counts {counts} (header: {cmax}) outside 1..{m}")
+        n = max(body_bytes(info.ntok(p), c, info.K) for p, c in zip(grp, counts))
+        if len(data) != HEADER_BYTES + gj + n:
+            raise ValueError(f"parity packet {j}: {len(data)} bytes, the header and counts imply {HEADER_BYTES + gj + n}")
+        rows[j] = 0
+        rows[j, :gj] = counts
+        rows[j, g:g + n] = np.frombuffer(data, np.uint8, n, HEADER_BYTES + gj)
+        got[j] = 1
+    return rows, got
+
+
+def fec_recover(bodies, nb_recv, rows, got, info: StreamInfo, fec: Fec):
+    """THE recovery rule -> (bodies, nb_recv, recovered uint8[P]), copies.  For a group j whose parity arrived (got[j] != 0), with
+    c_p = min(rows[j, p - j*g], m, nb): packet p is DEFICIENT when nb_recv[p] < c_p (lost, or thinned below its protected count).
+    When exactly one packet q of the group is deficient, row q becomes (XOR bytes) ^ XOR_{p != q} prefix(p) over its first
+    body_bytes(ntok_q, c_q, K) bytes and zero past them, nb_recv[q] = c_q, recovered[q] = 1: what ``thin`` of the sent packet to
+    c_q books carries.  In every other case (no parity, nothing deficient, two or more deficient) the group stays as it arrived."""
+    info = _check(info)
+    g, m, G, W = fec.resolve(info)
+    bodies = _fec_bodies(bodies, info, "fec_recover").copy()
+    nb_recv = np.asarray(nb_recv, np.uint8).reshape(-1).copy()
+    rows, got = np.asarray(rows, np.uint8).reshape(-1, g + W), np.asarray(got).reshape(-1)
+    if nb_recv.shape[0] != info.P or rows.shape[0] != G or got.shape[0] != G:
+        raise ValueError(f"fec_recover: {nb_recv.shape[0]} counts, {rows.shape[0]} parity rows, {got.shape[0]} flags for P={info.P}, G={G}")
+    recovered = np.zeros(info.P, np.uint8)
+    for j in range(G):
+        if not got[j]:
+            continue
+        grp = _fec_group(info, g, j)
+        c = {p: min(int(rows[j, p - j * g]), m, info.nb) for p in grp}
+        deficient = [p for p in grp if int(nb_recv[p]) < c[p]]
+        if len(deficient) != 1:
+            continue
+        q = deficient[0]
+        x = rows[j, g:].copy()
+        for p in grp:
+            if p != q:
+                x ^= _prefix(bodies[p], info.ntok(p), c[p], info.K, W)
+        n = body_bytes(info.ntok(q), c[q], info.K)
+        bodies[q] = 0
+        bodies[q, :n] = x[:n]
+        nb_recv[q], recovered[q] = c[q], 1
+    return bodies, nb_recv, recovered
+
+
+def fec_bits(info: StreamInfo, fec: Fec, nb_sent=None, headers: bool = True) -> int:
+    """Bits on the wire of one item's parity packets as ``frame_fec`` cuts them (``sent_bits``'s counterpart): per group the XOR
+    bytes, plus the 9-byte header and the count bytes when ``headers``."""
+    info = _check(info)
+    g, m, G, W = fec.resolve(info)
+    counts = _fec_counts(nb_sent, info, "fec_bits")
+    total = 0
+    for j in range(G):
+        grp = _fec_group(info, g, j)
+        total += max(body_bytes(info.ntok(p), min(m, int(counts[p])), info.K) for p in grp) + ((HEADER_BYTES + len(grp)) if headers else 0)
+    return 8 * total
+
+
+def fec_kbps(info: StreamInfo, fec: Fec, nb_sent=None, headers: bool = True, token_rate: float = 75.0) -> float:
+    """The rate of ``fec_bits`` in kbit/s at ``token_rate`` tokens per second: the overhead FEC adds to ``sent_kbps``."""
+    info = _check(info)
+    return fec_bits(info, fec, nb_sent, headers) * float(token_rate) / (1000.0 * info.T) if info.T else 0.0

@@ -246,6 +246,11 @@ class _ProposedBase(nn.Module):
         """clamp(scale, 5e-3, 0.5)   (Training/compare_dacvsproposal_5.py:314)."""
         return min(max(self._scale_raw(), 5e-3), 0.5)
 
+    def _rate_books(self, books_use):
+        """The books in use: StreamInfo.nb of what compress_packets sends."""
+        n_books = len(self.vq.books)
+        return n_books if books_use is None else max(0, min(int(books_use), n_books))
+
     def _rate_resolve(self, rate, books_use, packet_tok):
         """The refusals of sender rate control, before any launch -> (packet_tok, (min_books, mode, tol2, budget))."""
         from . import packets
@@ -278,6 +283,31 @@ class _ProposedBase(nn.Module):
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
         audio_rate.resolve(na_use, packet_tok, AR_CHUNK_TOK)
         return audio_rate, na_use, packet_tok
+
+    def _fec_resolve(self, fec, K, nb, packet_tok, what="fec"):
+        """The refusals of forward error correction, before any launch (packets.Fec.resolve against the 16-token chunk: a parity
+        group never straddles a chunk, which is what lets a streaming session emit the whole-item parity chunk by chunk)."""
+        from . import packets
+        if not isinstance(fec, packets.Fec):
+            raise ValueError(f"{what} must be a packets.Fec, not {type(fec).__name__}")
+        if ops.get_arith() != "f32":
+            raise ValueError(f"{what}: forward error correction claims bit-equality with the whole-item and streaming paths; arithmetic "
+                             f"mode {ops.get_arith()!r} makes no parity claim")
+        packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
+        fec.resolve(packets.StreamInfo(int(K), int(nb), AR_CHUNK_TOK, packet_tok), chunk_tok=AR_CHUNK_TOK)
+        return fec
+
+    @staticmethod
+    def _fec_gather(fec, fec_packets, info, B, who, what="fec"):
+        """Host: per item whatever parity packets arrived -> (rows uint8 [B, G, g + W], got uint8 [B, G])."""
+        from . import packets
+        if fec_packets is None or len(fec_packets) != B:
+            raise MvqError(f"{who}: {what}= needs {what}_packets, one list of parity packets per item (empty when none arrived)")
+        g, m, G, W = fec.resolve(info)
+        rows, got = np.empty((B, G, g + W), np.uint8), np.empty((B, G), np.uint8)
+        for b in range(B):
+            rows[b], got[b] = packets.gather_fec(fec_packets[b], info, fec)
+        return rows, got
 
     @torch.no_grad()
     def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False, z_prev=None,
@@ -795,7 +825,7 @@ class ProposedEval(_ProposedBase):
         return self.decode(codes_t, idx_t, books_use=books_use)
 
     @torch.no_grad()
-    def compress_packets(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None):
+    def compress_packets(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None, fec=None):
         """-> (infos, tactile_packets, audio_payloads) for a lossy channel: per item the session parameters
         packets.StreamInfo(K, nb, T_lat, packet_tok) (sent reliably out of band), the list of framed packets (``bytes``, packets.py)
         of its RVQ indices, and the audio codes as a v1 payload (the audio stream is assumed delivered, as the reference's PLC
@@ -804,9 +834,20 @@ class ProposedEval(_ProposedBase):
         ``rate`` (packets.Rate): the sender chooses each packet's book count on the device, closed loop
         (encode_latents_with_indices); the counts ride back behind the bodies in the same copy and every packet is cut to its
         count (packets.frame).  StreamInfo.nb stays the books in use; decompress_packets needs no change and returns
-        T_DEC(the sender's z_run) exactly."""
+        T_DEC(the sender's z_run) exactly.
+
+        ``fec`` (packets.Fec; None = today's path and return value): one XOR parity packet per group of ``fec.group`` packets over
+        their first ``fec.books`` books (under ``rate``: min(fec.books, the packet's own count)).  The parity rows are computed on the
+        device from the packed bodies (ops.fec_parity), ride back behind the bodies and counts in the same single device-to-host
+        copy and are framed by packets.frame_fec -> (infos, tactile_packets, audio_payloads, fec_packets), one list of parity
+        packets per item; the data packets are byte for byte those of the call without ``fec``.  The closed loop: a recovered packet
+        has c_q <= nb_sent[q] books, so the receiver's AR history departs from the sender's exactly as after a relay's ``thin``
+        to c_q books, and less than after a loss; with fec.books >= the books in use and at most one deficient packet per group
+        (all parity delivered) the receiver's result equals the lossless one bit for bit."""
         from . import bitstream, packets
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
+        if fec is not None:
+            self._fec_resolve(fec, self.vq.n_embed, self._rate_books(books_use), packet_tok)
         nb_sent = None
         if rate is None:
             _, codes, idx = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use)
@@ -815,6 +856,16 @@ class ProposedEval(_ProposedBase):
         nb, B, T = idx.shape
         info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
         bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
+        if fec is not None:                                                   # bodies, the counts under ``rate``, the parity rows: one copy
+            rows = ops.fec_parity(bodies, nb_sent, info, fec)
+            full, n_cnt = bodies.shape[2], 0 if nb_sent is None else info.P
+            host = torch.cat([bodies.reshape(B, -1)] + ([] if nb_sent is None else [nb_sent]) + [rows.reshape(B, -1)], dim=1).cpu().numpy()
+            cuts = np.cumsum([0, info.P * full, n_cnt])
+            hb, hc, hf = host[:, :cuts[1]].reshape(B, info.P, full), host[:, cuts[1]:cuts[2]], host[:, cuts[2]:]
+            codes = codes.cpu().numpy()
+            return ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b] if n_cnt else None) for b in range(B)],
+                    [bitstream.pack_indices(codes[b], self.A_QUANT.codebook_size) for b in range(B)],
+                    [packets.frame_fec(hf[b], info, fec) for b in range(B)])
         if nb_sent is None:
             bodies, counts = bodies.cpu().numpy(), [None] * B
         else:
@@ -827,11 +878,22 @@ class ProposedEval(_ProposedBase):
                 [bitstream.pack_indices(codes[b], k_audio) for b in range(B)])
 
     @torch.no_grad()
-    def decompress_packets(self, infos, tactile_packets, audio_payloads, books_use=None, conceal="predict", plc=None):
+    def decompress_packets(self, infos, tactile_packets, audio_payloads, books_use=None, conceal="predict", plc=None, fec=None,
+                           fec_packets=None):
         """-> (y [B,1,T], lost [B,T_lat] bool) from whatever packets arrived (missing, reordered, duplicated, thinned; items of
         one StreamInfo): packets.gather per item on the host, ONE upload of the bodies and per-packet book counts, the bit
-        unpacking on the device, then decode(nb_valid=...).  ``lost``: the tokens no book of which arrived."""
+        unpacking on the device, then decode(nb_valid=...).  ``lost``: the tokens no book of which arrived.
+
+        ``fec`` / ``fec_packets`` (packets.Fec and, per item, whatever parity packets arrived; None = today's path): packets.gather_fec
+        per item, the parity rows and ``got`` flags appended to the ONE upload, ops.fec_recover (packets.fec_recover, THE rule: a
+        group with its parity and exactly one deficient packet gets that packet back at its protected books) in place ahead of
+        ops.idx_unpack_packets; everything after is unchanged, and so are the return values -- ``lost`` is what is still lost after
+        recovery.  The result equals plain decompress_packets on the list in which every recovered packet is replaced by
+        packets.thin(sent_packet, c_q): the receiver's history departs from the sender's as after that thinning, less than after
+        the loss; with fec.books >= the books in use and at most one deficient packet per group it equals the lossless result."""
         from . import bitstream, packets
+        if fec is None and fec_packets is not None:
+            raise MvqError("decompress_packets: fec_packets needs fec=, the packets.Fec both ends agreed on")
         if not (len(infos) == len(tactile_packets) == len(audio_payloads)):
             raise MvqError("decompress_packets: one StreamInfo, one packet list and one audio payload per item")
         dev = self.proj_up.weight.device
@@ -844,20 +906,31 @@ class ProposedEval(_ProposedBase):
         if info.K != self.vq.n_embed:
             raise ValueError(f"decompress_packets: the stream has K = {info.K}, the model's codebook has {self.vq.n_embed}")
         P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
-        host = np.empty(B * P * (full + 1), np.uint8)                         # bodies, then nb_recv: one upload
-        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:].reshape(B, P)
+        n_fec = 0
+        if fec is not None:
+            self._fec_resolve(fec, info.K, info.nb, info.packet_tok)
+            frows, fgot = self._fec_gather(fec, fec_packets, info, B, "decompress_packets")
+            n_fec = frows.size + fgot.size
+        host = np.empty(B * P * (full + 1) + n_fec, np.uint8)                 # bodies, then nb_recv (then parity rows, flags): one upload
+        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
         for b in range(B):
             hb[b], hr[b] = packets.gather(tactile_packets[b], info)
+        if fec is not None:
+            o = B * P * (full + 1)
+            host[o:o + frows.size], host[o + frows.size:] = frows.reshape(-1), fgot.reshape(-1)
         codes = [self._payload(bitstream, p, self.A_QUANT.codebook_size, "audio") for p in audio_payloads]
         up = torch.from_numpy(host).to(dev)
-        idx, nb_valid = ops.idx_unpack_packets(up[:B * P * full].view(B, P, full), up[B * P * full:].view(B, P), info.K, info.nb,
-                                               info.T, info.packet_tok)
+        ub, ur = up[:B * P * full].view(B, P, full), up[B * P * full:B * P * (full + 1)].view(B, P)
+        if fec is not None:
+            ops.fec_recover(ub, ur, up[o:o + frows.size].view(frows.shape), up[o + frows.size:].view(fgot.shape), info, fec)
+        idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
         codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
         y = self.decode(codes_t, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc)
         return y, nb_valid == 0
 
     @torch.no_grad()
-    def compress_packets_av(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None, audio_books=None, audio_rate=None):
+    def compress_packets_av(self, a_1T, t_1T, books_use=None, packet_tok=None, rate=None, audio_books=None, audio_rate=None, fec=None,
+                            audio_fec=None):
         """compress_packets with the audio codes in layered packets too -> (infos, tactile_packets, audio_infos, audio_packets).
         The audio stream uses the tactile stream's format unchanged: per item StreamInfo(K = A_QUANT.codebook_size,
         nb = audio_books, Ta, packet_tok) and the framed packets of codes[b, :audio_books] (stage-major bodies: dropping the later
@@ -865,9 +938,19 @@ class ProposedEval(_ProposedBase):
         travel in.  The sender runs closed on both streams (encode_latents_with_indices; ``rate`` / ``audio_rate`` None = every
         packet whole).  Both sets of bodies are packed on the device and come back with both sets of counts in ONE device->host
         copy; packets.frame cuts each packet to its count.  decompress_packets_av with nothing lost returns T_DEC(the sender's
-        z_run) exactly."""
+        z_run) exactly.
+
+        ``fec`` / ``audio_fec`` (packets.Fec per stream; both None = today's path and return value): compress_packets(fec=) per
+        stream -- on the audio stream ``Fec.books`` counts stages -- the parity rows of both computed on the device from the packed
+        bodies and the device-side counts, still ONE device->host copy.  With either given the call returns the four elements and
+        then (fec_packets, audio_fec_packets), per item one list of parity packets per stream; a stream without a Fec gets empty
+        lists.  The closed loop: as compress_packets(fec=) says, on each stream."""
         from . import packets
         audio_rate, na_use, packet_tok = self._audio_rate_resolve(audio_rate, audio_books, packet_tok)
+        if fec is not None:
+            self._fec_resolve(fec, self.vq.n_embed, self._rate_books(books_use), packet_tok)
+        if audio_fec is not None:
+            self._fec_resolve(audio_fec, self.A_QUANT.codebook_size, na_use, packet_tok, what="audio_fec")
         _, codes, idx, nb_sent, na_sent = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use, rate=rate, packet_tok=packet_tok,
                                                                            audio_books=na_use, audio_rate=audio_rate)
         nb, B, T = idx.shape
@@ -876,21 +959,39 @@ class ProposedEval(_ProposedBase):
         bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
         abodies = ops.idx_pack_packets(codes[:, :na_use], ainfo.K, packet_tok, book_dim=1)
         full, afull = bodies.shape[2], abodies.shape[2]
-        cuts = np.cumsum([0, info.P * full, info.P, ainfo.P * afull, ainfo.P])
-        host = torch.cat([bodies.reshape(B, -1), nb_sent, abodies.reshape(B, -1), na_sent], dim=1).cpu().numpy()
-        hb, hc, ab, ac = (host[:, cuts[i]:cuts[i + 1]] for i in range(4))
+        parts = [bodies.reshape(B, -1), nb_sent, abodies.reshape(B, -1), na_sent]
+        if fec is not None:
+            parts.append(ops.fec_parity(bodies, nb_sent, info, fec).reshape(B, -1))
+        if audio_fec is not None:
+            parts.append(ops.fec_parity(abodies, na_sent, ainfo, audio_fec).reshape(B, -1))
+        cuts = np.cumsum([0] + [int(x.shape[1]) for x in parts])
+        host = torch.cat(parts, dim=1).cpu().numpy()
+        hb, hc, ab, ac, *hf = (host[:, cuts[i]:cuts[i + 1]] for i in range(len(parts)))
         hb, ab = hb.reshape(B, info.P, full), ab.reshape(B, ainfo.P, afull)
-        return ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b]) for b in range(B)],
-                [ainfo] * B, [packets.frame(ab[b], ainfo, nb_sent=ac[b]) for b in range(B)])
+        out = ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b]) for b in range(B)],
+               [ainfo] * B, [packets.frame(ab[b], ainfo, nb_sent=ac[b]) for b in range(B)])
+        if fec is None and audio_fec is None:
+            return out
+        tf = [packets.frame_fec(hf[0][b], info, fec) for b in range(B)] if fec is not None else [[] for _ in range(B)]
+        af = [packets.frame_fec(hf[-1][b], ainfo, audio_fec) for b in range(B)] if audio_fec is not None else [[] for _ in range(B)]
+        return out + (tf, af)
 
     @torch.no_grad()
-    def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None):
+    def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None,
+                              fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None):
         """-> (y [B,1,T], lost [B,T_lat] bool, audio_lost [B,Ta] bool) from whatever packets of BOTH streams arrived (missing,
         reordered, duplicated, thinned; items of one StreamInfo per stream): packets.gather per item and stream on the host, ONE
         upload of both streams' bodies and per-packet counts, the bit unpacking of both on the device (the audio indices are
         transposed to codes[B, nq, Ta] there), then decode(nb_valid=, na_valid=).  ``audio_lost``: the audio tokens no stage of
-        which arrived; they are +0 to the predictor (decode_latents)."""
+        which arrived; they are +0 to the predictor (decode_latents).
+
+        ``fec`` / ``fec_packets`` / ``audio_fec`` / ``audio_fec_packets``: decompress_packets(fec=) per stream -- packets.gather_fec per
+        item and stream, the parity rows and ``got`` flags of both behind the existing arrays in the ONE upload, ops.fec_recover on
+        each stream ahead of its ops.idx_unpack_packets.  The return values do not change; ``lost`` / ``audio_lost`` are what is still
+        lost after recovery.  The closed loop: as decompress_packets(fec=) says, on each stream."""
         from . import packets
+        if (fec is None and fec_packets is not None) or (audio_fec is None and audio_fec_packets is not None):
+            raise MvqError("decompress_packets_av: fec_packets / audio_fec_packets need fec= / audio_fec=, the packets.Fec both ends agreed on")
         if not (len(infos) == len(tactile_packets) == len(audio_infos) == len(audio_packets)):
             raise MvqError("decompress_packets_av: one StreamInfo and one packet list per item and stream")
         dev = self.proj_up.weight.device
@@ -912,27 +1013,39 @@ class ProposedEval(_ProposedBase):
                              "modalities advance together")
         P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
         Pa, afull = ainfo.P, packets.body_bytes(ainfo.packet_tok, ainfo.nb, ainfo.K)
-        cuts = np.cumsum([0, B * P * full, B * P, B * Pa * afull, B * Pa])
-        host = np.empty(cuts[-1], np.uint8)                                   # both streams' bodies and counts: one upload
+        extra = []                                                            # (fec, info, rows, got, slot of the stream's bodies)
+        for f, fp, inf, slot, what in ((fec, fec_packets, info, 0, "fec"), (audio_fec, audio_fec_packets, ainfo, 2, "audio_fec")):
+            if f is not None:
+                self._fec_resolve(f, inf.K, inf.nb, inf.packet_tok, what=what)
+                extra.append((f, inf, *self._fec_gather(f, fp, inf, B, "decompress_packets_av", what), slot))
+        cuts = np.cumsum([0, B * P * full, B * P, B * Pa * afull, B * Pa] + [x.size for e in extra for x in e[2:4]])
+        host = np.empty(cuts[-1], np.uint8)                                   # both streams' bodies and counts (parity rows, flags): one upload
         hb, hr, ab, ar = (host[cuts[i]:cuts[i + 1]] for i in range(4))
         hb, hr, ab, ar = hb.reshape(B, P, full), hr.reshape(B, P), ab.reshape(B, Pa, afull), ar.reshape(B, Pa)
         for b in range(B):
             hb[b], hr[b] = packets.gather(tactile_packets[b], info)
             ab[b], ar[b] = packets.gather(audio_packets[b], ainfo)
+        for i, e in enumerate(extra):
+            host[cuts[4 + 2 * i]:cuts[5 + 2 * i]], host[cuts[5 + 2 * i]:cuts[6 + 2 * i]] = e[2].reshape(-1), e[3].reshape(-1)
         up = torch.from_numpy(host).to(dev)
         ub, ur, uab, uar = (up[cuts[i]:cuts[i + 1]] for i in range(4))
-        idx, nb_valid = ops.idx_unpack_packets(ub.view(B, P, full), ur.view(B, P), info.K, info.nb, info.T, info.packet_tok)
-        aidx, na_valid = ops.idx_unpack_packets(uab.view(B, Pa, afull), uar.view(B, Pa), ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
+        ub, ur, uab, uar = ub.view(B, P, full), ur.view(B, P), uab.view(B, Pa, afull), uar.view(B, Pa)
+        for i, (f, inf, rows, got, slot) in enumerate(extra):
+            ops.fec_recover(*((ub, ur) if slot == 0 else (uab, uar)), up[cuts[4 + 2 * i]:cuts[5 + 2 * i]].view(rows.shape),
+                            up[cuts[5 + 2 * i]:cuts[6 + 2 * i]].view(got.shape), inf, f)
+        idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
+        aidx, na_valid = ops.idx_unpack_packets(uab, uar, ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
         codes = aidx.permute(1, 0, 2).contiguous()                            # [nq, B, Ta] -> [B, nq, Ta], on the device
         y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid)
         return y, nb_valid == 0, na_valid == 0
 
-    def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None):
+    def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
+                        fec=None, audio_fec=None):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
         time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
-                              out_rate=out_rate, graph=graph, audio=audio)
+                              out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec)
 
     def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
         """A pool of up to ``slots`` independent receiver sessions on this model (stream.StreamReceiverPool): ``open`` a
@@ -942,13 +1055,14 @@ class ProposedEval(_ProposedBase):
         return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
                                   out_rate=out_rate)
 
-    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None):
+    def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None,
+                      fec=None, audio_fec=None):
         """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
         get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output
         equals compress_packets on the whole item byte for byte (with ``rate``, a packets.Rate: compress_packets(rate=))."""
         from .stream import StreamSender
         return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate, audio=audio,
-                            audio_books=audio_books, audio_rate=audio_rate)
+                            audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec)
 
     def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None):
         """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,

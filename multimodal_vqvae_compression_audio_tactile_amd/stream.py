@@ -303,7 +303,7 @@ class _SenderCore:
     tokens go through a dense [G, C] copy (ops.stream_rows), everything else is the same launches on the group's window."""
 
     def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape, rate=None, audio="codes", audio_books=None,
-                 audio_rate=None):
+                 audio_rate=None, fec=None, audio_fec=None):
         import torch
         from . import proposed
         from .packets import StreamInfo, body_bytes, _check
@@ -336,6 +336,13 @@ class _SenderCore:
         if rate is not None:
             net._rate_resolve(rate, books_use, packet_tok)                             # ValueError before any session state exists
         self.rate = rate
+        if audio_fec is not None and not self.audio_packets:
+            raise ValueError(f"{who}: audio_fec goes with audio='packets'")
+        if fec is not None:                                                            # ValueError before any session state exists
+            net._fec_resolve(fec, self.K, self.nb, packet_tok)
+        if audio_fec is not None:
+            net._fec_resolve(audio_fec, self.K_audio, self.na, packet_tok, what="audio_fec")
+        self.fec, self.audio_fec = fec, audio_fec
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
         self.full = body_bytes(packet_tok, self.nb, self.K)
@@ -375,9 +382,13 @@ class _SenderCore:
         """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
         uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place.  With ``self.rate`` the loop
         runs closed (on the books each packet carries and on qa from the codes, as the receiver will) and the bodies come back as
-        uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back."""
+        uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back.  With ``self.fec`` /
+        ``self.audio_fec`` the parity rows of the window's packets (ops.fec_parity on the packed bodies and the device-side counts;
+        the window starts on a chunk, so its groups are the item's) follow everything else in the same uint8 [G, ...] array."""
         import torch
         from . import ops
+        from .packets import StreamInfo
+        n_tok = hi - lo
         if self.audio_packets:      # uint8 [G, P*full + P + P*afull + P]: tactile bodies, counts, audio bodies, counts: one read-back
             assert sl is None                                                          # the pools take no audio packets
             _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
@@ -387,7 +398,13 @@ class _SenderCore:
             bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
             abodies = ops.idx_pack_packets(codes[:, :self.na], self.K_audio, self.packet_tok, book_dim=1)
             G = bodies.shape[0]
-            return torch.cat([bodies.reshape(G, -1), nb_sent, abodies.reshape(G, -1), na_sent], dim=1), codes
+            parts = [bodies.reshape(G, -1), nb_sent, abodies.reshape(G, -1), na_sent]
+            if self.fec is not None:
+                parts.append(ops.fec_parity(bodies, nb_sent, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec).reshape(G, -1))
+            if self.audio_fec is not None:
+                parts.append(ops.fec_parity(abodies, na_sent, StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok),
+                                            self.audio_fec).reshape(G, -1))
+            return torch.cat(parts, dim=1), codes
         qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
         if self.rate is not None:
@@ -396,10 +413,19 @@ class _SenderCore:
             _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
                                                          packet_tok=self.packet_tok)
             bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
-            return torch.cat([bodies.reshape(bodies.shape[0], -1), nb_sent], dim=1), codes
+            parts = [bodies.reshape(bodies.shape[0], -1), nb_sent]
+            if self.fec is not None:
+                parts.append(ops.fec_parity(bodies, nb_sent, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec)
+                             .reshape(bodies.shape[0], -1))
+            return torch.cat(parts, dim=1), codes
         _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=carry, z_last_out=carry)
         if sl is not None:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
+        if self.fec is not None:
+            assert sl is None                                                          # the pools take no fec
+            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
+            rows = ops.fec_parity(bodies, None, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec)
+            return torch.cat([bodies.reshape(bodies.shape[0], -1), rows.reshape(bodies.shape[0], -1)], dim=1), codes
         return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
 
 
@@ -433,13 +459,22 @@ class StreamSender(_SenderCore):
     packets too.  ``push`` then returns (tactile_packets, audio_packets), both with the stream's sequence numbers, and ``finish``
     (tactile_packets, audio_packets, StreamInfo, audio StreamInfo); per item their concatenation equals compress_packets_av byte
     for byte.  Both loops run closed (``rate`` None is Rate()); both streams' bodies and counts come back in the push's ONE
-    read-back, so ``graph=True`` keeps working.  The default ``audio="codes"`` is the behaviour above exactly."""
+    read-back, so ``graph=True`` keeps working.  The default ``audio="codes"`` is the behaviour above exactly.
+
+    ``fec`` / ``audio_fec`` (packets.Fec; ``audio_fec`` needs ``audio="packets"``; both None: the behaviour above exactly): forward
+    error correction, DESIGN.md section 20.  The parity launch sits behind the packing inside the device step -- so inside the
+    captured steady step -- and the parity rows ride behind everything else in the push's ONE read-back.  Every ``push`` then
+    returns its usual values and then the chunk's parity packets: (tactile_packets, audio_codes, fec_packets), or with audio
+    packets (tactile_packets, audio_packets, fec_packets, audio_fec_packets) where a stream without a Fec gets empty lists;
+    ``finish`` returns its usual values and then the same parity lists.  Groups are numbered across the stream: chunk c's start at
+    c * (16 // packet_tok // group).  Per item the concatenation equals compress_packets(fec=) / compress_packets_av(fec=,
+    audio_fec=) byte for byte, data and parity."""
 
     def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None,
-                 audio_rate=None):
+                 audio_rate=None, fec=None, audio_fec=None):
         packet_tok, batch = int(packet_tok), int(batch)
         super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP), rate=rate, audio=audio,
-                         audio_books=audio_books, audio_rate=audio_rate)               # buffer: audio rows, then tactile rows
+                         audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec)   # buffer: audio rows, then tactile rows
         self.batch, self.graph = batch, bool(graph)
         self.fill = 0                                                                  # valid samples of every buffer row
         self.start = 0                                                                 # the token buf[:, 0] belongs to
@@ -472,17 +507,39 @@ class StreamSender(_SenderCore):
 
     def _framed(self, bodies, codes, n_tok):
         """ONE device-to-host copy of the bodies, then the headers with the stream's sequence numbers."""
-        from .packets import StreamInfo, frame
+        from .packets import StreamInfo, frame, frame_fec
         info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
         host = bodies.cpu().numpy()
         base = self.chunk * CHUNK_TOK // self.packet_tok
+        B = self.batch
+
+        def parity(f, inf, rows):                                                      # the stream's group numbers
+            if f is None:
+                return [[] for _ in range(B)]
+            return [frame_fec(rows[b], inf, f, seq_base=self.chunk * (CHUNK_TOK // self.packet_tok // f.group)) for b in range(B)]
+
+        def rows_bytes(f, inf):
+            if f is None:
+                return 0
+            g, _, G, W = f.resolve(inf)
+            return G * (g + W)
+
         if self.audio_packets:
             import numpy as np
             ainfo = StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok)
-            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P])
-            hb, hc, ab, ac = (host[:, cuts[i]:cuts[i + 1]] for i in range(4))
-            return ([frame(hb[b], info, nb_sent=hc[b], seq_base=base) for b in range(self.batch)],
-                    [frame(ab[b], ainfo, nb_sent=ac[b], seq_base=base) for b in range(self.batch)])
+            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P, rows_bytes(self.fec, info),
+                              rows_bytes(self.audio_fec, ainfo)])
+            hb, hc, ab, ac, hf, af = (host[:, cuts[i]:cuts[i + 1]] for i in range(6))
+            out = ([frame(hb[b], info, nb_sent=hc[b], seq_base=base) for b in range(B)],
+                   [frame(ab[b], ainfo, nb_sent=ac[b], seq_base=base) for b in range(B)])
+            if self.fec is None and self.audio_fec is None:
+                return out
+            return out + (parity(self.fec, info, hf), parity(self.audio_fec, ainfo, af))
+        if self.fec is not None:                                                       # bodies, (counts,) parity rows
+            host = host.reshape(B, -1)
+            cut, n_cnt = info.P * self.full, 0 if self.rate is None else info.P
+            return ([frame(host[b, :cut], info, nb_sent=host[b, cut:cut + n_cnt] if n_cnt else None, seq_base=base) for b in range(B)],
+                    codes, parity(self.fec, info, host[:, cut + n_cnt:]))
         if self.rate is None:
             return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
         cut = host.shape[1] - info.P                                                   # bodies, then the book count of each packet
@@ -490,9 +547,11 @@ class StreamSender(_SenderCore):
 
     def _nothing(self):
         import torch
+        none = lambda: [[] for _ in range(self.batch)]
         if self.audio_packets:
-            return [[] for _ in range(self.batch)], [[] for _ in range(self.batch)]
-        return [[] for _ in range(self.batch)], torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
+            return (none(), none()) + ((none(), none()) if self.fec is not None or self.audio_fec is not None else ())
+        return (none(), torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)) + \
+            ((none(),) if self.fec is not None else ())
 
     def _open(self, what):
         from ._lib import MvqError
@@ -541,12 +600,16 @@ class StreamSender(_SenderCore):
         with torch.no_grad():
             if not st.emit:                                              # an item shorter than one token: nothing to send
                 self.finished = True
-                return self._nothing() + self._infos(self.start + max(st.hi, 0))
+                return self._finished(self._nothing(), self.start + max(st.hi, 0))
             x = self._upload(a, t, n) if n else torch.empty(2 * self.batch, 0, device=self.dev)
             bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi)
             out = self._framed(bodies, codes, st.hi - st.lo)
             self.fill, self.chunk, self.finished = st.fill, st.chunk, True
-            return out + self._infos(self.start + st.hi)
+            return self._finished(out, self.start + st.hi)
+
+    def _finished(self, out, T):
+        """finish's return value: the two data elements, the StreamInfo(s), then the parity lists (sessions with a Fec)."""
+        return tuple(out[:2]) + self._infos(T) + tuple(out[2:])
 
     def _infos(self, T):
         from .packets import StreamInfo
@@ -599,11 +662,16 @@ class _ReceiverCore:
     int32 device copy, on those sessions of a pool: the same launches under another addressing (csrc/stream.hip), which is why a
     pool session computes what a solo one does."""
 
-    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None):
+    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check, body_bytes
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        if audio_fec is not None and audio is None:
+            raise ValueError("StreamReceiver: audio_fec goes with audio=(K_a, na)")
+        if fec is not None:
+            net._fec_resolve(fec, K, nb, packet_tok)
+        self.fec, self.audio_fec = fec, audio_fec
         self.audio = None                                                              # (K_a, na): the audio codes arrive as packets
         if audio is not None:
             _f32_only("StreamReceiver")
@@ -613,6 +681,8 @@ class _ReceiverCore:
                                  f"K = {net.A_QUANT.codebook_size} and {net.A_QUANT.n_codebooks} stages")
             _check(StreamInfo(K_a, na, CHUNK_TOK, packet_tok))
             self.audio, self.afull = (K_a, na), body_bytes(packet_tok, na, K_a)
+            if audio_fec is not None:
+                net._fec_resolve(audio_fec, K_a, na, packet_tok, what="audio_fec")
         self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
@@ -656,15 +726,30 @@ class _ReceiverCore:
         token moves on in place; for slots through a dense [G, C] copy, not written back for sessions that end (``last``: the
         next open() resets the slot)."""
         from . import ops
+        from .packets import StreamInfo
         G, full = (self.carry.shape[0] if codes is None else codes.shape[0]), self.full
         P = (n + self.packet_tok - 1) // self.packet_tok
-        idx, nbv = ops.idx_unpack_packets(up[:G * P * full].view(G, P, full), up[G * P * full:G * P * (full + 1)].view(G, P), self.K, self.nb,
-                                          n, self.packet_tok)
+        ub, ur = up[:G * P * full].view(G, P, full), up[G * P * full:G * P * (full + 1)].view(G, P)
+        o_fec = G * P * (full + 1) + (G * P * (self.afull + 1) if self.audio is not None else 0)   # the parity rows, flags: behind everything
+
+        def recover(f, inf, bodies, counts, o):               # packets.fec_recover in place, ahead of the unpack -> the offset behind
+            if f is None:
+                return o
+            g, _, Gr, W = f.resolve(inf)
+            assert sl is None                                 # the pools take no fec
+            nr = G * Gr * (g + W)
+            ops.fec_recover(bodies, counts, up[o:o + nr].view(G, Gr, g + W), up[o + nr:o + nr + G * Gr].view(G, Gr), inf, f)
+            return o + nr + G * Gr
+
+        o_fec = recover(self.fec, StreamInfo(self.K, self.nb, n, self.packet_tok), ub, ur, o_fec)
+        idx, nbv = ops.idx_unpack_packets(ub, ur, self.K, self.nb, n, self.packet_tok)
         nav = None
         if self.audio is not None:                            # behind the tactile arrays: the audio bodies, then their counts
             assert sl is None and codes is None
             o, afull = G * P * (full + 1), self.afull
-            aidx, nav = ops.idx_unpack_packets(up[o:o + G * P * afull].view(G, P, afull), up[o + G * P * afull:].view(G, P), self.audio[0],
+            uab, uar = up[o:o + G * P * afull].view(G, P, afull), up[o + G * P * afull:o + G * P * (afull + 1)].view(G, P)
+            recover(self.audio_fec, StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), uab, uar, o_fec)
+            aidx, nav = ops.idx_unpack_packets(uab, uar, self.audio[0],
                                                self.audio[1], n, self.packet_tok)
             codes = aidx.permute(1, 0, 2).contiguous()                                 # [na, G, n] -> [G, na, n], on the device
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
@@ -733,14 +818,25 @@ class StreamReceiver(_ReceiverCore):
     positional argument means the same) gather both streams, both go
     up in the ONE upload, both are unpacked on the device and the per-token stage counts go into the chunk's from_codes
     (decode_latents(na_valid=)); the steady step stays one captured graph with static body and count buffers.  The concatenated
-    output equals decompress_packets_av on the same packets.  ``audio=None``: today's behaviour exactly."""
+    output equals decompress_packets_av on the same packets.  ``audio=None``: today's behaviour exactly.
 
-    def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None):
+    ``fec`` / ``audio_fec`` (packets.Fec, the sender's; ``audio_fec`` needs ``audio=``; both None: today's behaviour exactly):
+    ``push(..., fec_packets=, audio_fec_packets=)`` and ``finish(...)`` likewise take, per item, whatever parity packets of the chunk
+    arrived (None: none did).  packets.gather_fec(seq_base=the chunk's first group) per item, the parity rows and ``got`` flags behind
+    the existing arrays in the ONE upload, ops.fec_recover in place ahead of each stream's unpack: recovery is inside the captured
+    steady step, whose only input stays the static upload buffer, so the graph replays under any loss pattern.  A parity packet of
+    an earlier chunk is counted in ``late`` and ignored, as a late data packet is.  The concatenated output equals
+    decompress_packets(fec=) / decompress_packets_av(fec=, audio_fec=) on the same packets."""
+
+    def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
+                 fec=None, audio_fec=None):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
             raise ValueError("StreamReceiver: batch must be at least 1")
-        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio)
+        if fec is not None or audio_fec is not None:
+            _f32_only("StreamReceiver")
+        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -749,25 +845,38 @@ class StreamReceiver(_ReceiverCore):
         self._g = None                                                                 # (graph, up_static, codes_static, y_static)
 
     # ------------------------------------------------------------------------------------------------------------ stages
-    def _gather(self, tactile_packets, n, audio_packets=None):
+    def _gather(self, tactile_packets, n, audio_packets=None, fec_packets=None, audio_fec_packets=None):
         """Host: per item whatever packets of this chunk arrived -> one uint8 array, bodies then counts (then, with audio
-        packets, the audio bodies and their counts)."""
+        packets, the audio bodies and their counts; then, with a Fec, per stream the parity rows and their ``got`` flags)."""
         import numpy as np
-        from .packets import StreamInfo, gather
+        from .packets import StreamInfo, gather, gather_fec
         info = StreamInfo(self.K, self.nb, n, self.packet_tok)
         B, P, full = self.batch, info.P, self.full
         afull = self.afull if self.audio is not None else 0
         n_audio = B * P * (afull + 1) if self.audio is not None else 0        # the audio bodies and their counts
-        host = np.empty(B * P * (full + 1) + n_audio, np.uint8)
+        par = []                                                              # (fec, info, the item's parity packets, offset)
+        n_fec = 0
+        for f, inf, pk in ((self.fec, info, fec_packets),
+                           (self.audio_fec, StreamInfo(*self.audio, n, self.packet_tok) if self.audio is not None else None, audio_fec_packets)):
+            if f is not None:
+                g, _, Gr, W = f.resolve(inf)
+                par.append((f, inf, [[] for _ in range(B)] if pk is None else self._packets_ok(pk), B * P * (full + 1) + n_audio + n_fec,
+                            g, Gr, W))
+                n_fec += B * Gr * (g + W + 1)
+        host = np.empty(B * P * (full + 1) + n_audio + n_fec, np.uint8)
         hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
         base, late = self.tokens // self.packet_tok, []
         for b in range(B):
             hb[b], hr[b] = gather(tactile_packets[b], info, seq_base=base, late=late)
         if self.audio is not None:
             ainfo, o = StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), B * P * (full + 1)
-            ab, ar = host[o:o + B * P * afull].reshape(B, P, afull), host[o + B * P * afull:].reshape(B, P)
+            ab, ar = host[o:o + B * P * afull].reshape(B, P, afull), host[o + B * P * afull:o + B * P * (afull + 1)].reshape(B, P)
             for b in range(B):
                 ab[b], ar[b] = gather(audio_packets[b], ainfo, seq_base=base, late=late)
+        for f, inf, pk, o, g, Gr, W in par:
+            fr, fg = host[o:o + B * Gr * (g + W)].reshape(B, Gr, g + W), host[o + B * Gr * (g + W):o + B * Gr * (g + W + 1)].reshape(B, Gr)
+            for b in range(B):                                                # the chunk's first group, in the stream's numbers
+                fr[b], fg[b] = gather_fec(pk[b], inf, f, seq_base=base // g, late=late)
         self.late += len(late)
         return host
 
@@ -783,7 +892,11 @@ class StreamReceiver(_ReceiverCore):
         return tactile_packets
 
     # ------------------------------------------------------------------------------------------------------------ session
-    def push(self, tactile_packets, audio_codes=None, *, audio_packets=None):
+    def _fec_args(self, what, fec_packets, audio_fec_packets):
+        if (fec_packets is not None and self.fec is None) or (audio_fec_packets is not None and self.audio_fec is None):
+            raise ValueError(f"StreamReceiver.{what}: fec_packets / audio_fec_packets need a session opened with fec= / audio_fec=")
+
+    def push(self, tactile_packets, audio_codes=None, *, audio_packets=None, fec_packets=None, audio_fec_packets=None):
         """One chunk: ``tactile_packets`` = ``batch`` iterables of the packets of chunk c that arrived (the stream's sequence
         numbers [c*16/packet_tok, (c+1)*16/packet_tok); missing, reordered, duplicated or thinned), ``audio_codes`` int [B, 32, 16].
         -> y [B, 1, n_emit] (1920 samples for the first push, then 5120; a third of that at out_rate=3000, less the resampler's
@@ -794,15 +907,16 @@ class StreamReceiver(_ReceiverCore):
         if self.finished:
             raise MvqError("StreamReceiver: push after finish")
         audio_codes = self._audio_arg("push", audio_codes, audio_packets)
+        self._fec_args("push", fec_packets, audio_fec_packets)
         if audio_codes is None:
             raise ValueError("StreamReceiver.push: a chunk needs its audio " + ("packets" if self.audio is not None else "codes"))
         tactile_packets = self._packets_ok(tactile_packets)
         n = CHUNK_TOK
         if self.audio is not None:                                            # the chunk's audio PACKETS
-            host, codes = self._gather(tactile_packets, n, self._packets_ok(audio_codes)), None
+            host, codes = self._gather(tactile_packets, n, self._packets_ok(audio_codes), fec_packets, audio_fec_packets), None
         else:
             codes = self._codes(audio_codes, CHUNK_TOK, CHUNK_TOK)
-            host = self._gather(tactile_packets, n)
+            host = self._gather(tactile_packets, n, None, fec_packets)
         plan = self._plan(n, False)
         consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)                   # the samples emitted so far
         with torch.no_grad():
@@ -824,7 +938,7 @@ class StreamReceiver(_ReceiverCore):
             raise ValueError(f"StreamReceiver.{what}: audio_packets or audio_codes, not both")
         return audio_packets
 
-    def finish(self, tactile_packets=None, audio_codes=None, tokens=None, *, audio_packets=None):
+    def finish(self, tactile_packets=None, audio_codes=None, tokens=None, *, audio_packets=None, fec_packets=None, audio_fec_packets=None):
         """Flush: optionally a last partial chunk of 1..15 tokens (its packets and audio_codes [B, 32, n]; with audio=(K_a, na)
         its packets of both streams and ``tokens`` = n, which no lost packet can tell), then every remaining sample up to
         320*T - 8.  Runs eagerly.  The session accepts nothing afterwards."""
@@ -833,6 +947,7 @@ class StreamReceiver(_ReceiverCore):
         if self.finished:
             raise MvqError("StreamReceiver: finish after finish")
         audio_codes = self._audio_arg("finish", audio_codes, audio_packets)
+        self._fec_args("finish", fec_packets, audio_fec_packets)
         if (tactile_packets is None) != (audio_codes is None):
             raise ValueError("StreamReceiver.finish: the last chunk needs both its packets and its audio codes")
         if tokens is not None and (self.audio is None or audio_codes is None):
@@ -843,12 +958,12 @@ class StreamReceiver(_ReceiverCore):
             if tokens is None or not 1 <= int(tokens) <= CHUNK_TOK - 1:
                 raise ValueError(f"StreamReceiver.finish: tokens = {tokens!r}; a last chunk of audio packets has 1..{CHUNK_TOK - 1} tokens")
             n = int(tokens)
-            host = self._gather(self._packets_ok(tactile_packets), n, self._packets_ok(audio_codes))
+            host = self._gather(self._packets_ok(tactile_packets), n, self._packets_ok(audio_codes), fec_packets, audio_fec_packets)
         elif audio_codes is not None:
             tactile_packets = self._packets_ok(tactile_packets)
             codes = self._codes(audio_codes, 1, CHUNK_TOK - 1)
             n = int(codes.shape[2])
-            host = self._gather(tactile_packets, n)
+            host = self._gather(tactile_packets, n, None, fec_packets)
         plan = self._plan(n, True)
         consumed = HOP * max(0, self.tokens - DEC_HALO_TOK)
         with torch.no_grad():
@@ -867,6 +982,8 @@ class StreamReceiver(_ReceiverCore):
             codes_s = None if codes is None else codes.to(self.dev).long().clone()
             g, y_s = _capture(self.dev, (self.hist, self.carry), lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
+            if self.fec is not None or self.audio_fec is not None:            # the eager run before the capture recovered in place
+                up_s.copy_(torch.from_numpy(host))
         else:
             g, up_s, codes_s, y_s = self._g
             up_s.copy_(torch.from_numpy(host))
