@@ -40,7 +40,8 @@ extern "C" {
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
- * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8;
+ * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8; audio concealment: mvq_attention_masked_f32,
+ * mvq_attention_seq_masked_f32, mvq_hold_fill_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
@@ -370,6 +371,31 @@ int mvq_attention_f32(const float* q, const float* k, const float* v, float* ctx
 int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float* ctx,
                           int batch, int heads, int dh, int tq, int tk,
                           size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
+
+/* Attention under a KEY MASK (the receiver's audio concealment "mask": a lost audio token is not a key).  kmask is uint8,
+ * item b's key j at b*m_stride_b + j, nonzero = present; J(b) = the ascending list of present j.  The result is bit-equal to
+ * mvq_attention_f32 / mvq_attention_seq_f32 on the item's K and V with the columns compacted to J(b) and Tk = |J(b)|: in the
+ * order of oracle/c/oracle.c::orc_attention, score = one fma chain over d ascending from +0 divided by sqrtf(dh); max, det_exp
+ * and l over J ascending; p_j / l; ctx[d] one fma chain over J ascending.  |J(b)| = 0 gives ctx = +0 for that item.  The K and V
+ * values of an absent column never reach the result (NaN or 1e30 there changes nothing): the chunk kernel compacts while it
+ * stages (one ballot per wave, slot = popcount of the present keys below), the sequence kernel skips absent columns in every
+ * pass (their e_j is +0, whose addition to l is exact; the value chain is predicated, not multiplied).  kmask == NULL is the
+ * unmasked launch.  Shape limits, addressing and refusals (before any launch) are those of the unmasked entry points.
+ * Forward only. */
+int mvq_attention_masked_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                             int batch, int heads, int dh, int tq, int tk,
+                             size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b,
+                             void* stream);
+int mvq_attention_seq_masked_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                 int batch, int heads, int dh, int tq, int tk,
+                                 size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b,
+                                 void* stream);
+
+/* Hold fill (the receiver's audio concealment "hold"), in place on contiguous x[batch, c, t]: y[b,c,t] = x[b,c,s(b,t)] with
+ * s(b,t) the largest t' <= t with valid[b,t'] != 0 (valid: uint8 [batch, t]); where there is none, carry[b,c] (carry: [batch, c]
+ * or NULL = +0).  Afterwards carry[b,c] = y[b,c,t-1] (t > 0), so a sequence is filled piece by piece.  Pure copies: -0, NaN and
+ * inf pass unchanged.  Only tokens with valid == 0 are written. */
+int mvq_hold_fill_f32(float* x, const uint8_t* valid, float* carry, int batch, int c, int t, void* stream);
 
 /* y = gelu_erf(x) elementwise (nn.GELU() in CrossPredictor.ffn). */
 int mvq_gelu_f32(const float* x, float* y, size_t n, void* stream);

@@ -900,6 +900,33 @@ int mvq_attention_f32(const float* q, const float* k, const float* v, float* ctx
     return e == hipSuccess ? MVQ_OK : hipfail(e, "attention");
 }
 
+int mvq_attention_masked_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                             int batch, int heads, int dh, int tq, int tk,
+                             size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b, void* stream)
+{
+    if (!kmask || tk <= 0)                   /* NULL mask, or no key to mask: the existing launch and the existing bits */
+        return mvq_attention_f32(q, k, v, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, stream);
+    if (batch < 0 || heads <= 0 || dh <= 0 || tq < 0 || tk > 64 || tq > 64 || (size_t)dh * (tq + 2 * tk) + (size_t)tq * tk > 16384)
+        return fail(MVQ_EINVAL, "attention_masked: bad shape (Tq, Tk <= 64; head slices must fit 64 KiB of LDS)");
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !ctx || !k || !v) return fail(MVQ_EINVAL, "attention_masked: null tensor");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_masked(q, k, v, kmask, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b,
+                                                k_stride_c, m_stride_b, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_masked");
+}
+
+int mvq_hold_fill_f32(float* x, const uint8_t* valid, float* carry, int batch, int c, int t, void* stream)
+{
+    if (batch < 0 || c < 0 || t < 0 || (c + 15) / 16 > 65535) return fail(MVQ_EINVAL, "hold_fill: bad shape");
+    if ((size_t)batch * c * t == 0) return MVQ_OK;
+    if (!x || !valid) return fail(MVQ_EINVAL, "hold_fill: null tensor");
+    hipError_t e = mvq::launch_hold_fill(x, valid, carry, batch, c, t, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "hold_fill");
+}
+
 int mvq_gelu_f32(const float* x, float* y, size_t n, void* stream)
 {
     if ((!x || !y) && n) return fail(MVQ_EINVAL, "gelu: null tensor");
@@ -1076,6 +1103,27 @@ int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float*
     if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
     hipError_t e = mvq::launch_attention_seq(q, k, v, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq");
+}
+
+int mvq_attention_seq_masked_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                 int batch, int heads, int dh, int tq, int tk,
+                                 size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b, void* stream)
+{
+    if (!kmask || tk <= 0)                   /* NULL mask, or no key to mask: the existing launch and the existing bits */
+        return mvq_attention_seq_f32(q, k, v, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, stream);
+    if (batch < 0 || heads <= 0 || dh <= 0 || tq < 0 || tq > kAttnSeqMaxT || tk > kAttnSeqMaxT)
+        return fail(MVQ_EINVAL, "attention_seq_masked: bad shape (Tq, Tk <= %d)", kAttnSeqMaxT);
+    int qt = 0, kt = 0;
+    size_t nf = 0;
+    if (!mvq::attn_seq_plan(dh, tk, &qt, &kt, &nf)) return fail(MVQ_EINVAL, "attention_seq_masked: dh = %d does not fit a query tile in LDS", dh);
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !ctx || !k || !v) return fail(MVQ_EINVAL, "attention_seq_masked: null tensor");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_seq_masked(q, k, v, kmask, ctx, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b,
+                                                    k_stride_c, m_stride_b, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq_masked");
 }
 
 size_t mvq_attention_seq_bwd_scratch_bytes(int batch, int heads, int tq, int tk)

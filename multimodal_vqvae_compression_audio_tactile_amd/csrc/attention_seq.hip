@@ -8,6 +8,10 @@
 // Structure: one block per (batch, head, query tile of QT rows).  The QT probability rows stay resident in LDS (row pitch
 // TkP); K and V go through one [dh][KT] LDS tile, K in the score pass and V in the value pass.  QT is the largest of 16, 8, 4,
 // 2, 1 whose footprint fits the 160 KiB of a CU (attn_seq_plan); at Tk = 8192, dh = 128 that is QT = 4.
+// MASKED (mvq_attention_seq_masked_f32, forward only): key j of item b is present when kmask[b*msb + j] != 0.  P keeps its
+// pitch and the plan its footprint; absent columns are not staged, the max / exp / value passes skip them and their e_j is
+// written as +0, whose addition to l is exact; the value chain is predicated by the tile's ballot of the mask, never
+// multiplied.  So the result is the plain kernel's on the compacted K / V, bit for bit, and no present key gives +0.
 //
 // Backward (not part of the bit-exact contract; checked against float64 autograd): four launches over a caller scratch of
 // 2 * B*H*Tq*Tk floats (P and dS), for Tq, Tk <= 512:
@@ -49,10 +53,11 @@ bool attn_seq_plan(int dh, int tk, int* qt, int* kt, size_t* lds_floats)
     return false;
 }
 
-template <int NPT>
+template <int NPT, bool MASKED>
 __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, float* __restrict__ ctx,
-    int H, int dh, int Tq, int Tk, int QT, int KT, int TkP, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+    int H, int dh, int Tq, int Tk, int QT, int KT, int TkP, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+    const uint8_t* __restrict__ kmask, size_t msb)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* P = sm;                                 // [QT][TkP]
@@ -64,6 +69,7 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
     const int i0 = blockIdx.y * QT;
     const int nq = min(QT, Tq - i0);
     const size_t qo = (size_t)b * qsb + (size_t)hd * dh * qsc, ko = (size_t)b * ksb + (size_t)hd * dh * ksc;
+    const uint8_t* mk = MASKED ? kmask + (size_t)b * msb : nullptr;          // this item's mask row
     for (int e = tid; e < dh * QT; e += ATT_SEQ_THREADS) {
         const int d = e / QT, i = e - d * QT;
         Qs[e] = i < nq ? Q[qo + (size_t)d * qsc + i0 + i] : 0.0f;
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
         __syncthreads();                                                     // previous tile consumed (and Qs written)
         for (int e = tid; e < dh * kt; e += ATT_SEQ_THREADS) {
             const int d = e / kt, jj = e - d * kt;
-            T[d * KT + jj] = K[ko + (size_t)d * ksc + j0 + jj];
+            T[d * KT + jj] = (!MASKED || mk[j0 + jj] != 0) ? K[ko + (size_t)d * ksc + j0 + jj] : 0.0f;
         }
         __syncthreads();
         for (int p = tid; p < nq * kt; p += ATT_SEQ_THREADS) {
@@ -100,10 +106,10 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
         for (int i = wave; i < nq; i += ATT_SEQ_THREADS / 64) {
             float* pr = P + (size_t)i * TkP;
             float m = -__builtin_inff();
-            for (int j = lane; j < Tk; j += 64) m = __builtin_fmaxf(m, pr[j]);
+            for (int j = lane; j < Tk; j += 64) if (!MASKED || mk[j] != 0) m = __builtin_fmaxf(m, pr[j]);
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, o));
-            for (int j = lane; j < Tk; j += 64) pr[j] = det_exp(pr[j] - m);
+            for (int j = lane; j < Tk; j += 64) pr[j] = (!MASKED || mk[j] != 0) ? det_exp(pr[j] - m) : 0.0f;
         }
         __syncthreads();
         if (tid < nq) {
@@ -120,7 +126,7 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
         __syncthreads();
         for (int e = tid; e < nq * Tk; e += ATT_SEQ_THREADS) {
             const int i = e / Tk, j = e - i * Tk;
-            P[(size_t)i * TkP + j] = P[(size_t)i * TkP + j] / Ls[i];
+            if (!MASKED || mk[j] != 0) P[(size_t)i * TkP + j] = P[(size_t)i * TkP + j] / Ls[i];
         }
     }
     // ---- values: ctx[d][i] = chain_j(P[i][j] V[d][j]), NPT outputs per thread held across the V tiles -----------------
@@ -132,9 +138,11 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
         __syncthreads();                                                     // P final / previous V tile consumed
         for (int e = tid; e < dh * kt; e += ATT_SEQ_THREADS) {
             const int d = e / kt, jj = e - d * kt;
-            T[d * KT + jj] = V[ko + (size_t)d * ksc + j0 + jj];
+            T[d * KT + jj] = (!MASKED || mk[j0 + jj] != 0) ? V[ko + (size_t)d * ksc + j0 + jj] : 0.0f;
         }
         __syncthreads();
+        unsigned long long tm = ~0ull;                                       // present keys of this tile (kt <= 64: one ballot)
+        if (MASKED) tm = __ballot(lane < kt && mk[j0 + lane] != 0);
 #pragma unroll
         for (int u = 0; u < NPT; ++u) {
             const int o = tid + u * ATT_SEQ_THREADS;
@@ -143,7 +151,11 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
                 const float* pr = P + (size_t)i * TkP + j0;
                 const float* vr = T + d * KT;
                 float a = acc[u];
-                for (int jj = 0; jj < kt; ++jj) a = dfma(pr[jj], vr[jj], a);
+                if (MASKED) {
+                    for (int jj = 0; jj < kt; ++jj) if ((tm >> jj) & 1ull) a = dfma(pr[jj], vr[jj], a);
+                } else {
+                    for (int jj = 0; jj < kt; ++jj) a = dfma(pr[jj], vr[jj], a);
+                }
                 acc[u] = a;
             }
         }
@@ -156,35 +168,67 @@ __global__ __launch_bounds__(ATT_SEQ_THREADS) void attention_seq_kernel(
     }
 }
 
-hipError_t launch_attention_seq(const float* q, const float* k, const float* v, float* ctx,
-                                int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
-                                hipStream_t s)
+// kmask == NULL: the plain kernels; otherwise the masked instantiations (same grid, same plan)
+static hipError_t launch_attention_seq_any(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                           int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                           size_t msb, hipStream_t s)
 {
     if (B * H == 0 || Tq == 0) return hipSuccess;
     int qt = 0, kt = 0;
     size_t nf = 0;
     if (!attn_seq_plan(dh, Tk, &qt, &kt, &nf)) return hipErrorInvalidValue;
     const int npt = (dh * qt + ATT_SEQ_THREADS - 1) / ATT_SEQ_THREADS;
-    static BigLdsOptIn o1, o2, o4, o8;
-    hipError_t e = o1.ensure(reinterpret_cast<const void*>(attention_seq_kernel<1>));
-    if (e == hipSuccess) e = o2.ensure(reinterpret_cast<const void*>(attention_seq_kernel<2>));
-    if (e == hipSuccess) e = o4.ensure(reinterpret_cast<const void*>(attention_seq_kernel<4>));
-    if (e == hipSuccess) e = o8.ensure(reinterpret_cast<const void*>(attention_seq_kernel<8>));
+    hipError_t e;
+    if (!kmask) {
+        static BigLdsOptIn o1, o2, o4, o8;
+        e = o1.ensure(reinterpret_cast<const void*>(attention_seq_kernel<1, false>));
+        if (e == hipSuccess) e = o2.ensure(reinterpret_cast<const void*>(attention_seq_kernel<2, false>));
+        if (e == hipSuccess) e = o4.ensure(reinterpret_cast<const void*>(attention_seq_kernel<4, false>));
+        if (e == hipSuccess) e = o8.ensure(reinterpret_cast<const void*>(attention_seq_kernel<8, false>));
+    } else {
+        static BigLdsOptIn m1, m2, m4, m8;
+        e = m1.ensure(reinterpret_cast<const void*>(attention_seq_kernel<1, true>));
+        if (e == hipSuccess) e = m2.ensure(reinterpret_cast<const void*>(attention_seq_kernel<2, true>));
+        if (e == hipSuccess) e = m4.ensure(reinterpret_cast<const void*>(attention_seq_kernel<4, true>));
+        if (e == hipSuccess) e = m8.ensure(reinterpret_cast<const void*>(attention_seq_kernel<8, true>));
+    }
     if (e != hipSuccess) return e;
     const dim3 grid(B * H, (Tq + qt - 1) / qt);
     const size_t lds = nf * sizeof(float);
     const int tkp = attn_seq_pitch(Tk);
-    const int pi = prof_enabled() ? prof_begin("attention_seq_kernel", 4.0 * B * H * (double)Tq * Tk * dh, s) : -1;
-#define MVQ_ATT_SEQ(N) hipLaunchKernelGGL(attention_seq_kernel<N>, grid, dim3(ATT_SEQ_THREADS), lds, s, q, k, v, ctx, H, dh, Tq, Tk, \
-                                          qt, kt, tkp, qsb, qsc, ksb, ksc)
-    if (npt <= 1) MVQ_ATT_SEQ(1);
-    else if (npt <= 2) MVQ_ATT_SEQ(2);
-    else if (npt <= 4) MVQ_ATT_SEQ(4);
-    else MVQ_ATT_SEQ(8);
+    const int pi = prof_enabled() ? prof_begin(kmask ? "attention_seq_masked_kernel" : "attention_seq_kernel",
+                                               4.0 * B * H * (double)Tq * Tk * dh, s) : -1;
+#define MVQ_ATT_SEQ(N, M) hipLaunchKernelGGL((attention_seq_kernel<N, M>), grid, dim3(ATT_SEQ_THREADS), lds, s, q, k, v, ctx, H, dh, Tq, \
+                                             Tk, qt, kt, tkp, qsb, qsc, ksb, ksc, kmask, msb)
+    if (!kmask) {
+        if (npt <= 1) MVQ_ATT_SEQ(1, false);
+        else if (npt <= 2) MVQ_ATT_SEQ(2, false);
+        else if (npt <= 4) MVQ_ATT_SEQ(4, false);
+        else MVQ_ATT_SEQ(8, false);
+    } else {
+        if (npt <= 1) MVQ_ATT_SEQ(1, true);
+        else if (npt <= 2) MVQ_ATT_SEQ(2, true);
+        else if (npt <= 4) MVQ_ATT_SEQ(4, true);
+        else MVQ_ATT_SEQ(8, true);
+    }
 #undef MVQ_ATT_SEQ
     e = hipGetLastError();
     prof_end(pi, s);
     return e;
+}
+
+hipError_t launch_attention_seq(const float* q, const float* k, const float* v, float* ctx,
+                                int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                hipStream_t s)
+{
+    return launch_attention_seq_any(q, k, v, nullptr, ctx, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, 0, s);
+}
+
+hipError_t launch_attention_seq_masked(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                       int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                       size_t msb, hipStream_t s)
+{
+    return launch_attention_seq_any(q, k, v, kmask, ctx, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, msb, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -582,26 +582,50 @@ hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamm
 // attention core: one block per (batch element, head).  Q, K, V head slices are staged in LDS; one thread per
 // (query, key) pair walks the dh-long score chain, Tq threads do the (ordered) softmax rows, then one thread per
 // (channel, query) output walks the Tk-long value chain.  Tq, Tk <= 64.
+// MASKED (mvq_attention_masked_f32): item b's key j is present when kmask[b*msb + j] != 0.  Tk <= 64 is one wave, so every
+// wave takes ONE ballot of the item's mask row; a present key's slot among the staged columns is the popcount of the
+// present keys below it, and absent columns are never loaded.  From there on the kernel is the plain one at Tk = the
+// number of present keys: the result is that of the plain launch on the compacted K / V, bit for bit, and 0 keys give +0.
 // ------------------------------------------------------------------------------------------------
+template <bool MASKED>
 __global__ __launch_bounds__(256) void attention_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, float* __restrict__ ctx,
-    int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+    int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+    const uint8_t* __restrict__ kmask, size_t msb)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Qs = sm;                       // [dh][Tq]
-    float* Ks = Qs + dh * Tq;             // [dh][Tk]
-    float* Vs = Ks + dh * Tk;             // [dh][Tk]
-    float* P = Vs + dh * Tk;              // [Tq][Tk]
     const int tid = threadIdx.x;
     const int b = blockIdx.x / H, hd = blockIdx.x - b * H;
     const float* q = Q + (size_t)b * qsb + (size_t)hd * dh * qsc;
     const float* kb = K + (size_t)b * ksb + (size_t)hd * dh * ksc;
     const float* vb = V + (size_t)b * ksb + (size_t)hd * dh * ksc;
+    unsigned long long present = 0;
+    const int TkAll = Tk;                 // columns in memory
+    if (MASKED) {
+        const int lane = tid & 63;
+        present = __ballot(lane < TkAll && kmask[(size_t)b * msb + lane] != 0);
+        Tk = __popcll(present);           // the same in every wave
+    }
+    float* Qs = sm;                       // [dh][Tq]
+    float* Ks = Qs + dh * Tq;             // [dh][Tk]
+    float* Vs = Ks + dh * Tk;             // [dh][Tk]
+    float* P = Vs + dh * Tk;              // [Tq][Tk]
     for (int e = tid; e < dh * Tq; e += 256) { const int d = e / Tq, i = e - d * Tq; Qs[e] = q[(size_t)d * qsc + i]; }
-    for (int e = tid; e < dh * Tk; e += 256) {
-        const int d = e / Tk, j = e - d * Tk;
-        Ks[e] = kb[(size_t)d * ksc + j];
-        Vs[e] = vb[(size_t)d * ksc + j];
+    if (MASKED) {
+        for (int e = tid; e < dh * TkAll; e += 256) {
+            const int d = e / TkAll, j = e - d * TkAll;
+            if ((present >> j) & 1ull) {
+                const int slot = __popcll(present & ((1ull << j) - 1ull));
+                Ks[d * Tk + slot] = kb[(size_t)d * ksc + j];
+                Vs[d * Tk + slot] = vb[(size_t)d * ksc + j];
+            }
+        }
+    } else {
+        for (int e = tid; e < dh * Tk; e += 256) {
+            const int d = e / Tk, j = e - d * Tk;
+            Ks[e] = kb[(size_t)d * ksc + j];
+            Vs[e] = vb[(size_t)d * ksc + j];
+        }
     }
     __syncthreads();
     const float rs = __builtin_sqrtf((float)dh);
@@ -645,8 +669,68 @@ hipError_t launch_attention(const float* q, const float* k, const float* v, floa
     if (B * H * Tq == 0) return hipSuccess;
     const size_t lds = ((size_t)dh * (Tq + 2 * Tk) + (size_t)Tq * Tk) * sizeof(float);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_kernel, dim3(B * H), dim3(256), lds, s, q, k, v, ctx, B, H, dh, Tq, Tk,
-                       qsb, qsc, ksb, ksc);
+    hipLaunchKernelGGL(attention_kernel<false>, dim3(B * H), dim3(256), lds, s, q, k, v, ctx, B, H, dh, Tq, Tk,
+                       qsb, qsc, ksb, ksc, (const uint8_t*)nullptr, (size_t)0);
+    return hipGetLastError();
+}
+
+// kmask != NULL, Tk > 0 (the entry point sends the other cases to launch_attention)
+hipError_t launch_attention_masked(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                   int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                   size_t msb, hipStream_t s)
+{
+    if (B * H * Tq == 0) return hipSuccess;
+    const size_t lds = ((size_t)dh * (Tq + 2 * Tk) + (size_t)Tq * Tk) * sizeof(float);
+    if (lds > 64 * 1024 || Tk > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_kernel<true>, dim3(B * H), dim3(256), lds, s, q, k, v, ctx, B, H, dh, Tq, Tk,
+                       qsb, qsc, ksb, ksc, kmask, msb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// hold fill (mvq_hold_fill_f32): y[b,c,t] = x[b,c,s(b,t)], s(b,t) = the largest t' <= t with valid[b,t'] != 0, else carry[b,c]
+// (+0 without carry); in place on x[B,C,T]; afterwards carry[b,c] = y[b,c,T-1].  Pure copies.
+// One block per (item, slab of HOLD_CH channels); its four waves take HOLD_CH / 4 channels each and walk the time axis in tiles
+// of 64 tokens, one lane per token.  Per tile a wave takes one ballot of valid[b, t0..t0+63]; lane t's source is the highest set
+// bit at or below it, or the last valid token of the tiles before (a wave-uniform index), so s(b, .) costs one ballot per tile
+// and every access runs along t.  Only tokens with valid == 0 are written, so a source column -- always a valid one -- is never
+// written by anybody: the in-place update has no hazard.  carry[b,c] is touched by the one wave that owns channel c, which
+// reads it before the single lane holding t = T-1 writes it.
+// ------------------------------------------------------------------------------------------------
+constexpr int HOLD_CH = 16;
+
+__global__ __launch_bounds__(256) void hold_fill_kernel(float* __restrict__ x, const uint8_t* __restrict__ valid,
+                                                        float* __restrict__ carry, int C, int T)
+{
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.y * HOLD_CH + wave * (HOLD_CH / 4);
+    const uint8_t* vr = valid + (size_t)b * T;
+    int prev = -1;                                           // last valid token before this tile (wave-uniform)
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool ok = t < T && vr[t] != 0;
+        const unsigned long long m = __ballot(ok);
+        const unsigned long long below = m & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+        const int src = below ? t0 + 63 - __clzll((long long)below) : prev;
+        if (t < T) {
+#pragma unroll
+            for (int u = 0; u < HOLD_CH / 4; ++u) {
+                const int c = c0 + u;
+                if (c >= C) break;
+                float* row = x + ((size_t)b * C + c) * T;
+                const float val = src >= 0 ? row[src] : (carry ? carry[(size_t)b * C + c] : 0.0f);
+                if (!ok) row[t] = val;
+                if (carry && t == T - 1) carry[(size_t)b * C + c] = val;
+            }
+        }
+        if (m) prev = t0 + 63 - __clzll((long long)m);
+    }
+}
+
+hipError_t launch_hold_fill(float* x, const uint8_t* valid, float* carry, int B, int C, int T, hipStream_t s)
+{
+    if ((size_t)B * C * T == 0) return hipSuccess;
+    hipLaunchKernelGGL(hold_fill_kernel, dim3(B, (C + HOLD_CH - 1) / HOLD_CH), dim3(256), 0, s, x, valid, carry, C, T);
     return hipGetLastError();
 }
 

@@ -47,6 +47,10 @@ hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamm
 hipError_t launch_attention(const float* q, const float* k, const float* v, float* ctx,
                             int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
                             hipStream_t s);
+hipError_t launch_attention_masked(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                   int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                   size_t msb, hipStream_t s);
+hipError_t launch_hold_fill(float* x, const uint8_t* valid, float* carry, int B, int C, int T, hipStream_t s);
 hipError_t launch_gelu(const float* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_strided3d(const float* a, size_t asb, size_t asc, const float* b2, size_t bsb, size_t bsc,
                             float* y, size_t ysb, size_t ysc, int B, int C, int n, hipStream_t s);
@@ -66,6 +70,9 @@ hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, 
 bool attn_seq_plan(int dh, int tk, int* qt, int* kt, size_t* lds_floats);      // attention_seq.hip
 hipError_t launch_attention_seq(const float* q, const float* k, const float* v, float* ctx,
                                 int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc, hipStream_t s);
+hipError_t launch_attention_seq_masked(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
+                                       int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                       size_t msb, hipStream_t s);
 hipError_t launch_attention_seq_bwd(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
                                     float* scratch, int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb,
                                     size_t ksc, hipStream_t s);

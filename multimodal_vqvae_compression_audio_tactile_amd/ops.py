@@ -824,14 +824,32 @@ def attention_kv_slice(q, k_all, v_all, heads, folded_batch, s, tk):
     return ctx
 
 
-def attention_into_(ctx, q, k, v, heads, batch, tq, tk, q_strides, k_strides, q_col=0, k_col=0):
+def _key_mask_u8(who, kmask, device):
+    if not isinstance(kmask, torch.Tensor) or kmask.device != device or kmask.dtype != torch.uint8 or not kmask.is_contiguous():
+        raise MvqError(f"{who}: kmask must be a contiguous uint8 tensor on the device of q (nonzero = key present)")
+    return kmask
+
+
+def attention_into_(ctx, q, k, v, heads, batch, tq, tk, q_strides, k_strides, q_col=0, k_col=0, kmask=None, m_stride=None):
     """ctx = attention of ``batch`` query groups against their own key groups, on views of token-folded [1, C, N] tensors:
     group g's query column i / channel c sits at q_col + g*q_strides[0] + c*q_strides[1] + i (ctx shares that addressing),
-    its keys likewise from k_col with k_strides.  Writes into ``ctx`` (the receiver's chunk-as-batch calls)."""
+    its keys likewise from k_col with k_strides.  Writes into ``ctx`` (the receiver's chunk-as-batch calls).
+    ``kmask`` (flat uint8 on the device, nonzero = key present): group g's key j is masked by kmask[k_col + g*m_stride + j]
+    (``m_stride`` defaults to k_strides[0]): mvq_attention_masked_f32, an absent key is not a key."""
     C = q.shape[1]
     if batch and tq and (q_col + (batch - 1) * q_strides[0] + (C - 1) * q_strides[1] + tq > q.numel()
                          or (tk and k_col + (batch - 1) * k_strides[0] + (C - 1) * k_strides[1] + tk > k.numel())):
         raise MvqError("attention_into_: a group reaches past the end of its tensor")
+    if kmask is not None:
+        kmask = _key_mask_u8("attention_into_", kmask, q.device)
+        ms = int(k_strides[0] if m_stride is None else m_stride)
+        if batch and tk and k_col + (batch - 1) * ms + tk > kmask.numel():
+            raise MvqError("attention_into_: a group's mask row reaches past the end of kmask")
+        check(_lib.lib().mvq_attention_masked_f32(q.data_ptr() + 4 * q_col, k.data_ptr() + 4 * k_col, v.data_ptr() + 4 * k_col,
+                                                  kmask.data_ptr() + k_col, ctx.data_ptr() + 4 * q_col, batch, heads, C // heads,
+                                                  tq, tk, int(q_strides[0]), int(q_strides[1]), int(k_strides[0]),
+                                                  int(k_strides[1]), ms, _stream()), "mvq_attention_masked_f32")
+        return ctx
     check(_lib.lib().mvq_attention_f32(q.data_ptr() + 4 * q_col, k.data_ptr() + 4 * k_col, v.data_ptr() + 4 * k_col,
                                        ctx.data_ptr() + 4 * q_col, batch, heads, C // heads, tq, tk, int(q_strides[0]),
                                        int(q_strides[1]), int(k_strides[0]), int(k_strides[1]), _stream()), "mvq_attention_f32")
@@ -865,13 +883,23 @@ def _attn_dims(q, k, folded_batch):
     return B, Tq, Tk, (Tq, B * Tq, Tk, B * Tk)
 
 
-def attention_seq(q, k, v, heads, folded_batch=None):
+def attention_seq(q, k, v, heads, folded_batch=None, kmask=None):
     """softmax(Q K^T / sqrt(dh)) V over whole sequences (Tq, Tk <= 8192): the arithmetic of ``attention`` -- bit-equal to it
-    wherever that kernel accepts the shape -- without its 64-token limit."""
+    wherever that kernel accepts the shape -- without its 64-token limit.
+    ``kmask`` (uint8 [B, Tk] on the device, nonzero = key present): mvq_attention_seq_masked_f32, item b attends over its present
+    keys only, bit-equal to this call on the compacted K / V.  Forward only."""
     q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v")
     B, Tq, Tk, strides = _attn_dims(q, k, folded_batch)
     C = q.shape[1]
     ctx = torch.empty_like(q)
+    if kmask is not None:
+        kmask = _key_mask_u8("attention_seq", kmask, q.device)
+        if tuple(kmask.shape) != (B, Tk):
+            raise MvqError(f"attention_seq: kmask {tuple(kmask.shape)} does not match [B={B}, Tk={Tk}]")
+        check(_lib.lib().mvq_attention_seq_masked_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), kmask.data_ptr(), ctx.data_ptr(), B,
+                                                      heads, C // heads, Tq, Tk, *strides, Tk, _stream()),
+              "mvq_attention_seq_masked_f32")
+        return ctx
     check(_lib.lib().mvq_attention_seq_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), ctx.data_ptr(), B, heads, C // heads,
                                            Tq, Tk, *strides, _stream()), "mvq_attention_seq_f32")
     return ctx
@@ -889,6 +917,23 @@ def attention_seq_bwd(q, k, v, g, heads, folded_batch=None):
                                                gk.data_ptr(), gv.data_ptr(), scratch.data_ptr(), B, heads, C // heads, Tq, Tk,
                                                *strides, _stream()), "mvq_attention_seq_bwd_f32")
     return gq, gk, gv
+
+
+def hold_fill_(x, valid, carry=None):
+    """In place on contiguous fp32 x[B, C, T]: a token with valid[b, t] == 0 (valid: uint8 [B, T]) takes the values of the most
+    recent valid token of its item; before the first one it takes carry[b] (``carry`` [B, C] fp32 or None = +0).  Afterwards
+    carry[b] = x[b, :, T-1], so a sequence is filled piece by piece (mvq_hold_fill_f32; pure copies).  Returns x."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise MvqError("hold_fill_: x must be a contiguous fp32 tensor [B, C, T] on the device (it is filled in place)")
+    B, C, T = x.shape
+    if not isinstance(valid, torch.Tensor) or valid.device != x.device or valid.dtype != torch.uint8 or tuple(valid.shape) != (B, T) \
+            or not valid.is_contiguous():
+        raise MvqError(f"hold_fill_: valid must be a contiguous uint8 tensor [B={B}, T={T}] on the device of x")
+    if carry is not None and not (isinstance(carry, torch.Tensor) and carry.device == x.device and carry.dtype == torch.float32
+                                  and tuple(carry.shape) == (B, C) and carry.is_contiguous()):
+        raise MvqError(f"hold_fill_: carry must be a contiguous fp32 tensor [B={B}, C={C}] on the device of x")
+    check(_lib.lib().mvq_hold_fill_f32(x.data_ptr(), valid.data_ptr(), _p(carry), B, C, T, _stream()), "mvq_hold_fill_f32")
+    return x
 
 
 def _mask_u8(mask, B, T, device):

@@ -120,11 +120,15 @@ class CrossPredictor(nn.Module):
         return ops.attention_fits(self.dh, tq, tk) and (not bwd or ops.attention_bwd_fits(self.dh, tq, tk))
 
     @torch.no_grad()
-    def run(self, zt_prev, za, folded_batch=None, kv_all=None, kv_slice=None, attend=None):
+    def run(self, zt_prev, za, folded_batch=None, kv_all=None, kv_slice=None, attend=None, key_mask=None):
         """zt_prev[B,C,Tq], za[B,C,Tk] (or both token-folded [1,C,B*T] with folded_batch=B) -> same layout.
         kv_all = keys_values(...) with kv_slice = (s, tk): attend to columns [s, s+tk) of the precomputed K / V.
-        attend: a callable Q -> ctx that does the attention itself (the receiver's chunk-as-batch calls)."""
+        attend: a callable Q -> ctx that does the attention itself (the receiver's chunk-as-batch calls).
+        key_mask (uint8 [B, Tk] on the device, nonzero = key present; inference only): item b attends over its present keys
+        alone, through the masked full-sequence kernel (bit-equal to the chunk kernel wherever that one fits)."""
         fb = folded_batch
+        if key_mask is not None and (attend is not None or kv_all is not None):
+            raise MvqError("CrossPredictor.run: key_mask goes with the plain call; attend / kv_all do their own attention")
         pe = self.pos.pe
         q = ops.layernorm_c(zt_prev, self.ln_q.weight.detach(), self.ln_q.bias.detach(), pe=pe, eps=self.ln_q.eps,
                             folded_batch=fb)
@@ -137,8 +141,11 @@ class CrossPredictor(nn.Module):
             kv = ops.layernorm_c(za, self.ln_kv.weight.detach(), self.ln_kv.bias.detach(), pe=pe, eps=self.ln_kv.eps,
                                  folded_batch=fb)
             Q, K, V = L["q"](q), L["k"](kv), L["v"](kv)
-            attn = ops.attention if self._chunk_kernels_fit(Q, K, fb) else ops.attention_seq   # whole-sequence calls (PLC)
-            ctx = attn(Q, K, V, self.h, folded_batch=fb)
+            if key_mask is not None:
+                ctx = ops.attention_seq(Q, K, V, self.h, folded_batch=fb, kmask=key_mask)
+            else:
+                attn = ops.attention if self._chunk_kernels_fit(Q, K, fb) else ops.attention_seq   # whole-sequence calls (PLC)
+                ctx = attn(Q, K, V, self.h, folded_batch=fb)
         y1 = L["o"](ctx, residual=q)                                        # out(ctx) + q
         hdn = ops.layernorm_c(y1, self.ffn[0].weight.detach(), self.ffn[0].bias.detach(), eps=self.ffn[0].eps,
                               folded_batch=fb)
@@ -161,15 +168,17 @@ class CrossPredictor(nn.Module):
         hdn = train.Gelu.apply(lin("f1", self.ffn[1], hdn))
         return lin("f3", self.ffn[3], hdn, y1)
 
-    def forward(self, zt_prev, za):
+    def forward(self, zt_prev, za, key_mask=None):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if key_mask is not None:
+                raise MvqError("CrossPredictor: key_mask is inference only (no backward under a key mask); use torch.no_grad()")
             B, C, Tq = zt_prev.shape
             fold = lambda x: x.permute(1, 0, 2).reshape(1, C, -1).contiguous()
             y = self.run_train(fold(zt_prev), fold(za), B)
             return y.reshape(C, B, Tq).permute(1, 0, 2).contiguous()
         if self.training and self.drop.p > 0:
             raise MvqError("CrossPredictor: train-mode dropout needs autograd enabled; call .eval() for inference")
-        return self.run(zt_prev, za)
+        return self.run(zt_prev, za, key_mask=key_mask)
 
 
 class ResidualVQEMA(nn.Module):
@@ -546,7 +555,8 @@ class _ProposedBase(nn.Module):
     # ------------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
     def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
-                       conceal="predict", plc=None, z_prev=None, z_last_out=None, na_valid=None):
+                       conceal="predict", plc=None, z_prev=None, z_last_out=None, na_valid=None, audio_conceal="zero", qa_prev=None,
+                       qa_last_out=None):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -569,9 +579,19 @@ class _ProposedBase(nn.Module):
         Lossy AUDIO stream: ``na_valid`` ([B, Ta] uint8 on the device: the stages of each audio token that arrived; bool: all or
         none; None = all, today's path launch for launch).  qa = A_QUANT.from_codes(codes, nq_valid=na_valid): a token sums only
         the stages it has, and an audio token of which NOTHING arrived is +0 in every channel -- the predictor attends over it as it
-        would over silence.  That is the unconcealed baseline; audio concealment (a key mask, holding the last token) is not built.
+        would over silence.  That is the unconcealed baseline, ``audio_conceal="zero"``.
         ``conceal`` acts on the tactile tokens only; "plc" is handed the same qa.  Needs ``audio_codes`` (not ``qa``); never read
         on the host.
+
+        ``audio_conceal`` acts on the audio tokens with na_valid == 0 (a token with at least one stage is a valid lower-rate token
+        in every mode).  "mask": a lost audio token is not a key -- the predictor's softmax and value sum run over the arrived keys
+        of the chunk, in ascending order, as if the lost columns were absent (mvq_attention_masked_f32; a chunk with none gives
+        ctx = 0, as ka = 0 does).  "hold": a lost token takes the latent qa of the most recent arrived token of its item, across
+        chunk borders, +0 before the first arrival (ops.hold_fill_ on qa right after from_codes), and then goes through ln_kv with
+        its own position as any token does.  ``qa_prev`` / ``qa_last_out`` ([B, C] fp32 on the device; may be one buffer) carry the
+        last held token between the pieces of a sequence, as z_prev / z_last_out carry the recursion; they belong to "hold".
+        conceal="plc" is handed what the predictor saw: the held qa, or qa with the key mask.  With na_valid=None every token
+        arrived and every mode is "zero".  The launch sequence depends on shapes and modes only.
 
         Streaming (stream.py): a chunk depends on the ones before it through z_run[..., s-1] alone, so a sequence is decoded
         piece by piece, each piece a whole number of 16-token chunks (the last may be shorter), with ``z_prev`` ([B, C] fp32 on the
@@ -625,6 +645,22 @@ class _ProposedBase(nn.Module):
             Ta = (audio_codes if qa is None else qa).shape[2]
             if conceal == "plc" and not 0 < Ta <= ops.ATTN_SEQ_MAX_T:
                 raise MvqError(f"decode_latents: conceal='plc' needs 1..{ops.ATTN_SEQ_MAX_T} audio tokens, got {Ta}")
+        if audio_conceal not in ("zero", "mask", "hold"):
+            raise MvqError(f"decode_latents: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
+        if audio_conceal != "zero" and (tactile_only or qa is not None):
+            raise MvqError(f"decode_latents: audio_conceal={audio_conceal!r} conceals the tokens of audio_codes; it goes with neither "
+                           "qa nor tactile_only")
+        if qa_prev is not None or qa_last_out is not None:
+            if audio_conceal != "hold":
+                raise MvqError("decode_latents: qa_prev / qa_last_out carry the held audio token; they belong to audio_conceal='hold'")
+            if na_valid is None:
+                raise MvqError("decode_latents: qa_prev / qa_last_out need na_valid (without it nothing is held)")
+            for t, name in ((qa_prev, "qa_prev"), (qa_last_out, "qa_last_out")):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32
+                                          and tuple(t.shape) == (B, C) and t.is_contiguous()):
+                    raise MvqError(f"decode_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {dev}")
+        if na_valid is None:
+            audio_conceal = "zero"                                            # every audio token arrived: nothing to conceal
         if na_valid is not None:
             if tactile_only or qa is not None:
                 raise MvqError("decode_latents: na_valid counts the stages of audio_codes; it goes with neither qa nor tactile_only")
@@ -650,7 +686,21 @@ class _ProposedBase(nn.Module):
         qa = ops._dev(qa.to(dev), "qa")                                       # fp32, contiguous
         if qa.shape[0] != B or qa.shape[1] != C:
             raise MvqError(f"decode_latents: qa {tuple(qa.shape)} does not match B={B}, C={C}")
-        z_run = self._rx_two_pass(qa, idx, books_use, nb_valid, z_prev)
+        key_mask = None
+        if audio_conceal == "hold":
+            carry = None                                                      # read, then moved on in place, by hold_fill_
+            if qa_last_out is not None:
+                carry = qa_last_out
+                if qa_prev is None:
+                    carry.zero_()
+                elif qa_prev.data_ptr() != carry.data_ptr():
+                    carry.copy_(qa_prev)
+            elif qa_prev is not None:
+                carry = qa_prev.clone()                                       # qa_prev itself stays as it was handed in
+            ops.hold_fill_(qa, na_valid, carry)
+        elif audio_conceal == "mask":
+            key_mask = na_valid                                               # nonzero = at least one stage arrived: a key
+        z_run = self._rx_two_pass(qa, idx, books_use, nb_valid, z_prev, key_mask=key_mask)
         if z_last_out is not None:                                            # before the post-pass: what the recursion reads
             ops.copy_strided_(z_last_out, 0, (C, 1), z_run, Tlat - 1, (C * Tlat, Tlat), B, C, 1)
         if conceal == "predict":
@@ -659,9 +709,13 @@ class _ProposedBase(nn.Module):
         if conceal == "zero":
             return ops.plc_mask_fill(z_run, None, lost)[0]                    # z_run * ~lost
         zt_in, _ = ops.plc_mask_fill(z_run, None, lost)                       # what AllPredPLC's predictor is fed
-        return ops.plc_mask_fill(z_run, plc.predict(zt_in, qa), lost, want_zt_in=False)[1]
+        if key_mask is not None:                                              # the PLC predictor sees what the AR predictor saw
+            z_plc = plc.predict(zt_in, qa, key_mask=key_mask)
+        else:
+            z_plc = plc.predict(zt_in, qa)
+        return ops.plc_mask_fill(z_run, z_plc, lost, want_zt_in=False)[1]
 
-    def _rx_two_pass(self, qa, idx, books_use, nb_valid=None, z_prev=None):
+    def _rx_two_pass(self, qa, idx, books_use, nb_valid=None, z_prev=None, key_mask=None):
         """Layout: every [.., B*Tlat] tensor of the plan is token-folded and PADDED per chunk -- column (b*NC + c)*16 + i holds
         token c*16 + i of item b (NC chunks, the tail chunk's columns past its end are filler) -- so "chunk" is a batch index of
         stride 16 and every chunk with 16 queries and 16 keys is ONE attention call (chunk as batch).  The tail chunk and chunks
@@ -670,7 +724,10 @@ class _ProposedBase(nn.Module):
           pass 1: every token with a zero query input (q = LN(PE[i])), z_run = proj_up(qD) + z_pred;
           pass 2: one query per chunk, input z_run[s-1], attending to its own chunk's keys; the result replaces position 0.
         Chunk 0 takes part in pass 2 with a zero input, recomputing its position 0 exactly as pass 1 did -- or, when this call
-        continues a sequence, with ``z_prev`` [B, C], the last token of the piece before (pass 2 then runs for one chunk too)."""
+        continues a sequence, with ``z_prev`` [B, C], the last token of the piece before (pass 2 then runs for one chunk too).
+        ``key_mask`` (uint8 [B, Ta_in], nonzero = the audio token arrived): folded once into the padded key layout ([N] uint8,
+        group stride 16, filler 0), so the chunk-as-batch call and the odd-chunk calls of both passes read ONE buffer through the
+        masked attention kernel; nothing is read on the host."""
         pr, L = self.predict, self.predict._lin
         B, C, Ta_in = qa.shape
         Tlat = idx.shape[2]
@@ -690,6 +747,16 @@ class _ProposedBase(nn.Module):
         ops.copy_strided_(qa_p, 0, (P, N), qa, 0, (C * Ta_in, Ta_in), B, C, Ta)
         kv = ops.layernorm_c(qa_p, pr.ln_kv.weight.detach(), pr.ln_kv.bias.detach(), pe=pr.pos.pe, eps=pr.ln_kv.eps, folded_batch=G)
         K, V = L["k"](kv), L["v"](kv)
+        km = None
+        if key_mask is not None:
+            if tuple(key_mask.shape) != (B, Ta_in) or key_mask.dtype != torch.uint8 or key_mask.device != dev:
+                raise MvqError(f"_rx_two_pass: key_mask must be uint8 [B={B}, Ta={Ta_in}] on {dev}")
+            if Ta_in == P:
+                km = key_mask.contiguous().view(-1)                           # already the padded layout
+            else:
+                km = torch.zeros(B, P, device=dev, dtype=torch.uint8)
+                km[:, :Ta].copy_(key_mask[:, :Ta])                            # nonzero = present; filler and missing audio: 0
+                km = km.view(-1)
         # qD of every token in one dequantisation
         qD_p = torch.empty(1, CODE_DIM, N, device=dev)
         self.vq.from_indices(idx, books_use, out=qD_p, out_strides=(P, N), nb_valid=nb_valid)   # loss changes qD alone
@@ -697,10 +764,10 @@ class _ProposedBase(nn.Module):
         def attend(Q, tq, q_strides, q_col_of):
             ctx = torch.empty_like(Q)
             if len(odd) < NC:
-                ops.attention_into_(ctx, Q, K, V, pr.h, G, tq, CH, q_strides, (CH, N))
+                ops.attention_into_(ctx, Q, K, V, pr.h, G, tq, CH, q_strides, (CH, N), kmask=km)
             for c in odd:
                 ops.attention_into_(ctx, Q, K, V, pr.h, B, min(tq, nt[c]), ka[c], (q_strides[0] * NC, q_strides[1]), (P, N),
-                                    q_col=q_col_of(c), k_col=c * CH)
+                                    q_col=q_col_of(c), k_col=c * CH, kmask=km)
             return ctx
 
         # pass 1
@@ -786,11 +853,11 @@ class ProposedEval(_ProposedBase):
 
     # ---------------------------------------------------------------------------------------------------------- receiver
     @torch.no_grad()
-    def decode(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None, na_valid=None):
+    def decode(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None, na_valid=None, audio_conceal="zero"):
         """Receiver: T_DEC(decode_latents(audio_codes, idx)) -- the waveform from the transmitted codes alone.  ``nb_valid`` /
-        ``conceal`` / ``plc`` / ``na_valid``: the lossy-channel arguments of decode_latents."""
+        ``conceal`` / ``plc`` / ``na_valid`` / ``audio_conceal``: the lossy-channel arguments of decode_latents."""
         return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc,
-                                              na_valid=na_valid))
+                                              na_valid=na_valid, audio_conceal=audio_conceal))
 
     @torch.no_grad()
     def decode_latents_tactile_only(self, idx, books_use=None, nb_valid=None, conceal="predict"):
@@ -978,18 +1045,21 @@ class ProposedEval(_ProposedBase):
 
     @torch.no_grad()
     def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None,
-                              fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None):
+                              fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None, audio_conceal="zero"):
         """-> (y [B,1,T], lost [B,T_lat] bool, audio_lost [B,Ta] bool) from whatever packets of BOTH streams arrived (missing,
         reordered, duplicated, thinned; items of one StreamInfo per stream): packets.gather per item and stream on the host, ONE
         upload of both streams' bodies and per-packet counts, the bit unpacking of both on the device (the audio indices are
         transposed to codes[B, nq, Ta] there), then decode(nb_valid=, na_valid=).  ``audio_lost``: the audio tokens no stage of
-        which arrived; they are +0 to the predictor (decode_latents).
+        which arrived; they are +0 to the predictor, or concealed as ``audio_conceal`` says ("zero" / "mask" / "hold":
+        decode_latents; what FEC recovered is not lost and is not concealed).
 
         ``fec`` / ``fec_packets`` / ``audio_fec`` / ``audio_fec_packets``: decompress_packets(fec=) per stream -- packets.gather_fec per
         item and stream, the parity rows and ``got`` flags of both behind the existing arrays in the ONE upload, ops.fec_recover on
         each stream ahead of its ops.idx_unpack_packets.  The return values do not change; ``lost`` / ``audio_lost`` are what is still
         lost after recovery.  The closed loop: as decompress_packets(fec=) says, on each stream."""
         from . import packets
+        if audio_conceal not in ("zero", "mask", "hold"):
+            raise MvqError(f"decompress_packets_av: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
         if (fec is None and fec_packets is not None) or (audio_fec is None and audio_fec_packets is not None):
             raise MvqError("decompress_packets_av: fec_packets / audio_fec_packets need fec= / audio_fec=, the packets.Fec both ends agreed on")
         if not (len(infos) == len(tactile_packets) == len(audio_infos) == len(audio_packets)):
@@ -1036,24 +1106,25 @@ class ProposedEval(_ProposedBase):
         idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
         aidx, na_valid = ops.idx_unpack_packets(uab, uar, ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
         codes = aidx.permute(1, 0, 2).contiguous()                            # [nq, B, Ta] -> [B, nq, Ta], on the device
-        y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid)
+        y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
+                        audio_conceal=audio_conceal)
         return y, nb_valid == 0, na_valid == 0
 
     def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                        fec=None, audio_fec=None):
+                        fec=None, audio_fec=None, audio_conceal="zero"):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
         time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
-                              out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec)
+                              out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal)
 
-    def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
+    def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None):
         """A pool of up to ``slots`` independent receiver sessions on this model (stream.StreamReceiverPool): ``open`` a
         session, ``step`` once per tick with the chunks that are ready (and the sessions that end); each session gets what a
         stream_receiver(batch=1) of its own would return, and the sessions of a tick share batched launches."""
         from .stream import StreamReceiverPool
         return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
-                                  out_rate=out_rate)
+                                  out_rate=out_rate, audio_conceal=audio_conceal)    # the pool takes no audio= and refuses an audio_conceal
 
     def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None,
                       fec=None, audio_fec=None):

@@ -662,11 +662,17 @@ class _ReceiverCore:
     int32 device copy, on those sessions of a pool: the same launches under another addressing (csrc/stream.hip), which is why a
     pool session computes what a solo one does."""
 
-    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None):
+    def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None,
+                 audio_conceal="zero"):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check, body_bytes
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        if audio_conceal not in ("zero", "mask", "hold"):
+            raise ValueError(f"StreamReceiver: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
+        if audio_conceal != "zero" and audio is None:
+            raise ValueError("StreamReceiver: audio_conceal goes with audio=(K_a, na)")
+        self.audio_conceal = audio_conceal
         if audio_fec is not None and audio is None:
             raise ValueError("StreamReceiver: audio_fec goes with audio=(K_a, na)")
         if fec is not None:
@@ -689,6 +695,7 @@ class _ReceiverCore:
         self.full = body_bytes(packet_tok, nb, K)
         self.n_audio_books = net.A_QUANT.n_codebooks
         self.carry = torch.zeros(rows, self.C, device=self.dev)                        # per session: z_run[..., -1] of the chunk before
+        self.qa_carry = torch.zeros(rows, self.C, device=self.dev) if audio_conceal == "hold" else None   # the last held audio token
         self.hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)       # per session: the last <= 20 latent tokens
         self.rs_state = self.rs_kernel = None
         if self.out_rate != proposed.EVAL_SR:
@@ -753,7 +760,11 @@ class _ReceiverCore:
                                                self.audio[1], n, self.packet_tok)
             codes = aidx.permute(1, 0, 2).contiguous()                                 # [na, G, n] -> [G, na, n], on the device
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
-        z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav)
+        if self.audio_conceal == "zero":
+            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav)
+        else:                                                 # "mask" is stateless per chunk; "hold" moves qa_carry on in place
+            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav,
+                                        audio_conceal=self.audio_conceal, qa_prev=self.qa_carry, qa_last_out=self.qa_carry)
         if sl is not None and not last:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
         if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
@@ -820,6 +831,12 @@ class StreamReceiver(_ReceiverCore):
     (decode_latents(na_valid=)); the steady step stays one captured graph with static body and count buffers.  The concatenated
     output equals decompress_packets_av on the same packets.  ``audio=None``: today's behaviour exactly.
 
+    ``audio_conceal`` ("zero" / "mask" / "hold", only with ``audio=``; decode_latents): what the predictor does with an audio token
+    no stage of which arrived.  "mask" is stateless per chunk; "hold" adds one fixed device buffer qa_carry [B, C] to the session
+    state -- the last held audio token, zero at the start, moved on in place by every chunk -- so the hold crosses chunk borders as
+    it does in decompress_packets_av(audio_conceal=).  The steady step stays ONE captured graph whose only input is the static
+    upload buffer.  "zero": today's behaviour exactly.
+
     ``fec`` / ``audio_fec`` (packets.Fec, the sender's; ``audio_fec`` needs ``audio=``; both None: today's behaviour exactly):
     ``push(..., fec_packets=, audio_fec_packets=)`` and ``finish(...)`` likewise take, per item, whatever parity packets of the chunk
     arrived (None: none did).  packets.gather_fec(seq_base=the chunk's first group) per item, the parity rows and ``got`` flags behind
@@ -829,14 +846,15 @@ class StreamReceiver(_ReceiverCore):
     decompress_packets(fec=) / decompress_packets_av(fec=, audio_fec=) on the same packets."""
 
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                 fec=None, audio_fec=None):
+                 fec=None, audio_fec=None, audio_conceal="zero"):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
             raise ValueError("StreamReceiver: batch must be at least 1")
         if fec is not None or audio_fec is not None:
             _f32_only("StreamReceiver")
-        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec)
+        super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
+                         audio_conceal=audio_conceal)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -980,7 +998,8 @@ class StreamReceiver(_ReceiverCore):
         if self._g is None:
             up_s = torch.from_numpy(host).to(self.dev)
             codes_s = None if codes is None else codes.to(self.dev).long().clone()
-            g, y_s = _capture(self.dev, (self.hist, self.carry), lambda: self._device_step(up_s, codes_s, n, *plan))
+            state = (self.hist, self.carry) + ((self.qa_carry,) if self.qa_carry is not None else ())
+            g, y_s = _capture(self.dev, state, lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
             if self.fec is not None or self.audio_fec is not None:            # the eager run before the capture recovered in place
                 up_s.copy_(torch.from_numpy(host))
@@ -1011,7 +1030,9 @@ class StreamReceiverPool(_ReceiverCore):
              -> the emit slice (-> ops.resample_stream_slots): _ReceiverCore's sequence on the group's slots.
     ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick."""
 
-    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000):
+    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None):
+        if audio_conceal is not None:
+            raise ValueError("StreamReceiverPool: the pool takes no audio= packets and so no audio_conceal")
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
         _receiver_args("StreamReceiverPool", net, K, nb, packet_tok, conceal, out_rate)
         if slots < 1:

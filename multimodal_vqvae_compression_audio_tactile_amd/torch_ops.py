@@ -21,6 +21,7 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   idx_pack_packets            mvq_idx_pack_packets_u8    lossy receiver: indices -> packet bodies uint8 [B,P,body_full] (packets.py)
   idx_unpack_packets          mvq_idx_unpack_packets     lossy receiver: bodies + per-packet book counts -> (idx, nb_valid)
   attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
+  attention_seq_masked_f32    mvq_attention_seq_masked_f32 the same under a key mask uint8 [B,Tk] (receiver audio concealment "mask")
   mel_ssim_f32                mvq_mel_ssim_f32           mel ST-SIM of column-listed image pairs (PLC/PLC1_eval.py:270-333)
 
 Weights are the PACKED images of ``ops.pack_conv1d`` / ``ops.pack_conv_transpose1d`` (made once per weight load).  Import this module
@@ -143,7 +144,7 @@ def _(z, gy, stack):
 
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
-              "ema_update_f32", "attention_seq_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes",
+              "ema_update_f32", "attention_seq_f32", "attention_seq_masked_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes",
               "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets", "dac_rvq_from_codes_layers")
 
 
@@ -154,6 +155,16 @@ def attention_seq_f32(q: Tensor, k: Tensor, v: Tensor, heads: int) -> Tensor:
 
 @attention_seq_f32.register_fake
 def _(q, k, v, heads):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op(f"{NS}::attention_seq_masked_f32", mutates_args=())
+def attention_seq_masked_f32(q: Tensor, k: Tensor, v: Tensor, kmask: Tensor, heads: int) -> Tensor:
+    return ops.attention_seq(q, k, v, heads, kmask=kmask)
+
+
+@attention_seq_masked_f32.register_fake
+def _(q, k, v, kmask, heads):
     return q.new_empty(q.shape)
 
 
