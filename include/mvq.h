@@ -40,7 +40,7 @@ extern "C" {
  * mvq_attention_seq_f32 / mvq_attention_seq_bwd_f32 with mvq_attention_seq_bwd_scratch_bytes, and mvq_plc_mask_fill_f32 /
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
- * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8; audio concealment: mvq_attention_masked_f32,
+ * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8, mvq_fec_rs_parity_u8, mvq_fec_rs_recover_u8; audio concealment: mvq_attention_masked_f32,
  * mvq_attention_seq_masked_f32, mvq_hold_fill_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
@@ -300,6 +300,27 @@ int mvq_fec_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* ro
  * No atomics. */
 int mvq_fec_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch, int nb,
                        int t, int k, int packet_tok, int group, int books, void* stream);
+
+/* Reed-Solomon parity (additive, same ABI version; no reference counterpart): parity = r rows per group, 1 <= r <= 4, a systematic
+ * MDS erasure code over GF(2^8) (polynomial x^8+x^4+x^3+x^2+1 = 0x11d, generator 2).  Packet u of its group (u < g <= 16) has the
+ * coefficient A[i][u] = 2^(i*u) in parity i; every square submatrix of the 4 x 16 matrix A is nonsingular.  rows[B, G, r, g + W]:
+ * row [j, i] = the g count bytes of the XOR row, then the GF sum over the group's packets of A[i][u] * prefix(u), so row [j, 0] IS
+ * the XOR row of mvq_fec_parity_u8.  Refused before any launch (MVQ_EINVAL "bad shape"): what the XOR entry points refuse, and
+ * parity outside 1..4; batch == 0 or t == 0 is a no-op.  packets.py (fec_rows / fec_recover with Fec.parity) is the numpy
+ * definition.  Parity: one thread per output byte, EVERY byte of rows_out written, no atomics. */
+int mvq_fec_rs_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k,
+                         int packet_tok, int group, int books, int parity, void* stream);
+/* Recovery in place, as mvq_fec_recover_u8, from rows[B, G, r, g + W] and got[B, G], a BITMASK: bit i set = parity i of the group
+ * arrived (bits at and above r are ignored).  The counts c_p = min(count byte, m, nb) come from the lowest arrived parity; D = the
+ * deficient packets (nb_recv[p] < c_p), ascending.  When 1 <= |D| <= (arrived parities): with i_k the |D| LOWEST arrived indices,
+ * per byte the syndromes S_k = parity_{i_k} ^ sum_{u not in D} A[i_k][u] * prefix(u), the system M x = S with M[k][d] = A[i_k][q_d]
+ * is solved (Gauss-Jordan without pivoting on the inverse, once per block) and every q in D gets row q = x_q over its first
+ * ceil(c_q*ntok_q*bits / 8) bytes and zero past them, nb_recv[q] = c_q, recovered[q] = 1.  In every other case the group is left
+ * exactly as it arrived.  One block of 64 threads per (item, group); rows of D are only written, the others only read; the counts
+ * are written behind a barrier; recovered[B, P] (NULL = not written) has every element written.  No atomics, no tables.  With
+ * parity == 1 and got in {0, 1} both entry points compute what the XOR entry points compute. */
+int mvq_fec_rs_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch,
+                          int nb, int t, int k, int packet_tok, int group, int books, int parity, void* stream);
 
 /* Audio transport (additive, same ABI version; no reference counterpart).  The DAC quantiser is a residual VQ, so the first m stages
  * of a token's codes are a valid lower-rate code: the audio codes travel in the layered packets of the tactile stream

@@ -86,6 +86,8 @@ EXPORTS = {
     "mvq_idx_unpack_packets": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "mvq_fec_parity_u8": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
     "mvq_fec_recover_u8": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
+    "mvq_fec_rs_parity_u8": (c_int, [c_void_p] * 3 + [c_int] * 8 + [c_void_p]),
+    "mvq_fec_rs_recover_u8": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "mvq_rvq_dequant_layers_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_rvq_rate_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                  c_size_t, c_void_p, c_size_t, c_void_p] + [c_int] * 9 + [c_float, c_int, c_void_p]),

@@ -825,6 +825,32 @@ int mvq_fec_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, c
     return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_recover");
 }
 
+// ---- Reed-Solomon parity, r rows per group (kernels in fec_rs.hip): the XOR entry points' refusals, and parity outside 1..4 ----
+int mvq_fec_rs_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k,
+                         int packet_tok, int group, int books, int parity, void* stream)
+{
+    const int bits = fec_bits("fec_rs_parity", batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "fec_rs_parity: bad shape parity=%d (1..4)", parity);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!rows_out || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_rs_parity: null tensor");
+    hipError_t e = mvq::launch_fec_rs_parity(bodies, nb_sent, rows_out, batch, nb, t, bits, packet_tok, group, books, parity, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_rs_parity");
+}
+
+int mvq_fec_rs_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch,
+                          int nb, int t, int k, int packet_tok, int group, int books, int parity, void* stream)
+{
+    const int bits = fec_bits("fec_rs_recover", batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "fec_rs_recover: bad shape parity=%d (1..4)", parity);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!nb_recv || !rows || !got || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_rs_recover: null tensor");
+    hipError_t e = mvq::launch_fec_rs_recover(bodies, nb_recv, rows, got, recovered, batch, nb, t, bits, packet_tok, group, books, parity,
+                                              S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_rs_recover");
+}
+
 int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,
                                int t, int nb_use, int k, size_t out_sb, size_t out_sd, void* stream)
 {

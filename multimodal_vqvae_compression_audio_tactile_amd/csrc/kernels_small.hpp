@@ -142,6 +142,11 @@ hipError_t launch_fec_parity(const uint8_t* bodies, const uint8_t* nb_sent, uint
                              int g, int m, hipStream_t s);
 hipError_t launch_fec_recover(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int B,
                               int nb, int T, int bits, int ptok, int g, int m, hipStream_t s);
+// fec_rs.hip: the same with r parity rows per group over GF(2^8) (1 <= r <= 4): rows[B, G, r, g + W], got a bitmask of arrived parities
+hipError_t launch_fec_rs_parity(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows, int B, int nb, int T, int bits, int ptok,
+                                int g, int m, int r, hipStream_t s);
+hipError_t launch_fec_rs_recover(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int B,
+                                 int nb, int T, int bits, int ptok, int g, int m, int r, hipStream_t s);
 // rate.hip: closed-loop sender rate control (mvq_rvq_rate_f32); rvq_rate_check returns an MVQ_* code, its text through set_last_error
 int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget,
                    const char* who = "rvq_rate");     // ``who`` prefixes the message (the audio rate control passes its own name)

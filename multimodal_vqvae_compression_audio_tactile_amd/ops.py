@@ -636,18 +636,20 @@ def idx_unpack_packets(bodies, nb_recv, k, nb, T, packet_tok):
 
 
 def _fec_shape(name, info, fec):
-    """(K, nb, T, packet_tok, P, body_full, g, m, G, W) after the checks the C ABI repeats."""
+    """(K, nb, T, packet_tok, P, body_full, g, m, G, W, r, the shape of one item's parity rows) after the checks the C ABI
+    repeats: (G, g + W) for r == 1, (G, r, g + W) for the Reed-Solomon code."""
     from .packets import StreamInfo
     try:
         info = StreamInfo(*(int(v) for v in info))
-        g, m = int(fec.group), int(fec.books)
+        g, m, r = int(fec.group), int(fec.books), int(fec.parity)
     except (TypeError, ValueError, AttributeError) as e:
         raise MvqError(f"{name}: info must be a packets.StreamInfo and fec a packets.Fec ({e})") from None
     P, full = _packet_shape(name, info.K, info.nb, info.T, info.packet_tok)
-    if not 1 <= g <= 16 or not 1 <= m <= info.nb:
-        raise MvqError(f"{name}: Fec(group={g}, books={m}) outside group 1..16, books 1..nb = {info.nb}")
+    if not 1 <= g <= 16 or not 1 <= m <= info.nb or not 1 <= r <= 4:
+        raise MvqError(f"{name}: Fec(group={g}, books={m}, parity={r}) outside group 1..16, books 1..nb = {info.nb}, parity 1..4")
     from .packets import body_bytes
-    return info.K, info.nb, info.T, info.packet_tok, P, full, g, m, (P + g - 1) // g, body_bytes(info.packet_tok, m, info.K)
+    G, W = (P + g - 1) // g, body_bytes(info.packet_tok, m, info.K)
+    return info.K, info.nb, info.T, info.packet_tok, P, full, g, m, G, W, r, ((G, g + W) if r == 1 else (G, r, g + W))
 
 
 def _fec_u8(name, what, t, shape, dev=None, contiguous=False):
@@ -662,32 +664,43 @@ def _fec_u8(name, what, t, shape, dev=None, contiguous=False):
 
 def fec_parity(bodies, nb_sent, info, fec):
     """bodies uint8 [B, P, body_full] and nb_sent uint8 [B, P] (None: every packet carries info.nb books) -> the parity rows uint8
-    [B, G, g + W]: packets.fec_rows per item, bit for bit (mvq_fec_parity_u8)."""
-    K, nb, T, ptok, P, full, g, m, G, W = _fec_shape("fec_parity", info, fec)
+    [B, G, g + W]: packets.fec_rows per item, bit for bit (mvq_fec_parity_u8).  With fec.parity = r > 1 the Reed-Solomon rows uint8
+    [B, G, r, g + W] (mvq_fec_rs_parity_u8)."""
+    K, nb, T, ptok, P, full, g, m, G, W, r, rshape = _fec_shape("fec_parity", info, fec)
     bodies = _fec_u8("fec_parity", "bodies", bodies, (None, P, full))
     B = bodies.shape[0]
     if nb_sent is not None:
         nb_sent = _fec_u8("fec_parity", "nb_sent", nb_sent, (B, P), bodies.device)
-    rows = torch.empty(B, G, g + W, device=bodies.device, dtype=torch.uint8)
-    check(_lib.lib().mvq_fec_parity_u8(bodies.data_ptr(), _p(nb_sent), rows.data_ptr(), B, nb, T, K, ptok, g, m, _stream()),
-          "mvq_fec_parity_u8")
+    rows = torch.empty(B, *rshape, device=bodies.device, dtype=torch.uint8)
+    if r == 1:
+        check(_lib.lib().mvq_fec_parity_u8(bodies.data_ptr(), _p(nb_sent), rows.data_ptr(), B, nb, T, K, ptok, g, m, _stream()),
+              "mvq_fec_parity_u8")
+    else:
+        check(_lib.lib().mvq_fec_rs_parity_u8(bodies.data_ptr(), _p(nb_sent), rows.data_ptr(), B, nb, T, K, ptok, g, m, r, _stream()),
+              "mvq_fec_rs_parity_u8")
     return rows
 
 
 def fec_recover(bodies, nb_recv, rows, got, info, fec, want_recovered=False):
     """packets.fec_recover per item on the device, IN PLACE on bodies uint8 [B, P, body_full] and nb_recv uint8 [B, P] (both
     contiguous), from the parity rows uint8 [B, G, g + W] and got uint8 [B, G] (0 = the group's parity did not arrive): where
-    exactly one packet of a group is deficient it is rebuilt to its protected books (mvq_fec_recover_u8).
+    exactly one packet of a group is deficient it is rebuilt to its protected books (mvq_fec_recover_u8).  With fec.parity = r > 1:
+    rows uint8 [B, G, r, g + W] and got a bitmask (bit i: parity i of the group arrived); any d <= (arrived parities) deficient
+    packets of a group are rebuilt together (mvq_fec_rs_recover_u8).
     -> (bodies, nb_recv), with ``want_recovered`` also recovered uint8 [B, P]."""
-    K, nb, T, ptok, P, full, g, m, G, W = _fec_shape("fec_recover", info, fec)
+    K, nb, T, ptok, P, full, g, m, G, W, r, rshape = _fec_shape("fec_recover", info, fec)
     bodies = _fec_u8("fec_recover", "bodies", bodies, (None, P, full), contiguous=True)
     B = bodies.shape[0]
     nb_recv = _fec_u8("fec_recover", "nb_recv", nb_recv, (B, P), bodies.device, contiguous=True)
-    rows = _fec_u8("fec_recover", "rows", rows, (B, G, g + W), bodies.device)
+    rows = _fec_u8("fec_recover", "rows", rows, (B, *rshape), bodies.device)
     got = _fec_u8("fec_recover", "got", got, (B, G), bodies.device)
     recovered = torch.empty(B, P, device=bodies.device, dtype=torch.uint8) if want_recovered else None
-    check(_lib.lib().mvq_fec_recover_u8(bodies.data_ptr(), nb_recv.data_ptr(), rows.data_ptr(), got.data_ptr(), _p(recovered), B, nb, T, K,
-                                        ptok, g, m, _stream()), "mvq_fec_recover_u8")
+    if r == 1:
+        check(_lib.lib().mvq_fec_recover_u8(bodies.data_ptr(), nb_recv.data_ptr(), rows.data_ptr(), got.data_ptr(), _p(recovered), B, nb, T,
+                                            K, ptok, g, m, _stream()), "mvq_fec_recover_u8")
+    else:
+        check(_lib.lib().mvq_fec_rs_recover_u8(bodies.data_ptr(), nb_recv.data_ptr(), rows.data_ptr(), got.data_ptr(), _p(recovered), B, nb,
+                                               T, K, ptok, g, m, r, _stream()), "mvq_fec_rs_recover_u8")
     return (bodies, nb_recv, recovered) if want_recovered else (bodies, nb_recv)
 
 

@@ -30,6 +30,11 @@ first m books of every group of g data packets.  A body's first m books are a va
 parity is a packet thinned to m books: nothing downstream of ``fec_recover`` knows about it.  Parity packets travel in a list of
 their own; the data packets, ``gather``, ``thin``, ``frame`` and ``VERSION`` are unchanged.  ``fec_rows`` / ``fec_recover`` are the
 definition the device kernels (ops.fec_parity / ops.fec_recover) equal bit for bit.
+
+``Fec(group, books, parity=r)``, r in 2..4: a systematic Reed-Solomon erasure code over GF(2^8) (polynomial 0x11d, generator 2)
+with r parity packets per group.  Parity i has coefficient A[i][u] = 2^(i*u) for the group's packet u, so parity 0 is the XOR
+packet above, byte for byte (magic ``MF``); parity i >= 1 travels with magic ``MR`` and one index byte behind the header.  Every
+square submatrix of A (4 x 16) is nonsingular: any d deficient packets of a group come back from any d of its parity packets.
 """
 from __future__ import annotations
 
@@ -43,7 +48,9 @@ from .bitstream import index_bits
 
 MAGIC = b"MP"
 FEC_MAGIC = b"MF"                           # a parity packet (frame_fec); ``gather`` refuses it by its magic
+FEC_RS_MAGIC = b"MR"                        # parity index i >= 1 of a Fec with parity > 1: the header, one byte i, then as ``MF``
 FEC_MAX_GROUP = 16
+FEC_MAX_PARITY = 4
 VERSION = 1
 _HEADER = struct.Struct("<2sBIBB")
 HEADER_BYTES = _HEADER.size                 # 9
@@ -318,28 +325,96 @@ def gather(packets: Iterable, info: StreamInfo, seq_base: int = 0, late: Optiona
 
 
 # ------------------------------------------------------------------------------------------------ forward error correction
-@dataclasses.dataclass(frozen=True)
+def _gf_tables():
+    """GF(2^8), polynomial x^8 + x^4 + x^3 + x^2 + 1 (0x11d), generator 2 -> (exp uint8[512] with exp[i] = 2^i, doubled so that
+    exp[log a + log b] needs no modulo; log uint8[256], log[0] unused)."""
+    exp, log, x = np.zeros(512, np.uint8), np.zeros(256, np.uint8), 1
+    for i in range(255):
+        exp[i], log[x] = x, i
+        x = (x << 1) ^ (0x11d if x & 0x80 else 0)
+    exp[255:510] = exp[:255]
+    return exp, log
+
+
+GF_EXP, GF_LOG = _gf_tables()
+
+
+def gf_mul(a, b):
+    """The GF(2^8) product, elementwise (scalars or uint8 arrays, broadcast)."""
+    a, b = np.asarray(a, np.uint8), np.asarray(b, np.uint8)
+    return np.where((a == 0) | (b == 0), np.uint8(0), GF_EXP[GF_LOG[a].astype(np.int64) + GF_LOG[b]])
+
+
+def gf_inv(a: int) -> int:
+    """The inverse of a nonzero field element."""
+    if not 1 <= int(a) <= 255:
+        raise ZeroDivisionError("gf_inv: 0 has no inverse")
+    return int(GF_EXP[255 - int(GF_LOG[int(a)])])
+
+
+def fec_coef(i: int, u: int) -> int:
+    """A[i][u] = (2^u)^i: the coefficient of the group's packet u in parity i."""
+    return int(GF_EXP[(int(i) * int(u)) % 255])
+
+
+def gf_solve_matrix(idx, cols) -> np.ndarray:
+    """The inverse of M[k][d] = A[idx[k]][cols[d]] (len(idx) == len(cols)) by Gauss-Jordan without pivoting: every leading minor
+    of M is a square submatrix of A, none of which is singular."""
+    d = len(cols)
+    aug = [[fec_coef(i, q) for q in cols] + [int(k == e) for e in range(d)] for k, i in enumerate(idx)]
+    for k in range(d):
+        if aug[k][k] == 0:
+            raise ZeroDivisionError("gf_solve_matrix: a zero pivot (indices outside the 4 x 16 code?)")
+        inv = gf_inv(aug[k][k])
+        aug[k] = [int(gf_mul(inv, v)) for v in aug[k]]
+        for e in range(d):
+            if e != k and aug[e][k]:
+                f = aug[e][k]
+                aug[e] = [v ^ int(gf_mul(f, w)) for v, w in zip(aug[e], aug[k])]
+    return np.array([row[d:] for row in aug], np.uint8).reshape(d, d)
+
+
+@dataclasses.dataclass(frozen=True, repr=False)
 class Fec:
-    """XOR parity over the first ``books`` books of every ``group`` consecutive packets; both ends know it out of band, like
+    """Parity over the first ``books`` books of every ``group`` consecutive packets; both ends know it out of band, like
     StreamInfo.  Parity group j covers packets [j*group, min(P, (j+1)*group)): G = ceil(P / group) groups per item.  Packet p,
     sent with nb_sent[p] books, is protected to c_p = min(books, nb_sent[p]) books: unequal error protection, the base books only.
-    ``resolve`` checks the values against a stream's shape."""
+    ``parity`` = r packets per group: 1 is the XOR packet; 2..4 a Reed-Solomon code over GF(2^8) whose parity 0 is that XOR packet
+    and which recovers any d <= (arrived parity packets of the group) deficient packets.  ``resolve`` checks the values against a
+    stream's shape."""
     group: int
     books: int
+    parity: int = 1
 
     def __post_init__(self):
-        for name in ("group", "books"):
+        for name in ("group", "books", "parity"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"Fec: {name} = {v!r} is not an integer")
 
+    def __repr__(self):
+        return f"Fec(group={self.group!r}, books={self.books!r}" + (")" if self.parity == 1 else f", parity={self.parity!r})")
+
+    @property
+    def r(self) -> int:
+        """The parity packets per group, validated: 1..4."""
+        r = int(self.parity)
+        if not 1 <= r <= FEC_MAX_PARITY:
+            raise ValueError(f"Fec: parity = {r} outside 1..{FEC_MAX_PARITY}")
+        return r
+
+    def rows_shape(self, info: StreamInfo) -> tuple:
+        """The shape of one item's parity rows: (G, g + W), with parity > 1 (G, r, g + W)."""
+        g, _, G, W = self.resolve(info)
+        return (G, g + W) if self.r == 1 else (G, self.r, g + W)
+
     def resolve(self, info: StreamInfo, chunk_tok: Optional[int] = None):
-        """-> (g, m, G, W): the group size, the protected books, the groups per item and the width of the XOR field,
-        body_bytes(packet_tok, m, K).  ValueError on group outside 1..16, books outside 1..nb, K < 2 (bodies of no bits), and,
-        with ``chunk_tok`` (the model's 16-token chunk), a group that does not divide the chunk_tok // packet_tok packets of a
-        chunk: a group never straddles a chunk."""
+        """-> (g, m, G, W): the group size, the protected books, the groups per item and the width of the code field,
+        body_bytes(packet_tok, m, K).  ValueError on group outside 1..16, books outside 1..nb, parity outside 1..4, K < 2 (bodies
+        of no bits), and, with ``chunk_tok`` (the model's 16-token chunk), a group that does not divide the chunk_tok //
+        packet_tok packets of a chunk: a group never straddles a chunk."""
         info = _check(info)
-        g, m = int(self.group), int(self.books)
+        g, m, _ = int(self.group), int(self.books), self.r
         if not 1 <= g <= FEC_MAX_GROUP:
             raise ValueError(f"Fec: group = {g} outside 1..{FEC_MAX_GROUP}")
         if not 1 <= m <= info.nb:
@@ -382,18 +457,23 @@ def fec_rows(bodies, nb_sent, info: StreamInfo, fec: Fec) -> np.ndarray:
     """bodies[P, body_full], nb_sent (None or a scalar: every packet; or P counts) -> the item's parity uint8[G, g + W].
     Bytes 0..g-1 of row j: c_p = min(m, nb_sent[p]) of the group's packets (0 in the slots of a short tail group); bytes g..g+W-1:
     the XOR over the group's packets of prefix(p), the first body_bytes(ntok_p, c_p, K) bytes of row p with the bits of book c_p
-    and above cleared in the last one, zero-extended to W."""
+    and above cleared in the last one, zero-extended to W.
+    With fec.parity = r > 1 -> uint8[G, r, g + W]: row [j, i] carries the same count bytes, then the GF(2^8) sum over the group's
+    packets u = p - j*g of A[i][u] * prefix(p); A[0][u] = 1, so row [j, 0] is the XOR row."""
     info = _check(info)
     g, m, G, W = fec.resolve(info)
+    r = fec.r
     bodies, counts = _fec_bodies(bodies, info, "fec_rows"), _fec_counts(nb_sent, info, "fec_rows")
     if counts.size and (counts.min() < 0 or counts.max() > 255):
         raise ValueError("fec_rows: a book count outside 0..255")
-    rows = np.zeros((G, g + W), np.uint8)
+    rows = np.zeros((G, r, g + W), np.uint8)
     for p in range(info.P):
         j, c = p // g, min(m, int(counts[p]))
-        rows[j, p - j * g] = c
-        rows[j, g:] ^= _prefix(bodies[p], info.ntok(p), c, info.K, W)
-    return rows
+        rows[j, :, p - j * g] = c
+        prefix = _prefix(bodies[p], info.ntok(p), c, info.K, W)
+        for i in range(r):
+            rows[j, i, g:] ^= gf_mul(fec_coef(i, p - j * g), prefix)
+    return rows.reshape(fec.rows_shape(info))
 
 
 def _fec_group(info: StreamInfo, g: int, j: int) -> range:
@@ -404,24 +484,28 @@ def frame_fec(rows, info: StreamInfo, fec: Fec, seq_base: int = 0) -> list:
     """rows[G, g + W] (fec_rows) -> one ``bytes`` per group: the 9-byte header of the data packets with magic b"MF",
     seq = seq_base + j, the ``ntok`` byte holding the packets of the group g_j and the ``nb_sent`` byte max_p c_p; then the g_j count
     bytes; then the XOR bytes cut to max_p body_bytes(ntok_p, c_p, K) (everything past that is zero by construction).
-    ``seq_base`` (streaming): ``info`` describes one chunk and group j is numbered seq_base + j, the stream's group number."""
+    ``seq_base`` (streaming): ``info`` describes one chunk and group j is numbered seq_base + j, the stream's group number.
+    With fec.parity = r > 1: rows[G, r, g + W] -> r packets per group, group-major.  Index 0 is the ``MF`` packet above, unchanged;
+    index i >= 1 has magic b"MR", the same header fields, one byte i, then the count bytes and the code bytes cut the same way."""
     info = _check(info)
     g, m, G, W = fec.resolve(info)
+    r = fec.r
     seq_base = int(seq_base)
     if not 0 <= seq_base <= 2 ** 32 - G:
         raise ValueError(f"frame_fec: seq_base = {seq_base} with G = {G} groups leaves the 32-bit sequence number")
-    rows = np.asarray(rows, np.uint8).reshape(-1, g + W)
+    rows = np.asarray(rows, np.uint8).reshape(-1, r, g + W)
     if rows.shape[0] != G:
-        raise ValueError(f"frame_fec: {rows.shape[0]} parity rows for G={G} groups")
+        raise ValueError(f"frame_fec: {rows.shape[0] * r} parity rows for G={G} groups of {r}")
     out = []
     for j in range(G):
         grp = _fec_group(info, g, j)
-        counts = [int(v) for v in rows[j, :len(grp)]]
-        if any(not 1 <= c <= m for c in counts):
-            raise ValueError(f"frame_fec: group {j}: a count outside 1..{m}")
-        n = max(body_bytes(info.ntok(p), c, info.K) for p, c in zip(grp, counts))
-        out.append(_HEADER.pack(FEC_MAGIC, VERSION, seq_base + j, len(grp), max(counts)) + rows[j, :len(grp)].tobytes()
-                   + rows[j, g:g + n].tobytes())
+        for i in range(r):
+            counts = [int(v) for v in rows[j, i, :len(grp)]]
+            if any(not 1 <= c <= m for c in counts):
+                raise ValueError(f"frame_fec: group {j}: a count outside 1..{m}")
+            n = max(body_bytes(info.ntok(p), c, info.K) for p, c in zip(grp, counts))
+            out.append(_HEADER.pack(FEC_RS_MAGIC if i else FEC_MAGIC, VERSION, seq_base + j, len(grp), max(counts))
+                       + (bytes([i]) if i else b"") + rows[j, i, :len(grp)].tobytes() + rows[j, i, g:g + n].tobytes())
     return out
 
 
@@ -429,22 +513,31 @@ def gather_fec(fec_packets: Iterable, info: StreamInfo, fec: Fec, seq_base: int 
     """Any iterable of received parity packets -> (rows uint8[G, g + W], got uint8[G]).  Rows of groups whose parity did not arrive
     stay zero with got = 0; duplicates are harmless.  Raises ValueError as ``gather`` does: bad magic or version, a group number
     at or past seq_base + G, a g_j or a count that disagrees with ``info`` / ``fec``, a length that disagrees with the header and
-    the counts.  ``seq_base`` / ``late`` as in ``gather``, in group numbers."""
+    the counts.  ``seq_base`` / ``late`` as in ``gather``, in group numbers.
+    With fec.parity = r > 1 -> (rows uint8[G, r, g + W], got uint8[G], a BITMASK: bit i set = parity i of the group arrived).
+    ``MR`` packets are taken too (refused as a bad magic when r == 1); also refused: an index byte outside 1..r-1, and two parity
+    packets of one group whose count bytes disagree."""
     info = _check(info)
     g, m, G, W = fec.resolve(info)
+    r = fec.r
     seq_base = int(seq_base)
     if not 0 <= seq_base <= 2 ** 32 - G:
         raise ValueError(f"gather_fec: seq_base = {seq_base} with G = {G} groups leaves the 32-bit sequence number")
-    rows, got = np.zeros((G, g + W), np.uint8), np.zeros(G, np.uint8)
+    rows, got = np.zeros((G, r, g + W), np.uint8), np.zeros(G, np.uint8)
     for pkt in fec_packets:
         data = bytes(pkt)
         if len(data) < HEADER_BYTES:
             raise ValueError(f"parity packet: {len(data)} bytes, shorter than the {HEADER_BYTES}-byte header")
         magic, version, seq, gj, cmax = _HEADER.unpack_from(data, 0)
-        if magic != FEC_MAGIC:
+        if magic != FEC_MAGIC and not (magic == FEC_RS_MAGIC and r > 1):
             raise ValueError(f"parity packet: bad magic {magic!r}")
         if version != VERSION:
             raise ValueError(f"parity packet: unsupported version {version}")
+        i, head = 0, HEADER_BYTES                                            # the parity index; where the count bytes start
+        if magic == FEC_RS_MAGIC:
+            if len(data) < HEADER_BYTES + 1 or not 1 <= data[HEADER_BYTES] < r:
+                raise ValueError(f"parity packet: parity index {list(data[HEADER_BYTES:HEADER_BYTES + 1])} outside 1..{r - 1}")
+            i, head = data[HEADER_BYTES], HEADER_BYTES + 1
         j = seq - seq_base
         if j < 0:
             if late is None:
@@ -456,19 +549,22 @@ def gather_fec(fec_packets: Iterable, info: StreamInfo, fec: Fec, seq_base: int 
         grp = _fec_group(info, g, j)
         if gj != len(grp):
             raise ValueError(f"parity packet {j}: covers {gj} packets, the stream has {len(grp)} there")
-        if len(data) < HEADER_BYTES + gj:
+        if len(data) < head + gj:
             raise ValueError(f"parity packet {j}: {len(data)} bytes, shorter than its {gj} count bytes")
-        counts = list(data[HEADER_BYTES:HEADER_BYTES + gj])
+        counts = list(data[head:head + gj])
         if any(not 1 <= c <= m for c in counts) or max(counts) != cmax:
             raise ValueError(f"parity packet {j}: counts {counts} (header: {cmax}) outside 1..{m}")
         n = max(body_bytes(info.ntok(p), c, info.K) for p, c in zip(grp, counts))
-        if len(data) != HEADER_BYTES + gj + n:
-            raise ValueError(f"parity packet {j}: {len(data)} bytes, the header and counts imply {HEADER_BYTES + gj + n}")
-        rows[j] = 0
-        rows[j, :gj] = counts
-        rows[j, g:g + n] = np.frombuffer(data, np.uint8, n, HEADER_BYTES + gj)
-        got[j] = 1
-    return rows, got
+        if len(data) != head + gj + n:
+            raise ValueError(f"parity packet {j}: {len(data)} bytes, the header and counts imply {head + gj + n}")
+        for k in range(r):
+            if k != i and got[j] >> k & 1 and list(rows[j, k, :gj]) != counts:
+                raise ValueError(f"parity packet {j}: counts {counts} of parity {i} disagree with parity {k}'s {list(rows[j, k, :gj])}")
+        rows[j, i] = 0
+        rows[j, i, :gj] = counts
+        rows[j, i, g:g + n] = np.frombuffer(data, np.uint8, n, head + gj)
+        got[j] |= 1 << i
+    return rows.reshape(fec.rows_shape(info)), got
 
 
 def fec_recover(bodies, nb_recv, rows, got, info: StreamInfo, fec: Fec):
@@ -476,45 +572,63 @@ def fec_recover(bodies, nb_recv, rows, got, info: StreamInfo, fec: Fec):
     c_p = min(rows[j, p - j*g], m, nb): packet p is DEFICIENT when nb_recv[p] < c_p (lost, or thinned below its protected count).
     When exactly one packet q of the group is deficient, row q becomes (XOR bytes) ^ XOR_{p != q} prefix(p) over its first
     body_bytes(ntok_q, c_q, K) bytes and zero past them, nb_recv[q] = c_q, recovered[q] = 1: what ``thin`` of the sent packet to
-    c_q books carries.  In every other case (no parity, nothing deficient, two or more deficient) the group stays as it arrived."""
+    c_q books carries.  In every other case (no parity, nothing deficient, two or more deficient) the group stays as it arrived.
+
+    With fec.parity = r > 1 (rows[G, r, g + W], got a bitmask of the arrived parity indices below r): the counts come from the
+    lowest arrived index; with D the deficient packets and 1 <= |D| <= (arrived parities), the |D| LOWEST arrived indices i_k
+    give, per byte, the syndromes S_k = parity_{i_k} ^ sum_{u not in D} A[i_k][u] * prefix(u); M x = S with M[k][d] = A[i_k][q_d]
+    is solved and every q in D is rebuilt as above, all together.  With r == 1 this is the rule above word for word."""
     info = _check(info)
     g, m, G, W = fec.resolve(info)
+    r = fec.r
     bodies = _fec_bodies(bodies, info, "fec_recover").copy()
     nb_recv = np.asarray(nb_recv, np.uint8).reshape(-1).copy()
-    rows, got = np.asarray(rows, np.uint8).reshape(-1, g + W), np.asarray(got).reshape(-1)
+    rows, got = np.asarray(rows, np.uint8).reshape(-1, r, g + W), np.asarray(got).reshape(-1)
     if nb_recv.shape[0] != info.P or rows.shape[0] != G or got.shape[0] != G:
-        raise ValueError(f"fec_recover: {nb_recv.shape[0]} counts, {rows.shape[0]} parity rows, {got.shape[0]} flags for P={info.P}, G={G}")
+        raise ValueError(f"fec_recover: {nb_recv.shape[0]} counts, {rows.shape[0] * r} parity rows, {got.shape[0]} flags for P={info.P}, "
+                         f"G={G}, parity={r}")
     recovered = np.zeros(info.P, np.uint8)
     for j in range(G):
-        if not got[j]:
+        arrived = ([0] if got[j] else []) if r == 1 else [i for i in range(r) if int(got[j]) >> i & 1]
+        if not arrived:
             continue
         grp = _fec_group(info, g, j)
-        c = {p: min(int(rows[j, p - j * g]), m, info.nb) for p in grp}
+        c = {p: min(int(rows[j, arrived[0], p - j * g]), m, info.nb) for p in grp}
         deficient = [p for p in grp if int(nb_recv[p]) < c[p]]
-        if len(deficient) != 1:
+        if not 1 <= len(deficient) <= len(arrived):
             continue
-        q = deficient[0]
-        x = rows[j, g:].copy()
+        use = arrived[:len(deficient)]
+        syn = rows[j, use, g:].copy()                                        # [|D|, W]
         for p in grp:
-            if p != q:
-                x ^= _prefix(bodies[p], info.ntok(p), c[p], info.K, W)
-        n = body_bytes(info.ntok(q), c[q], info.K)
-        bodies[q] = 0
-        bodies[q, :n] = x[:n]
-        nb_recv[q], recovered[q] = c[q], 1
+            if p not in deficient:
+                prefix = _prefix(bodies[p], info.ntok(p), c[p], info.K, W)
+                for k, i in enumerate(use):
+                    syn[k] ^= gf_mul(fec_coef(i, p - j * g), prefix)
+        inv = gf_solve_matrix(use, [q - j * g for q in deficient])
+        for d, q in enumerate(deficient):
+            x = np.zeros(W, np.uint8)
+            for k in range(len(use)):
+                x ^= gf_mul(inv[d, k], syn[k])
+            n = body_bytes(info.ntok(q), c[q], info.K)
+            bodies[q] = 0
+            bodies[q, :n] = x[:n]
+            nb_recv[q], recovered[q] = c[q], 1
     return bodies, nb_recv, recovered
 
 
 def fec_bits(info: StreamInfo, fec: Fec, nb_sent=None, headers: bool = True) -> int:
     """Bits on the wire of one item's parity packets as ``frame_fec`` cuts them (``sent_bits``'s counterpart): per group the XOR
-    bytes, plus the 9-byte header and the count bytes when ``headers``."""
+    bytes, plus the 9-byte header and the count bytes when ``headers``; fec.parity = r such packets per group, those of index
+    i >= 1 with their index byte."""
     info = _check(info)
     g, m, G, W = fec.resolve(info)
+    r = fec.r
     counts = _fec_counts(nb_sent, info, "fec_bits")
     total = 0
     for j in range(G):
         grp = _fec_group(info, g, j)
-        total += max(body_bytes(info.ntok(p), min(m, int(counts[p])), info.K) for p in grp) + ((HEADER_BYTES + len(grp)) if headers else 0)
+        total += r * max(body_bytes(info.ntok(p), min(m, int(counts[p])), info.K) for p in grp) \
+            + ((r * (HEADER_BYTES + len(grp)) + r - 1) if headers else 0)
     return 8 * total
 
 

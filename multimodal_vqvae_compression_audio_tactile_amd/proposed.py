@@ -308,12 +308,13 @@ class _ProposedBase(nn.Module):
 
     @staticmethod
     def _fec_gather(fec, fec_packets, info, B, who, what="fec"):
-        """Host: per item whatever parity packets arrived -> (rows uint8 [B, G, g + W], got uint8 [B, G])."""
+        """Host: per item whatever parity packets arrived -> (rows uint8 [B, G, g + W], got uint8 [B, G]); with fec.parity = r > 1
+        rows uint8 [B, G, r, g + W] and got the bitmask of the arrived parity indices."""
         from . import packets
         if fec_packets is None or len(fec_packets) != B:
             raise MvqError(f"{who}: {what}= needs {what}_packets, one list of parity packets per item (empty when none arrived)")
-        g, m, G, W = fec.resolve(info)
-        rows, got = np.empty((B, G, g + W), np.uint8), np.empty((B, G), np.uint8)
+        rshape = fec.rows_shape(info)
+        rows, got = np.empty((B, *rshape), np.uint8), np.empty((B, rshape[0]), np.uint8)
         for b in range(B):
             rows[b], got[b] = packets.gather_fec(fec_packets[b], info, fec)
         return rows, got
@@ -910,7 +911,9 @@ class ProposedEval(_ProposedBase):
         packets per item; the data packets are byte for byte those of the call without ``fec``.  The closed loop: a recovered packet
         has c_q <= nb_sent[q] books, so the receiver's AR history departs from the sender's exactly as after a relay's ``thin``
         to c_q books, and less than after a loss; with fec.books >= the books in use and at most one deficient packet per group
-        (all parity delivered) the receiver's result equals the lossless one bit for bit."""
+        (all parity delivered) the receiver's result equals the lossless one bit for bit.  With ``fec.parity = r > 1`` (Reed-Solomon
+        over GF(2^8)) every group gets r parity packets, group-major in the item's list -- index 0 the XOR packet unchanged, the
+        others with magic ``MR`` -- and "one deficient packet" above reads "at most as many as parity packets of the group arrived"."""
         from . import bitstream, packets
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
         if fec is not None:
@@ -957,7 +960,9 @@ class ProposedEval(_ProposedBase):
         ops.idx_unpack_packets; everything after is unchanged, and so are the return values -- ``lost`` is what is still lost after
         recovery.  The result equals plain decompress_packets on the list in which every recovered packet is replaced by
         packets.thin(sent_packet, c_q): the receiver's history departs from the sender's as after that thinning, less than after
-        the loss; with fec.books >= the books in use and at most one deficient packet per group it equals the lossless result."""
+        the loss; with fec.books >= the books in use and at most one deficient packet per group it equals the lossless result.
+        With ``fec.parity = r > 1`` the upload carries r rows per group and ``got`` as a bitmask of the arrived parity indices; a
+        group gets back any d <= (arrived parities) deficient packets, still in the one launch."""
         from . import bitstream, packets
         if fec is None and fec_packets is not None:
             raise MvqError("decompress_packets: fec_packets needs fec=, the packets.Fec both ends agreed on")

@@ -468,7 +468,7 @@ class StreamSender(_SenderCore):
     packets (tactile_packets, audio_packets, fec_packets, audio_fec_packets) where a stream without a Fec gets empty lists;
     ``finish`` returns its usual values and then the same parity lists.  Groups are numbered across the stream: chunk c's start at
     c * (16 // packet_tok // group).  Per item the concatenation equals compress_packets(fec=) / compress_packets_av(fec=,
-    audio_fec=) byte for byte, data and parity."""
+    audio_fec=) byte for byte, data and parity.  A Fec with parity = r > 1 emits r packets per group (``MF``, then ``MR``)."""
 
     def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None,
                  audio_rate=None, fec=None, audio_fec=None):
@@ -522,7 +522,7 @@ class StreamSender(_SenderCore):
             if f is None:
                 return 0
             g, _, G, W = f.resolve(inf)
-            return G * (g + W)
+            return G * f.r * (g + W)                                                   # r parity rows per group
 
         if self.audio_packets:
             import numpy as np
@@ -744,8 +744,8 @@ class _ReceiverCore:
                 return o
             g, _, Gr, W = f.resolve(inf)
             assert sl is None                                 # the pools take no fec
-            nr = G * Gr * (g + W)
-            ops.fec_recover(bodies, counts, up[o:o + nr].view(G, Gr, g + W), up[o + nr:o + nr + G * Gr].view(G, Gr), inf, f)
+            nr = G * Gr * f.r * (g + W)                       # r parity rows per group; ``got`` is then a bitmask
+            ops.fec_recover(bodies, counts, up[o:o + nr].view(G, *f.rows_shape(inf)), up[o + nr:o + nr + G * Gr].view(G, Gr), inf, f)
             return o + nr + G * Gr
 
         o_fec = recover(self.fec, StreamInfo(self.K, self.nb, n, self.packet_tok), ub, ur, o_fec)
@@ -879,8 +879,8 @@ class StreamReceiver(_ReceiverCore):
             if f is not None:
                 g, _, Gr, W = f.resolve(inf)
                 par.append((f, inf, [[] for _ in range(B)] if pk is None else self._packets_ok(pk), B * P * (full + 1) + n_audio + n_fec,
-                            g, Gr, W))
-                n_fec += B * Gr * (g + W + 1)
+                            g, Gr, f.r * (g + W)))
+                n_fec += B * Gr * (f.r * (g + W) + 1)
         host = np.empty(B * P * (full + 1) + n_audio + n_fec, np.uint8)
         hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
         base, late = self.tokens // self.packet_tok, []
@@ -891,8 +891,8 @@ class StreamReceiver(_ReceiverCore):
             ab, ar = host[o:o + B * P * afull].reshape(B, P, afull), host[o + B * P * afull:o + B * P * (afull + 1)].reshape(B, P)
             for b in range(B):
                 ab[b], ar[b] = gather(audio_packets[b], ainfo, seq_base=base, late=late)
-        for f, inf, pk, o, g, Gr, W in par:
-            fr, fg = host[o:o + B * Gr * (g + W)].reshape(B, Gr, g + W), host[o + B * Gr * (g + W):o + B * Gr * (g + W + 1)].reshape(B, Gr)
+        for f, inf, pk, o, g, Gr, rw in par:                                  # rw: the bytes of a group's r parity rows
+            fr, fg = host[o:o + B * Gr * rw].reshape(B, *f.rows_shape(inf)), host[o + B * Gr * rw:o + B * Gr * (rw + 1)].reshape(B, Gr)
             for b in range(B):                                                # the chunk's first group, in the stream's numbers
                 fr[b], fg[b] = gather_fec(pk[b], inf, f, seq_base=base // g, late=late)
         self.late += len(late)

@@ -12,11 +12,14 @@ books x K = 512, 32 audio stages x K = 1024, packets of 2 tokens, Fec(4, 3) on t
   (e) loss                     over a seeded channel at 5 / 10 / 20 % independent packet loss (data and parity alike), per stream the
                                share of lost packets recovered, and per chunk index the max |z_run(sender) - z_run(receiver)| over the
                                batch with and without FEC.
+  --parity G:R[,G:R...]        extra codes Fec(G, 3, R) + Fec(G, 4, R) (Reed-Solomon for R > 1): out["parity"] gets, per code, (b) to
+                               (e) again -- the kernel times then name fec_rs_parity_kernel / fec_rs_recover_kernel.  Without the
+                               option the output is what it was.
 Timing: torch.cuda events around each call after the warm-ups, median of the repeats; the events bracket host work too.  Seeded
 synthetic weights and signals: the times mean something, the recovered shares follow from the loss model alone, and the drift
 exercises plumbing only.
 
-  python tools/fec_bench.py [--repeats 10] [--warmup 3] [--batches 1,6,256] [--a-root PATH] [--a-runs 3]
+  python tools/fec_bench.py [--repeats 10] [--warmup 3] [--batches 1,6,256] [--a-root PATH] [--a-runs 3] [--parity 8:2,4:2]
 """
 import argparse
 import json
@@ -69,14 +72,15 @@ def steady_recv(net, B, sent, n_push, graph, fecs=None):
     rx = net.stream_receiver(K, BOOKS, batch=B, graph=graph, audio=(KA, STAGES), **({} if fecs is None else {"fec": fecs[0], "audio_fec": fecs[1]}))
     stamp = lambda p, seq: bytes(p[:3]) + struct.pack("<I", seq) + bytes(p[7:])
 
-    def chunk(lists, c, per):
-        return [[stamp(p, per * c + i) for i, p in enumerate(lists[b][per:2 * per])] for b in range(B)]
+    def chunk(lists, c, per, r=1):                                      # ``per`` numbers per chunk, r packets under each (parity)
+        return [[stamp(p, per * c + i // r) for i, p in enumerate(lists[b][per * r:2 * per * r])] for b in range(B)]
     per = 16 // PTOK
     pushes = []
     for c in range(n_push):
         kw = {"audio_packets": chunk(sent[3], c, per)}
         if fecs is not None:
-            kw.update(fec_packets=chunk(sent[4], c, per // fecs[0].group), audio_fec_packets=chunk(sent[5], c, per // fecs[1].group))
+            kw.update(fec_packets=chunk(sent[4], c, per // fecs[0].group, fecs[0].parity),
+                      audio_fec_packets=chunk(sent[5], c, per // fecs[1].group, fecs[1].parity))
         pushes.append((chunk(sent[1], c, per), kw))
     state = {"c": 0}
 
@@ -117,17 +121,19 @@ def rows_of(net, args, synth, fecs=None):
     return rows
 
 
-def children(args, root):
-    """``--a-runs`` fresh child processes measuring the existing paths of the package under ``root``."""
-    runs = []
-    for _ in range(args.a_runs):
-        child = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--old-only", "--root", str(root), "--repeats",
-                                str(args.repeats), "--warmup", str(args.warmup), "--batches", args.batches],
-                               capture_output=True, text=True, timeout=900)
-        if child.returncode != 0:
-            raise SystemExit(f"measuring {root} failed:\n" + child.stdout[-2000:] + child.stderr[-2000:])
-        runs.append({int(k): v for k, v in json.loads(child.stdout.strip().splitlines()[-1])["old"].items()})
-    return runs
+def children(args, roots):
+    """``--a-runs`` fresh child processes per tree measuring the existing paths of the package under each of ``roots``, the trees
+    alternating (so a drift of the machine over the call lands on both) -> one list of runs per tree."""
+    return [list(runs) for runs in zip(*([child_run(args, root) for root in roots] for _ in range(args.a_runs)))] or [[] for _ in roots]
+
+
+def child_run(args, root):
+    child = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--old-only", "--root", str(root), "--repeats",
+                            str(args.repeats), "--warmup", str(args.warmup), "--batches", args.batches],
+                           capture_output=True, text=True, timeout=900)
+    if child.returncode != 0:
+        raise SystemExit(f"measuring {root} failed:\n" + child.stdout[-2000:] + child.stderr[-2000:])
+    return {int(k): v for k, v in json.loads(child.stdout.strip().splitlines()[-1])["old"].items()}
 
 
 def loss_rows(net, a, t, fecs, rates, seed, packets):
@@ -166,6 +172,25 @@ def loss_rows(net, a, t, fecs, rates, seed, packets):
     return out
 
 
+KERNELS = ("fec_parity_kernel", "fec_recover_kernel", "fec_rs_parity_kernel", "fec_rs_recover_kernel")
+
+
+def kernels_and_overhead(net, a, t, fecs, ops, packets):
+    """(c) and (d) for one batch and one pair of codes."""
+    sent = net.compress_packets_av(a, t, fec=fecs[0], audio_fec=fecs[1])
+    ops.profile_begin()
+    net.compress_packets_av(a, t, fec=fecs[0], audio_fec=fecs[1])
+    net.decompress_packets_av(*sent[:4], fec=fecs[0], fec_packets=sent[4], audio_fec=fecs[1], audio_fec_packets=sent[5])
+    prof = ops.profile_end()
+    info, ainfo = sent[0][0], sent[2][0]
+    return {"kernel_us": {k: 1e6 * prof[k]["seconds"] / prof[k]["launches"] for k in KERNELS if k in prof},
+            "overhead_kbps": {
+                "tactile": {"bodies": packets.fec_kbps(info, fecs[0], headers=False), "with_headers": packets.fec_kbps(info, fecs[0]),
+                            "data_bodies": packets.sent_kbps(info.nb, info, headers=False), "data_with_headers": packets.sent_kbps(info.nb, info)},
+                "audio": {"bodies": packets.fec_kbps(ainfo, fecs[1], headers=False), "with_headers": packets.fec_kbps(ainfo, fecs[1]),
+                          "data_bodies": packets.sent_kbps(ainfo.nb, ainfo, headers=False), "data_with_headers": packets.sent_kbps(ainfo.nb, ainfo)}}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=10)
@@ -174,6 +199,7 @@ def main():
     ap.add_argument("--a-root", default=None, help="a built checkout of the parent commit: the existing paths are also measured on it, in child processes")
     ap.add_argument("--a-runs", type=int, default=3)
     ap.add_argument("--loss-batch", type=int, default=6)
+    ap.add_argument("--parity", default=None, help="extra codes G:R[,G:R...]: Fec(G, 3, R) + Fec(G, 4, R), reported under out['parity']")
     ap.add_argument("--old-only", action="store_true", help="internal: print the existing paths' rows for the package under --root and exit")
     ap.add_argument("--root", default=str(ROOT))
     args = ap.parse_args()
@@ -185,8 +211,7 @@ def main():
         return
     from multimodal_vqvae_compression_audio_tactile_amd import ops, packets
     fecs = (packets.Fec(4, 3), packets.Fec(4, 4))
-    parent = children(args, args.a_root) if args.a_root else []
-    here = children(args, ROOT)
+    parent, here = children(args, [args.a_root, ROOT]) if args.a_root else ([], children(args, [ROOT])[0])
     net = _net(dev)
     with_fec = rows_of(net, args, synth, fecs)
     out = {"books": BOOKS, "K": K, "T_lat": 75, "packet_tok": PTOK, "repeats": args.repeats, "warmup": args.warmup,
@@ -203,22 +228,21 @@ def main():
                              ranges_overlap=min(runs) <= max(pr) and min(pr) <= max(runs))
                 row["existing"][key] = e
             a, t = synth.audio_segments(B, seed=11).to(dev), synth.tactile_segments(B, seed=11).to(dev)
-            sent = net.compress_packets_av(a, t, fec=fecs[0], audio_fec=fecs[1])
-            ops.profile_begin()
-            net.compress_packets_av(a, t, fec=fecs[0], audio_fec=fecs[1])
-            net.decompress_packets_av(*sent[:4], fec=fecs[0], fec_packets=sent[4], audio_fec=fecs[1], audio_fec_packets=sent[5])
-            prof = ops.profile_end()
-            row["kernel_us"] = {k: 1e6 * prof[k]["seconds"] / prof[k]["launches"] for k in ("fec_parity_kernel", "fec_recover_kernel") if k in prof}
-            info, ainfo = sent[0][0], sent[2][0]
-            row["overhead_kbps"] = {
-                "tactile": {"bodies": packets.fec_kbps(info, fecs[0], headers=False), "with_headers": packets.fec_kbps(info, fecs[0]),
-                            "data_bodies": packets.sent_kbps(info.nb, info, headers=False), "data_with_headers": packets.sent_kbps(info.nb, info)},
-                "audio": {"bodies": packets.fec_kbps(ainfo, fecs[1], headers=False), "with_headers": packets.fec_kbps(ainfo, fecs[1]),
-                          "data_bodies": packets.sent_kbps(ainfo.nb, ainfo, headers=False), "data_with_headers": packets.sent_kbps(ainfo.nb, ainfo)}}
+            row.update(kernels_and_overhead(net, a, t, fecs, ops, packets))
             out["rows"].append(row)
         B = args.loss_batch
         a, t = synth.audio_segments(B, seed=11).to(dev), synth.tactile_segments(B, seed=11).to(dev)
         out["loss"] = {"B": B, "rates": loss_rows(net, a, t, fecs, (0.05, 0.10, 0.20), 5, packets)}
+        if args.parity:                                                   # the same channel seeds: the codes see the same data losses
+            out["parity"] = []
+            for g, r in ((int(v) for v in spec.split(":")) for spec in args.parity.split(",")):
+                f2 = (packets.Fec(g, 3, r), packets.Fec(g, 4, r))
+                timed_rows, entry = rows_of(net, args, synth, f2), {"fec": [g, 3, r], "audio_fec": [g, 4, r], "rows": []}
+                for Bk in (int(b) for b in args.batches.split(",")):
+                    ak, tk = synth.audio_segments(Bk, seed=11).to(dev), synth.tactile_segments(Bk, seed=11).to(dev)
+                    entry["rows"].append({"B": Bk, "fec": timed_rows[Bk], **kernels_and_overhead(net, ak, tk, f2, ops, packets)})
+                entry["loss"] = {"B": B, "rates": loss_rows(net, a, t, f2, (0.05, 0.10, 0.20), 5, packets)}
+                out["parity"].append(entry)
     print(json.dumps(out))
 
 
