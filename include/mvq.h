@@ -46,7 +46,8 @@ extern "C" {
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
  * mvq_ar_latents_staged_rate_f32; audio transport: mvq_dac_rvq_from_codes_layers_f32, mvq_dac_rvq_rate_f32,
- * mvq_dac_rvq_rate_workspace_bytes).
+ * mvq_dac_rvq_rate_workspace_bytes; the stateful streaming decoder: mvq_stream_stage_window_f32, mvq_stream_stage_window_slots_f32,
+ * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -702,6 +703,31 @@ int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state,
  * h_in or h_out > cap, a negative size, or a null pointer with a non-empty shape. */
 int mvq_stream_window_f32(float* hist, int h_in, const float* z_new, int n, float* win, int h_out, int cap, int batch, int c,
                           void* stream);
+/* mvq_stream_stage_window_f32: the window of one STAGE of the stateful streaming decoder:
+ * mvq_stream_window_f32 with the new columns taken from a SLICE of a wider tensor, so the crop of the producer's inexact edges and
+ * the window build are one pass.  src[batch, c, src_t] (row pitch src_t); the stage's tail of session b is the [c, cap] block at
+ * tail + b * tail_stride (tail = the session state + the stage's fixed offset, tail_stride = the floats of one session's state).
+ *   win[b, ch, 0 .. win_t) = [tail[0 .. h_in) | src[b, ch, src_off .. src_off + n) | zeros]   (win_t >= h_in + n: a zero tail keeps the
+ *                                                                                            consumer's rows a multiple of 4)
+ *   tail[0 .. h_out)       = the last h_out columns of [tail | new]
+ * in ONE launch under mvq_stream_window_f32's ownership rule (a block reads its (b, ch) rows completely and rewrites only them
+ * after a barrier).  16-byte loads and stores when h_in, n, h_out, cap, src_t, src_off, win_t and tail_stride are multiples of 4
+ * and the pointers 16-byte aligned, 4-byte ones otherwise; no atomics, no scratch.  Tail columns at and past h_out keep their
+ * values.  MVQ_EINVAL before any launch on h_out > h_in + n, h_in or h_out > cap, src_off + n > src_t, win_t < h_in + n,
+ * tail_stride < c * cap, a negative size, or a null pointer with a non-empty shape; batch = 0, c = 0 or h_in + n = 0 returns
+ * MVQ_OK without a launch (win is then not written).
+ * src_seg / win_seg = 1: dense rows, as above.  > 1 (at most 64): PACKED latent-rate rows (below): item b is segment b % seg of
+ * row b / seg, src_t / win_t then being the segment period and a row seg * period columns -- what mvq_conv1d_packed_rows_f32 reads
+ * and writes, so a stage window can be built from a packed producer into packed rows for a packed consumer.  Only the segments
+ * of the batch's own items are written: with batch % win_seg != 0 the caller zeroes the last row's spare segments.
+ * mvq_stream_stage_window_slots_f32: the same kernel body with session g of the group on the state row slots[g] of a pool of
+ * n_slots rows (the receiver pool's rules below: a slot outside [0, n_slots) reads as zeros and stores nothing; n_group = 0
+ * returns MVQ_OK without a launch). */
+int mvq_stream_stage_window_f32(float* tail, size_t tail_stride, int h_in, const float* src, int src_t, int src_seg, int src_off, int n,
+                                float* win, int win_t, int win_seg, int h_out, int cap, int batch, int c, void* stream);
+int mvq_stream_stage_window_slots_f32(float* tail, size_t tail_stride, const int32_t* slots, int n_group, int n_slots, int h_in,
+                                      const float* src, int src_t, int src_seg, int src_off, int n, float* win, int win_t, int win_seg,
+                                      int h_out, int cap, int c, void* stream);
 /* mvq_stream_samples_f32: the sample state of a streaming SENDER session.  buf[rows, cap] fp32 (row pitch
  * cap, the first `fill` samples of every row valid; rows = the audio rows then the tactile rows, so one launch serves both
  * modalities) and x_new[rows, n] (contiguous).  Per row, with v = [buf[0 .. fill) | x_new[0 .. n)]:
@@ -805,6 +831,38 @@ int mvq_encoder_fwd_f32(const mvq_stack* s, const float* x, float* z, void* work
 int mvq_decoder_out_len(const mvq_stack* s, int t);
 size_t mvq_decoder_workspace_bytes(const mvq_stack* s, int batch, int t);      /* covers fwd, fwd_saving and bwd_input */
 int mvq_decoder_fwd_f32(const mvq_stack* s, const float* z, float* y, void* workspace, size_t workspace_bytes, int batch, int t, void* stream);
+/* Stateful streaming decode: T_DEC piece by piece, every stage -- model.0, each DecoderBlock, the final conv --
+ * keeping the tail of its own input in a per-session state row instead of decoding a 36-token window for 16 tokens.  Fed the
+ * pieces of a sequence (pushes of any n <= 1024, then ONE call with last != 0 and the remaining n >= 0 tokens), the emitted pieces are
+ * those of the window schedule -- samples [320 * (N' - 10), 320 * (N - 10)) clamped at 0 for a step from N' to N tokens, up to
+ * 320 * T - 8 with `last` -- and concatenated they equal mvq_decoder_fwd_f32 of the whole sequence bit for bit: no conv kernel's
+ * result depends on column position or row length, and a stage computes only columns whose receptive field lies inside its window
+ * or at a true sequence edge.  Decoders with rates whose emit range the 10-token rule covers and without output_padding;
+ * otherwise MVQ_EUNSUPPORTED.
+ *   mvq_decoder_stream_plan            host arithmetic only (no device call; works on a description-only handle): the stages of
+ *                                      the step that takes n tokens after tokens_before.  stages == NULL: -> the stage count.
+ *                                      Else stages[count][5] = (h_in, src_off, n_new, h_out, cap) per stage -- its window is
+ *                                      [h_in tail columns | columns [src_off, src_off + n_new) of its producer's output], the last
+ *                                      h_out of it are kept, cap = the tail's capacity -- and emit[2] = the [e0, e1) of the final
+ *                                      conv's output that is emitted; -> the stage count, or a negative status.
+ *   mvq_decoder_stream_state_floats    floats of one session's state: the stage tails [cin, cap] one after the other (the block
+ *                                      tails hold values that carry the block's leading Snake already, as the producer writes
+ *                                      them).  A new session needs no clearing: it reads no tail (h_in = 0 everywhere).
+ *   mvq_decoder_stream_workspace_bytes the workspace of the call below for these arguments
+ *   mvq_decoder_stream_fwd_f32         state[n_slots, state_floats]; slots == NULL: session g is row g (n_group <= n_slots), else
+ *                                      row slots[g] (int32 on the device, distinct, the receiver pool's rules);
+ *                                      z_new[n_group, input_channel, n] -> y[n_group, d_out, y_len], the state moved on in place.
+ *                                      Per stage ONE mvq_stream_stage_window launch, then the launches of mvq_decoder_fwd_f32 for
+ *                                      that stage on the window; at the batch sizes where mvq_decoder_fwd_f32 runs its head on
+ *                                      PACKED latent-rate rows this call does too (the windows of model.0 and of the first
+ *                                      transposed conv are built in packed rows).  All tokens_before >= 16 give the same launch
+ *                                      sequence, so the steady step can be captured.  y_len must be e1 - e0 of the plan and the
+ *                                      workspace large enough: MVQ_EINVAL otherwise, before any launch. */
+int mvq_decoder_stream_plan(const mvq_stack* s, int tokens_before, int n, int last, int32_t* stages, int stages_cap, int32_t* emit);
+size_t mvq_decoder_stream_state_floats(const mvq_stack* s);
+size_t mvq_decoder_stream_workspace_bytes(const mvq_stack* s, int n_group, int tokens_before, int n, int last);
+int mvq_decoder_stream_fwd_f32(const mvq_stack* s, float* state, const int32_t* slots, int n_group, int n_slots, const float* z_new, int n,
+                               int tokens_before, int last, float* y, int y_len, void* workspace, size_t workspace_bytes, void* stream);
 size_t mvq_decoder_saved_bytes(const mvq_stack* s, int batch, int t);
 int mvq_decoder_fwd_saving_f32(const mvq_stack* s, const float* z, float* y, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
                                int batch, int t, void* stream);

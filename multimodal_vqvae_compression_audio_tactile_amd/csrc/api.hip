@@ -1422,6 +1422,50 @@ int mvq_stream_window_slots_f32(float* hist, const int32_t* slots, int n_group, 
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_window_slots");
 }
 
+// The checks the two stage-window entry points share (`sessions` = batch or n_group); `rows` = sessions * c.
+static int stream_stage_window_bad(const char* who, int sessions, size_t tail_stride, int h_in, int src_t, int src_seg, int src_off, int n,
+                                   int win_t, int win_seg, int h_out, int cap, int c)
+{
+    if (int rc = stream_window_sizes_bad(who, sessions, h_in, n, h_out, cap, c)) return rc;
+    if (src_t < 0 || src_off < 0 || win_t < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
+    if (src_seg < 1 || win_seg < 1 || src_seg > 64 || win_seg > 64) return fail(MVQ_EINVAL, "%s: src_seg = %d / win_seg = %d segments per row", who, src_seg, win_seg);
+    if ((long long)src_off + n > src_t) return fail(MVQ_EINVAL, "%s: columns [%d, %d + %d) lie outside the source rows of %d", who, src_off, src_off, n, src_t);
+    if (win_t < h_in + n || win_t > (1 << 20)) return fail(MVQ_EINVAL, "%s: window rows of %d columns for h_in + n = %d + %d", who, win_t, h_in, n);
+    if ((h_in || h_out) && tail_stride < (size_t)c * cap)
+        return fail(MVQ_EINVAL, "%s: a session stride of %zu floats holds no [%d, %d] tail", who, tail_stride, c, cap);
+    return MVQ_OK;
+}
+
+int mvq_stream_stage_window_f32(float* tail, size_t tail_stride, int h_in, const float* src, int src_t, int src_seg, int src_off, int n,
+                                float* win, int win_t, int win_seg, int h_out, int cap, int batch, int c, void* stream)
+{
+    if (int rc = stream_stage_window_bad("stream_stage_window", batch, tail_stride, h_in, src_t, src_seg, src_off, n, win_t, win_seg, h_out, cap, c))
+        return rc;
+    const size_t rows = (size_t)batch * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (rows > 0x7FFFFFFFu) return fail(MVQ_EINVAL, "stream_stage_window: too many rows");
+    if (!win || (!tail && (h_in || h_out)) || (!src && n)) return fail(MVQ_EINVAL, "stream_stage_window: null tensor");
+    hipError_t e = mvq::launch_stream_stage_window(tail, tail_stride, nullptr, src, src_t, src_seg, src_off, win, win_t, win_seg, h_in, n, h_out,
+                                                   cap, c, 0, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_stage_window");
+}
+
+int mvq_stream_stage_window_slots_f32(float* tail, size_t tail_stride, const int32_t* slots, int n_group, int n_slots, int h_in,
+                                      const float* src, int src_t, int src_seg, int src_off, int n, float* win, int win_t, int win_seg,
+                                      int h_out, int cap, int c, void* stream)
+{
+    if (int rc = stream_stage_window_bad("stream_stage_window_slots", n_group, tail_stride, h_in, src_t, src_seg, src_off, n, win_t, win_seg, h_out,
+                                         cap, c))
+        return rc;
+    if (int rc = slots_shape_bad("stream_stage_window_slots", n_group, n_slots, c)) return rc;
+    const size_t rows = (size_t)n_group * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (!slots || !win || (!tail && (h_in || h_out)) || (!src && n)) return fail(MVQ_EINVAL, "stream_stage_window_slots: null tensor");
+    hipError_t e = mvq::launch_stream_stage_window(tail, tail_stride, slots, src, src_t, src_seg, src_off, win, win_t, win_seg, h_in, n, h_out,
+                                                   cap, c, n_slots, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_stage_window_slots");
+}
+
 int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
                            void* stream)
 {

@@ -157,6 +157,9 @@ hipError_t launch_rvq_rate(const float* z, size_t z_sb, size_t z_sd, const int32
 // stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024).  slots ==
 // nullptr: every session of the buffers, densely; else the G sessions slots[G] (a device list) of a pool of n_slots, C rows per
 // session and rows = G*C <= INT_MAX
+hipError_t launch_stream_stage_window(float* tail, size_t tail_stride, const int32_t* slots, const float* src, int src_t, int src_seg,
+                                      int src_off, float* win, int win_t, int win_seg, int h_in, int n, int h_out, int cap, int C,
+                                      int n_slots, size_t rows, hipStream_t s);
 hipError_t launch_stream_window(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out, int cap,
                                 int C, int n_slots, size_t rows, hipStream_t s);
 hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B, int n_new,

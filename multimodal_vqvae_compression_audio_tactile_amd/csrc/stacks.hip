@@ -511,6 +511,177 @@ void decoder_plan(Run& r, const mvq_stack& s, const float* z, float* y_out, int 
     r.ar.release(h);
 }
 
+// ---- stateful streaming decode ---------------------------------------------------------------------------
+// Every stage -- model.0, each DecoderBlock, the final conv -- keeps the tail of its own input between the steps of a session, so
+// a step computes each stage on [tail | the producer's new exact columns] only.  stream_stages() is the geometry (the Python
+// mirror's stream.DEC_STAGES / DEC_STAGE_TAILS), stream_plan() one step's arithmetic (stream.decoder_stage_plan), and
+// decoder_stream_plan() walks it: per stage ONE mvq_stream_stage_window launch and then the launches decoder_plan issues for that
+// stage on the window.  At throughput batches the head keeps decoder_plan's PACKED latent-rate rows (stream_use_packed): the
+// stage-window kernel writes model.0's window straight into packed rows and builds the first block's window from model.0's packed
+// output into packed rows again, so the crop and the tail between the two cost no unpacking.
+constexpr int STREAM_HALO_TOK = 10;                    // the emit rule of the window schedule (stream.DEC_HALO_TOK)
+constexpr int STREAM_RU_LOSS = 3 * (1 + 3 + 9);        // columns the three units (k7, dilations 1, 3, 9) lose at a cut edge
+struct StreamStage { int s, off, loss, cap, cin; size_t at; };     // at: offset of the stage's [cin, cap] tail in a session's state row
+struct StreamStep { int h_in, src_off, n_new, h_out; };
+struct StreamPlan { std::vector<StreamStep> st; int e0 = 0, e1 = 0; };
+
+bool stream_stages(const mvq_stack& s, std::vector<StreamStage>* out, size_t* floats)
+{
+    if (!s.decoder || s.out_padding || s.first.ks != 7 || s.last.ks != 7) return false;
+    std::vector<StreamStage> v;
+    v.push_back({1, 0, 3, 0, s.first.cin, 0});
+    for (auto& b : s.blocks) v.push_back({b.res.stride, b.res.stride - 2 * b.res.pad, b.res.stride - b.res.pad + STREAM_RU_LOSS, 0, b.res.cin, 0});
+    v.push_back({1, 0, 3, 0, s.last.cin, 0});
+    long long hop = 1, add = 0;                        // a stage's input after N tokens of pushes: hop * N + add columns
+    size_t at = 0;
+    for (size_t k = 0; k < v.size(); ++k) {
+        StreamStage& g = v[k];
+        long long need = (2 * g.loss - g.off + g.s - 1) / g.s;
+        if (k + 1 == v.size()) {                       // the final conv also holds back what the schedule emits a step later
+            const long long hold = add + hop * STREAM_HALO_TOK;
+            if (hold < g.loss) return false;           // the schedule's halo is shorter than the stack's right-edge loss
+            if (hold + g.loss > need) need = hold + g.loss;
+        }
+        g.cap = ceil4((int)need);
+        g.at = at;
+        at += (size_t)g.cin * g.cap;
+        hop *= g.s;
+        add = add * g.s + g.off - g.loss;
+    }
+    *out = v;
+    if (floats) *floats = at;
+    return true;
+}
+
+int stream_plan(const mvq_stack& s, const std::vector<StreamStage>& sg, int before, int n, bool last, StreamPlan* p)
+{
+    // n <= 1024: every stage window then stays far below the 2^20 columns mvq_stream_stage_window_f32 accepts, so no launch of a
+    // walk can be refused for its size after earlier ones ran
+    if (before < 0 || n < 0 || before > (1 << 24) || n > 1024) return sfail(MVQ_EINVAL, "decoder_stream: tokens_before = %d, n = %d", before, n);
+    long long hv = before, src_off = 0, n_new = n, a = 0, hi = 0, hop = 1;
+    p->st.clear();
+    for (auto& g : sg) {
+        const long long h_in = hv < g.cap ? hv : g.cap, w = h_in + n_new;
+        a = hv - h_in;
+        const long long keep = w < g.cap ? w : g.cap;
+        p->st.push_back({(int)h_in, (int)src_off, (int)n_new, last ? 0 : (int)keep});
+        long long done = hv > 0 ? hv * g.s + g.off - g.loss : 0;
+        if (done < 0) done = 0;
+        const long long next_hv = done;
+        done -= a * g.s;                               // handed on before, local to this window's output
+        hi = (w > 0 ? w * g.s + g.off : 0) - (last ? 0 : g.loss);
+        if (hi < done) hi = done;
+        src_off = done; n_new = hi - done;
+        hv = next_hv;
+        hop *= g.s;
+    }
+    const long long g0 = hop * (before > STREAM_HALO_TOK ? before - STREAM_HALO_TOK : 0);
+    long long g1 = last ? decoder_len(s, before + n) : hop * (before + n > STREAM_HALO_TOK ? before + n - STREAM_HALO_TOK : 0);
+    p->e0 = p->e1 = 0;
+    if (g1 > g0) {
+        if (g0 < a || g1 - a > hi) return sfail(MVQ_EUNSUPPORTED, "decoder_stream: the emit range lies outside the final stage's exact columns");
+        p->e0 = (int)(g0 - a); p->e1 = (int)(g1 - a);
+    }
+    return MVQ_OK;
+}
+
+// the stage-window launch of stage `g`: dense or through the slot list
+int stage_window(const StreamStage& g, const StreamStep& st, size_t state_floats, float* state, const int32_t* slots, int G, int n_slots,
+                 const float* src, int src_t, int src_seg, float* win, int win_t, int win_seg, void* stream)
+{
+    float* tail = state ? state + g.at : nullptr;
+    return slots ? mvq_stream_stage_window_slots_f32(tail, state_floats, slots, G, n_slots, st.h_in, src, src_t, src_seg, st.src_off, st.n_new, win,
+                                                     win_t, win_seg, st.h_out, g.cap, g.cin, stream)
+                 : mvq_stream_stage_window_f32(tail, state_floats, st.h_in, src, src_t, src_seg, st.src_off, st.n_new, win, win_t, win_seg, st.h_out,
+                                               g.cap, G, g.cin, stream);
+}
+
+// decoder_use_packed for the head of a step: model.0 on windows of w0 columns, the first transposed conv on windows of w1
+bool stream_use_packed(const mvq_stack& s, int G, int w0, int w1)
+{
+    return w0 > 0 && w0 <= 1024 && s.blocks.size() >= 1 && decoder_use_packed(s, G, w1);
+}
+
+// state[sessions, state_floats] (row g or slots[g]), z_new[G, cin, n] -> y[G, d_out, e1 - e0]
+void decoder_stream_plan(Run& r, const mvq_stack& s, const std::vector<StreamStage>& sg, const StreamPlan& p, size_t state_floats, float* state,
+                         const int32_t* slots, int G, int n_slots, const float* z_new, float* y_out)
+{
+    const int nb = (int)s.blocks.size(), ns = (int)sg.size();
+    const float* src = z_new;
+    float* src_buf = nullptr;                          // the producer's output when it lives in the arena
+    int src_t = p.st[0].n_new;
+    int k0 = 0;
+    const int w0 = p.st[0].h_in + p.st[0].n_new, w1 = p.st[1].h_in + p.st[1].n_new;
+    if (stream_use_packed(s, G, w0, w1)) {
+        // model.0 and the first block's transposed conv on PACKED rows (decoder_plan's head): pack_seg sessions side by side in a
+        // GEMM row, each segment ceil4(w + 3) columns of which w are the window and the rest the zeros the conv pads with
+        const Conv& c0 = s.first;
+        const Block& b0 = s.blocks[0];
+        const Conv& up_ = b0.res;
+        const int seg = s.pack_seg, Gp = (G + seg - 1) / seg, per0 = ceil4(w0 + 3), per1 = ceil4(w1 + 3);
+        const size_t n0 = (size_t)Gp * c0.cin * seg * per0, n1 = (size_t)Gp * up_.cin * seg * per1;
+        float* zp = r.ar.alloc(n0);
+        if (G % seg) r.launch([&] { return hip_rc(hipMemsetAsync(zp, 0, n0 * 4, hip_stream(r.stream)), "decoder_stream_fwd: memset"); });
+        r.launch([&] { return stage_window(sg[0], p.st[0], state_floats, state, slots, G, n_slots, z_new, src_t, 1, zp, per0, seg, r.stream); });
+        float* hp = r.ar.alloc((size_t)Gp * c0.cout * seg * per0);
+        r.launch([&] { return mvq_conv1d_packed_rows_f32(zp, c0.wp, c0.bias, nullptr, b0.alpha, hp, nullptr, nullptr, Gp, c0.cin, c0.cout, 7, 1, 3,
+                                                         MVQ_ACT_NONE, seg, per0, w0, r.stream); });
+        r.ar.release(zp);
+        float* wp1 = r.ar.alloc(n1);
+        if (G % seg) r.launch([&] { return hip_rc(hipMemsetAsync(wp1, 0, n1 * 4, hip_stream(r.stream)), "decoder_stream_fwd: memset"); });
+        r.launch([&] { return stage_window(sg[1], p.st[1], state_floats, state, slots, G, n_slots, hp, per0, seg, wp1, per1, seg, r.stream); });
+        r.ar.release(hp);
+        const int tout = (w1 - 1) * up_.stride - 2 * up_.pad + 2 * up_.stride;
+        const bool wide = b0.width >= s.presnaked_min_c;
+        float* u = r.ar.alloc((size_t)G * up_.cout * tout);
+        float* us = wide ? r.ar.alloc((size_t)G * up_.cout * tout) : nullptr;
+        r.launch([&] { return mvq_conv_transpose1d_packed_rows_f32(wp1, up_.wp, up_.bias, nullptr, nullptr, u, us, us ? b0.ru[0].alpha_a : nullptr, Gp,
+                                                                   up_.cin, up_.cout, up_.stride, up_.pad, seg, per1, w1, G, r.stream); });
+        r.ar.release(wp1);
+        src_buf = run_units(r, s, b0, G, tout, u, us, nb > 1 ? s.blocks[1].alpha : s.alpha_last, 0);
+        src = src_buf; src_t = tout;
+        k0 = 2;
+    }
+    for (int k = k0; k < ns && r.ok(); ++k) {
+        const StreamStage& g = sg[k];
+        const StreamStep& st = p.st[k];
+        const int W = st.h_in + st.n_new;
+        if (W == 0) { r.ar.release(src_buf); src_buf = nullptr; src = nullptr; src_t = 0; continue; }
+        // rows that are not a multiple of 4 are carried zero-padded, as decoder_plan carries them
+        const int rows = (W % 4 && g.cin % 32 == 0) ? ceil4(W) : W;
+        float* win = r.ar.alloc((size_t)G * g.cin * rows);
+        r.launch([&] { return stage_window(g, st, state_floats, state, slots, G, n_slots, src, src_t, 1, win, rows, 1, r.stream); });
+        r.ar.release(src_buf);
+        if (k == 0) {
+            const Conv& c0 = s.first;
+            float* h = r.ar.alloc((size_t)G * c0.cout * rows);
+            r.launch([&] { return mvq_conv1d_padded_f32(win, c0.wp, c0.bias, nullptr, nullptr, s.blocks[0].alpha, h, nullptr, nullptr, G, c0.cin, rows,
+                                                        c0.cout, 7, 1, 1, 3, MVQ_ACT_NONE, rows != W ? W : 0, r.stream); });
+            r.ar.release(win);
+            src_buf = h; src_t = rows;
+        } else if (k <= nb) {
+            const float* nxt = k < nb ? s.blocks[k].alpha : s.alpha_last;
+            int tn = 0, rn = 0;
+            src_buf = decoder_block(r, s, s.blocks[k - 1], G, win, rows, W, nxt, &tn, &rn);
+            src_t = rn;
+        } else {
+            const Conv& cl = s.last;
+            float* yt = r.ar.alloc((size_t)G * cl.cout * rows);
+            r.launch([&] { return mvq_conv1d_padded_f32(win, cl.wp, cl.bias, nullptr, nullptr, nullptr, yt, nullptr, nullptr, G, cl.cin, rows, cl.cout, 7, 1,
+                                                        1, 3, MVQ_ACT_TANH, 0, r.stream); });
+            r.ar.release(win);
+            const int ne = p.e1 - p.e0;
+            if (ne > 0)
+                r.launch([&] { return mvq_copy3d_f32(yt + p.e0, (size_t)cl.cout * rows, (size_t)rows, y_out, (size_t)cl.cout * ne, (size_t)ne, G, cl.cout, ne,
+                                                     r.stream); });
+            r.ar.release(yt);
+            src_buf = nullptr;
+        }
+        src = src_buf;
+    }
+    r.ar.release(src_buf);
+}
+
 // ---- training config: saving forward + backward w.r.t. the input (weights frozen) -------------------------------------------------
 // Saved forward, in this order (a bump allocation over `saved`): h0 [model.0 output], per block: u [transposed conv output], then
 // per unit: t7 [7-tap pre-activation] and the unit's output; y.  Every tensor is written by its producer kernel directly.
@@ -739,6 +910,57 @@ int mvq_decoder_fwd_f32(const mvq_stack* s, const float* z, float* y, void* work
     if (!z || !y || !workspace) return sfail(MVQ_EINVAL, "decoder_fwd: null tensor");
     return plan_run(workspace, workspace_bytes, stream, "decoder_fwd", [&](Run& r) { decoder_plan(r, *s, z, y, batch, t); });
 }
+// ---- stateful streaming decode: the C face of stream_stages / stream_plan / decoder_stream_plan
+int mvq_decoder_stream_plan(const mvq_stack* s, int tokens_before, int n, int last, int32_t* stages, int stages_cap, int32_t* emit)
+{
+    std::vector<StreamStage> sg;
+    if (!s || !stream_stages(*s, &sg, nullptr)) return sfail(MVQ_EUNSUPPORTED, "decoder_stream_plan: not a decoder stack the stage plan covers");
+    const int ns = (int)sg.size();
+    if (!stages) return ns;                                  /* the size query */
+    if (stages_cap < ns) return sfail(MVQ_EINVAL, "decoder_stream_plan: room for %d stages, the stack has %d", stages_cap, ns);
+    StreamPlan p;
+    if (int rc = stream_plan(*s, sg, tokens_before, n, last != 0, &p)) return rc;
+    for (int k = 0; k < ns; ++k) {
+        int32_t* o = stages + 5 * k;
+        o[0] = p.st[k].h_in; o[1] = p.st[k].src_off; o[2] = p.st[k].n_new; o[3] = p.st[k].h_out; o[4] = sg[k].cap;
+    }
+    if (emit) { emit[0] = p.e0; emit[1] = p.e1; }
+    return ns;
+}
+size_t mvq_decoder_stream_state_floats(const mvq_stack* s)
+{
+    std::vector<StreamStage> sg;
+    size_t floats = 0;
+    return (s && stream_stages(*s, &sg, &floats)) ? floats : 0;
+}
+size_t mvq_decoder_stream_workspace_bytes(const mvq_stack* s, int n_group, int tokens_before, int n, int last)
+{
+    std::vector<StreamStage> sg;
+    size_t floats = 0;
+    StreamPlan p;
+    if (!s || n_group <= 0 || !stream_stages(*s, &sg, &floats) || stream_plan(*s, sg, tokens_before, n, last != 0, &p) != MVQ_OK) return 0;
+    return plan_peak([&](Run& r) { decoder_stream_plan(r, *s, sg, p, floats, nullptr, nullptr, n_group, n_group, nullptr, nullptr); });
+}
+int mvq_decoder_stream_fwd_f32(const mvq_stack* s, float* state, const int32_t* slots, int n_group, int n_slots, const float* z_new, int n,
+                               int tokens_before, int last, float* y, int y_len, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!s || !s->decoder || !s->first.wp) return sfail(MVQ_EINVAL, "decoder_stream_fwd: not a decoder stack with weights");
+    std::vector<StreamStage> sg;
+    size_t floats = 0;
+    if (!stream_stages(*s, &sg, &floats)) return sfail(MVQ_EUNSUPPORTED, "decoder_stream_fwd: a stack the stage plan does not cover");
+    if (n_group < 0 || n_slots < 0 || n_group > n_slots) return sfail(MVQ_EINVAL, "decoder_stream_fwd: a group of %d sessions, %d state rows", n_group, n_slots);
+    StreamPlan p;
+    if (int rc = stream_plan(*s, sg, tokens_before, n, last != 0, &p)) return rc;
+    if (y_len != p.e1 - p.e0) return sfail(MVQ_EINVAL, "decoder_stream_fwd: y_len = %d, the step emits %d samples", y_len, p.e1 - p.e0);
+    if (n_group == 0) return MVQ_OK;
+    bool any = false;
+    for (auto& st : p.st) any = any || st.h_in + st.n_new > 0;
+    if (!any) return MVQ_OK;
+    if (!state || !workspace || (!z_new && n) || (!y && y_len)) return sfail(MVQ_EINVAL, "decoder_stream_fwd: null tensor");
+    return plan_run(workspace, workspace_bytes, stream, "decoder_stream_fwd",
+                    [&](Run& r) { decoder_stream_plan(r, *s, sg, p, floats, state, slots, n_group, n_slots, z_new, y); });
+}
+
 size_t mvq_decoder_saved_bytes(const mvq_stack* s, int batch, int t)
 {
     if (!s || !s->decoder || batch <= 0 || t <= 0) return 0;

@@ -1,5 +1,5 @@
-// stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32 and
-// mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
+// stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32,
+// mvq_stream_stage_window_f32 (the stateful decoder's per-stage window) and mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
 // the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
 // every time (a captured graph replays it).  A POOL of sessions keeps one row block per session slot in
 // the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
@@ -74,6 +74,59 @@ __global__ __launch_bounds__(256) void stream_window_kernel(float* __restrict__ 
         const int r = e / h_out, j = e - r * h_out;
         size_t at;
         if (ses.row(row0 + r, at)) hist[at * (size_t)cap + j] = wb[r * W + skip + j];
+    }
+}
+
+// The window of one decoder STAGE of the stateful streaming decoder: stream_window_kernel with the new
+// columns taken from a slice of a wider tensor, the crop of the producer's inexact edges folded into the window build.
+//   win(g, c)[0 .. win_t) = [tail(g, c)[0 .. h_in) | src(g, c)[src_off .. src_off + n) | zeros],
+//   then tail(g, c)[0 .. h_out) = win(g, c)[W - h_out .. W),   W = h_in + n <= win_t.
+// Rows of src and win: with seg == 1 the dense row g*C + c of pitch src_t / win_t; with seg > 1 PACKED latent-rate rows
+// (include/mvq.h): item g is segment g % seg of row (g / seg)*C + c, the segments src_t / win_t columns apart -- the layout
+// mvq_conv1d_packed_rows_f32 reads and writes, so the head of the stack stays packed at throughput batches.  The zero tail of a
+// window row (or segment) is the zero padding its consumer reads.  tail(g, c) = tail + session*tail_stride + c*cap: a stage's tail
+// is a [C, cap] block at a fixed offset of the session's state row, session = g or slots[g].  Same ownership rule as
+// stream_window_kernel: a block owns `rpb` consecutive (g, c), reads them completely, writes their part of win (a buffer of its
+// own), and rewrites only its own tail rows after the barrier.  A slot outside [0, n_slots) reads zeros and stores nothing.
+// V = float4 when every column count, pitch and offset is a multiple of 4 and every pointer 16-byte aligned (the launcher
+// decides; all counts are then in units of V), else float.
+struct StageRows {
+    int pitch, seg;                                                      // columns of a row (or segment); segments per row
+    __device__ size_t at(int g, int c, int C) const
+    {
+        return ((size_t)(g / seg) * C + c) * ((size_t)seg * pitch) + (size_t)(g % seg) * pitch;
+    }
+};
+template <bool SLOTS, class V>
+__global__ __launch_bounds__(256) void stream_stage_window_kernel(V* tail, const V* __restrict__ src, V* win, int h_in, int n, int h_out,
+                                                                  int cap, size_t tail_stride, StageRows sr, int src_off, StageRows wr,
+                                                                  int C, int rpb, size_t rows, Sessions<SLOTS> ses)
+{
+    const size_t row0 = (size_t)blockIdx.x * rpb;
+    const int nrow = (int)(rows - row0 < (size_t)rpb ? rows - row0 : (size_t)rpb);
+    const int W = h_in + n, win_t = wr.pitch;
+    const int total = nrow * win_t;
+    const V zero{};
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int r = e / win_t, j = e - r * win_t;
+        const int g = (int)((row0 + r) / C), c = (int)((row0 + r) - (size_t)g * C);
+        V v = zero;
+        if (j < h_in) {
+            size_t s;
+            if (ses.session(g, s)) v = tail[s * tail_stride + (size_t)c * cap + j];
+        } else if (j < W) {
+            v = src[sr.at(g, c, C) + src_off + (j - h_in)];
+        }
+        win[wr.at(g, c, C) + j] = v;
+    }
+    __syncthreads();
+    const int skip = W - h_out;
+    const int total_h = nrow * h_out;
+    for (int e = threadIdx.x; e < total_h; e += 256) {
+        const int r = e / h_out, j = e - r * h_out;
+        const int g = (int)((row0 + r) / C), c = (int)((row0 + r) - (size_t)g * C);
+        size_t s;
+        if (ses.session(g, s)) tail[s * tail_stride + (size_t)c * cap + j] = win[wr.at(g, c, C) + skip + j];
     }
 }
 
@@ -246,6 +299,41 @@ hipError_t launch_stream_window(float* hist, const int32_t* slots, const float* 
     else
         hipLaunchKernelGGL(stream_window_kernel<false>, grid, block, 0, s, hist, z_new, win, h_in, n, h_out, cap, rows,
                            Sessions<false>{});
+    return hipGetLastError();
+}
+
+// slots == nullptr: the dense instantiation; else the group slots[rows / C] of a pool of n_slots sessions.  The entry points have
+// checked every size; src_seg / win_seg: 1 = dense rows, else packed rows of that many segments.
+hipError_t launch_stream_stage_window(float* tail, size_t tail_stride, const int32_t* slots, const float* src, int src_t, int src_seg,
+                                      int src_off, float* win, int win_t, int win_seg, int h_in, int n, int h_out, int cap, int C,
+                                      int n_slots, size_t rows, hipStream_t s)
+{
+    if (rows == 0 || h_in + n == 0) return hipSuccess;
+    int rpb = 2048 / win_t;                                             // about 2048 window elements per block
+    rpb = rpb < 1 ? 1 : (rpb > WIN_ROWS ? WIN_ROWS : rpb);
+    const dim3 grid((unsigned)((rows + rpb - 1) / rpb)), block(256);
+    const bool vec = !((h_in | n | h_out | cap | src_t | src_off | win_t) & 3) && !(tail_stride & 3) &&
+                     !(((uintptr_t)tail | (uintptr_t)src | (uintptr_t)win) & 15);
+    if (vec) {
+        float4* t4 = reinterpret_cast<float4*>(tail);
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* w4 = reinterpret_cast<float4*>(win);
+        const StageRows sr{src_t / 4, src_seg}, wr{win_t / 4, win_seg};
+        if (slots)
+            hipLaunchKernelGGL((stream_stage_window_kernel<true, float4>), grid, block, 0, s, t4, s4, w4, h_in / 4, n / 4, h_out / 4, cap / 4,
+                               tail_stride / 4, sr, src_off / 4, wr, C, rpb, rows, Sessions<true>{slots, n_slots, C});
+        else
+            hipLaunchKernelGGL((stream_stage_window_kernel<false, float4>), grid, block, 0, s, t4, s4, w4, h_in / 4, n / 4, h_out / 4, cap / 4,
+                               tail_stride / 4, sr, src_off / 4, wr, C, rpb, rows, Sessions<false>{});
+    } else {
+        const StageRows sr{src_t, src_seg}, wr{win_t, win_seg};
+        if (slots)
+            hipLaunchKernelGGL((stream_stage_window_kernel<true, float>), grid, block, 0, s, tail, src, win, h_in, n, h_out, cap, tail_stride,
+                               sr, src_off, wr, C, rpb, rows, Sessions<true>{slots, n_slots, C});
+        else
+            hipLaunchKernelGGL((stream_stage_window_kernel<false, float>), grid, block, 0, s, tail, src, win, h_in, n, h_out, cap, tail_stride,
+                               sr, src_off, wr, C, rpb, rows, Sessions<false>{});
+    }
     return hipGetLastError();
 }
 

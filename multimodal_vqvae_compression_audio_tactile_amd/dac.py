@@ -490,6 +490,21 @@ class Decoder(nn.Module):
             del xin
         return m[0].dgrad(g, saved["z_len"])
 
+    # ---- stateful streaming decode: T_DEC piece by piece, every stage keeping the tail of its input -----------
+    def stream_state(self, rows):
+        """The decoder state of ``rows`` streaming sessions, fp32 [rows, S] on the weights' device (Stack.decoder_stream_state)."""
+        return self.stack().decoder_stream_state(rows, device=next(self.parameters()).device)
+
+    @torch.no_grad()
+    def forward_stream(self, state, z_new, tokens_before, last, slots=None, slots_dev=None):
+        """One step: z_new[G, C, n] after ``tokens_before`` tokens -> the samples the window schedule emits for it; ``state`` moves
+        on in place.  The pieces of a sequence concatenated equal forward(z) bit for bit.  ONE C call, mvq_decoder_stream_fwd_f32;
+        there is no Python-walked form, so the opt-in arithmetic modes and USE_STACKS = False are refused."""
+        if not USE_STACKS:
+            raise ValueError("Decoder.forward_stream: the stateful decoder exists as the library's plan only; the plan overrides in the "
+                             "environment switch the stack calls off")
+        return self.stack().decoder_stream_fwd(state, z_new, tokens_before, last, slots=slots, slots_dev=slots_dev)
+
     def forward(self, z):
         """Inference: the fused fast path.  With autograd enabled and z.requires_grad (the reference's training step,
         Training/compare_dacvsproposal_5.py:322,393): saving forward + HIP backward w.r.t. z; weights stay frozen."""

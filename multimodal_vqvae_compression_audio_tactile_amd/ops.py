@@ -1354,6 +1354,47 @@ def stream_window_slots(hist, slots, h_in, z_new, h_out, slots_dev=None):
     return _stream_window("stream_window_slots", hist, h_in, z_new, h_out, sd)
 
 
+def _stream_stage_window(who, tail, h_in, src, src_off, n, h_out, cap, tail_off, win_t, sd):
+    """stream_stage_window and stream_stage_window_slots: ``sd`` None for the dense sessions, else the group's device slot list."""
+    src = _dev(src, "src")
+    if not isinstance(tail, torch.Tensor) or tail.dim() != 2 or src.dim() != 3 or tail.dtype != torch.float32 or not tail.is_cuda \
+            or not tail.is_contiguous() or tail.device != src.device:
+        raise MvqError(f"{who}: the state must be a contiguous fp32 HIP tensor [sessions, floats] and src [B, C, src_t] on its device")
+    rows, stride = tail.shape
+    B, C, src_t = src.shape
+    h_in, src_off, n, h_out, cap, tail_off = (int(v) for v in (h_in, src_off, n, h_out, cap, tail_off))
+    if sd is None and B > rows:
+        raise MvqError(f"{who}: {B} sessions, the state has {rows} rows")
+    if cap < 0 or tail_off < 0 or tail_off + C * cap > stride:
+        raise MvqError(f"{who}: a [{C}, {cap}] tail at offset {tail_off} does not fit a state row of {stride} floats")
+    win_t = max(h_in, 0) + max(n, 0) if win_t is None else int(win_t)
+    win = torch.empty(B, C, max(win_t, 0), device=src.device, dtype=torch.float32)
+    tp = tail.data_ptr() + 4 * tail_off
+    if sd is None:
+        check(_lib.lib().mvq_stream_stage_window_f32(tp, stride, h_in, src.data_ptr(), src_t, 1, src_off, n, win.data_ptr(), win_t, 1, h_out, cap,
+                                                     B, C, _stream()), "mvq_stream_stage_window_f32")
+    else:
+        check(_lib.lib().mvq_stream_stage_window_slots_f32(tp, stride, sd.data_ptr(), B, rows, h_in, src.data_ptr(), src_t, 1, src_off, n,
+                                                           win.data_ptr(), win_t, 1, h_out, cap, C, _stream()),
+              "mvq_stream_stage_window_slots_f32")
+    return win
+
+
+def stream_stage_window(state, h_in, src, src_off, n, h_out, cap, tail_off=0, win_t=None):
+    """One stage window of the stateful streaming decoder (mvq_stream_stage_window_f32): win[B, C, win_t] = [tail[..., :h_in] |
+    src[..., src_off:src_off + n] | zeros], then tail[..., :h_out] <- the last h_out columns of [tail | new], in one launch.
+    ``state``: contiguous fp32 [sessions, floats], updated in place; the stage's tail of session b is the [C, cap] block at
+    state[b, tail_off:].  Dense rows (the packed-row forms of the entry point are the stack call's own).  ``win_t`` None: h_in + n.  With h_in + n = 0 nothing is launched and ``win`` is not written."""
+    return _stream_stage_window("stream_stage_window", state, h_in, src, src_off, n, h_out, cap, tail_off, win_t, None)
+
+
+def stream_stage_window_slots(state, slots, h_in, src, src_off, n, h_out, cap, tail_off=0, win_t=None, slots_dev=None):
+    """stream_stage_window for the sessions ``slots`` (host integers) of a pool: session g of src / win on state[slots[g]]
+    (mvq_stream_stage_window_slots_f32); unlisted rows are not touched."""
+    _, sd = _slot_list("stream_stage_window_slots", slots, state, 2, slots_dev)
+    return _stream_stage_window("stream_stage_window_slots", state, h_in, src, src_off, n, h_out, cap, tail_off, win_t, sd)
+
+
 def resample_stream_slots(x_new, kern, state, slots, consumed, orig, newf, width, final=False, slots_dev=None):
     """resample_stream for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots] moved on
     in place (mvq_resample_stream_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of ``orig`` of at
@@ -1791,6 +1832,72 @@ class Stack:
         if y.numel():
             ws = self._ws(z, B, t)
             check(_lib.lib().mvq_decoder_fwd_f32(self.handle, z.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, t, _stream()), "mvq_decoder_fwd_f32")
+        return y
+
+    # ---- stateful streaming decode (include/mvq.h)
+    def decoder_stream_state_floats(self):
+        return int(_lib.lib().mvq_decoder_stream_state_floats(self.handle))
+
+    def decoder_stream_state(self, rows, device=None):
+        """The state of ``rows`` streaming sessions: fp32 [rows, S], every stage's tail at a fixed offset of a row.  Not cleared: a new
+        session reads none of it."""
+        S = self.decoder_stream_state_floats()
+        if self.kind != "decoder" or S == 0:
+            raise MvqError("Stack.decoder_stream_state: not a decoder stack the stage plan covers")
+        if int(rows) < 1:
+            raise MvqError("Stack.decoder_stream_state: rows must be at least 1")
+        return torch.empty(int(rows), S, device=self.blob.device if device is None else device, dtype=torch.float32)
+
+    def decoder_stream_plan(self, tokens_before, n, last=False):
+        """-> (stages, (e0, e1)): per stage (h_in, src_off, n_new, h_out, cap) of the step (mvq_decoder_stream_plan, host only)."""
+        import ctypes
+        L = _lib.lib()
+        ns = int(L.mvq_decoder_stream_plan(self.handle, 0, 0, 0, None, 0, None))
+        if ns <= 0:
+            check(ns or -2, "mvq_decoder_stream_plan")
+        buf, emit = (ctypes.c_int32 * (5 * ns))(), (ctypes.c_int32 * 2)()
+        rc = int(L.mvq_decoder_stream_plan(self.handle, int(tokens_before), int(n), int(bool(last)), buf, ns, emit))
+        if rc < 0:
+            check(rc, "mvq_decoder_stream_plan")
+        return tuple(tuple(buf[5 * k:5 * k + 5]) for k in range(ns)), (int(emit[0]), int(emit[1]))
+
+    def decoder_stream_fwd(self, state, z_new, tokens_before, last=False, slots=None, slots_dev=None):
+        """One step of the stateful decoder: z_new[G, C, n] after ``tokens_before`` tokens -> y[G, d_out, n_emit] (mvq_decoder_stream_fwd_f32);
+        ``state`` (decoder_stream_state) moves on in place.  ``slots`` None: session g is state row g; else host integers, session
+        g on state[slots[g]] (``slots_dev``: their int32 device copy when the caller uploaded it already).  Only arithmetic mode
+        "f32" (the opt-in modes scale per item)."""
+        if get_arith() != "f32":
+            raise ValueError(f"Stack.decoder_stream_fwd: arithmetic mode {get_arith()!r} scales per item; only 'f32' is equal piece by piece")
+        S = self.decoder_stream_state_floats()
+        if not isinstance(state, torch.Tensor) or state.dim() != 2 or state.shape[1] != S or state.dtype != torch.float32:
+            raise ValueError(f"Stack.decoder_stream_fwd: the state must be an fp32 tensor [sessions, {S}] (decoder_stream_state), got "
+                             f"{tuple(state.shape) if isinstance(state, torch.Tensor) else type(state).__name__}")
+        z_new = _dev(z_new, "z_new")
+        if not state.is_cuda or not state.is_contiguous() or state.device != z_new.device:
+            raise ValueError("Stack.decoder_stream_fwd: the state must be contiguous and on z_new's device")
+        if z_new.dim() != 3 or z_new.shape[1] != self.desc.input_channel:
+            raise ValueError(f"Stack.decoder_stream_fwd: z_new must be [G, {self.desc.input_channel}, n], got {tuple(z_new.shape)}")
+        G, _, n = z_new.shape
+        sd = None
+        if slots is not None:
+            g, sd = _slot_list("Stack.decoder_stream_fwd", slots, state, 2, slots_dev)
+            if g != G:
+                raise ValueError(f"Stack.decoder_stream_fwd: {g} slots for {G} sessions")
+        elif G > state.shape[0]:
+            raise ValueError(f"Stack.decoder_stream_fwd: {G} sessions, the state has {state.shape[0]} rows")
+        before, last = int(tokens_before), bool(last)
+        _, (e0, e1) = self.decoder_stream_plan(before, n, last)
+        y = torch.empty(G, self.desc.d_out, e1 - e0, device=z_new.device, dtype=torch.float32)
+        if G == 0:
+            return y
+        key = ("stream", G, min(before, 16), n, last)
+        nb = self._ws_bytes.get(key)
+        if nb is None:
+            nb = self._ws_bytes[key] = max(int(_lib.lib().mvq_decoder_stream_workspace_bytes(self.handle, G, before, n, int(last))), 256)
+        ws = torch.empty(nb, device=z_new.device, dtype=torch.uint8)
+        check(_lib.lib().mvq_decoder_stream_fwd_f32(self.handle, state.data_ptr(), None if sd is None else sd.data_ptr(), G, state.shape[0],
+                                                    z_new.data_ptr(), n, before, int(last), y.data_ptr(), e1 - e0, ws.data_ptr(), ws.numel(),
+                                                    _stream()), "mvq_decoder_stream_fwd_f32")
         return y
 
     def decoder_fwd_saving(self, z):

@@ -1116,20 +1116,24 @@ class ProposedEval(_ProposedBase):
         return y, nb_valid == 0, na_valid == 0
 
     def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                        fec=None, audio_fec=None, audio_conceal="zero"):
+                        fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
-        time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit."""
+        time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit.
+        ``decoder="stateful"``: the same tensors from the stateful decoder (per-stage history instead of the 36-token window)."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
-                              out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal)
+                              out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,
+                              decoder=decoder)
 
-    def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None):
+    def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
+                             decoder="window"):
         """A pool of up to ``slots`` independent receiver sessions on this model (stream.StreamReceiverPool): ``open`` a
         session, ``step`` once per tick with the chunks that are ready (and the sessions that end); each session gets what a
         stream_receiver(batch=1) of its own would return, and the sessions of a tick share batched launches."""
         from .stream import StreamReceiverPool
         return StreamReceiverPool(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
-                                  out_rate=out_rate, audio_conceal=audio_conceal)    # the pool takes no audio= and refuses an audio_conceal
+                                  out_rate=out_rate, audio_conceal=audio_conceal,    # the pool takes no audio= and refuses an audio_conceal
+                                  decoder=decoder)
 
     def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None,
                       fec=None, audio_fec=None):

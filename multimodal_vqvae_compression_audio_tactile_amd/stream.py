@@ -22,6 +22,10 @@ of a 75-token item reproduces the whole-item latents bit for bit except for the 
 a window that starts on a multiple of 320 samples keeps every stage's stride alignment, so a true sequence edge is exact
 (tests/test_sender_cpu.py: the sender's schedule is exact at halo 8 and not at halo 7).
 
+``StreamReceiver(decoder="stateful")`` replaces the latent window by a history PER DECODER STAGE: every stage
+keeps the tail of its own input and a step computes it on [tail | new columns] only; ``decoder_stage_plan`` is that step's host
+arithmetic (DEC_STAGES, DEC_STAGE_TAILS), and every call returns the window mode's tensor.
+
 ``schedule`` / ``sender_schedule`` are host arithmetic only; ``StreamReceiver`` / ``StreamSender`` are the session objects
 (``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).  ``StreamReceiverPool`` (``ProposedEval.stream_receiver_pool``)
 serves receiver sessions that join, run and leave independently: their state lies in slots of one set of device buffers and a
@@ -110,6 +114,97 @@ def _window_plan(before: int, n: int, last: bool) -> Tuple[int, int, int, int]:
     g0 = HOP * max(0, before - DEC_HALO_TOK)
     g1 = max(0, HOP * (before + n) - DEC_TAIL) if last else HOP * max(0, before + n - DEC_HALO_TOK)
     return h, min(2 * DEC_HALO_TOK, h + n), g0 - HOP * a, g1 - HOP * a
+
+
+DEC_RATES = (8, 5, 4, 2)          # dac.DEC_RATES, restated so that decoder_stage_plan() needs no torch
+DEC_RU_LOSS = 3 * (1 + 3 + 9)     # columns the three ResidualUnits (k7, dilations 1, 3, 9) lose at a cut edge
+
+
+def _dec_stage_geometry(rates=DEC_RATES):
+    """The decoder's stages as (stride s, off, loss): a window of w > 0 input columns makes w*s + off output columns, of which
+    ``loss`` at every edge that is not the sequence's are inexact.  model.0 and the final conv are k7 (s = 1, loss 3); a
+    DecoderBlock is a transposed conv (kernel 2s, padding p = ceil(s/2): off = s - 2p, it loses s - p columns) and three units."""
+    blocks = tuple((s, s - 2 * ((s + 1) // 2), s - (s + 1) // 2 + DEC_RU_LOSS) for s in rates)
+    return ((1, 0, 3),) + blocks + ((1, 0, 3),)
+
+
+DEC_STAGES = _dec_stage_geometry()
+# Tail columns a stage keeps of its own input (DESIGN.md section 23).  The least that is exact: ceil((2*loss - off) / s) -- the
+# next window's first exact output column must not lie past the last one already handed on -- 6, 11, 17, 21, 40; the final conv
+# also holds back the samples between the stateful right edge (320*N - 3141) and the schedule's (320*(N - 10)) and needs 65.
+# Each is rounded up to a multiple of 4, so that the steady windows (24, 28, 148, 664, 2600, 5188 columns) are too.
+DEC_STAGE_TAILS = (8, 12, 20, 24, 40, 68)
+
+
+class StageStep(NamedTuple):
+    """One stage of one step: the window is [h_in tail columns | the producer's output columns [src_off, src_off + n_new)], and
+    the last ``h_out`` columns of it are the tail afterwards."""
+    h_in: int
+    src_off: int
+    n_new: int
+    h_out: int
+
+
+class StagePlan(NamedTuple):
+    """``stages``: model.0, the four DecoderBlocks, the final conv; [e0, e1): the emitted samples, local to the final conv's output."""
+    stages: Tuple[StageStep, ...]
+    e0: int
+    e1: int
+
+
+def dec_stage_min_tails() -> Tuple[int, ...]:
+    """The least tail every stage may keep: the first exact output column of the next window, (have - h)*s + loss, must not lie
+    past the last column handed on, have*s + off - loss; the final conv must also reach back to the schedule's emit border,
+    320*(N - 10), from its input's 320*N - 3138 columns."""
+    need = [-(-(2 * loss - off) // s) for s, off, loss in DEC_STAGES]
+    hop, add = 1, 0
+    for s, off, loss in DEC_STAGES[:-1]:
+        hop, add = hop * s, add * s + off - loss
+    assert hop == HOP and hop * DEC_HALO_TOK + add >= DEC_STAGES[-1][2]         # the schedule's right margin covers the stack's loss
+    need[-1] = max(need[-1], hop * DEC_HALO_TOK + add + DEC_STAGES[-1][2])
+    return tuple(need)
+
+
+assert dec_stage_min_tails() == (6, 11, 17, 21, 40, 65)
+assert all(t >= m and t % 4 == 0 and t - m < 4 for t, m in zip(DEC_STAGE_TAILS, dec_stage_min_tails()))
+
+
+def _dec_stage_have(tokens: int) -> List[int]:
+    """Input columns every stage has received once ``tokens`` tokens went through pushes: what its producer could hand on, every
+    window's right edge being cut (w*s + off - loss of its columns so far)."""
+    have, x = [], int(tokens)
+    for s, off, loss in DEC_STAGES:
+        have.append(x)
+        x = max(0, x * s + off - loss) if x > 0 else 0
+    return have
+
+
+def decoder_stage_plan(tokens_before: int, n: int, last: bool = False, tails=DEC_STAGE_TAILS) -> StagePlan:
+    """The stateful decoder's step that takes ``n`` new tokens after ``tokens_before`` (host arithmetic; the library's
+    mvq_decoder_stream_plan says the same).  Stage k's window covers its global input columns [a, b), a = have - h_in; its output
+    column j is global column a*s + j.  Exact outputs: all of the window's, less ``loss`` at the left unless a == 0 and at the
+    right unless ``last``.  What is handed on is what is exact and was not handed on before.  ``last`` flushes every stage against
+    its true right edge (n = 0 too: the tails alone) and keeps nothing.  The emitted samples are stream.schedule's.  The plan
+    depends on tokens_before only through min(tokens_before, 16): from 16 tokens on every tail is full.  ``tails`` other than
+    DEC_STAGE_TAILS are for the tests: a tail below dec_stage_min_tails() hands on inexact columns."""
+    before, n, last = int(tokens_before), int(n), bool(last)
+    if before < 0 or n < 0:
+        raise ValueError(f"decoder_stage_plan: tokens_before = {before}, n = {n}")
+    have = _dec_stage_have(before)
+    stages, src_off, n_new, a, hi = [], 0, n, 0, 0
+    for (s, off, loss), cap, hv in zip(DEC_STAGES, tails, have):
+        h_in = min(cap, hv)
+        a, w = hv - h_in, h_in + n_new
+        stages.append(StageStep(h_in, src_off, n_new, 0 if last else min(cap, w)))
+        done = (max(0, hv * s + off - loss) if hv > 0 else 0) - a * s      # handed on before, local to this window's output
+        hi = max(done, (w * s + off if w > 0 else 0) - (0 if last else loss))
+        src_off, n_new = done, hi - done
+    g0 = HOP * max(0, before - DEC_HALO_TOK)                               # the final conv has s = 1: its output column j is sample a + j
+    g1 = max(0, HOP * (before + n) - DEC_TAIL) if last else HOP * max(0, before + n - DEC_HALO_TOK)
+    if g1 <= g0:
+        return StagePlan(tuple(stages), 0, 0)
+    assert g0 >= a and g1 - a <= hi
+    return StagePlan(tuple(stages), g0 - a, g1 - a)
 
 
 def resample_stream_out_len(consumed: int, n_new: int, orig: int, width: int, final: bool = False) -> int:
@@ -663,11 +758,19 @@ class _ReceiverCore:
     pool session computes what a solo one does."""
 
     def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None,
-                 audio_conceal="zero"):
+                 audio_conceal="zero", decoder="window"):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check, body_bytes
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        if decoder not in ("window", "stateful"):
+            raise ValueError(f"StreamReceiver: decoder must be 'window' or 'stateful', not {decoder!r}")
+        self.decoder = decoder
+        if decoder == "stateful":
+            _f32_only("StreamReceiver(decoder='stateful')")
+            if tuple(net.T_DEC._desc[2]) != DEC_RATES or net.T_DEC._desc[4]:
+                raise ValueError(f"StreamReceiver: decoder rates {tuple(net.T_DEC._desc[2])}; the stage plan is written for {DEC_RATES} "
+                                 "without output_padding")
         if audio_conceal not in ("zero", "mask", "hold"):
             raise ValueError(f"StreamReceiver: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
         if audio_conceal != "zero" and audio is None:
@@ -696,7 +799,11 @@ class _ReceiverCore:
         self.n_audio_books = net.A_QUANT.n_codebooks
         self.carry = torch.zeros(rows, self.C, device=self.dev)                        # per session: z_run[..., -1] of the chunk before
         self.qa_carry = torch.zeros(rows, self.C, device=self.dev) if audio_conceal == "hold" else None   # the last held audio token
-        self.hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)       # per session: the last <= 20 latent tokens
+        self.hist = self.dec_state = None
+        if decoder == "window":
+            self.hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)   # per session: the last <= 20 latent tokens
+        else:                                                                          # per session: every decoder stage's tail (section 23)
+            self.dec_state = net.T_DEC.stream_state(rows)
         self.rs_state = self.rs_kernel = None
         if self.out_rate != proposed.EVAL_SR:
             from .resample import sinc_resample_kernel
@@ -771,9 +878,17 @@ class _ReceiverCore:
             z = ops.plc_mask_fill(z, None, nbv == 0)[0]
         return z
 
-    def _window_decode(self, z, h_in, h_out, e0, e1, sl=None):
-        """Device: window = [history | z] (history updated in place), T_DEC on it, samples [e0, e1) of the window's output."""
+    def _window_decode(self, z, h_in, h_out, e0, e1, sl=None, last=False):
+        """Device: window = [history | z] (history updated in place), T_DEC on it, samples [e0, e1) of the window's output.
+        decoder="stateful": the same samples from T_DEC.forward_stream, every stage on [its tail | its new columns] (dec_state updated
+        in place).  h_in = min(tokens_before, 20) stands for tokens_before there: the stage plan depends on it only through
+        min(tokens_before, 16)."""
         from . import ops
+        if self.dec_state is not None:
+            y = self.net.T_DEC.forward_stream(self.dec_state, z, h_in, last, slots=None if sl is None else sl[0],
+                                              slots_dev=None if sl is None else sl[1])
+            assert y.shape[-1] == e1 - e0
+            return y
         if sl is None:
             win = ops.stream_window(self.hist, h_in, z, h_out)
         else:
@@ -788,7 +903,7 @@ class _ReceiverCore:
         if h_in + n == 0:
             return torch.empty(G, 1, 0, device=self.dev)
         z = self._latents(up, codes, n, sl, last) if n else torch.empty(G, self.C, 0, device=self.dev)
-        return self._window_decode(z, h_in, h_out, e0, e1, sl)
+        return self._window_decode(z, h_in, h_out, e0, e1, sl, last)
 
     def _decimate(self, y, consumed, last, sl=None):
         """out_rate=3000: the emitted piece through the streamed resampler, ``consumed`` = the samples the sessions emitted before
@@ -843,10 +958,15 @@ class StreamReceiver(_ReceiverCore):
     the existing arrays in the ONE upload, ops.fec_recover in place ahead of each stream's unpack: recovery is inside the captured
     steady step, whose only input stays the static upload buffer, so the graph replays under any loss pattern.  A parity packet of
     an earlier chunk is counted in ``late`` and ignored, as a late data packet is.  The concatenated output equals
-    decompress_packets(fec=) / decompress_packets_av(fec=, audio_fec=) on the same packets."""
+    decompress_packets(fec=) / decompress_packets_av(fec=, audio_fec=) on the same packets.
+
+    ``decoder="stateful"`` (the default "window" is the sequence above, launch for launch): instead of T_DEC on
+    the 36-token window, T_DEC.forward_stream -- every decoder stage keeps the tail of its own input in dec_state [B, S] (it replaces
+    the history [B, C, 20]) and computes only its new columns.  Every push / finish returns exactly the window mode's tensor; the
+    steady step stays ONE captured graph; everything in front of the latents and behind the samples is untouched."""
 
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                 fec=None, audio_fec=None, audio_conceal="zero"):
+                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
@@ -854,7 +974,7 @@ class StreamReceiver(_ReceiverCore):
         if fec is not None or audio_fec is not None:
             _f32_only("StreamReceiver")
         super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
-                         audio_conceal=audio_conceal)
+                         audio_conceal=audio_conceal, decoder=decoder)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -998,7 +1118,8 @@ class StreamReceiver(_ReceiverCore):
         if self._g is None:
             up_s = torch.from_numpy(host).to(self.dev)
             codes_s = None if codes is None else codes.to(self.dev).long().clone()
-            state = (self.hist, self.carry) + ((self.qa_carry,) if self.qa_carry is not None else ())
+            state = (self.hist if self.dec_state is None else self.dec_state, self.carry) + \
+                ((self.qa_carry,) if self.qa_carry is not None else ())
             g, y_s = _capture(self.dev, state, lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
             if self.fec is not None or self.audio_fec is not None:            # the eager run before the capture recovered in place
@@ -1028,9 +1149,13 @@ class StreamReceiverPool(_ReceiverCore):
       device per group of G sessions: ops.idx_unpack_packets -> ops.stream_rows (the carried tokens, pool -> dense [G, C]) ->
              decode_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.stream_window_slots -> T_DEC on [G, C, window]
              -> the emit slice (-> ops.resample_stream_slots): _ReceiverCore's sequence on the group's slots.
-    ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick."""
+    ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick.
 
-    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None):
+    ``decoder="stateful"``: as for StreamReceiver -- dec_state [S, floats] replaces hist, and a group's decode is
+    T_DEC.forward_stream on the group's slots.  ``open`` leaves a slot's dec_state as it is: a new session reads no tail."""
+
+    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
+                 decoder="window"):
         if audio_conceal is not None:
             raise ValueError("StreamReceiverPool: the pool takes no audio= packets and so no audio_conceal")
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
@@ -1038,7 +1163,7 @@ class StreamReceiverPool(_ReceiverCore):
         if slots < 1:
             raise ValueError("StreamReceiverPool: slots must be at least 1")
         _f32_only("StreamReceiverPool")
-        super().__init__(net, K, nb, packet_tok, slots, books_use, conceal, out_rate)
+        super().__init__(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, decoder=decoder)
         self.slots = slots
         self._free = list(range(slots))                                                # ascending: open() takes the lowest
         self._sess = {}                                                                # sid -> [slot, tokens, late]

@@ -17,7 +17,10 @@ The two ratios are reported, not gated.  Timing: torch.cuda events around each c
 chunk of a session that keeps running (the packets of one chunk are re-numbered on the host for each).  Seeded synthetic weights
 and signals: only the times mean anything.
 
-  python tools/stream_pool_bench.py [--repeats 10] [--warmup 3] [--sessions 1,6,64,256]
+With --decoder stateful every row also carries "stateful": the same rounds on StreamReceiverPool(decoder="stateful") (DESIGN.md
+section 23), measured in the same run right after the window-mode pool's, and window_round_over_stateful_round.
+
+  python tools/stream_pool_bench.py [--repeats 10] [--warmup 3] [--sessions 1,6,64,256] [--decoder window|stateful]
 """
 import argparse
 import json
@@ -53,9 +56,9 @@ def spread(ms):
     return {"median": statistics.median(ms), "min": min(ms), "max": max(ms), "n": len(ms)}
 
 
-def pool_rounds(net, chunk, codes, S, warmup, repeats):
+def pool_rounds(net, chunk, codes, S, warmup, repeats, **kw):
     """-> (per-round sums, the times of the ticks that served a session) of `repeats` steady rounds."""
-    pool = net.stream_receiver_pool(K, BOOKS, slots=S)
+    pool = net.stream_receiver_pool(K, BOOKS, slots=S, **kw)
     sids = [pool.open() for _ in range(S)]
 
     def tick(t):
@@ -107,6 +110,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sessions", default="1,6,64,256")
+    ap.add_argument("--decoder", choices=("window", "stateful"), default="window",
+                    help="stateful: also measure StreamReceiverPool(decoder='stateful') in the same run")
     args = ap.parse_args()
     sys.path.insert(0, str(ROOT))
     from multimodal_vqvae_compression_audio_tactile_amd import bitstream, build_proposed, synth
@@ -132,6 +137,10 @@ def main():
             row["round_over_lockstep"] = row["round_ms"]["median"] / lock["median"]
             row["round_over_solo"] = row["round_ms"]["median"] / row["solo_total_ms"]
             row["real_time_factor"] = row["round_ms"]["median"] / CHUNK_MS
+            if args.decoder == "stateful":
+                r2, s2 = pool_rounds(net, chunk, codes, S, args.warmup, args.repeats, decoder="stateful")
+                row["stateful"] = {"tick_ms": spread(s2), "round_ms": spread(r2)}
+                row["window_round_over_stateful_round"] = row["round_ms"]["median"] / row["stateful"]["round_ms"]["median"]
             out["rows"].append(row)
     print(json.dumps(out))
     slow = [r["S"] for r in out["rows"] if r["round_ms"]["median"] >= CHUNK_MS]
