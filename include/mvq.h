@@ -47,7 +47,9 @@ extern "C" {
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
  * mvq_ar_latents_staged_rate_f32; audio transport: mvq_dac_rvq_from_codes_layers_f32, mvq_dac_rvq_rate_f32,
  * mvq_dac_rvq_rate_workspace_bytes; the stateful streaming decoder: mvq_stream_stage_window_f32, mvq_stream_stage_window_slots_f32,
- * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32).
+ * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32; the
+ * stateful streaming encoder: mvq_stream_stage_window_snake_f32, mvq_stream_stage_window_snake_slots_f32, mvq_encoder_stream_plan,
+ * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -728,6 +730,18 @@ int mvq_stream_stage_window_f32(float* tail, size_t tail_stride, int h_in, const
 int mvq_stream_stage_window_slots_f32(float* tail, size_t tail_stride, const int32_t* slots, int n_group, int n_slots, int h_in,
                                       const float* src, int src_t, int src_seg, int src_off, int n, float* win, int win_t, int win_seg,
                                       int h_out, int cap, int c, void* stream);
+/* mvq_stream_stage_window_snake_f32 / _slots_f32: the stage window of a WIDE block of the stateful streaming ENCODER (DESIGN.md
+ * section 24).  The same body on dense rows (no packed forms) with a second output beside win:
+ *   win_s[b, ch, j] = det_snake(win[b, ch, j], alpha[ch], 1.0f / (alpha[ch] + 1e-9f))   for j < h_in + n, +0 in the zero tail,
+ * the function and the reciprocal expression of the conv epilogues' dual output, so win_s is bit for bit the Snake copy the
+ * producer of a whole-signal encode writes beside its raw output.  The tail stays RAW (a snaked tail would double the state).
+ * win_s[batch, c, win_t] has win's layout, alpha[c].  The checks, the ownership rule, the 16-byte / 4-byte choice (win_s must be
+ * aligned too) and the slot rules are mvq_stream_stage_window_f32's; no atomics, no LDS, no scratch. */
+int mvq_stream_stage_window_snake_f32(float* tail, size_t tail_stride, int h_in, const float* src, int src_t, int src_off, int n, float* win,
+                                      float* win_s, const float* alpha, int win_t, int h_out, int cap, int batch, int c, void* stream);
+int mvq_stream_stage_window_snake_slots_f32(float* tail, size_t tail_stride, const int32_t* slots, int n_group, int n_slots, int h_in,
+                                            const float* src, int src_t, int src_off, int n, float* win, float* win_s, const float* alpha,
+                                            int win_t, int h_out, int cap, int c, void* stream);
 /* mvq_stream_samples_f32: the sample state of a streaming SENDER session.  buf[rows, cap] fp32 (row pitch
  * cap, the first `fill` samples of every row valid; rows = the audio rows then the tactile rows, so one launch serves both
  * modalities) and x_new[rows, n] (contiguous).  Per row, with v = [buf[0 .. fill) | x_new[0 .. n)]:
@@ -828,6 +842,36 @@ int mvq_stack_set_plan(mvq_stack* s, int vpack_min_batch, int pack_min_batch);
 int mvq_encoder_out_len(const mvq_stack* s, int t);
 size_t mvq_encoder_workspace_bytes(const mvq_stack* s, int batch, int t);
 int mvq_encoder_fwd_f32(const mvq_stack* s, const float* x, float* z, void* workspace, size_t workspace_bytes, int batch, int t, void* stream);
+/* Stateful streaming encode: A_ENC / T_ENC piece by piece, every stage -- block.0 (k7), each EncoderBlock,
+ * the final Snake + k3 -- keeping the tail of its own input in a per-session state row, so a step encodes only the samples that
+ * were not encoded yet instead of a 32-token window for 16 tokens.  Fed the pieces of a signal (calls with any n <= 2^20 - 256 samples,
+ * then ONE call with last != 0 and the remaining n >= 0 samples) the emitted latent columns are, per call, those whose receptive
+ * field [320 j - 2501, 320 j + 2812] lies inside the samples so far (clamped at the signal's edges; everything left with `last`),
+ * and concatenated they equal mvq_encoder_fwd_f32 of the whole signal bit for bit: a stage's window starts on a global column
+ * that is a multiple of its stride, and only output columns whose inputs are exact are handed on.
+ *   mvq_encoder_stream_plan            host arithmetic only (no device call; works on a description-only handle).  stages ==
+ *                                      NULL: -> the stage count.  Else stages[count][5] = (h_in, src_off, n_new, h_out, cap) per
+ *                                      stage -- its window is [h_in tail columns | columns [src_off, src_off + n_new) of its
+ *                                      producer's output], the last h_out of it are kept -- and emit[2] = the GLOBAL latent
+ *                                      columns [t0, t1) the step emits (z_len = t1 - t0; they are the columns [src_off', src_off' +
+ *                                      z_len) of the k3 conv's output, src_off' = what a further stage would be handed); -> the
+ *                                      stage count, or a negative status.
+ *   mvq_encoder_stream_state_floats    floats of one session's state: the RAW stage tails [cin, cap] one after the other (the k3
+ *                                      stage's holds values that carry the final Snake, as its producer writes them).  A new
+ *                                      session needs no clearing: it reads no tail.
+ *   mvq_encoder_stream_workspace_bytes the workspace of the call below for these arguments
+ *   mvq_encoder_stream_fwd_f32         state[n_slots, state_floats]; slots == NULL: session g is row g, else row slots[g] (int32 on
+ *                                      the device, distinct); x_new[n_group, 1, n] -> z[n_group, d_latent, z_len], the state moved
+ *                                      on in place.  Per stage ONE stage-window launch (mvq_stream_stage_window_f32, or _snake_f32
+ *                                      in front of a block of 65 channels or more, which needs its input raw and snaked) and then
+ *                                      the launches mvq_encoder_fwd_f32 issues for that stage, on dense rows at every batch size.
+ *                                      z_len must be t1 - t0 of the plan and the workspace large enough: MVQ_EINVAL otherwise,
+ *                                      before any launch. */
+int mvq_encoder_stream_plan(const mvq_stack* s, long long samples_before, int n, int last, int32_t* stages, int stages_cap, long long* emit);
+size_t mvq_encoder_stream_state_floats(const mvq_stack* s);
+size_t mvq_encoder_stream_workspace_bytes(const mvq_stack* s, int n_group, long long samples_before, int n, int last);
+int mvq_encoder_stream_fwd_f32(const mvq_stack* s, float* state, const int32_t* slots, int n_group, int n_slots, const float* x_new, int n,
+                               long long samples_before, int last, float* z, int z_len, void* workspace, size_t workspace_bytes, void* stream);
 int mvq_decoder_out_len(const mvq_stack* s, int t);
 size_t mvq_decoder_workspace_bytes(const mvq_stack* s, int batch, int t);      /* covers fwd, fwd_saving and bwd_input */
 int mvq_decoder_fwd_f32(const mvq_stack* s, const float* z, float* y, void* workspace, size_t workspace_bytes, int batch, int t, void* stream);

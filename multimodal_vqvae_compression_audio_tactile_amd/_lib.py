@@ -142,7 +142,10 @@ EXPORTS = {
     "mvq_stream_stage_window_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 4 + [c_void_p] + [c_int] * 6 + [c_void_p]),
     "mvq_stream_stage_window_slots_f32": (c_int, [c_void_p, c_size_t, c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 4 + [c_void_p]
                                           + [c_int] * 5 + [c_void_p]),
-    "mvq_stream_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "mvq_stream_stage_window_snake_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
+    "mvq_stream_stage_window_snake_slots_f32": (c_int, [c_void_p, c_size_t, c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 3 + [c_void_p] * 3
+                                                + [c_int] * 4 + [c_void_p]),
+    "mvq_stream_rows_f32":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mvq_sumsq_partial_f32": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "mvq_adamw_f32": (c_int, [c_void_p] * 5 + [c_size_t] + [c_float] * 5 + [c_int, c_void_p]),
     "mvq_conv1d_padded_f32": (c_int, [c_void_p] * 9 + [c_int] * 10 + [c_void_p]),
@@ -170,7 +173,12 @@ EXPORTS = {
     "mvq_decoder_out_len": (c_int, [c_void_p, c_int]),
     "mvq_decoder_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "mvq_decoder_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
-    "mvq_decoder_stream_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mvq_encoder_stream_plan": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mvq_encoder_stream_state_floats": (c_size_t, [c_void_p]),
+    "mvq_encoder_stream_workspace_bytes": (c_size_t, [c_void_p, c_int, ctypes.c_longlong, c_int, c_int]),
+    "mvq_encoder_stream_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p, c_int,
+                                           c_void_p, c_size_t, c_void_p]),
+    "mvq_decoder_stream_plan":(c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mvq_decoder_stream_state_floats": (c_size_t, [c_void_p]),
     "mvq_decoder_stream_workspace_bytes": (c_size_t, [c_void_p] + [c_int] * 4),
     "mvq_decoder_stream_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,

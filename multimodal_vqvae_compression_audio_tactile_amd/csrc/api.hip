@@ -1466,6 +1466,36 @@ int mvq_stream_stage_window_slots_f32(float* tail, size_t tail_stride, const int
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_stage_window_slots");
 }
 
+// The stage window with its Snake beside it (the stateful encoder's wide blocks): dense rows only, the same checks.
+int mvq_stream_stage_window_snake_f32(float* tail, size_t tail_stride, int h_in, const float* src, int src_t, int src_off, int n, float* win,
+                                      float* win_s, const float* alpha, int win_t, int h_out, int cap, int batch, int c, void* stream)
+{
+    if (int rc = stream_stage_window_bad("stream_stage_window_snake", batch, tail_stride, h_in, src_t, 1, src_off, n, win_t, 1, h_out, cap, c)) return rc;
+    const size_t rows = (size_t)batch * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (rows > 0x7FFFFFFFu) return fail(MVQ_EINVAL, "stream_stage_window_snake: too many rows");
+    if (!win || !win_s || !alpha || (!tail && (h_in || h_out)) || (!src && n)) return fail(MVQ_EINVAL, "stream_stage_window_snake: null tensor");
+    hipError_t e = mvq::launch_stream_stage_window_snake(tail, tail_stride, nullptr, src, src_t, src_off, win, win_s, alpha, win_t, h_in, n, h_out,
+                                                         cap, c, 0, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_stage_window_snake");
+}
+
+int mvq_stream_stage_window_snake_slots_f32(float* tail, size_t tail_stride, const int32_t* slots, int n_group, int n_slots, int h_in,
+                                            const float* src, int src_t, int src_off, int n, float* win, float* win_s, const float* alpha,
+                                            int win_t, int h_out, int cap, int c, void* stream)
+{
+    if (int rc = stream_stage_window_bad("stream_stage_window_snake_slots", n_group, tail_stride, h_in, src_t, 1, src_off, n, win_t, 1, h_out, cap, c))
+        return rc;
+    if (int rc = slots_shape_bad("stream_stage_window_snake_slots", n_group, n_slots, c)) return rc;
+    const size_t rows = (size_t)n_group * c;
+    if (rows == 0 || h_in + n == 0) return MVQ_OK;
+    if (!slots || !win || !win_s || !alpha || (!tail && (h_in || h_out)) || (!src && n))
+        return fail(MVQ_EINVAL, "stream_stage_window_snake_slots: null tensor");
+    hipError_t e = mvq::launch_stream_stage_window_snake(tail, tail_stride, slots, src, src_t, src_off, win, win_s, alpha, win_t, h_in, n, h_out,
+                                                         cap, c, n_slots, rows, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_stage_window_snake_slots");
+}
+
 int mvq_stream_samples_f32(float* buf, int fill, const float* x_new, int n, float* win, int w, int drop, int cap, int rows,
                            void* stream)
 {

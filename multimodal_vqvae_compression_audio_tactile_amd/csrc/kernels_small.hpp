@@ -160,6 +160,9 @@ hipError_t launch_rvq_rate(const float* z, size_t z_sb, size_t z_sd, const int32
 hipError_t launch_stream_stage_window(float* tail, size_t tail_stride, const int32_t* slots, const float* src, int src_t, int src_seg,
                                       int src_off, float* win, int win_t, int win_seg, int h_in, int n, int h_out, int cap, int C,
                                       int n_slots, size_t rows, hipStream_t s);
+hipError_t launch_stream_stage_window_snake(float* tail, size_t tail_stride, const int32_t* slots, const float* src, int src_t, int src_off,
+                                            float* win, float* win_s, const float* alpha, int win_t, int h_in, int n, int h_out, int cap,
+                                            int C, int n_slots, size_t rows, hipStream_t s);
 hipError_t launch_stream_window(float* hist, const int32_t* slots, const float* z_new, float* win, int h_in, int n, int h_out, int cap,
                                 int C, int n_slots, size_t rows, hipStream_t s);
 hipError_t launch_resample_stream(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B, int n_new,

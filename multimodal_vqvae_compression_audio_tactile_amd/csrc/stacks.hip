@@ -682,6 +682,154 @@ void decoder_stream_plan(Run& r, const mvq_stack& s, const std::vector<StreamSta
     r.ar.release(src_buf);
 }
 
+// ---- stateful streaming encode ---------------------------------------------------------------------------
+// The sender's counterpart: block.0 (k7), each EncoderBlock (three units, Snake, strided conv of kernel 2s / stride s / padding p)
+// and the final Snake + k3 each keep the RAW tail of their own input.  Two things the decoder did not need: a block's window must
+// start on a global column that is a multiple of its stride (output column J reads input [J*s - p, J*s - p + 2s), so another
+// start shifts the output grid), hence the tail actually used is the largest h <= cap with (have - h) % s == 0; and a wide block
+// needs its input raw AND snaked, which the snake form of the stage-window kernel writes from the raw tail.
+// enc_stream_stages() is the geometry (stream.ENC_STAGES / ENC_STAGE_TAILS), enc_stream_plan() one step's arithmetic
+// (stream.encoder_stage_plan), encoder_stream_plan() the walk: per stage ONE stage-window launch, then encoder_plan's launches for
+// that stage on dense rows (the virtually packed latent-rate tail of encoder_plan is not used: section 24 says why).
+struct EncStage { int s, ks, p, loss, cap, cin; bool wide; size_t at; };
+struct EncStep { int h_in, src_off, n_new, h_out, out_off, n_out; };    // [out_off, out_off + n_out): the window's output columns handed on
+struct EncPlan { std::vector<EncStep> st; long long t0 = 0, t1 = 0; };
+constexpr int ENC_STREAM_MAX_N = (1 << 20) - 256;                      // every stage window stays within mvq_stream_stage_window_f32's 2^20 columns
+
+bool enc_stream_stages(const mvq_stack& s, std::vector<EncStage>* out, size_t* floats)
+{
+    if (s.decoder || s.blocks.empty() || s.first.ks != 7 || s.first.pad != 3 || s.last.ks != 3 || s.last.pad != 1) return false;
+    std::vector<EncStage> v;
+    v.push_back({1, 7, 3, 0, 0, s.first.cin, false, 0});
+    for (auto& b : s.blocks) v.push_back({b.res.stride, b.res.ks, b.res.pad, STREAM_RU_LOSS, 0, b.res.cin, b.width >= s.presnaked_min_c, 0});
+    v.push_back({1, 3, 1, 0, 0, s.last.cin, false, 0});
+    size_t at = 0;
+    for (auto& g : v) {
+        // the least tail: with d outputs handed on the next window must start at a multiple of s at or below d*s - p - loss, and
+        // have - d*s is at most loss - p + ks - 1
+        const int need = g.loss - g.p + g.ks - 1 + g.s * ((g.p + g.loss + g.s - 1) / g.s);
+        g.cap = ceil4(need);
+        g.at = at;
+        at += (size_t)g.cin * g.cap;
+    }
+    *out = v;
+    if (floats) *floats = at;
+    return true;
+}
+
+// output columns of `have` input columns that are exact with the right edge cut / with the right edge the signal's
+long long enc_done(const EncStage& g, long long have) { const long long x = have - g.loss + g.p - g.ks; return x < 0 ? 0 : x / g.s + 1; }
+long long enc_total(const EncStage& g, long long have) { const long long x = have + 2 * g.p - g.ks; return (have <= 0 || x < 0) ? 0 : x / g.s + 1; }
+long long enc_tail(const EncStage& g, long long have) { return have <= g.cap ? have : have - (have - g.cap + g.s - 1) / g.s * g.s; }
+
+int enc_stream_plan(const std::vector<EncStage>& sg, long long before, int n, bool last, EncPlan* p)
+{
+    if (before < 0 || n < 0 || before > (1LL << 40) || n > ENC_STREAM_MAX_N)
+        return sfail(MVQ_EINVAL, "encoder_stream: samples_before = %lld, n = %d", before, n);
+    long long hv = before, src_off = 0, n_new = n, d0 = 0, d1 = 0;
+    p->st.clear();
+    for (auto& g : sg) {
+        const long long h_in = enc_tail(g, hv), a = hv - h_in, w = h_in + n_new;
+        const long long h_out = last ? 0 : enc_tail(g, hv + n_new);
+        d0 = enc_done(g, hv);
+        d1 = last ? enc_total(g, hv + n_new) : enc_done(g, hv + n_new);
+        if (d1 < d0) d1 = d0;
+        long long off = d0 - a / g.s;
+        if (d1 == d0) off = 0;
+        else if ((a > 0 && d0 * g.s - g.p - g.loss < a) || off < 0 || d1 - a / g.s > conv_len((int)w, g.ks, g.s, 1, g.p))
+            return sfail(MVQ_EUNSUPPORTED, "encoder_stream: a stage's tail does not reach back to its first new output column");
+        p->st.push_back({(int)h_in, (int)src_off, (int)n_new, (int)h_out, (int)off, (int)(d1 - d0)});
+        hv = d0; src_off = off; n_new = d1 - d0;
+    }
+    p->t0 = d0; p->t1 = d1;
+    return MVQ_OK;
+}
+
+// Row length of a stage's window of W columns.  The MFMA-tiled stages (cin % 32 == 0) carry zero-padded rows (include/mvq.h,
+// "Zero-padded rows"): a window length is whatever the tails and rule 1 make it, and a row that is no multiple of 4 would put every
+// conv of the stage on its 4-byte paths.  A block's rows are rounded up until its strided conv's output rows are a multiple of 4
+// too; the zero tail is the padding the convs read anyway, so the true columns keep their bits.
+int enc_stream_rows(const EncStage& g, int W)
+{
+    if (g.cin % 32) return W;
+    int R = ceil4(W);
+    if (g.loss)
+        for (int i = 0; i < 32 && conv_len(R, g.ks, g.s, 1, g.p) % 4; ++i) R += 4;
+    return R;
+}
+
+// state[sessions, state_floats] (row g or slots[g]), x_new[G, 1, n] -> z[G, d_latent, t1 - t0]
+void encoder_stream_plan(Run& r, const mvq_stack& s, const std::vector<EncStage>& sg, const EncPlan& p, size_t state_floats, float* state,
+                         const int32_t* slots, int G, int n_slots, const float* x_new, float* z)
+{
+    const int nb = (int)s.blocks.size(), ns = (int)sg.size();
+    const float* src = x_new;
+    float* src_buf = nullptr;                          // the producer's output when it lives in the arena
+    int src_t = p.st[0].n_new;
+    for (int k = 0; k < ns && r.ok(); ++k) {
+        const EncStage& g = sg[k];
+        const EncStep& st = p.st[k];
+        const int W = st.h_in + st.n_new;
+        // nothing to hand on and no tail to move on: the stage does not run this step
+        if (W == 0 || (st.n_out == 0 && (st.n_new == 0 || st.h_out == 0))) { r.ar.release(src_buf); src_buf = nullptr; src = nullptr; src_t = 0; continue; }
+        const int R = enc_stream_rows(g, W), tv = R != W ? W : 0;
+        float* win = r.ar.alloc((size_t)G * g.cin * R);
+        float* win_s = g.wide ? r.ar.alloc((size_t)G * g.cin * R) : nullptr;
+        float* tail = state ? state + g.at : nullptr;
+        if (g.wide) {
+            const float* al = s.blocks[k - 1].ru[0].alpha_a;
+            r.launch([&] {
+                return slots ? mvq_stream_stage_window_snake_slots_f32(tail, state_floats, slots, G, n_slots, st.h_in, src, src_t, st.src_off, st.n_new,
+                                                                       win, win_s, al, R, st.h_out, g.cap, g.cin, r.stream)
+                             : mvq_stream_stage_window_snake_f32(tail, state_floats, st.h_in, src, src_t, st.src_off, st.n_new, win, win_s, al, R,
+                                                                 st.h_out, g.cap, G, g.cin, r.stream); });
+        } else {
+            r.launch([&] {
+                return slots ? mvq_stream_stage_window_slots_f32(tail, state_floats, slots, G, n_slots, st.h_in, src, src_t, 1, st.src_off, st.n_new,
+                                                                 win, R, 1, st.h_out, g.cap, g.cin, r.stream)
+                             : mvq_stream_stage_window_f32(tail, state_floats, st.h_in, src, src_t, 1, st.src_off, st.n_new, win, R, 1, st.h_out,
+                                                           g.cap, G, g.cin, r.stream); });
+        }
+        r.ar.release(src_buf);
+        src_buf = nullptr;
+        if (st.n_out == 0) {                           // the window only moved the tail on
+            r.ar.release(win); r.ar.release(win_s);
+            src = nullptr; src_t = 0;
+            continue;
+        }
+        if (k == 0) {
+            const Conv& c0 = s.first;
+            float* h = r.ar.alloc((size_t)G * c0.cout * W);
+            r.launch([&] { return mvq_conv1d_padded_f32(win, c0.wp, c0.bias, nullptr, nullptr, nullptr, h, nullptr, nullptr, G, c0.cin, W, c0.cout, 7, 1, 1, 3,
+                                                        MVQ_ACT_NONE, 0, r.stream); });
+            r.ar.release(win);
+            src_buf = h; src_t = W;
+        } else if (k <= nb) {
+            const Block& b = s.blocks[k - 1];
+            const Conv& d = b.res;
+            float* h = run_units(r, s, b, G, R, win, win_s, b.alpha, tv);
+            const int tout = conv_len(R, d.ks, d.stride, 1, d.pad);     // the columns past conv_len(W) read the zero tail and are never handed on
+            const float* a_out = k == nb ? s.alpha_last : nullptr;
+            float* y = r.ar.alloc((size_t)G * d.cout * tout);
+            r.launch([&] { return mvq_conv1d_padded_f32(h, d.wp, d.bias, nullptr, nullptr, a_out, y, nullptr, nullptr, G, d.cin, R, d.cout, d.ks, d.stride, 1,
+                                                        d.pad, MVQ_ACT_NONE, 0, r.stream); });
+            r.ar.release(h);
+            src_buf = y; src_t = tout;
+        } else {
+            const Conv& cl = s.last;
+            float* yt = r.ar.alloc((size_t)G * cl.cout * R);
+            r.launch([&] { return mvq_conv1d_padded_f32(win, cl.wp, cl.bias, nullptr, nullptr, nullptr, yt, nullptr, nullptr, G, cl.cin, R, cl.cout, 3, 1, 1, 1,
+                                                        MVQ_ACT_NONE, tv, r.stream); });
+            r.ar.release(win);
+            r.launch([&] { return mvq_copy3d_f32(yt + st.out_off, (size_t)cl.cout * R, (size_t)R, z, (size_t)cl.cout * st.n_out, (size_t)st.n_out, G, cl.cout,
+                                                 st.n_out, r.stream); });
+            r.ar.release(yt);
+        }
+        src = src_buf;
+    }
+    r.ar.release(src_buf);
+}
+
 // ---- training config: saving forward + backward w.r.t. the input (weights frozen) -------------------------------------------------
 // Saved forward, in this order (a bump allocation over `saved`): h0 [model.0 output], per block: u [transposed conv output], then
 // per unit: t7 [7-tap pre-activation] and the unit's output; y.  Every tensor is written by its producer kernel directly.
@@ -890,6 +1038,60 @@ int mvq_encoder_fwd_f32(const mvq_stack* s, const float* x, float* z, void* work
         if (rc != MVQ_EUNSUPPORTED) return rc;         // no LDS-DMA form for this shape / MVQ_NO_DMA: the plain plan (same results)
     }
     return plan_run(workspace, workspace_bytes, stream, "encoder_fwd", [&](Run& r) { encoder_plan(r, *s, x, z, batch, t, false); });
+}
+// ---- stateful streaming encode: the C face of enc_stream_stages / enc_stream_plan / encoder_stream_plan
+int mvq_encoder_stream_plan(const mvq_stack* s, long long samples_before, int n, int last, int32_t* stages, int stages_cap, long long* emit)
+{
+    std::vector<EncStage> sg;
+    if (!s || !enc_stream_stages(*s, &sg, nullptr)) return sfail(MVQ_EUNSUPPORTED, "encoder_stream_plan: not an encoder stack the stage plan covers");
+    const int ns = (int)sg.size();
+    if (!stages) return ns;                                  /* the size query */
+    if (stages_cap < ns) return sfail(MVQ_EINVAL, "encoder_stream_plan: room for %d stages, the stack has %d", stages_cap, ns);
+    EncPlan p;
+    if (int rc = enc_stream_plan(sg, samples_before, n, last != 0, &p)) return rc;
+    for (int k = 0; k < ns; ++k) {
+        int32_t* o = stages + 5 * k;
+        o[0] = p.st[k].h_in; o[1] = p.st[k].src_off; o[2] = p.st[k].n_new; o[3] = p.st[k].h_out; o[4] = sg[k].cap;
+    }
+    if (emit) { emit[0] = p.t0; emit[1] = p.t1; }
+    return ns;
+}
+size_t mvq_encoder_stream_state_floats(const mvq_stack* s)
+{
+    std::vector<EncStage> sg;
+    size_t floats = 0;
+    return (s && enc_stream_stages(*s, &sg, &floats)) ? floats : 0;
+}
+size_t mvq_encoder_stream_workspace_bytes(const mvq_stack* s, int n_group, long long samples_before, int n, int last)
+{
+    std::vector<EncStage> sg;
+    size_t floats = 0;
+    EncPlan p;
+    if (!s || n_group <= 0 || !enc_stream_stages(*s, &sg, &floats) || enc_stream_plan(sg, samples_before, n, last != 0, &p) != MVQ_OK) return 0;
+    return plan_peak([&](Run& r) { encoder_stream_plan(r, *s, sg, p, floats, nullptr, nullptr, n_group, n_group, nullptr, nullptr); });
+}
+int mvq_encoder_stream_fwd_f32(const mvq_stack* s, float* state, const int32_t* slots, int n_group, int n_slots, const float* x_new, int n,
+                               long long samples_before, int last, float* z, int z_len, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!s || s->decoder) return sfail(MVQ_EINVAL, "encoder_stream_fwd: not an encoder stack");
+    std::vector<EncStage> sg;
+    size_t floats = 0;
+    if (!enc_stream_stages(*s, &sg, &floats)) return sfail(MVQ_EUNSUPPORTED, "encoder_stream_fwd: a stack the stage plan does not cover");
+    if (n_group < 0 || n_slots < 0 || n_group > n_slots) return sfail(MVQ_EINVAL, "encoder_stream_fwd: a group of %d sessions, %d state rows", n_group, n_slots);
+    EncPlan p;
+    if (int rc = enc_stream_plan(sg, samples_before, n, last != 0, &p)) return rc;
+    if ((long long)z_len != p.t1 - p.t0) return sfail(MVQ_EINVAL, "encoder_stream_fwd: z_len = %d, the step emits %lld columns", z_len, p.t1 - p.t0);
+    if (n_group == 0) return MVQ_OK;
+    bool any = false;
+    for (auto& st : p.st) any = any || st.n_new > 0 || st.n_out > 0;
+    if (!any) return MVQ_OK;
+    if (!state || !workspace || (!x_new && n) || (!z && z_len)) return sfail(MVQ_EINVAL, "encoder_stream_fwd: null tensor");
+    auto walk = [&](Run& r) { encoder_stream_plan(r, *s, sg, p, floats, state, slots, n_group, n_slots, x_new, z); };
+    if (!s->first.wp) {                                      // a description-only handle is refused where a real one would launch
+        if (workspace_bytes < plan_peak(walk)) return sfail(MVQ_EINVAL, "encoder_stream_fwd: workspace too small (see the matching *_workspace_bytes query)");
+        return sfail(MVQ_EINVAL, "encoder_stream_fwd: a stack without weights");
+    }
+    return plan_run(workspace, workspace_bytes, stream, "encoder_stream_fwd", walk);
 }
 
 int mvq_decoder_out_len(const mvq_stack* s, int t) { return (s && s->decoder) ? decoder_len(*s, t) : 0; }

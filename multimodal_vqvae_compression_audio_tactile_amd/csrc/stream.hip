@@ -1,5 +1,6 @@
 // stream.hip -- the state kernels of the streaming sessions (include/mvq.h): the receiver's mvq_stream_window_f32,
-// mvq_stream_stage_window_f32 (the stateful decoder's per-stage window) and mvq_resample_stream_f32, the sender's mvq_stream_samples_f32.  Each keeps its session state in a fixed device buffer that
+// mvq_stream_stage_window_f32 (the stateful decoder's per-stage window) and mvq_resample_stream_f32, the sender's mvq_stream_samples_f32
+// and mvq_stream_stage_window_snake_f32 (the stateful encoder's raw + Snake window of a wide block).  Each keeps its session state in a fixed device buffer that
 // the kernel itself updates in place, so the steady step of a session is the same launch sequence on the same addresses
 // every time (a captured graph replays it).  A POOL of sessions keeps one row block per session slot in
 // the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
@@ -97,10 +98,23 @@ struct StageRows {
         return ((size_t)(g / seg) * C + c) * ((size_t)seg * pitch) + (size_t)(g % seg) * pitch;
     }
 };
-template <bool SLOTS, class V>
+// SNAKE (the stateful streaming ENCODER's wide blocks): the launch also writes the window's Snake,
+//   win_s(g, c)[j] = det_snake(win(g, c)[j], alpha[c], 1.0f / (alpha[c] + 1e-9f)) for j < W and +0 in the zero tail,
+// the function and the reciprocal expression of the conv epilogues' dual output, so win_s is bit for bit what the producer would
+// have written beside the raw activation; the tail stays raw.  win_s has win's layout.  SnakeOut<false> is empty: the instantiations
+// without it carry no extra argument.
+template <bool SNAKE, class V> struct SnakeOut;
+template <class V> struct SnakeOut<false, V> {};
+template <class V> struct SnakeOut<true, V> { V* win_s; const float* alpha; };
+__device__ __forceinline__ float snake_of(float v, float al, float inv) { return det_snake(v, al, inv); }
+__device__ __forceinline__ float4 snake_of(float4 v, float al, float inv)
+{
+    return make_float4(det_snake(v.x, al, inv), det_snake(v.y, al, inv), det_snake(v.z, al, inv), det_snake(v.w, al, inv));
+}
+template <bool SLOTS, class V, bool SNAKE = false>
 __global__ __launch_bounds__(256) void stream_stage_window_kernel(V* tail, const V* __restrict__ src, V* win, int h_in, int n, int h_out,
                                                                   int cap, size_t tail_stride, StageRows sr, int src_off, StageRows wr,
-                                                                  int C, int rpb, size_t rows, Sessions<SLOTS> ses)
+                                                                  int C, int rpb, size_t rows, Sessions<SLOTS> ses, SnakeOut<SNAKE, V> so = {})
 {
     const size_t row0 = (size_t)blockIdx.x * rpb;
     const int nrow = (int)(rows - row0 < (size_t)rpb ? rows - row0 : (size_t)rpb);
@@ -118,6 +132,10 @@ __global__ __launch_bounds__(256) void stream_stage_window_kernel(V* tail, const
             v = src[sr.at(g, c, C) + src_off + (j - h_in)];
         }
         win[wr.at(g, c, C) + j] = v;
+        if constexpr (SNAKE) {
+            const float al = so.alpha[c];
+            so.win_s[wr.at(g, c, C) + j] = j < W ? snake_of(v, al, 1.0f / (al + 1e-9f)) : zero;
+        }
     }
     __syncthreads();
     const int skip = W - h_out;
@@ -333,6 +351,42 @@ hipError_t launch_stream_stage_window(float* tail, size_t tail_stride, const int
         else
             hipLaunchKernelGGL((stream_stage_window_kernel<false, float>), grid, block, 0, s, tail, src, win, h_in, n, h_out, cap, tail_stride,
                                sr, src_off, wr, C, rpb, rows, Sessions<false>{});
+    }
+    return hipGetLastError();
+}
+
+// launch_stream_stage_window on dense rows with the Snake copy win_s (layout of win) beside win: the SNAKE instantiations
+hipError_t launch_stream_stage_window_snake(float* tail, size_t tail_stride, const int32_t* slots, const float* src, int src_t, int src_off,
+                                            float* win, float* win_s, const float* alpha, int win_t, int h_in, int n, int h_out, int cap,
+                                            int C, int n_slots, size_t rows, hipStream_t s)
+{
+    if (rows == 0 || h_in + n == 0) return hipSuccess;
+    int rpb = 2048 / win_t;
+    rpb = rpb < 1 ? 1 : (rpb > WIN_ROWS ? WIN_ROWS : rpb);
+    const dim3 grid((unsigned)((rows + rpb - 1) / rpb)), block(256);
+    const bool vec = !((h_in | n | h_out | cap | src_t | src_off | win_t) & 3) && !(tail_stride & 3) &&
+                     !(((uintptr_t)tail | (uintptr_t)src | (uintptr_t)win | (uintptr_t)win_s) & 15);
+    if (vec) {
+        float4* t4 = reinterpret_cast<float4*>(tail);
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* w4 = reinterpret_cast<float4*>(win);
+        const SnakeOut<true, float4> so{reinterpret_cast<float4*>(win_s), alpha};
+        const StageRows sr{src_t / 4, 1}, wr{win_t / 4, 1};
+        if (slots)
+            hipLaunchKernelGGL((stream_stage_window_kernel<true, float4, true>), grid, block, 0, s, t4, s4, w4, h_in / 4, n / 4, h_out / 4,
+                               cap / 4, tail_stride / 4, sr, src_off / 4, wr, C, rpb, rows, Sessions<true>{slots, n_slots, C}, so);
+        else
+            hipLaunchKernelGGL((stream_stage_window_kernel<false, float4, true>), grid, block, 0, s, t4, s4, w4, h_in / 4, n / 4, h_out / 4,
+                               cap / 4, tail_stride / 4, sr, src_off / 4, wr, C, rpb, rows, Sessions<false>{}, so);
+    } else {
+        const SnakeOut<true, float> so{win_s, alpha};
+        const StageRows sr{src_t, 1}, wr{win_t, 1};
+        if (slots)
+            hipLaunchKernelGGL((stream_stage_window_kernel<true, float, true>), grid, block, 0, s, tail, src, win, h_in, n, h_out, cap,
+                               tail_stride, sr, src_off, wr, C, rpb, rows, Sessions<true>{slots, n_slots, C}, so);
+        else
+            hipLaunchKernelGGL((stream_stage_window_kernel<false, float, true>), grid, block, 0, s, tail, src, win, h_in, n, h_out, cap,
+                               tail_stride, sr, src_off, wr, C, rpb, rows, Sessions<false>{}, so);
     }
     return hipGetLastError();
 }

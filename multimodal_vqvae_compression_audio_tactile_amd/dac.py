@@ -328,6 +328,21 @@ class Encoder(nn.Module):
             return self.stack().encoder_fwd(x)
         return self.forward_plan(x)
 
+    # ---- stateful streaming encode: the encoder piece by piece, every stage keeping the tail of its input ----
+    def stream_state(self, rows):
+        """The encoder state of ``rows`` streaming sessions, fp32 [rows, S] on the weights' device (Stack.encoder_stream_state)."""
+        return self.stack().encoder_stream_state(rows, device=next(self.parameters()).device)
+
+    @torch.no_grad()
+    def forward_stream(self, state, x_new, samples_before, last, slots=None, slots_dev=None):
+        """One step: x_new[G, 1, n] after ``samples_before`` samples -> the latent columns that became exact; ``state`` moves on in
+        place.  The pieces of a signal concatenated equal forward(x) bit for bit.  ONE C call, mvq_encoder_stream_fwd_f32; there
+        is no Python-walked form, so the opt-in arithmetic modes and USE_STACKS = False are refused."""
+        if not USE_STACKS:
+            raise ValueError("Encoder.forward_stream: the stateful encoder exists as the library's plan only; the plan overrides in the "
+                             "environment switch the stack calls off")
+        return self.stack().encoder_stream_fwd(state, x_new, samples_before, last, slots=slots, slots_dev=slots_dev)
+
     @torch.no_grad()
     def forward_plan(self, x):
         """The same launch plan walked from Python over the per-layer entry points (the opt-in arithmetic modes and A/B runs)."""

@@ -1395,6 +1395,43 @@ def stream_stage_window_slots(state, slots, h_in, src, src_off, n, h_out, cap, t
     return _stream_stage_window("stream_stage_window_slots", state, h_in, src, src_off, n, h_out, cap, tail_off, win_t, sd)
 
 
+def stream_stage_window_snake(state, h_in, src, src_off, n, h_out, cap, alpha, tail_off=0, win_t=None, slots=None, slots_dev=None):
+    """stream_stage_window with the window's Snake beside it (mvq_stream_stage_window_snake_f32 / _slots_f32; the stateful
+    encoder's wide blocks) -> (win, win_s), win_s = snake(win, alpha) on the h_in + n window columns and +0
+    in the zero tail; the tail stays raw.  ``alpha`` fp32 [C] (any shape of C elements).  ``slots`` None: dense sessions."""
+    who = "stream_stage_window_snake"
+    src = _dev(src, "src")
+    alpha = _dev(alpha, "alpha").reshape(-1).contiguous()
+    if not isinstance(state, torch.Tensor) or state.dim() != 2 or src.dim() != 3 or state.dtype != torch.float32 or not state.is_cuda \
+            or not state.is_contiguous() or state.device != src.device:
+        raise MvqError(f"{who}: the state must be a contiguous fp32 HIP tensor [sessions, floats] and src [B, C, src_t] on its device")
+    rows, stride = state.shape
+    B, C, src_t = src.shape
+    h_in, src_off, n, h_out, cap, tail_off = (int(v) for v in (h_in, src_off, n, h_out, cap, tail_off))
+    sd = None
+    if slots is not None:
+        _, sd = _slot_list(who, slots, state, 2, slots_dev)
+    elif B > rows:
+        raise MvqError(f"{who}: {B} sessions, the state has {rows} rows")
+    if alpha.numel() != C or alpha.dtype != torch.float32:
+        raise MvqError(f"{who}: alpha must hold {C} fp32 values")
+    if cap < 0 or tail_off < 0 or tail_off + C * cap > stride:
+        raise MvqError(f"{who}: a [{C}, {cap}] tail at offset {tail_off} does not fit a state row of {stride} floats")
+    win_t = max(h_in, 0) + max(n, 0) if win_t is None else int(win_t)
+    win = torch.empty(B, C, max(win_t, 0), device=src.device, dtype=torch.float32)
+    win_s = torch.empty_like(win)
+    tp = state.data_ptr() + 4 * tail_off
+    if sd is None:
+        check(_lib.lib().mvq_stream_stage_window_snake_f32(tp, stride, h_in, src.data_ptr(), src_t, src_off, n, win.data_ptr(), win_s.data_ptr(),
+                                                           alpha.data_ptr(), win_t, h_out, cap, B, C, _stream()),
+              "mvq_stream_stage_window_snake_f32")
+    else:
+        check(_lib.lib().mvq_stream_stage_window_snake_slots_f32(tp, stride, sd.data_ptr(), B, rows, h_in, src.data_ptr(), src_t, src_off, n,
+                                                                 win.data_ptr(), win_s.data_ptr(), alpha.data_ptr(), win_t, h_out, cap, C,
+                                                                 _stream()), "mvq_stream_stage_window_snake_slots_f32")
+    return win, win_s
+
+
 def resample_stream_slots(x_new, kern, state, slots, consumed, orig, newf, width, final=False, slots_dev=None):
     """resample_stream for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots] moved on
     in place (mvq_resample_stream_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of ``orig`` of at
@@ -1899,6 +1936,73 @@ class Stack:
                                                     z_new.data_ptr(), n, before, int(last), y.data_ptr(), e1 - e0, ws.data_ptr(), ws.numel(),
                                                     _stream()), "mvq_decoder_stream_fwd_f32")
         return y
+
+    # ---- stateful streaming encode (include/mvq.h)
+    def encoder_stream_state_floats(self):
+        return int(_lib.lib().mvq_encoder_stream_state_floats(self.handle))
+
+    def encoder_stream_state(self, rows, device=None):
+        """The state of ``rows`` streaming sender sessions: fp32 [rows, S], every stage's raw tail at a fixed offset of a row.  Not
+        cleared: a new session reads none of it."""
+        S = self.encoder_stream_state_floats()
+        if self.kind != "encoder" or S == 0:
+            raise MvqError("Stack.encoder_stream_state: not an encoder stack the stage plan covers")
+        if int(rows) < 1:
+            raise MvqError("Stack.encoder_stream_state: rows must be at least 1")
+        return torch.empty(int(rows), S, device=self.blob.device if device is None else device, dtype=torch.float32)
+
+    def encoder_stream_plan(self, samples_before, n, last=False):
+        """-> (stages, (t0, t1)): per stage (h_in, src_off, n_new, h_out, cap) of the step and the global latent columns it emits
+        (mvq_encoder_stream_plan, host only)."""
+        import ctypes
+        L = _lib.lib()
+        ns = int(L.mvq_encoder_stream_plan(self.handle, 0, 0, 0, None, 0, None))
+        if ns <= 0:
+            check(ns or -2, "mvq_encoder_stream_plan")
+        buf, emit = (ctypes.c_int32 * (5 * ns))(), (ctypes.c_longlong * 2)()
+        rc = int(L.mvq_encoder_stream_plan(self.handle, int(samples_before), int(n), int(bool(last)), buf, ns, emit))
+        if rc < 0:
+            check(rc, "mvq_encoder_stream_plan")
+        return tuple(tuple(buf[5 * k:5 * k + 5]) for k in range(ns)), (int(emit[0]), int(emit[1]))
+
+    def encoder_stream_fwd(self, state, x_new, samples_before, last=False, slots=None, slots_dev=None):
+        """One step of the stateful encoder: x_new[G, 1, n] after ``samples_before`` samples -> z[G, d_latent, n_emit]
+        (mvq_encoder_stream_fwd_f32); ``state`` (encoder_stream_state) moves on in place.  ``slots`` None: session g is state row g;
+        else host integers, session g on state[slots[g]] (``slots_dev``: their int32 device copy when the caller uploaded it
+        already).  Only arithmetic mode "f32" (the opt-in modes scale per item)."""
+        if get_arith() != "f32":
+            raise ValueError(f"Stack.encoder_stream_fwd: arithmetic mode {get_arith()!r} scales per item; only 'f32' is equal piece by piece")
+        S = self.encoder_stream_state_floats()
+        if not isinstance(state, torch.Tensor) or state.dim() != 2 or state.shape[1] != S or state.dtype != torch.float32:
+            raise ValueError(f"Stack.encoder_stream_fwd: the state must be an fp32 tensor [sessions, {S}] (encoder_stream_state), got "
+                             f"{tuple(state.shape) if isinstance(state, torch.Tensor) else type(state).__name__}")
+        x_new = _dev(x_new, "x_new")
+        if not state.is_cuda or not state.is_contiguous() or state.device != x_new.device:
+            raise ValueError("Stack.encoder_stream_fwd: the state must be contiguous and on x_new's device")
+        if x_new.dim() != 3 or x_new.shape[1] != 1:
+            raise ValueError(f"Stack.encoder_stream_fwd: x_new must be [G, 1, n], got {tuple(x_new.shape)}")
+        G, _, n = x_new.shape
+        sd = None
+        if slots is not None:
+            g, sd = _slot_list("Stack.encoder_stream_fwd", slots, state, 2, slots_dev)
+            if g != G:
+                raise ValueError(f"Stack.encoder_stream_fwd: {g} slots for {G} sessions")
+        elif G > state.shape[0]:
+            raise ValueError(f"Stack.encoder_stream_fwd: {G} sessions, the state has {state.shape[0]} rows")
+        before, last = int(samples_before), bool(last)
+        stages, (t0, t1) = self.encoder_stream_plan(before, n, last)
+        z = torch.empty(G, self.desc.d_latent, t1 - t0, device=x_new.device, dtype=torch.float32)
+        if G == 0:
+            return z
+        key = ("enc_stream", G, stages, last)                     # the launches are a function of the plan alone
+        nb = self._ws_bytes.get(key)
+        if nb is None:
+            nb = self._ws_bytes[key] = max(int(_lib.lib().mvq_encoder_stream_workspace_bytes(self.handle, G, before, n, int(last))), 256)
+        ws = torch.empty(nb, device=x_new.device, dtype=torch.uint8)
+        check(_lib.lib().mvq_encoder_stream_fwd_f32(self.handle, state.data_ptr(), None if sd is None else sd.data_ptr(), G, state.shape[0],
+                                                    x_new.data_ptr(), n, before, int(last), z.data_ptr(), t1 - t0, ws.data_ptr(), ws.numel(),
+                                                    _stream()), "mvq_encoder_stream_fwd_f32")
+        return z
 
     def decoder_fwd_saving(self, z):
         """-> (y, saved): the training forward; `saved` (one uint8 tensor) goes to decoder_bwd_input."""

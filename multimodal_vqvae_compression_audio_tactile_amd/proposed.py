@@ -1136,20 +1136,21 @@ class ProposedEval(_ProposedBase):
                                   decoder=decoder)
 
     def stream_sender(self, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None, audio_rate=None,
-                      fec=None, audio_fec=None):
+                      fec=None, audio_fec=None, encoder="window"):
         """A streaming sender session on this model (stream.StreamSender): ``push`` samples of both modalities as they come,
         get back the packets and audio codes of each 16-token chunk they complete, ``finish`` to flush; the concatenated output
-        equals compress_packets on the whole item byte for byte (with ``rate``, a packets.Rate: compress_packets(rate=))."""
+        equals compress_packets on the whole item byte for byte (with ``rate``, a packets.Rate: compress_packets(rate=)).
+        ``encoder="stateful"``: the same return values from the stateful encoders (per-stage history instead of the 32-token window)."""
         from .stream import StreamSender
         return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate, audio=audio,
-                            audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec)
+                            audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec, encoder=encoder)
 
-    def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None):
+    def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None, encoder="window"):
         """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,
         ``step`` once per tick with the samples that arrived (1..16 tokens per session, and the sessions that end); each
         session gets what a stream_sender(batch=1) of its own would return, and the sessions of a tick share batched encodes."""
         from .stream import StreamSenderPool
-        return StreamSenderPool(self, packet_tok=packet_tok, slots=slots, books_use=books_use)
+        return StreamSenderPool(self, packet_tok=packet_tok, slots=slots, books_use=books_use, encoder=encoder)
 
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):

@@ -26,6 +26,10 @@ a window that starts on a multiple of 320 samples keeps every stage's stride ali
 keeps the tail of its own input and a step computes it on [tail | new columns] only; ``decoder_stage_plan`` is that step's host
 arithmetic (DEC_STAGES, DEC_STAGE_TAILS), and every call returns the window mode's tensor.
 
+``StreamSender(encoder="stateful")`` does the same for the sender's 2x encoder window: every encoder stage keeps
+the raw tail of its own input, ``encoder_stage_plan`` is a step's host arithmetic (ENC_STAGES, ENC_STAGE_TAILS) and
+``sender_step_stateful`` the session's; every call returns the window mode's packets and codes.
+
 ``schedule`` / ``sender_schedule`` are host arithmetic only; ``StreamReceiver`` / ``StreamSender`` are the session objects
 (``ProposedEval.stream_receiver`` / ``ProposedEval.stream_sender``).  ``StreamReceiverPool`` (``ProposedEval.stream_receiver_pool``)
 serves receiver sessions that join, run and leave independently: their state lies in slots of one set of device buffers and a
@@ -207,6 +211,88 @@ def decoder_stage_plan(tokens_before: int, n: int, last: bool = False, tails=DEC
     return StagePlan(tuple(stages), g0 - a, g1 - a)
 
 
+ENC_RU_LOSS = DEC_RU_LOSS         # an EncoderBlock's three units lose the same 39 columns at a cut edge
+
+
+def _enc_stage_geometry(rates=ENC_RATES):
+    """The encoder's stages as (stride s, kernel ks, padding p, loss): output column J of a stage reads its input columns
+    [J*s - p, J*s - p + ks) -- after ``loss`` columns were lost at every cut edge in front of the conv.  block.0 is k7 (padding 3),
+    an EncoderBlock three units (loss 39) and a conv of kernel 2s, stride s, padding ceil(s/2), the last stage Snake + k3."""
+    return ((1, 7, 3, 0),) + tuple((s, 2 * s, (s + 1) // 2, ENC_RU_LOSS) for s in rates) + ((1, 3, 1, 0),)
+
+
+ENC_STAGES = _enc_stage_geometry()
+# Tail columns a stage keeps of its own (raw) input (DESIGN.md section 24): enc_stage_min_tails() rounded up to a multiple of 4.
+ENC_STAGE_TAILS = (8, 84, 88, 92, 100, 4)
+ENC_STREAM_MAX_N = (1 << 20) - 256   # samples of one step: every stage window stays within the stage-window kernel's 2^20 columns
+
+
+def _enc_done(have: int, s: int, ks: int, p: int, loss: int) -> int:
+    """Output columns of ``have`` input columns that are exact while the right edge is cut: J*s - p + ks <= have - loss."""
+    x = have - loss + p - ks
+    return x // s + 1 if x >= 0 else 0
+
+
+def _enc_total(have: int, s: int, ks: int, p: int) -> int:
+    """Output columns of ``have`` input columns whose right edge is the signal's (the conv's own length)."""
+    x = have + 2 * p - ks
+    return x // s + 1 if have > 0 and x >= 0 else 0
+
+
+def _enc_tail(have: int, s: int, cap: int) -> int:
+    """Rule 1: the tail actually used, the largest h <= min(cap, have) with (have - h) % s == 0 -- the window then starts on a
+    global column that is a multiple of the stride."""
+    return have if have <= cap else have - -(-(have - cap) // s) * s
+
+
+def enc_stage_min_tails() -> Tuple[int, ...]:
+    """The least tail every stage may keep for ANY number of input columns.  With d outputs handed on (the largest d with
+    d*s - p + ks <= have - loss) the next window must start at a multiple of s at or below d*s - p - loss, its first new output
+    column's left-most exact input; the largest such start is d*s - s*ceil((p + loss)/s), and have - d*s is at most
+    loss - p + ks - 1.  77 + 2s plus the alignment slack for a block, 6 for k7, 2 for k3."""
+    return tuple(loss - p + ks - 1 + s * -(-(p + loss) // s) for s, ks, p, loss in ENC_STAGES)
+
+
+assert enc_stage_min_tails() == (6, 81, 88, 90, 98, 2)
+assert all(t >= m and t % 4 == 0 and t - m < 4 for t, m in zip(ENC_STAGE_TAILS, enc_stage_min_tails()))
+
+
+class EncStagePlan(NamedTuple):
+    """``stages``: block.0, the four EncoderBlocks, the Snake + k3; [t0, t1): the GLOBAL latent columns (tokens) the step emits,
+    ``off`` their first column local to the k3 window's output."""
+    stages: Tuple[StageStep, ...]
+    t0: int
+    t1: int
+    off: int
+
+
+def encoder_stage_plan(samples_before: int, n: int, last: bool = False, tails=ENC_STAGE_TAILS, align: bool = True) -> EncStagePlan:
+    """The stateful encoder's step that takes ``n`` new samples after ``samples_before`` (host arithmetic; the library's
+    mvq_encoder_stream_plan says the same).  Stage k has received ``have`` columns; its window is [h_in tail columns | n_new new
+    ones], h_in by rule 1 (_enc_tail), so it covers global input columns [a, have + n_new) with a % s == 0 and its output column j
+    is global column a/s + j.  Rule 2: global output column J is exact if J*s - p >= a + loss (or a == 0) and J*s - p + ks <=
+    have + n_new - loss (or ``last``: the true right edge).  What is handed on is what is exact and was not handed on before, so a
+    stage's ``have`` is a function of samples_before alone.  ``last`` flushes every stage against its true right edge (n = 0 too:
+    the tails alone) and keeps nothing.  ``tails`` other than ENC_STAGE_TAILS and ``align`` = False (the plain tail min(cap, have),
+    a window start off the stride grid) are for the tests: both hand on inexact columns."""
+    before, n, last = int(samples_before), int(n), bool(last)
+    if before < 0 or n < 0 or n > ENC_STREAM_MAX_N:
+        raise ValueError(f"encoder_stage_plan: samples_before = {before}, n = {n}")
+    stages, have, src_off, n_new, d0, d1, off = [], before, 0, n, 0, 0, 0
+    for (s, ks, p, loss), cap in zip(ENC_STAGES, tails):
+        tail = (lambda hv: _enc_tail(hv, s, cap)) if align else (lambda hv: min(hv, cap))
+        h_in = tail(have)
+        a = have - h_in
+        stages.append(StageStep(h_in, src_off, n_new, 0 if last else tail(have + n_new)))
+        d0 = _enc_done(have, s, ks, p, loss)
+        d1 = max(d0, _enc_total(have + n_new, s, ks, p) if last else _enc_done(have + n_new, s, ks, p, loss))
+        off = d0 - a // s if d1 > d0 else 0
+        if tails is ENC_STAGE_TAILS and align and d1 > d0:
+            assert off >= 0 and (a == 0 or d0 * s - p - loss >= a)
+        have, src_off, n_new = d0, off, d1 - d0
+    return EncStagePlan(tuple(stages), d0, d1, off)
+
+
 def resample_stream_out_len(consumed: int, n_new: int, orig: int, width: int, final: bool = False) -> int:
     """Outputs a resample_stream call completes after ``consumed`` samples: the count mvq_resample_stream_f32 checks."""
     hold = (width + orig - 1) // orig
@@ -295,6 +381,33 @@ def sender_step(fill: int, start: int, chunk: int, n: int, last: bool = False) -
     return SenderStep(True, HOP * (end - start), drop, lo, lo + CHUNK_TOK, fill + n - drop, new_start, c + 1)
 
 
+def sender_step_stateful(fill: int, start: int, chunk: int, n: int, last: bool = False) -> SenderStep:
+    """``sender_step`` for encoder="stateful" (StreamSender and StreamSenderPool both call it).  The schedule
+    is sender_schedule's -- chunk c leaves with the push after which 16c + 24 tokens are in hand -- but the encoders are fed only
+    the samples they have not seen: the buffer holds ``fill`` un-encoded samples from token ``start`` on (``start`` tokens are
+    encoded: samples_before = 320*start).  An emitting push feeds the w samples up to token 16c + 24 -- 24 tokens for chunk 0, 16
+    in the steady state -- and the buffer drops exactly those (drop = w); ``finish`` feeds everything left (any count, none too:
+    the stage tails alone are flushed against the true edge).  [lo, hi) are the emitted tokens relative to token ``start``, as in
+    sender_step; here the tokens of chunk c lie up to 8 tokens BEFORE the samples fed, so lo may be negative: the stateful encode
+    returns exactly hi - lo tokens and nothing is sliced."""
+    fill, start, c, n, last = int(fill), int(start), int(chunk), int(n), bool(last)
+    if fill < 0 or start < 0 or c < 0 or n < 0 or fill % HOP and not last:
+        raise ValueError(f"sender_step_stateful: fill = {fill}, start = {start}, chunk = {c}, n = {n}")
+    lo = CHUNK_TOK * c - start
+    if last:
+        T = enc_tokens(HOP * start + fill + n)                            # the item's tokens
+        if T <= CHUNK_TOK * c:
+            return SenderStep(False, 0, 0, lo, T - start, 0, start, c)
+        return SenderStep(True, fill + n, fill + n, lo, T - start, 0, start, (T + CHUNK_TOK - 1) // CHUNK_TOK)
+    if n % HOP or not HOP <= n <= PUSH_MAX_TOK * HOP:
+        raise ValueError(f"sender_step_stateful: a push of {n} samples")
+    end = CHUNK_TOK * (c + 1) + ENC_HALO_TOK                              # the first token chunk c does not need
+    if start + (fill + n) // HOP < end:
+        return SenderStep(False, 0, 0, 0, 0, fill + n, start, c)
+    w = HOP * (end - start)
+    return SenderStep(True, w, w, lo, lo + CHUNK_TOK, fill + n - w, end, c + 1)
+
+
 class SenderGroup(NamedTuple):
     """Sender sessions of one tick that share a launch sequence: ``key`` = ("append",), ("emit", min(chunk, 1)) or
     ("finish", fill + n, lo); ``sids`` ascending; ``w`` the window in samples and [lo, hi) the tokens of it that are emitted
@@ -307,7 +420,7 @@ class SenderGroup(NamedTuple):
     steps: Tuple[SenderStep, ...]
 
 
-def sender_pool_groups(sessions) -> List[SenderGroup]:
+def sender_pool_groups(sessions, stateful: bool = False) -> List[SenderGroup]:
     """``sessions``: (sid, fill, start, chunk, n, last) of every session that takes a step this tick (``sender_step``'s
     arguments).  -> the groups that do device work, ordered by key.
 
@@ -318,17 +431,23 @@ def sender_pool_groups(sessions) -> List[SenderGroup]:
         lo = 8, whatever it holds and whatever it pushed: ("emit", 0) and ("emit", 1);
       * a finisher's window is all it holds, fill + n samples, emitted from lo on: ("finish", fill + n, lo).  One whose window
         holds no token past lo does no device work and is in no group.
-    Nothing coarser is sound: windows of different lengths are never merged by padding, only a true edge is exact."""
+    Nothing coarser is sound: windows of different lengths are never merged by padding, only a true edge is exact.
+
+    ``stateful`` (encoder="stateful", ``sender_step_stateful``): the same keys, read as what the encoder STAGE plan depends on.
+    encoder_stage_plan depends on samples_before = 320*start only through chunk 0 (nothing encoded) against any later chunk
+    (16c + 8 tokens encoded: every stage's tail is full and its column count mod its stride is that of every later chunk), so
+    ("emit", min(chunk, 1)) stands; a finisher's plan depends on that class and on its un-encoded sample count:
+    ("finish", fill + n, min(chunk, 1))."""
     seen, by_key, step_of = set(), {}, {}
     for sid, fill, start, chunk, n, last in sessions:
         if sid in seen:
             raise ValueError(f"sender_pool_groups: session {sid} is listed twice")
         seen.add(sid)
-        st = sender_step(fill, start, chunk, n, last)
+        st = (sender_step_stateful if stateful else sender_step)(fill, start, chunk, n, last)
         if last:
             if not st.emit:
                 continue
-            key = ("finish", st.w, st.lo)
+            key = ("finish", st.w, min(int(chunk), 1) if stateful else st.lo)
         else:
             key = ("emit", min(int(chunk), 1)) if st.emit else ("append",)
         by_key.setdefault(key, []).append(sid)
@@ -398,7 +517,7 @@ class _SenderCore:
     tokens go through a dense [G, C] copy (ops.stream_rows), everything else is the same launches on the group's window."""
 
     def __init__(self, who, net, packet_tok, books_use, sessions, buf_shape, rate=None, audio="codes", audio_books=None,
-                 audio_rate=None, fec=None, audio_fec=None):
+                 audio_rate=None, fec=None, audio_fec=None, encoder="window"):
         import torch
         from . import proposed
         from .packets import StreamInfo, body_bytes, _check
@@ -407,7 +526,10 @@ class _SenderCore:
                              "(a packet must never straddle two chunks)")
         if sessions < 1:
             raise ValueError(f"{who}: {'batch' if who == 'StreamSender' else 'slots'} must be at least 1")
-        _f32_only(who)
+        if encoder not in ("window", "stateful"):
+            raise ValueError(f"{who}: encoder must be 'window' or 'stateful', not {encoder!r}")
+        self.encoder = encoder
+        _f32_only(who if encoder == "window" else f"{who}(encoder='stateful')")
         assert proposed.AR_CHUNK_TOK == CHUNK_TOK
         for enc in (net.A_ENC, net.T_ENC):
             if tuple(enc._desc[1]) != ENC_RATES:
@@ -444,6 +566,41 @@ class _SenderCore:
         self.n_audio_books = net.A_QUANT.n_codebooks
         self.buf = torch.zeros(*buf_shape, device=self.dev)                            # per session: an audio and a tactile row
         self.carry = torch.zeros(sessions, self.C, device=self.dev)                    # per session: z_run[..., -1] of the chunk before
+        self.enc_state = None                                                          # stateful: (audio, tactile) stage tails [sessions, S]
+        if encoder == "stateful":                                                      # allocated once, never cleared: a new session reads no tail
+            self.enc_state = (net.A_ENC.stream_state(sessions), net.T_ENC.stream_state(sessions))
+        self._step = sender_step if encoder == "window" else sender_step_stateful
+
+    def _branches_stateful(self, a_w, t_w, n_tok, before, last, sl=None, want_za=False):
+        """``_branches`` for encoder="stateful": the same two stack calls on the same two HIP streams under the same rule, each
+        A_ENC / T_ENC.forward_stream on the samples that were not encoded yet (``before`` samples were; enc_state moves on in
+        place).  They return exactly the chunk's n_tok tokens, so nothing is sliced."""
+        import torch
+        from . import ops
+        net = self.net
+        slots, slots_dev = (None, None) if sl is None else sl
+        sa, st_ = self.enc_state
+        if a_w.shape[0] > net.TWO_STREAM_MAX_BATCH or not a_w.is_cuda or ops.get_arith() != "f32":
+            za_c = net.A_ENC.forward_stream(sa, a_w, before, last, slots=slots, slots_dev=slots_dev)
+            qa, codes, *_ = net.A_QUANT(za_c)
+            zt = net.T_ENC.forward_stream(st_, t_w, before, last, slots=slots, slots_dev=slots_dev)
+            assert za_c.shape[-1] == zt.shape[-1] == n_tok
+            return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
+        cur = torch.cuda.current_stream()
+        side = getattr(net, "_side_stream", None)
+        if side is None or side.device != a_w.device:
+            side = torch.cuda.Stream(device=a_w.device)
+            net._side_stream = side
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            za_c = net.A_ENC.forward_stream(sa, a_w, before, last, slots=slots, slots_dev=slots_dev)
+            qa, codes, *_ = net.A_QUANT(za_c)
+        zt = net.T_ENC.forward_stream(st_, t_w, before, last, slots=slots, slots_dev=slots_dev)
+        cur.wait_stream(side)
+        for x in (za_c, qa, codes):
+            x.record_stream(cur)
+        assert za_c.shape[-1] == zt.shape[-1] == n_tok
+        return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
 
     def _branches(self, a_w, t_w, lo, hi, want_za=False):
         """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt) and, with
@@ -473,20 +630,25 @@ class _SenderCore:
             x.record_stream(cur)
         return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
 
-    def _encode(self, win, lo, hi, sl=None):
+    def _encode(self, win, lo, hi, sl=None, before=None, last=False):
         """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
         uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place.  With ``self.rate`` the loop
         runs closed (on the books each packet carries and on qa from the codes, as the receiver will) and the bodies come back as
         uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back.  With ``self.fec`` /
         ``self.audio_fec`` the parity rows of the window's packets (ops.fec_parity on the packed bodies and the device-side counts;
-        the window starts on a chunk, so its groups are the item's) follow everything else in the same uint8 [G, ...] array."""
+        the window starts on a chunk, so its groups are the item's) follow everything else in the same uint8 [G, ...] array.
+        encoder="stateful": ``win`` holds only the samples not encoded yet, ``before`` samples were (``last``: the finish), and the
+        latents come from ``_branches_stateful``; everything behind them is the same."""
         import torch
         from . import ops
         from .packets import StreamInfo
         n_tok = hi - lo
         if self.audio_packets:      # uint8 [G, P*full + P + P*afull + P]: tactile bodies, counts, audio bodies, counts: one read-back
             assert sl is None                                                          # the pools take no audio packets
-            _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
+            if self.enc_state is None:
+                _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
+            else:
+                _, codes, zt, za = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, want_za=True)
             qa, _, na_sent = self.net.A_QUANT.rate(za, codes, self.audio_rate, self.packet_tok, self.na)
             _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=self.carry, z_last_out=self.carry, rate=self.rate,
                                                          packet_tok=self.packet_tok)
@@ -500,7 +662,10 @@ class _SenderCore:
                 parts.append(ops.fec_parity(abodies, na_sent, StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok),
                                             self.audio_fec).reshape(G, -1))
             return torch.cat(parts, dim=1), codes
-        qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
+        if self.enc_state is None:
+            qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
+        else:
+            qa, codes, zt = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, sl)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
         if self.rate is not None:
             assert sl is None                                                          # the pools take no rate
@@ -563,13 +728,20 @@ class StreamSender(_SenderCore):
     packets (tactile_packets, audio_packets, fec_packets, audio_fec_packets) where a stream without a Fec gets empty lists;
     ``finish`` returns its usual values and then the same parity lists.  Groups are numbered across the stream: chunk c's start at
     c * (16 // packet_tok // group).  Per item the concatenation equals compress_packets(fec=) / compress_packets_av(fec=,
-    audio_fec=) byte for byte, data and parity.  A Fec with parity = r > 1 emits r packets per group (``MF``, then ``MR``)."""
+    audio_fec=) byte for byte, data and parity.  A Fec with parity = r > 1 emits r packets per group (``MF``, then ``MR``).
+
+    ``encoder="stateful"`` (the default "window" is the sequence above, launch for launch): instead of A_ENC and
+    T_ENC on the 24- / 32-token window, A_ENC / T_ENC.forward_stream on the samples that were not encoded yet (24 tokens for chunk 0,
+    then 16; ``sender_step_stateful``) -- every encoder stage keeps the tail of its own input in enc_state (two [B, S] buffers) and
+    returns exactly the chunk's tokens; the sample buffer holds un-encoded samples only.  Every push / finish returns exactly the
+    window mode's values; the steady step stays ONE captured graph; everything behind the latents is untouched."""
 
     def __init__(self, net, packet_tok=2, batch=1, books_use=None, graph=False, rate=None, audio="codes", audio_books=None,
-                 audio_rate=None, fec=None, audio_fec=None):
+                 audio_rate=None, fec=None, audio_fec=None, encoder="window"):
         packet_tok, batch = int(packet_tok), int(batch)
         super().__init__("StreamSender", net, packet_tok, books_use, batch, (2 * batch, SEND_CAP_TOK * HOP), rate=rate, audio=audio,
-                         audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec)   # buffer: audio rows, then tactile rows
+                         audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec,   # buffer: audio rows, then tactile rows
+                         encoder=encoder)
         self.batch, self.graph = batch, bool(graph)
         self.fill = 0                                                                  # valid samples of every buffer row
         self.start = 0                                                                 # the token buf[:, 0] belongs to
@@ -583,11 +755,12 @@ class StreamSender(_SenderCore):
         return self.start + self.fill // HOP
 
     # ------------------------------------------------------------------------------------------------------------ stages
-    def _device_step(self, x, fill, w, drop, lo, hi):
+    def _device_step(self, x, fill, w, drop, lo, hi, before=None, last=False):
         """Device: samples -> window -> latents of tokens [lo, hi) of the window -> (packet bodies uint8 [B, P, full], audio codes
-        int64 [B, 32, hi - lo]); the buffer and the carried token move on in place."""
+        int64 [B, 32, hi - lo]); the buffer and the carried token move on in place (encoder="stateful": the encoder states too,
+        ``before`` = the samples encoded so far)."""
         from . import ops
-        return self._encode(ops.stream_samples(self.buf, fill, x, w, drop).view(2, self.batch, w), lo, hi)
+        return self._encode(ops.stream_samples(self.buf, fill, x, w, drop).view(2, self.batch, w), lo, hi, before=before, last=last)
 
     def _samples(self, a, t, what, tail=False):
         """The checks of a push, before any launch -> (a, t) and n."""
@@ -664,13 +837,13 @@ class StreamSender(_SenderCore):
         from . import ops
         self._open("push")
         a, t, n = self._samples(a, t, "push")
-        st = sender_step(self.fill, self.start, self.chunk, n)
+        st = self._step(self.fill, self.start, self.chunk, n)
         with torch.no_grad():
             if not st.emit:
                 ops.stream_samples(self.buf, self.fill, self._upload(a, t, n), 0, 0)
                 self.fill = st.fill
                 return self._nothing()
-            plan = (self.fill, st.w, st.drop, st.lo, st.hi)
+            plan = (self.fill, st.w, st.drop, st.lo, st.hi) + (() if self.enc_state is None else (HOP * self.start,))
             if self.graph and self.chunk > 0 and n == CHUNK_TOK * HOP and (self._g is None or self._g[1] == self.fill):   # the steady step
                 bodies, codes = self._replay(a, t, n, plan)
             else:
@@ -691,13 +864,18 @@ class StreamSender(_SenderCore):
         n = 0
         if a is not None:
             a, t, n = self._samples(a, t, "finish", tail=True)
-        st = sender_step(self.fill, self.start, self.chunk, n, last=True)
+        st = self._step(self.fill, self.start, self.chunk, n, last=True)
+        if st.w > ENC_STREAM_MAX_N and self.enc_state is not None:
+            raise ValueError(f"StreamSender.finish: {st.w} samples left to encode; encoder='stateful' takes at most {ENC_STREAM_MAX_N} in one step")
         with torch.no_grad():
             if not st.emit:                                              # an item shorter than one token: nothing to send
                 self.finished = True
                 return self._finished(self._nothing(), self.start + max(st.hi, 0))
             x = self._upload(a, t, n) if n else torch.empty(2 * self.batch, 0, device=self.dev)
-            bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi)
+            if self.enc_state is None:
+                bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi)
+            else:
+                bodies, codes = self._device_step(x, self.fill, st.w, st.drop, st.lo, st.hi, HOP * self.start, True)
             out = self._framed(bodies, codes, st.hi - st.lo)
             self.fill, self.chunk, self.finished = st.fill, st.chunk, True
             return self._finished(out, self.start + st.hi)
@@ -718,7 +896,8 @@ class StreamSender(_SenderCore):
         B = self.batch
         if self._g is None:
             x_s = self._upload(a, t, n)
-            g, (bodies_s, codes_s) = _capture(self.dev, (self.buf, self.carry), lambda: self._device_step(x_s, *plan))
+            state = (self.buf, self.carry) + (() if self.enc_state is None else self.enc_state)
+            g, (bodies_s, codes_s) = _capture(self.dev, state, lambda: self._device_step(x_s, *plan))
             self._g = (g, plan[0], x_s, bodies_s, codes_s)
         else:
             g, _, x_s, bodies_s, codes_s = self._g
@@ -1325,11 +1504,15 @@ class StreamSenderPool(_SenderCore):
              [G, C]) -> _ar_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.idx_pack_packets: _SenderCore's
              sequence on the group's slots.  The append group is the sample-state launch alone;
       copy   ONE device-to-host copy of all groups' packet bodies, then packets.frame(seq_base=) per session with ITS chunk.
-    Nothing is captured as a graph: the group sizes change from tick to tick."""
+    Nothing is captured as a graph: the group sizes change from tick to tick.
 
-    def __init__(self, net, packet_tok=2, slots=64, books_use=None):
+    ``encoder="stateful"``: as for StreamSender -- enc_state (two [S, floats] buffers) beside the sample buffers, a group's encode is
+    A_ENC / T_ENC.forward_stream on the group's slots, fed the members' un-encoded samples (``sender_pool_groups(stateful=True)``
+    groups by what the stage plan depends on).  ``open`` leaves a slot's enc_state as it is: a new session reads no tail."""
+
+    def __init__(self, net, packet_tok=2, slots=64, books_use=None, encoder="window"):
         packet_tok, slots = int(packet_tok), int(slots)
-        super().__init__("StreamSenderPool", net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP))
+        super().__init__("StreamSenderPool", net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), encoder=encoder)
         self.slots = slots
         self._free = list(range(slots))                                                # ascending: open() takes the lowest
         self._sess = {}                                                                # sid -> [slot, fill, start, chunk]
@@ -1420,11 +1603,14 @@ class StreamSenderPool(_SenderCore):
         work = self._inputs(pushes, finishes)
         if not work:
             return {}
-        groups = sender_pool_groups((sid, *self._sess[sid][1:], w[2], w[3]) for sid, w in work.items())
+        stateful = self.enc_state is not None
+        groups = sender_pool_groups(((sid, *self._sess[sid][1:], w[2], w[3]) for sid, w in work.items()), stateful=stateful)
         steps = {sid: st for g in groups for sid, st in zip(g.sids, g.steps)}
         for sid, w in work.items():                                      # the finishers without a token: no device work
             if sid not in steps:
-                steps[sid] = sender_step(*self._sess[sid][1:], w[2], w[3])
+                steps[sid] = self._step(*self._sess[sid][1:], w[2], w[3])
+        if stateful and any(g.w > ENC_STREAM_MAX_N for g in groups):
+            raise ValueError(f"StreamSenderPool: encoder='stateful' takes at most {ENC_STREAM_MAX_N} samples in one step")
         cap = self.buf.shape[2]
         # ONE host array: the descriptor tables of all groups (int32 [5] per session), then their slot lists
         tables = [ops.stream_samples_desc([(self._sess[sid][0], self._sess[sid][1], work[sid][2], st.drop)
@@ -1450,7 +1636,9 @@ class StreamSenderPool(_SenderCore):
                 G = len(g.sids)
                 win = ops.stream_samples_slots(self.buf, [r[:4] for r in rows], x_all[x0:x0 + x_total], g.w, desc_dev=desc_all[s0:s0 + G])
                 if g.hi > g.lo:
-                    bodies, codes = self._encode(win, g.lo, g.hi, sl=([r[0] for r in rows], slots_all[s0:s0 + G]))
+                    # stateful: the stage plan is the same for every member (sender_pool_groups), so the first one's samples_before
+                    bodies, codes = self._encode(win, g.lo, g.hi, sl=([r[0] for r in rows], slots_all[s0:s0 + G]),
+                                                 before=HOP * self._sess[g.sids[0]][2] if stateful else None, last=g.key[0] == "finish")
                     bodies_all.append(bodies.reshape(-1))
                     per = bodies.numel() // G
                     for i, sid in enumerate(g.sids):

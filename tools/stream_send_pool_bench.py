@@ -18,12 +18,14 @@ x K = 512, packets of 2 tokens), all in this one process,
   (e) solo_ms          one steady eager StreamSender(batch=1).push of 16 tokens, and solo_total_ms = S times that: one session
                        object per session, the only way to serve independent sessions without the pool (it leaves out the 15
                        append launches per chunk that a solo session fed token by token also pays); round_over_solo = (c) / (S * (e)).
+  (f) --encoder stateful   the pool (and (d), (e)) with encoder="stateful" (DESIGN.md section 24); "both": the rows of both modes
+                       in this one process, each row tagged "encoder".
 The two ratios are reported, not gated.  The samples of every call are HOST tensors, as they arrive, in all three.  Timing:
 torch.cuda events around each call (they bracket the host work too) after --warmup rounds in the steady state; --repeats rounds
 are timed, (d) and (e) as many calls.  Every timed call encodes real next samples of sessions that keep running (a 1-s signal per
 session, repeated).  Seeded synthetic weights and signals: only the times mean anything.
 
-  python tools/stream_send_pool_bench.py [--repeats 10] [--warmup 3] [--sessions 1,6,64,256]
+  python tools/stream_send_pool_bench.py [--repeats 10] [--warmup 3] [--sessions 1,6,64,256] [--encoder window|stateful|both]
 """
 import argparse
 import json
@@ -54,11 +56,15 @@ def spread(ms):
     return {"median": statistics.median(ms), "min": min(ms), "max": max(ms), "n": len(ms)} if ms else None
 
 
-def pool_ticks(net, a, t, S, stagger, warmup, repeats):
+def enc_kw(encoder):
+    return {} if encoder == "window" else {"encoder": encoder}
+
+
+def pool_ticks(net, a, t, S, stagger, warmup, repeats, encoder="window"):
     """A pool of S sessions, session i starting (i mod 16 if ``stagger`` else 0) ticks late, every open session pushing one token
     per tick.  -> (per-round sums, the times of the ticks that emitted, the times of the ticks that only appended) of
     ``repeats`` steady rounds."""
-    pool = net.stream_sender_pool(slots=S)
+    pool = net.stream_sender_pool(slots=S, **enc_kw(encoder))
     late = [i % ROUND if stagger else 0 for i in range(S)]
     sids, fed = {}, [0] * S
 
@@ -95,9 +101,9 @@ def pool_ticks(net, a, t, S, stagger, warmup, repeats):
     return rounds, emit, append
 
 
-def lockstep_steps(net, a, t, B, warmup, repeats):
+def lockstep_steps(net, a, t, B, warmup, repeats, encoder="window"):
     """``repeats`` steady eager 16-token pushes of a StreamSender(batch=B) on the first B sessions' signals."""
-    tx = net.stream_sender(batch=B)
+    tx = net.stream_sender(batch=B, **enc_kw(encoder))
     c = {"n": 0}
     n_steps = a.shape[-1] // (ROUND * HOP)
 
@@ -116,6 +122,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sessions", default="1,6,64,256")
+    ap.add_argument("--encoder", default="window", choices=("window", "stateful", "both"))
     args = ap.parse_args()
     sys.path.insert(0, str(ROOT))
     from multimodal_vqvae_compression_audio_tactile_amd import build_proposed, synth
@@ -130,13 +137,15 @@ def main():
         S_max = max(sizes)
         a, t = synth.audio_segments(S_max, seed=11), synth.tactile_segments(S_max, seed=11)        # on the host, [S, 1, 24000]
         assert a.shape[-1] == SIGNAL_TOK * HOP and not a.is_cuda
-        solo = spread(lockstep_steps(net, a, t, 1, args.warmup, args.repeats))
-        for S in sizes:
-            rounds, emit, append = pool_ticks(net, a, t, S, True, args.warmup, args.repeats)
+        modes = ("window", "stateful") if args.encoder == "both" else (args.encoder,)
+        solos = {m: spread(lockstep_steps(net, a, t, 1, args.warmup, args.repeats, m)) for m in modes}
+        for S, mode in ((S, m) for S in sizes for m in modes):
+            solo = solos[mode]
+            rounds, emit, append = pool_ticks(net, a, t, S, True, args.warmup, args.repeats, mode)
             if S >= ROUND:                                            # every tick of the staggered workload emits
-                append = pool_ticks(net, a, t, S, False, 0, max(1, args.repeats // 5))[2]
-            lock = spread(lockstep_steps(net, a, t, S, args.warmup, args.repeats))
-            row = {"S": S, "emitting_per_tick": S / ROUND, "tick_emit_ms": spread(emit), "tick_append_ms": spread(append),
+                append = pool_ticks(net, a, t, S, False, 0, max(1, args.repeats // 5), mode)[2]
+            lock = spread(lockstep_steps(net, a, t, S, args.warmup, args.repeats, mode))
+            row = {"S": S, "encoder": mode, "emitting_per_tick": S / ROUND, "tick_emit_ms": spread(emit), "tick_append_ms": spread(append),
                    "round_ms": spread(rounds), "lockstep_ms": lock, "solo_ms": solo, "solo_total_ms": S * solo["median"]}
             row["round_over_lockstep"] = row["round_ms"]["median"] / lock["median"]
             row["round_over_solo"] = row["round_ms"]["median"] / row["solo_total_ms"]
