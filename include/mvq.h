@@ -41,7 +41,7 @@ extern "C" {
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
  * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8, mvq_fec_rs_parity_u8, mvq_fec_rs_recover_u8; audio concealment: mvq_attention_masked_f32,
- * mvq_attention_seq_masked_f32, mvq_hold_fill_f32;
+ * mvq_attention_seq_masked_f32, mvq_hold_fill_f32; the audio/FEC pools: mvq_hold_fill_slots_f32;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
@@ -420,6 +420,12 @@ int mvq_attention_seq_masked_f32(const float* q, const float* k, const float* v,
  * or NULL = +0).  Afterwards carry[b,c] = y[b,c,t-1] (t > 0), so a sequence is filled piece by piece.  Pure copies: -0, NaN and
  * inf pass unchanged.  Only tokens with valid == 0 are written. */
 int mvq_hold_fill_f32(float* x, const uint8_t* valid, float* carry, int batch, int c, int t, void* stream);
+/* The same for the sessions of a pool (the same kernel body under slot addressing): item g of x[n_group, c, t] / valid[n_group, t]
+ * reads and writes the carry row slots[g] of carry_pool[n_slots, c]; rows no slot names are untouched.  A slot outside
+ * [0, n_slots) has no row: +0 is read as the carry and none is stored (the caller refuses such a list, and a repeated slot, on
+ * the host).  carry_pool and slots are required; n_group <= n_slots. */
+int mvq_hold_fill_slots_f32(float* x, const uint8_t* valid, float* carry_pool, const int32_t* slots, int n_group, int n_slots,
+                            int c, int t, void* stream);
 
 /* y = gelu_erf(x) elementwise (nn.GELU() in CrossPredictor.ffn). */
 int mvq_gelu_f32(const float* x, float* y, size_t n, void* stream);

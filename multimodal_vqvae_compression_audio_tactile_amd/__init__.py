@@ -28,6 +28,7 @@ All compute runs in libmvq_hip.so (hand-written HIP for gfx950); there is no CPU
 from . import bitstream, ops, optim, packets, stream, synth, train  # noqa: F401
 from .resample import Resample, StreamResample, resample_to  # noqa: F401
 from .stream import StreamReceiver, StreamReceiverPool, StreamSender, StreamSenderPool  # noqa: F401
+from .stream import PoolChunk, StreamReceiverPoolAV, StreamSenderPoolAV  # noqa: F401
 from .losses import MelCosineLoss, MultiResSTFTLoss, TrainingLoss, safe_l1, stsim_batch  # noqa: F401
 from ._lib import MvqError, build, lib  # noqa: F401
 from .dac import plan_overrides  # noqa: F401

@@ -113,6 +113,7 @@ EXPORTS = {
     "mvq_attention_masked_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_attention_seq_masked_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_hold_fill_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "mvq_hold_fill_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "mvq_attention_seq_bwd_scratch_bytes": (c_size_t, [c_int] * 4),
     "mvq_attention_seq_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_plc_mask_fill_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_void_p]),

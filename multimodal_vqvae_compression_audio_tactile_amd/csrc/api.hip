@@ -1534,6 +1534,17 @@ int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_sl
     return e == hipSuccess ? MVQ_OK : hipfail(e, "stream_rows");
 }
 
+int mvq_hold_fill_slots_f32(float* x, const uint8_t* valid, float* carry_pool, const int32_t* slots, int n_group, int n_slots, int c,
+                            int t, void* stream)
+{
+    if (c < 0 || t < 0 || (c + 15) / 16 > 65535) return fail(MVQ_EINVAL, "hold_fill_slots: bad shape");
+    if (int rc = slots_shape_bad("hold_fill_slots", n_group, n_slots, c)) return rc;
+    if ((size_t)n_group * c * t == 0) return MVQ_OK;
+    if (!x || !valid || !carry_pool || !slots) return fail(MVQ_EINVAL, "hold_fill_slots: null tensor");
+    hipError_t e = mvq::launch_hold_fill_slots(x, valid, carry_pool, slots, n_group, n_slots, c, t, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "hold_fill_slots");
+}
+
 int mvq_sumsq_partial_f32(const float* x, float* partial, int n_partial, size_t n, void* stream)
 {
     if (!partial || n_partial <= 0 || n_partial > 4096 || (!x && n)) return fail(MVQ_EINVAL, "sumsq_partial: bad argument");

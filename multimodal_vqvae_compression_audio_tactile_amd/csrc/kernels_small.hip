@@ -699,12 +699,43 @@ hipError_t launch_attention_masked(const float* q, const float* k, const float* 
 // ------------------------------------------------------------------------------------------------
 constexpr int HOLD_CH = 16;
 
+// Where item b's carry row lies: the dense call's carry[b] (NULL carry: none), or row slots[b] of a pool of n_slots rows
+// (mvq_hold_fill_slots_f32: the sessions of a group).  A slot outside [0, n_slots) has no row, as in the
+// other slot kernels (stream.hip): +0 is read as the carry and none is stored.  ``open(b)`` is what a thread keeps of item b:
+// has(carry) -- whether there is a row; at(b, C, c) -- the index of its channel c in the carry buffer.
+struct HoldDense {
+    struct Row {
+        __device__ bool has(const float* carry) const { return carry != nullptr; }
+        __device__ size_t at(int b, int C, int c) const { return (size_t)b * C + c; }
+    };
+    __device__ Row open(int) const { return Row{}; }
+};
+struct HoldSlots {
+    const int32_t* slots;
+    int n_slots;
+    struct Row {
+        int slot;
+        bool ok;
+        __device__ bool has(const float*) const { return ok; }
+        __device__ size_t at(int, int C, int c) const { return (size_t)slot * C + c; }
+    };
+    __device__ Row open(int b) const
+    {
+        const int slot = slots[b];
+        return Row{slot, slot >= 0 && slot < n_slots};
+    }
+};
+
+// ONE body: ROWS is the addressing, SLOT_ARGS what it is built from -- none for the dense call, whose kernel so keeps its five
+// arguments and its device code, or (slots, n_slots).
+template <class ROWS, class... SLOT_ARGS>
 __global__ __launch_bounds__(256) void hold_fill_kernel(float* __restrict__ x, const uint8_t* __restrict__ valid,
-                                                        float* __restrict__ carry, int C, int T)
+                                                        float* __restrict__ carry, int C, int T, SLOT_ARGS... slot_args)
 {
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c0 = blockIdx.y * HOLD_CH + wave * (HOLD_CH / 4);
     const uint8_t* vr = valid + (size_t)b * T;
+    const auto cr = ROWS{slot_args...}.open(b);              // item b's carry row, or none
     int prev = -1;                                           // last valid token before this tile (wave-uniform)
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
@@ -718,9 +749,9 @@ __global__ __launch_bounds__(256) void hold_fill_kernel(float* __restrict__ x, c
                 const int c = c0 + u;
                 if (c >= C) break;
                 float* row = x + ((size_t)b * C + c) * T;
-                const float val = src >= 0 ? row[src] : (carry ? carry[(size_t)b * C + c] : 0.0f);
+                const float val = src >= 0 ? row[src] : (cr.has(carry) ? carry[cr.at(b, C, c)] : 0.0f);
                 if (!ok) row[t] = val;
-                if (carry && t == T - 1) carry[(size_t)b * C + c] = val;
+                if (cr.has(carry) && t == T - 1) carry[cr.at(b, C, c)] = val;
             }
         }
         if (m) prev = t0 + 63 - __clzll((long long)m);
@@ -730,7 +761,17 @@ __global__ __launch_bounds__(256) void hold_fill_kernel(float* __restrict__ x, c
 hipError_t launch_hold_fill(float* x, const uint8_t* valid, float* carry, int B, int C, int T, hipStream_t s)
 {
     if ((size_t)B * C * T == 0) return hipSuccess;
-    hipLaunchKernelGGL(hold_fill_kernel, dim3(B, (C + HOLD_CH - 1) / HOLD_CH), dim3(256), 0, s, x, valid, carry, C, T);
+    hipLaunchKernelGGL(hold_fill_kernel<HoldDense>, dim3(B, (C + HOLD_CH - 1) / HOLD_CH), dim3(256), 0, s, x, valid, carry, C, T);
+    return hipGetLastError();
+}
+
+// item g of x[G, C, T] / valid[G, T] on carry row slots[g] of carry_pool[n_slots, C]
+hipError_t launch_hold_fill_slots(float* x, const uint8_t* valid, float* carry_pool, const int32_t* slots, int G, int n_slots, int C,
+                                  int T, hipStream_t s)
+{
+    if ((size_t)G * C * T == 0) return hipSuccess;
+    hipLaunchKernelGGL((hold_fill_kernel<HoldSlots, const int32_t*, int>), dim3(G, (C + HOLD_CH - 1) / HOLD_CH), dim3(256), 0, s, x, valid,
+                       carry_pool, C, T, slots, n_slots);
     return hipGetLastError();
 }
 

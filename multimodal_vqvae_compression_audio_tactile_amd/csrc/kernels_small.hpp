@@ -51,6 +51,8 @@ hipError_t launch_attention_masked(const float* q, const float* k, const float* 
                                    int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
                                    size_t msb, hipStream_t s);
 hipError_t launch_hold_fill(float* x, const uint8_t* valid, float* carry, int B, int C, int T, hipStream_t s);
+hipError_t launch_hold_fill_slots(float* x, const uint8_t* valid, float* carry_pool, const int32_t* slots, int G, int n_slots, int C,
+                                  int T, hipStream_t s);
 hipError_t launch_gelu(const float* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_strided3d(const float* a, size_t asb, size_t asc, const float* b2, size_t bsb, size_t bsc,
                             float* y, size_t ysb, size_t ysc, int B, int C, int n, hipStream_t s);

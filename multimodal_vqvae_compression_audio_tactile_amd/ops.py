@@ -932,16 +932,28 @@ def attention_seq_bwd(q, k, v, g, heads, folded_batch=None):
     return gq, gk, gv
 
 
-def hold_fill_(x, valid, carry=None):
+def hold_fill_(x, valid, carry=None, slots=None, slots_dev=None):
     """In place on contiguous fp32 x[B, C, T]: a token with valid[b, t] == 0 (valid: uint8 [B, T]) takes the values of the most
     recent valid token of its item; before the first one it takes carry[b] (``carry`` [B, C] fp32 or None = +0).  Afterwards
-    carry[b] = x[b, :, T-1], so a sequence is filled piece by piece (mvq_hold_fill_f32; pure copies).  Returns x."""
+    carry[b] = x[b, :, T-1], so a sequence is filled piece by piece (mvq_hold_fill_f32; pure copies).  Returns x.
+    ``slots`` (host integers, one per item; ``slots_dev``: their int32 device copy when the caller uploaded it already): the items
+    are sessions of a pool and ``carry`` is the pool's buffer [S, C] -- item b reads and writes row slots[b] of it, every other
+    row stays as it is (mvq_hold_fill_slots_f32, the same kernel body).  An out-of-range or repeated slot is refused here."""
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
         raise MvqError("hold_fill_: x must be a contiguous fp32 tensor [B, C, T] on the device (it is filled in place)")
     B, C, T = x.shape
     if not isinstance(valid, torch.Tensor) or valid.device != x.device or valid.dtype != torch.uint8 or tuple(valid.shape) != (B, T) \
             or not valid.is_contiguous():
         raise MvqError(f"hold_fill_: valid must be a contiguous uint8 tensor [B={B}, T={T}] on the device of x")
+    if slots is not None or slots_dev is not None:
+        if slots is None:
+            raise MvqError("hold_fill_: slots_dev is the device copy of slots; the host list is required")
+        G, sd = _slot_list("hold_fill_", slots, carry, 2, slots_dev)
+        if G != B or carry.shape[1] != C or carry.device != x.device:
+            raise MvqError(f"hold_fill_: {G} slots of a pool {tuple(carry.shape)} for x [B={B}, C={C}, T={T}] on {x.device}")
+        check(_lib.lib().mvq_hold_fill_slots_f32(x.data_ptr(), valid.data_ptr(), carry.data_ptr(), sd.data_ptr(), B, carry.shape[0], C, T,
+                                                 _stream()), "mvq_hold_fill_slots_f32")
+        return x
     if carry is not None and not (isinstance(carry, torch.Tensor) and carry.device == x.device and carry.dtype == torch.float32
                                   and tuple(carry.shape) == (B, C) and carry.is_contiguous()):
         raise MvqError(f"hold_fill_: carry must be a contiguous fp32 tensor [B={B}, C={C}] on the device of x")

@@ -557,7 +557,7 @@ class _ProposedBase(nn.Module):
     @torch.no_grad()
     def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
                        conceal="predict", plc=None, z_prev=None, z_last_out=None, na_valid=None, audio_conceal="zero", qa_prev=None,
-                       qa_last_out=None):
+                       qa_last_out=None, qa_slots=None, qa_slots_dev=None):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -591,6 +591,9 @@ class _ProposedBase(nn.Module):
         chunk borders, +0 before the first arrival (ops.hold_fill_ on qa right after from_codes), and then goes through ln_kv with
         its own position as any token does.  ``qa_prev`` / ``qa_last_out`` ([B, C] fp32 on the device; may be one buffer) carry the
         last held token between the pieces of a sequence, as z_prev / z_last_out carry the recursion; they belong to "hold".
+        ``qa_slots`` (host integers, one per item; ``qa_slots_dev`` their int32 device copy): the items are sessions of a pool and
+        qa_prev / qa_last_out are ONE buffer, the pool's [S, C] -- item b's held token is row qa_slots[b] of it
+        (ops.hold_fill_(slots=); stream.StreamReceiverPoolAV).
         conceal="plc" is handed what the predictor saw: the held qa, or qa with the key mask.  With na_valid=None every token
         arrived and every mode is "zero".  The launch sequence depends on shapes and modes only.
 
@@ -657,9 +660,13 @@ class _ProposedBase(nn.Module):
             if na_valid is None:
                 raise MvqError("decode_latents: qa_prev / qa_last_out need na_valid (without it nothing is held)")
             for t, name in ((qa_prev, "qa_prev"), (qa_last_out, "qa_last_out")):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32
-                                          and tuple(t.shape) == (B, C) and t.is_contiguous()):
-                    raise MvqError(f"decode_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {dev}")
+                if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 2
+                                          and (qa_slots is not None or t.shape[0] == B) and t.shape[1] == C and t.is_contiguous()):
+                    raise MvqError(f"decode_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {dev}"
+                                   + (" (with qa_slots: the pool's [S, C])" if qa_slots is not None else ""))
+        if qa_slots is not None or qa_slots_dev is not None:
+            if qa_slots is None or qa_prev is None or qa_last_out is None or qa_prev.data_ptr() != qa_last_out.data_ptr():
+                raise MvqError("decode_latents: qa_slots address the rows of ONE pool buffer handed in as qa_prev and qa_last_out both")
         if na_valid is None:
             audio_conceal = "zero"                                            # every audio token arrived: nothing to conceal
         if na_valid is not None:
@@ -690,7 +697,9 @@ class _ProposedBase(nn.Module):
         key_mask = None
         if audio_conceal == "hold":
             carry = None                                                      # read, then moved on in place, by hold_fill_
-            if qa_last_out is not None:
+            if qa_slots is not None:
+                ops.hold_fill_(qa, na_valid, qa_last_out, slots=qa_slots, slots_dev=qa_slots_dev)
+            elif qa_last_out is not None:
                 carry = qa_last_out
                 if qa_prev is None:
                     carry.zero_()
@@ -698,7 +707,8 @@ class _ProposedBase(nn.Module):
                     carry.copy_(qa_prev)
             elif qa_prev is not None:
                 carry = qa_prev.clone()                                       # qa_prev itself stays as it was handed in
-            ops.hold_fill_(qa, na_valid, carry)
+            if qa_slots is None:
+                ops.hold_fill_(qa, na_valid, carry)
         elif audio_conceal == "mask":
             key_mask = na_valid                                               # nonzero = at least one stage arrived: a key
         z_run = self._rx_two_pass(qa, idx, books_use, nb_valid, z_prev, key_mask=key_mask)
@@ -1151,6 +1161,25 @@ class ProposedEval(_ProposedBase):
         session gets what a stream_sender(batch=1) of its own would return, and the sessions of a tick share batched encodes."""
         from .stream import StreamSenderPool
         return StreamSenderPool(self, packet_tok=packet_tok, slots=slots, books_use=books_use, encoder=encoder)
+
+    def stream_sender_pool_av(self, packet_tok=2, slots=64, books_use=None, rate=None, audio="packets", audio_books=None, audio_rate=None,
+                              fec=None, audio_fec=None, encoder="window"):
+        """stream_sender_pool for the whole link (stream.StreamSenderPoolAV): ``rate``, ``audio`` / ``audio_books`` / ``audio_rate``,
+        ``fec`` / ``audio_fec`` and ``encoder`` mean what they mean on stream_sender, and each session gets what a
+        stream_sender(batch=1) with the same options would return.  ``audio="codes"``: a tactile-only stream with rate= / fec=."""
+        from .stream import StreamSenderPoolAV
+        return StreamSenderPoolAV(self, packet_tok=packet_tok, slots=slots, books_use=books_use, rate=rate, audio=audio,
+                                  audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec, encoder=encoder)
+
+    def stream_receiver_pool_av(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio=None,
+                                fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
+        """stream_receiver_pool for the whole link (stream.StreamReceiverPoolAV): ``audio=(K_a, na)``, ``fec`` / ``audio_fec``,
+        ``audio_conceal`` and ``decoder`` mean what they mean on stream_receiver, and each session gets what a
+        stream_receiver(batch=1) with the same options would return.  ``audio=None``: the audio codes arrive as codes."""
+        from .stream import StreamReceiverPoolAV
+        return StreamReceiverPoolAV(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
+                                    out_rate=out_rate, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,
+                                    decoder=decoder)
 
     @staticmethod
     def _payload(bitstream, payload, k_expected, what):

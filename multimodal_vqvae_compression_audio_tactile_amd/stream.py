@@ -36,6 +36,9 @@ serves receiver sessions that join, run and leave independently: their state lie
 tick batches whichever sessions have a chunk ready, grouped by ``pool_groups``.  ``StreamSenderPool``
 (``ProposedEval.stream_sender_pool``) is the same for sender sessions, which push 1..16 tokens of samples at a time: ``sender_step``
 is a session's host arithmetic, ``sender_pool_groups`` the sessions of a tick that share an encode.
+``StreamSenderPoolAV`` / ``StreamReceiverPoolAV`` (``ProposedEval.stream_sender_pool_av`` / ``stream_receiver_pool_av``) are the two
+pools with every option of the lockstep sessions -- rate control, audio packets, FEC on both streams, audio concealment: the same
+sessions and groups, ``receiver_layout`` the upload of a group, ``_SenderCore._frame_one`` a session's framing.
 """
 from __future__ import annotations
 
@@ -341,6 +344,43 @@ def pool_groups(sessions, orig: int = RS_ORIG, width: int = RS_WIDTH) -> List[Po
     return out
 
 
+class RxLayout(NamedTuple):
+    """Byte offsets of a group's upload (``receiver_layout``); an absent part has offset None.  ``fec`` / ``audio_fec``: (rows, got)."""
+    P: int
+    bodies: int
+    counts: int
+    abodies: object
+    acounts: object
+    fec: object
+    audio_fec: object
+    size: int
+
+
+def receiver_layout(G: int, n: int, full: int, afull, fec, audio_fec, packet_tok: int) -> RxLayout:
+    """The layout of what a receiver step uploads for ``G`` items of ``n`` tokens, as _ReceiverCore._latents reads it (host
+    arithmetic; StreamReceiver._gather with G = batch and StreamReceiverPoolAV.step with G = a group's sessions both build it):
+    the tactile bodies uint8 [G, P, full], their counts [G, P]; with ``afull`` not None (audio packets) the audio bodies
+    [G, P, afull] and their counts [G, P]; then per stream with a Fec -- ``fec`` / ``audio_fec`` = (group g, parity r, width W) as
+    Fec.resolve gives them for the stream, or None -- its parity rows [G, Gr, r*(g + W)], Gr = ceil(P / g), then ``got`` [G, Gr]."""
+    G, n, full, packet_tok = int(G), int(n), int(full), int(packet_tok)
+    P = (n + packet_tok - 1) // packet_tok
+    o = G * P * (full + 1)
+    ab = ac = None
+    if afull is not None:
+        ab, ac = o, o + G * P * int(afull)
+        o += G * P * (int(afull) + 1)
+    at = []
+    for f in (fec, audio_fec):
+        if f is None:
+            at.append(None)
+            continue
+        g, r, W = (int(v) for v in f)
+        nr = G * ((P + g - 1) // g) * r * (g + W)
+        at.append((o, o + nr))
+        o += nr + G * ((P + g - 1) // g)
+    return RxLayout(P, 0, G * P * full, ab, ac, at[0], at[1], o)
+
+
 class SenderStep(NamedTuple):
     """What one ``push`` / ``finish`` of a sender session does: ``emit`` -- whether an encoder window runs; then the window's ``w``
     samples, the ``drop`` samples the buffer loses, the tokens [lo, hi) of the window that are emitted (``finish`` without an
@@ -644,14 +684,16 @@ class _SenderCore:
         from .packets import StreamInfo
         n_tok = hi - lo
         if self.audio_packets:      # uint8 [G, P*full + P + P*afull + P]: tactile bodies, counts, audio bodies, counts: one read-back
-            assert sl is None                                                          # the pools take no audio packets
             if self.enc_state is None:
                 _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
             else:
-                _, codes, zt, za = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, want_za=True)
+                _, codes, zt, za = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, sl, want_za=True)
+            carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
             qa, _, na_sent = self.net.A_QUANT.rate(za, codes, self.audio_rate, self.packet_tok, self.na)
-            _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=self.carry, z_last_out=self.carry, rate=self.rate,
+            _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
                                                          packet_tok=self.packet_tok)
+            if sl is not None and not last:                                            # a session that ends needs no carry
+                ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
             bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
             abodies = ops.idx_pack_packets(codes[:, :self.na], self.K_audio, self.packet_tok, book_dim=1)
             G = bodies.shape[0]
@@ -668,10 +710,11 @@ class _SenderCore:
             qa, codes, zt = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, sl)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
         if self.rate is not None:
-            assert sl is None                                                          # the pools take no rate
             qa = self.net.A_QUANT.from_codes(codes)[0]
             _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
                                                          packet_tok=self.packet_tok)
+            if sl is not None and not last:                                            # a session that ends needs no carry
+                ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
             bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
             parts = [bodies.reshape(bodies.shape[0], -1), nb_sent]
             if self.fec is not None:
@@ -682,11 +725,43 @@ class _SenderCore:
         if sl is not None:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
         if self.fec is not None:
-            assert sl is None                                                          # the pools take no fec
             bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
             rows = ops.fec_parity(bodies, None, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec)
             return torch.cat([bodies.reshape(bodies.shape[0], -1), rows.reshape(bodies.shape[0], -1)], dim=1), codes
         return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
+
+    def _frame_one(self, row, n_tok, chunk):
+        """Host: ONE session's bytes of ``_encode``'s array (bodies, then with a rate the book counts, with audio packets the audio
+        bodies and their counts, then per stream with a Fec its parity rows) -> the headers with the stream's sequence numbers, the
+        session being at chunk ``chunk``: (tactile_packets,) or (tactile_packets, audio_packets), then one parity list per stream
+        that may have a Fec -- (fec_packets,), with audio packets (fec_packets, audio_fec_packets) -- when the session has any."""
+        import numpy as np
+        from .packets import StreamInfo, frame, frame_fec
+        info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
+        row = np.asarray(row, np.uint8).reshape(-1)
+        base = chunk * CHUNK_TOK // self.packet_tok
+
+        def parity(f, inf, rows):                                                      # the stream's group numbers
+            return [] if f is None else frame_fec(rows, inf, f, seq_base=chunk * (CHUNK_TOK // self.packet_tok // f.group))
+
+        def rows_bytes(f, inf):
+            if f is None:
+                return 0
+            g, _, G, W = f.resolve(inf)
+            return G * f.r * (g + W)                                                   # r parity rows per group
+
+        if self.audio_packets:
+            ainfo = StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok)
+            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P, rows_bytes(self.fec, info),
+                              rows_bytes(self.audio_fec, ainfo)])
+            hb, hc, ab, ac, hf, af = (row[cuts[i]:cuts[i + 1]] for i in range(6))
+            out = (frame(hb, info, nb_sent=hc, seq_base=base), frame(ab, ainfo, nb_sent=ac, seq_base=base))
+            if self.fec is None and self.audio_fec is None:
+                return out
+            return out + (parity(self.fec, info, hf), parity(self.audio_fec, ainfo, af))
+        cut, n_cnt = info.P * self.full, 0 if self.rate is None else info.P            # bodies, (counts,) parity rows
+        out = (frame(row[:cut], info, nb_sent=row[cut:cut + n_cnt] if n_cnt else None, seq_base=base),)
+        return out if self.fec is None else out + (parity(self.fec, info, row[cut + n_cnt:]),)
 
 
 class StreamSender(_SenderCore):
@@ -774,44 +849,13 @@ class StreamSender(_SenderCore):
         return x
 
     def _framed(self, bodies, codes, n_tok):
-        """ONE device-to-host copy of the bodies, then the headers with the stream's sequence numbers."""
-        from .packets import StreamInfo, frame, frame_fec
-        info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
-        host = bodies.cpu().numpy()
-        base = self.chunk * CHUNK_TOK // self.packet_tok
-        B = self.batch
-
-        def parity(f, inf, rows):                                                      # the stream's group numbers
-            if f is None:
-                return [[] for _ in range(B)]
-            return [frame_fec(rows[b], inf, f, seq_base=self.chunk * (CHUNK_TOK // self.packet_tok // f.group)) for b in range(B)]
-
-        def rows_bytes(f, inf):
-            if f is None:
-                return 0
-            g, _, G, W = f.resolve(inf)
-            return G * f.r * (g + W)                                                   # r parity rows per group
-
+        """ONE device-to-host copy of the bodies, then the headers with the stream's sequence numbers (_SenderCore._frame_one per
+        item, every item at the session's chunk)."""
+        host = bodies.cpu().numpy().reshape(self.batch, -1)
+        cols = [list(c) for c in zip(*(self._frame_one(host[b], n_tok, self.chunk) for b in range(self.batch)))]
         if self.audio_packets:
-            import numpy as np
-            ainfo = StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok)
-            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P, rows_bytes(self.fec, info),
-                              rows_bytes(self.audio_fec, ainfo)])
-            hb, hc, ab, ac, hf, af = (host[:, cuts[i]:cuts[i + 1]] for i in range(6))
-            out = ([frame(hb[b], info, nb_sent=hc[b], seq_base=base) for b in range(B)],
-                   [frame(ab[b], ainfo, nb_sent=ac[b], seq_base=base) for b in range(B)])
-            if self.fec is None and self.audio_fec is None:
-                return out
-            return out + (parity(self.fec, info, hf), parity(self.audio_fec, ainfo, af))
-        if self.fec is not None:                                                       # bodies, (counts,) parity rows
-            host = host.reshape(B, -1)
-            cut, n_cnt = info.P * self.full, 0 if self.rate is None else info.P
-            return ([frame(host[b, :cut], info, nb_sent=host[b, cut:cut + n_cnt] if n_cnt else None, seq_base=base) for b in range(B)],
-                    codes, parity(self.fec, info, host[:, cut + n_cnt:]))
-        if self.rate is None:
-            return [frame(host[b], info, seq_base=base) for b in range(self.batch)], codes
-        cut = host.shape[1] - info.P                                                   # bodies, then the book count of each packet
-        return [frame(host[b, :cut], info, nb_sent=host[b, cut:], seq_base=base) for b in range(self.batch)], codes
+            return tuple(cols)
+        return (cols[0], codes) + tuple(cols[1:])
 
     def _nothing(self):
         import torch
@@ -937,35 +981,35 @@ class _ReceiverCore:
     pool session computes what a solo one does."""
 
     def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None,
-                 audio_conceal="zero", decoder="window"):
+                 audio_conceal="zero", decoder="window", who="StreamReceiver"):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check, body_bytes
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
         if decoder not in ("window", "stateful"):
-            raise ValueError(f"StreamReceiver: decoder must be 'window' or 'stateful', not {decoder!r}")
+            raise ValueError(f"{who}: decoder must be 'window' or 'stateful', not {decoder!r}")
         self.decoder = decoder
         if decoder == "stateful":
-            _f32_only("StreamReceiver(decoder='stateful')")
+            _f32_only(f"{who}(decoder='stateful')")
             if tuple(net.T_DEC._desc[2]) != DEC_RATES or net.T_DEC._desc[4]:
-                raise ValueError(f"StreamReceiver: decoder rates {tuple(net.T_DEC._desc[2])}; the stage plan is written for {DEC_RATES} "
+                raise ValueError(f"{who}: decoder rates {tuple(net.T_DEC._desc[2])}; the stage plan is written for {DEC_RATES} "
                                  "without output_padding")
         if audio_conceal not in ("zero", "mask", "hold"):
-            raise ValueError(f"StreamReceiver: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
+            raise ValueError(f"{who}: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
         if audio_conceal != "zero" and audio is None:
-            raise ValueError("StreamReceiver: audio_conceal goes with audio=(K_a, na)")
+            raise ValueError(f"{who}: audio_conceal goes with audio=(K_a, na)")
         self.audio_conceal = audio_conceal
         if audio_fec is not None and audio is None:
-            raise ValueError("StreamReceiver: audio_fec goes with audio=(K_a, na)")
+            raise ValueError(f"{who}: audio_fec goes with audio=(K_a, na)")
         if fec is not None:
             net._fec_resolve(fec, K, nb, packet_tok)
         self.fec, self.audio_fec = fec, audio_fec
         self.audio = None                                                              # (K_a, na): the audio codes arrive as packets
         if audio is not None:
-            _f32_only("StreamReceiver")
+            _f32_only(who)
             K_a, na = (int(v) for v in audio)
             if K_a != net.A_QUANT.codebook_size or not 1 <= na <= net.A_QUANT.n_codebooks:
-                raise ValueError(f"StreamReceiver: the audio stream has K = {K_a}, nb = {na}; the model's audio quantiser has "
+                raise ValueError(f"{who}: the audio stream has K = {K_a}, nb = {na}; the model's audio quantiser has "
                                  f"K = {net.A_QUANT.codebook_size} and {net.A_QUANT.n_codebooks} stages")
             _check(StreamInfo(K_a, na, CHUNK_TOK, packet_tok))
             self.audio, self.afull = (K_a, na), body_bytes(packet_tok, na, K_a)
@@ -1000,7 +1044,7 @@ class _ReceiverCore:
             who, want = "StreamReceiver", f"[B={self.carry.shape[0]}, n_codebooks, tokens]"
             shape_ok = codes.dim() == 3 and codes.shape[0] == self.carry.shape[0]
         else:
-            who, want = f"StreamReceiverPool: session {sid}", "[n_codebooks, tokens] or [1, n_codebooks, tokens]"
+            who, want = f"{self._who}: session {sid}", "[n_codebooks, tokens] or [1, n_codebooks, tokens]"
             if codes.dim() == 3 and codes.shape[0] == 1:
                 codes = codes[0]
             shape_ok = codes.dim() == 2
@@ -1013,6 +1057,19 @@ class _ReceiverCore:
             raise ValueError(f"{who}: {codes.shape[-1]} audio tokens for a chunk of {want} tokens")
         return codes
 
+    def _layout(self, G, n):
+        """receiver_layout of ``G`` items of ``n`` tokens for this session's streams."""
+        from .packets import StreamInfo
+
+        def code(f, K, nb):
+            if f is None:
+                return None
+            g, _, _, W = f.resolve(StreamInfo(K, nb, n, self.packet_tok))
+            return g, f.r, W
+
+        return receiver_layout(G, n, self.full, self.afull if self.audio is not None else None, code(self.fec, self.K, self.nb),
+                               code(self.audio_fec, *self.audio) if self.audio_fec is not None else None, self.packet_tok)
+
     # ------------------------------------------------------------------------------------------------ the device sequence
     def _latents(self, up, codes, n, sl=None, last=False):
         """Device: upload (the G*P packet bodies, then their G*P counts) and codes [G, 32, n] -> indices -> latents [G, C, n].  The carried
@@ -1020,7 +1077,7 @@ class _ReceiverCore:
         next open() resets the slot)."""
         from . import ops
         from .packets import StreamInfo
-        G, full = (self.carry.shape[0] if codes is None else codes.shape[0]), self.full
+        G, full = (self.carry.shape[0] if codes is None else codes.shape[0]) if sl is None else len(sl[0]), self.full
         P = (n + self.packet_tok - 1) // self.packet_tok
         ub, ur = up[:G * P * full].view(G, P, full), up[G * P * full:G * P * (full + 1)].view(G, P)
         o_fec = G * P * (full + 1) + (G * P * (self.afull + 1) if self.audio is not None else 0)   # the parity rows, flags: behind everything
@@ -1029,7 +1086,6 @@ class _ReceiverCore:
             if f is None:
                 return o
             g, _, Gr, W = f.resolve(inf)
-            assert sl is None                                 # the pools take no fec
             nr = G * Gr * f.r * (g + W)                       # r parity rows per group; ``got`` is then a bitmask
             ops.fec_recover(bodies, counts, up[o:o + nr].view(G, *f.rows_shape(inf)), up[o + nr:o + nr + G * Gr].view(G, Gr), inf, f)
             return o + nr + G * Gr
@@ -1038,7 +1094,7 @@ class _ReceiverCore:
         idx, nbv = ops.idx_unpack_packets(ub, ur, self.K, self.nb, n, self.packet_tok)
         nav = None
         if self.audio is not None:                            # behind the tactile arrays: the audio bodies, then their counts
-            assert sl is None and codes is None
+            assert codes is None
             o, afull = G * P * (full + 1), self.afull
             uab, uar = up[o:o + G * P * afull].view(G, P, afull), up[o + G * P * afull:o + G * P * (afull + 1)].view(G, P)
             recover(self.audio_fec, StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), uab, uar, o_fec)
@@ -1050,7 +1106,8 @@ class _ReceiverCore:
             z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav)
         else:                                                 # "mask" is stateless per chunk; "hold" moves qa_carry on in place
             z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav,
-                                        audio_conceal=self.audio_conceal, qa_prev=self.qa_carry, qa_last_out=self.qa_carry)
+                                        audio_conceal=self.audio_conceal, qa_prev=self.qa_carry, qa_last_out=self.qa_carry,
+                                        **({} if sl is None or self.qa_carry is None else {"qa_slots": sl[0], "qa_slots_dev": sl[1]}))
         if sl is not None and not last:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
         if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
@@ -1163,37 +1220,32 @@ class StreamReceiver(_ReceiverCore):
 
     # ------------------------------------------------------------------------------------------------------------ stages
     def _gather(self, tactile_packets, n, audio_packets=None, fec_packets=None, audio_fec_packets=None):
-        """Host: per item whatever packets of this chunk arrived -> one uint8 array, bodies then counts (then, with audio
-        packets, the audio bodies and their counts; then, with a Fec, per stream the parity rows and their ``got`` flags)."""
+        """Host: per item whatever packets of this chunk arrived -> one uint8 array laid out by ``receiver_layout``: bodies then
+        counts (then, with audio packets, the audio bodies and their counts; then, with a Fec, per stream the parity rows and their
+        ``got`` flags)."""
         import numpy as np
         from .packets import StreamInfo, gather, gather_fec
         info = StreamInfo(self.K, self.nb, n, self.packet_tok)
-        B, P, full = self.batch, info.P, self.full
-        afull = self.afull if self.audio is not None else 0
-        n_audio = B * P * (afull + 1) if self.audio is not None else 0        # the audio bodies and their counts
-        par = []                                                              # (fec, info, the item's parity packets, offset)
-        n_fec = 0
-        for f, inf, pk in ((self.fec, info, fec_packets),
-                           (self.audio_fec, StreamInfo(*self.audio, n, self.packet_tok) if self.audio is not None else None, audio_fec_packets)):
-            if f is not None:
-                g, _, Gr, W = f.resolve(inf)
-                par.append((f, inf, [[] for _ in range(B)] if pk is None else self._packets_ok(pk), B * P * (full + 1) + n_audio + n_fec,
-                            g, Gr, f.r * (g + W)))
-                n_fec += B * Gr * (f.r * (g + W) + 1)
-        host = np.empty(B * P * (full + 1) + n_audio + n_fec, np.uint8)
-        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
+        ainfo = StreamInfo(*self.audio, n, self.packet_tok) if self.audio is not None else None
+        B, lay = self.batch, self._layout(self.batch, n)
+        P, full = lay.P, self.full
+        par = [(f, inf, [[] for _ in range(B)] if pk is None else self._packets_ok(pk), at)       # before anything is gathered
+               for f, inf, pk, at in ((self.fec, info, fec_packets, lay.fec), (self.audio_fec, ainfo, audio_fec_packets, lay.audio_fec))
+               if f is not None]
+        host = np.empty(lay.size, np.uint8)
+        hb, hr = host[lay.bodies:lay.counts].reshape(B, P, full), host[lay.counts:lay.counts + B * P].reshape(B, P)
         base, late = self.tokens // self.packet_tok, []
         for b in range(B):
             hb[b], hr[b] = gather(tactile_packets[b], info, seq_base=base, late=late)
         if self.audio is not None:
-            ainfo, o = StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), B * P * (full + 1)
-            ab, ar = host[o:o + B * P * afull].reshape(B, P, afull), host[o + B * P * afull:o + B * P * (afull + 1)].reshape(B, P)
+            ab, ar = host[lay.abodies:lay.acounts].reshape(B, P, self.afull), host[lay.acounts:lay.acounts + B * P].reshape(B, P)
             for b in range(B):
                 ab[b], ar[b] = gather(audio_packets[b], ainfo, seq_base=base, late=late)
-        for f, inf, pk, o, g, Gr, rw in par:                                  # rw: the bytes of a group's r parity rows
-            fr, fg = host[o:o + B * Gr * rw].reshape(B, *f.rows_shape(inf)), host[o + B * Gr * rw:o + B * Gr * (rw + 1)].reshape(B, Gr)
+        for f, inf, pk, (o_rows, o_got) in par:
+            fr = host[o_rows:o_got].reshape(B, *f.rows_shape(inf))
+            fg = host[o_got:o_got + B * fr.shape[1]].reshape(B, fr.shape[1])
             for b in range(B):                                                # the chunk's first group, in the stream's numbers
-                fr[b], fg[b] = gather_fec(pk[b], inf, f, seq_base=base // g, late=late)
+                fr[b], fg[b] = gather_fec(pk[b], inf, f, seq_base=base // int(f.group), late=late)
         self.late += len(late)
         return host
 
@@ -1333,6 +1385,8 @@ class StreamReceiverPool(_ReceiverCore):
     ``decoder="stateful"``: as for StreamReceiver -- dec_state [S, floats] replaces hist, and a group's decode is
     T_DEC.forward_stream on the group's slots.  ``open`` leaves a slot's dec_state as it is: a new session reads no tail."""
 
+    _who = "StreamReceiverPool"
+
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
                  decoder="window"):
         if audio_conceal is not None:
@@ -1364,7 +1418,7 @@ class StreamReceiverPool(_ReceiverCore):
         try:
             return self._sess[sid]
         except (KeyError, TypeError):
-            raise MvqError(f"StreamReceiverPool: {what}: no open session {sid!r} (never opened, finished or closed)") from None
+            raise MvqError(f"{self._who}: {what}: no open session {sid!r} (never opened, finished or closed)") from None
 
     def tokens(self, sid):
         """Tokens session ``sid`` has received."""
@@ -1379,9 +1433,11 @@ class StreamReceiverPool(_ReceiverCore):
         resampler state to zero on the device, the history count (the session's tokens) to zero."""
         from ._lib import MvqError
         if not self._free:
-            raise MvqError(f"StreamReceiverPool: all {self.slots} slots hold a session")
+            raise MvqError(f"{self._who}: all {self.slots} slots hold a session")
         slot = self._free.pop(0)
         self.carry[slot].zero_()
+        if self.qa_carry is not None:                                                  # StreamReceiverPoolAV(audio_conceal="hold")
+            self.qa_carry[slot].zero_()
         if self.rs_state is not None:
             self.rs_state[slot].zero_()
         sid, self._next_sid = self._next_sid, self._next_sid + 1
@@ -1510,6 +1566,8 @@ class StreamSenderPool(_SenderCore):
     A_ENC / T_ENC.forward_stream on the group's slots, fed the members' un-encoded samples (``sender_pool_groups(stateful=True)``
     groups by what the stage plan depends on).  ``open`` leaves a slot's enc_state as it is: a new session reads no tail."""
 
+    _who = "StreamSenderPool"
+
     def __init__(self, net, packet_tok=2, slots=64, books_use=None, encoder="window"):
         packet_tok, slots = int(packet_tok), int(slots)
         super().__init__("StreamSenderPool", net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), encoder=encoder)
@@ -1535,7 +1593,7 @@ class StreamSenderPool(_SenderCore):
         try:
             return self._sess[sid]
         except (KeyError, TypeError):
-            raise MvqError(f"StreamSenderPool: {what}: no open session {sid!r} (never opened, finished or closed)") from None
+            raise MvqError(f"{self._who}: {what}: no open session {sid!r} (never opened, finished or closed)") from None
 
     def tokens(self, sid):
         """Tokens of samples session ``sid`` has received."""
@@ -1547,7 +1605,7 @@ class StreamSenderPool(_SenderCore):
         device, the fill to zero on the host (which makes whatever the slot's buffer rows hold irrelevant)."""
         from ._lib import MvqError
         if not self._free:
-            raise MvqError(f"StreamSenderPool: all {self.slots} slots hold a session")
+            raise MvqError(f"{self._who}: all {self.slots} slots hold a session")
         slot = self._free.pop(0)
         self.carry[slot].zero_()
         sid, self._next_sid = self._next_sid, self._next_sid + 1
@@ -1568,22 +1626,36 @@ class StreamSenderPool(_SenderCore):
         work = {}
         for sid in pushes:
             if sid in finishes:
-                raise ValueError(f"StreamSenderPool: session {sid!r} is both pushed and finished in one tick")
+                raise ValueError(f"{self._who}: session {sid!r} is both pushed and finished in one tick")
         for last, items in ((False, pushes), (True, finishes)):
             for sid, item in items.items():
                 fill = self._get(sid, "finish" if last else "push")[1]
                 if item is None:
                     if not last:
-                        raise ValueError(f"StreamSenderPool: session {sid}: a push needs its samples (a, t)")
+                        raise ValueError(f"{self._who}: session {sid}: a push needs its samples (a, t)")
                     work[sid] = (None, None, 0, True)
                     continue
                 try:
                     a, t = item
                 except (TypeError, ValueError):
-                    raise ValueError(f"StreamSenderPool: session {sid}: the samples (a, t) of both modalities expected") from None
-                a, t, n = _sender_samples(f"StreamSenderPool: session {sid}", "finish" if last else "push", a, t, 1, fill, tail=last)
+                    raise ValueError(f"{self._who}: session {sid}: the samples (a, t) of both modalities expected") from None
+                a, t, n = _sender_samples(f"{self._who}: session {sid}", "finish" if last else "push", a, t, 1, fill, tail=last)
                 work[sid] = (a, t, n, last)
         return work
+
+    def _frame(self, row, n_tok, chunk, codes):
+        """Host: one session's bytes of the tick's read-back -> what its push returns, the session being at chunk ``chunk``."""
+        from .packets import StreamInfo, frame
+        return frame(row, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), seq_base=chunk * CHUNK_TOK // self.packet_tok), codes
+
+    def _nothing(self):
+        """What a push that completes no chunk returns."""
+        import torch
+        return [], torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
+
+    def _infos(self, T):
+        from .packets import StreamInfo
+        return (StreamInfo(self.K, self.nb, T, self.packet_tok),)
 
     def step(self, pushes, finishes=None):
         """One tick.  ``pushes``: {sid: (a, t)}, the next samples [1, 1, 320*m] of both modalities, 1 <= m <= 16, m per session;
@@ -1597,9 +1669,8 @@ class StreamSenderPool(_SenderCore):
         import numpy as np
         import torch
         from . import ops
-        from .packets import StreamInfo, frame
         pushes, finishes = dict(pushes or {}), dict(finishes or {})
-        _f32_only("StreamSenderPool")
+        _f32_only(self._who)
         work = self._inputs(pushes, finishes)
         if not work:
             return {}
@@ -1610,16 +1681,15 @@ class StreamSenderPool(_SenderCore):
             if sid not in steps:
                 steps[sid] = self._step(*self._sess[sid][1:], w[2], w[3])
         if stateful and any(g.w > ENC_STREAM_MAX_N for g in groups):
-            raise ValueError(f"StreamSenderPool: encoder='stateful' takes at most {ENC_STREAM_MAX_N} samples in one step")
+            raise ValueError(f"{self._who}: encoder='stateful' takes at most {ENC_STREAM_MAX_N} samples in one step")
         cap = self.buf.shape[2]
         # ONE host array: the descriptor tables of all groups (int32 [5] per session), then their slot lists
         tables = [ops.stream_samples_desc([(self._sess[sid][0], self._sess[sid][1], work[sid][2], st.drop)
-                                           for sid, st in zip(g.sids, g.steps)], g.w, cap, "StreamSenderPool") for g in groups]
+                                           for sid, st in zip(g.sids, g.steps)], g.w, cap, self._who) for g in groups]
         n_sess = sum(len(g.sids) for g in groups)
         host = np.asarray([r for rows, _ in tables for r in rows], np.int32).reshape(n_sess, 5)
         host = np.concatenate([host.reshape(-1), host[:, 0]])
         pieces = [x.reshape(-1) for g in groups for sid in g.sids if work[sid][2] for x in work[sid][:2]]
-        empty = torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
         out, bodies_all, framing = {}, [], []
         with torch.no_grad():
             if groups:
@@ -1648,16 +1718,228 @@ class StreamSenderPool(_SenderCore):
             if bodies_all:                                                # ONE device-to-host copy of the tick's packet bodies
                 host_b = (bodies_all[0] if len(bodies_all) == 1 else torch.cat(bodies_all)).cpu().numpy()
         for sid, at, per, n_tok, codes in framing:
-            base = self._sess[sid][3] * CHUNK_TOK // self.packet_tok
-            out[sid] = (frame(host_b[at:at + per], StreamInfo(self.K, self.nb, n_tok, self.packet_tok), seq_base=base), codes)
+            out[sid] = self._frame(host_b[at:at + per], n_tok, self._sess[sid][3], codes)
+        nothing = None
         for sid, w in work.items():
             st = steps[sid]
             if sid not in out:
-                out[sid] = ([], empty)
-            if w[3]:
-                out[sid] += (StreamInfo(self.K, self.nb, self._sess[sid][2] + max(st.hi, 0), self.packet_tok),)
+                nothing = self._nothing() if nothing is None else nothing
+                out[sid] = tuple([] if isinstance(v, list) else v for v in nothing)    # the empty codes tensor is shared
+            if w[3]:                                                      # the StreamInfo(s) behind the two data elements
+                out[sid] = tuple(out[sid][:2]) + self._infos(self._sess[sid][2] + max(st.hi, 0)) + tuple(out[sid][2:])
                 self.close(sid)
             else:
                 self._sess[sid][1:] = [st.fill, st.start, st.chunk]
         self.last_groups = tuple(groups)
         return out
+
+
+class PoolChunk(NamedTuple):
+    """What StreamReceiverPoolAV.step takes for one session of a tick: the chunk's tactile packets that arrived, its ``audio`` --
+    the audio packets that arrived for a pool opened with audio=(K_a, na), else the audio codes int [32, n] -- then, for a pool
+    opened with fec= / audio_fec=, the parity packets of each stream that arrived (None: none did); ``tokens`` (1..15) belongs to
+    a finish whose audio travels as packets, as StreamReceiver.finish(tokens=).  A plain tuple of the first 2..5 values does too."""
+    tactile_packets: object
+    audio: object
+    fec_packets: object = None
+    audio_fec_packets: object = None
+    tokens: object = None
+
+
+class StreamReceiverPoolAV(StreamReceiverPool):
+    """StreamReceiverPool for the whole link: the options of StreamReceiver -- ``audio=(K_a, na)`` (the audio
+    codes arrive as layered packets), ``fec`` / ``audio_fec``, ``audio_conceal``, beside ``conceal``, ``out_rate`` and ``decoder`` --
+    with the same meaning and the same refusals.  Sessions are StreamReceiverPool's (open / close / active / free / tokens / late).
+    Every session gets from ``step`` exactly what a ``StreamReceiver(batch=1)`` with the same options, fed the same data, returns
+    from ``push`` / ``finish``, bit for bit.
+
+    A tick is StreamReceiverPool's with a wider upload: per group of G sessions (``pool_groups``, unchanged) ONE segment laid out by
+    ``receiver_layout`` -- tactile bodies, counts, audio bodies, counts, per stream the parity rows and their ``got`` flags -- filled
+    session by session (packets.gather / gather_fec against ITS token count); ONE upload of the slot lists and all segments (and
+    ONE of the audio codes, for audio=None only); then per group _ReceiverCore's sequence on the group's slots: ops.fec_recover in
+    place, both unpacks, the carried token through ops.stream_rows, decode_latents -- "hold" addresses the held audio token qa_carry
+    [S, C] through the slot list (ops.hold_fill_(slots=)) -- and the decode.  Nothing is read back.  ``open`` resets the slot's
+    carried token, held audio token and resampler state."""
+
+    _who = "StreamReceiverPoolAV"
+
+    def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio=None, fec=None,
+                 audio_fec=None, audio_conceal="zero", decoder="window"):
+        K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
+        _receiver_args(self._who, net, K, nb, packet_tok, conceal, out_rate)
+        if slots < 1:
+            raise ValueError(f"{self._who}: slots must be at least 1")
+        _f32_only(self._who)
+        _ReceiverCore.__init__(self, net, K, nb, packet_tok, slots, books_use, conceal, out_rate, audio=audio, fec=fec,
+                               audio_fec=audio_fec, audio_conceal=audio_conceal, decoder=decoder, who=self._who)
+        self.slots = slots
+        self._free = list(range(slots))                                                # ascending: open() takes the lowest
+        self._sess = {}                                                                # sid -> [slot, tokens, late]
+        self._next_sid = 0
+
+    def _inputs(self, pushes, finishes):
+        """Host: every session's input of this tick, checked and gathered; raises before anything has changed.
+        -> {sid: (n, last, parts, codes [32, n] or None, late packets)}; ``parts``: the session's arrays in the order of
+        ``receiver_layout`` -- (bodies, counts[, audio bodies, audio counts][, rows, got per stream with a Fec]) -- or None."""
+        from .packets import StreamInfo, gather, gather_fec
+        who, work = self._who, {}
+        for sid in pushes:
+            if sid in finishes:
+                raise ValueError(f"{who}: session {sid!r} is both pushed and finished in one tick")
+        audio_what = "audio_packets" if self.audio is not None else "audio_codes"
+        for last, items in ((False, pushes), (True, finishes)):
+            for sid, item in items.items():
+                tokens = self._get(sid, "finish" if last else "push")[1]
+                if item is None:
+                    if not last:
+                        raise ValueError(f"{who}: session {sid}: a push needs (packets, {audio_what})")
+                    work[sid] = (0, True, None, None, 0)
+                    continue
+                try:
+                    item = PoolChunk(*item)
+                except TypeError:
+                    raise ValueError(f"{who}: session {sid}: (packets, {audio_what}[, fec_packets, audio_fec_packets[, tokens]]) "
+                                     "expected") from None
+                if item.tactile_packets is None or item.audio is None:
+                    raise ValueError(f"{who}: session {sid}: a chunk needs both its packets and its {audio_what}")
+                if (item.fec_packets is not None and self.fec is None) or (item.audio_fec_packets is not None and self.audio_fec is None):
+                    raise ValueError(f"{who}: session {sid}: fec_packets / audio_fec_packets need a pool opened with fec= / audio_fec=")
+                codes = None
+                if self.audio is not None:
+                    if not last:
+                        if item.tokens is not None:
+                            raise ValueError(f"{who}: session {sid}: tokens= belongs to a finish; a push is a {CHUNK_TOK}-token chunk")
+                        n = CHUNK_TOK
+                    elif item.tokens is None or not 1 <= int(item.tokens) <= CHUNK_TOK - 1:
+                        raise ValueError(f"{who}: session {sid}: tokens = {item.tokens!r}; a last chunk of audio packets has "
+                                         f"1..{CHUNK_TOK - 1} tokens")
+                    else:
+                        n = int(item.tokens)
+                else:
+                    if item.tokens is not None:
+                        raise ValueError(f"{who}: session {sid}: tokens= counts a last chunk of audio PACKETS (a pool with "
+                                         "audio=(K_a, na)); audio codes carry their own length")
+                    codes = self._codes(item.audio, 1, CHUNK_TOK - 1, sid) if last else self._codes(item.audio, CHUNK_TOK, CHUNK_TOK, sid)
+                    n = int(codes.shape[1])
+                base, late = tokens // self.packet_tok, []
+                info = StreamInfo(self.K, self.nb, n, self.packet_tok)
+                parts = list(gather(item.tactile_packets, info, seq_base=base, late=late))
+                ainfo = None
+                if self.audio is not None:
+                    ainfo = StreamInfo(*self.audio, n, self.packet_tok)
+                    parts += gather(item.audio, ainfo, seq_base=base, late=late)
+                for f, inf, pk in ((self.fec, info, item.fec_packets), (self.audio_fec, ainfo, item.audio_fec_packets)):
+                    if f is not None:                                        # the chunk's first group, in the stream's numbers
+                        parts += gather_fec([] if pk is None else pk, inf, f, seq_base=base // int(f.group), late=late)
+                work[sid] = (n, last, parts, codes, len(late))
+        return work
+
+    def step(self, pushes, finishes=None):
+        """One tick.  ``pushes``: {sid: PoolChunk or (packets, audio[, fec_packets[, audio_fec_packets]])} -- ``audio`` the chunk's
+        audio packets (a pool with audio=(K_a, na)) or its audio codes int [32, 16] / [1, 32, 16]; ``finishes``: {sid: the same for
+        a last chunk of 1..15 tokens -- with audio packets PoolChunk(..., tokens=n) -- or None} for the sessions that end with this
+        tick.  -> {sid: y [1, 1, n_emit]}: per session what StreamReceiver(batch=1, the pool's options).push / .finish returns.
+        A finished session's slot is freed.  ValueError / MvqError for any one session (a packet of a later chunk, parity packets
+        without the matching fec=, a missing tokens=, a wrong code shape, an unknown sid, a sid in both maps) comes before the first
+        device call and leaves every session as it was."""
+        import numpy as np
+        import torch
+        pushes, finishes = dict(pushes or {}), dict(finishes or {})
+        _f32_only(self._who)
+        work = self._inputs(pushes, finishes)
+        if not work:
+            return {}
+        groups = pool_groups((sid, self._sess[sid][1], w[0], w[1]) for sid, w in work.items())
+        # ONE host array: the slot lists of all groups (int32, first: aligned), then per group its segment (receiver_layout)
+        n_sess = sum(len(g.sids) for g in groups)
+        size, where = 4 * n_sess, []
+        for g in groups:
+            lay = self._layout(len(g.sids), g.key[1]) if g.key[1] else None
+            where.append((size, lay))
+            size += lay.size if lay is not None else 0
+        host = np.empty(size, np.uint8)
+        slot_lists = [[self._sess[sid][0] for sid in g.sids] for g in groups]
+        host[:4 * n_sess] = np.asarray([s for sl in slot_lists for s in sl], np.int32).view(np.uint8)
+        flat_codes = []
+        for g, (o, lay) in zip(groups, where):
+            if lay is None:
+                continue
+            G = len(g.sids)
+            starts = [lay.bodies, lay.counts] + ([lay.abodies, lay.acounts] if lay.abodies is not None else []) + \
+                [v for at in (lay.fec, lay.audio_fec) if at is not None for v in at]
+            for i, sid in enumerate(g.sids):                             # every part is [G, bytes of one session]
+                for at, end, part in zip(starts, starts[1:] + [lay.size], work[sid][2]):
+                    per = (end - at) // G
+                    host[o + at + i * per:o + at + (i + 1) * per] = np.asarray(part, np.uint8).reshape(-1)
+                if self.audio is None:
+                    flat_codes.append(work[sid][3].reshape(-1))
+        out = {}
+        with torch.no_grad():
+            up = torch.from_numpy(host).to(self.dev)
+            if flat_codes:
+                if any(c.is_cuda for c in flat_codes):
+                    codes_all = torch.cat([c.to(self.dev, torch.int64) for c in flat_codes])
+                else:
+                    codes_all = torch.cat([c.to(torch.int64) for c in flat_codes]).to(self.dev)
+            slots_all = up[:4 * n_sess].view(torch.int32)
+            s0 = c0 = 0
+            for g, slots, (o, lay) in zip(groups, slot_lists, where):
+                G, (_, n, last) = len(g.sids), g.key
+                sl = (slots, slots_all[s0:s0 + G])
+                codes = None
+                if n and self.audio is None:
+                    codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n)
+                    c0 += G * self.n_audio_books * n
+                seg = up[o:o + lay.size] if lay is not None else None
+                y = self._decimate(self._device_step(seg, codes, n, *g.plan, sl=sl, last=last), g.consumed, last, sl)
+                s0 += G
+                for i, sid in enumerate(g.sids):
+                    out[sid] = y[i:i + 1]
+        for sid, w in work.items():
+            if w[1]:
+                self.close(sid)
+            else:
+                self._sess[sid][1] += w[0]
+                self._sess[sid][2] += w[4]
+        return out
+
+
+class StreamSenderPoolAV(StreamSenderPool):
+    """StreamSenderPool for the whole link: the options of StreamSender -- ``rate``, ``audio="packets"`` with
+    ``audio_books`` / ``audio_rate``, ``fec`` / ``audio_fec``, ``encoder`` -- with the same meaning and the same refusals.  Sessions
+    are StreamSenderPool's (open / close / active / free / tokens).  Every session gets from ``step`` exactly what a
+    ``StreamSender(batch=1)`` with the same options, fed the same samples, returns from ``push`` / ``finish``, byte for byte: the
+    one item's values (a list of packets where the lockstep sender returns a list of one list).
+
+    A tick is StreamSenderPool's -- ``sender_pool_groups`` is unchanged, the options do not enter the launch parameters -- with
+    _SenderCore._encode's wider array per group (bodies, book counts, audio bodies and counts, parity rows), still ONE
+    device-to-host copy of all groups' arrays, and _SenderCore._frame_one per session with ITS chunk number."""
+
+    _who = "StreamSenderPoolAV"
+
+    def __init__(self, net, packet_tok=2, slots=64, books_use=None, rate=None, audio="packets", audio_books=None, audio_rate=None,
+                 fec=None, audio_fec=None, encoder="window"):
+        packet_tok, slots = int(packet_tok), int(slots)
+        _SenderCore.__init__(self, self._who, net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), rate=rate, audio=audio,
+                             audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec, encoder=encoder)
+        self.slots = slots
+        self._free = list(range(slots))                                                # ascending: open() takes the lowest
+        self._sess = {}                                                                # sid -> [slot, fill, start, chunk]
+        self._next_sid = 0
+        self.last_groups = ()                                                          # the SenderGroups of the last tick
+
+    def _nothing(self):
+        """What a push that completes no chunk returns (StreamSender._nothing for the one item)."""
+        import torch
+        if self.audio_packets:
+            return ([], []) + (([], []) if self.fec is not None or self.audio_fec is not None else ())
+        return ([], torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)) + (([],) if self.fec is not None else ())
+
+    def _frame(self, row, n_tok, chunk, codes):
+        framed = self._frame_one(row, n_tok, chunk)
+        return framed if self.audio_packets else (framed[0], codes) + framed[1:]
+
+    def _infos(self, T):
+        from .packets import StreamInfo
+        info = (StreamInfo(self.K, self.nb, T, self.packet_tok),)
+        return info + (StreamInfo(self.K_audio, self.na, T, self.packet_tok),) if self.audio_packets else info

@@ -20,12 +20,18 @@ x K = 512, packets of 2 tokens), all in this one process,
                        append launches per chunk that a solo session fed token by token also pays); round_over_solo = (c) / (S * (e)).
   (f) --encoder stateful   the pool (and (d), (e)) with encoder="stateful" (DESIGN.md section 24); "both": the rows of both modes
                        in this one process, each row tagged "encoder".
+  (g) --link av        the same rows on StreamSenderPoolAV: both streams rate-controlled, the audio codes in
+                       layered packets, with --fec also Fec(4, 3) on the tactile and Fec(8, 4, 2) on the audio stream; (d) and (e)
+                       are StreamSender with the same options.  Each row also carries "plain_round_ms", the plain pool's round in
+                       the same run, and "host_ms" / "frame_ms": the host time of a round's 16 step calls (time.perf_counter; it
+                       includes the wait for the tick's one read-back) and the part of it spent framing packets.
 The two ratios are reported, not gated.  The samples of every call are HOST tensors, as they arrive, in all three.  Timing:
 torch.cuda events around each call (they bracket the host work too) after --warmup rounds in the steady state; --repeats rounds
 are timed, (d) and (e) as many calls.  Every timed call encodes real next samples of sessions that keep running (a 1-s signal per
 session, repeated).  Seeded synthetic weights and signals: only the times mean anything.
 
   python tools/stream_send_pool_bench.py [--repeats 10] [--warmup 3] [--sessions 1,6,64,256] [--encoder window|stateful|both]
+                                         [--link plain|av [--fec]]
 """
 import argparse
 import json
@@ -60,11 +66,30 @@ def enc_kw(encoder):
     return {} if encoder == "window" else {"encoder": encoder}
 
 
-def pool_ticks(net, a, t, S, stagger, warmup, repeats, encoder="window"):
+def av_kw(fec):
+    """The options of --link av, for the pool and the lockstep sender alike."""
+    from multimodal_vqvae_compression_audio_tactile_amd.packets import Fec, Rate
+    kw = dict(rate=Rate(min_books=2, tol2=0.84), audio="packets", audio_rate=Rate(min_books=2, tol2=0.5))
+    return dict(kw, fec=Fec(4, 3), audio_fec=Fec(8, 4, 2)) if fec else kw
+
+
+def pool_ticks(net, a, t, S, stagger, warmup, repeats, encoder="window", av=None, host=None):
     """A pool of S sessions, session i starting (i mod 16 if ``stagger`` else 0) ticks late, every open session pushing one token
     per tick.  -> (per-round sums, the times of the ticks that emitted, the times of the ticks that only appended) of
-    ``repeats`` steady rounds."""
-    pool = net.stream_sender_pool(slots=S, **enc_kw(encoder))
+    ``repeats`` steady rounds.  ``av``: the options of a StreamSenderPoolAV; ``host``: a dict that receives the host times per round."""
+    import time
+    pool = net.stream_sender_pool(slots=S, **enc_kw(encoder)) if av is None else net.stream_sender_pool_av(slots=S, **av, **enc_kw(encoder))
+    spent = {"frame": 0.0, "step": 0.0}
+    if host is not None:
+        frame = pool._frame
+
+        def timed_frame(*args):
+            t0 = time.perf_counter()
+            try:
+                return frame(*args)
+            finally:
+                spent["frame"] += time.perf_counter() - t0
+        pool._frame = timed_frame
     late = [i % ROUND if stagger else 0 for i in range(S)]
     sids, fed = {}, [0] * S
 
@@ -91,19 +116,23 @@ def pool_ticks(net, a, t, S, stagger, warmup, repeats, encoder="window"):
         for _ in range(ROUND):
             pushes = tick(now)                                        # slicing the signals is the caller's work
             got = {}
+            t0 = time.perf_counter()
             ms = event_ms(lambda: got.update(pool.step(pushes)))
+            spent["step"] += time.perf_counter() - t0
             total += ms
-            (emit if any(pk for pk, _ in got.values()) else append).append(ms)
+            (emit if any(v[0] for v in got.values()) else append).append(ms)
             now += 1
         rounds.append(total)
+    if host is not None:
+        host.update(host_ms=1e3 * spent["step"] / repeats, frame_ms=1e3 * spent["frame"] / repeats)
     for s in sids.values():
         pool.close(s)
     return rounds, emit, append
 
 
-def lockstep_steps(net, a, t, B, warmup, repeats, encoder="window"):
+def lockstep_steps(net, a, t, B, warmup, repeats, encoder="window", av=None):
     """``repeats`` steady eager 16-token pushes of a StreamSender(batch=B) on the first B sessions' signals."""
-    tx = net.stream_sender(batch=B, **enc_kw(encoder))
+    tx = net.stream_sender(batch=B, **(av or {}), **enc_kw(encoder))
     c = {"n": 0}
     n_steps = a.shape[-1] // (ROUND * HOP)
 
@@ -123,7 +152,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sessions", default="1,6,64,256")
     ap.add_argument("--encoder", default="window", choices=("window", "stateful", "both"))
+    ap.add_argument("--link", choices=("plain", "av"), default="plain", help="av: StreamSenderPoolAV on both streams (section 25)")
+    ap.add_argument("--fec", action="store_true", help="--link av: Fec(4, 3) on the tactile and Fec(8, 4, 2) on the audio stream")
     args = ap.parse_args()
+    if args.fec and args.link != "av":
+        raise SystemExit("stream_send_pool_bench: --fec goes with --link av")
     sys.path.insert(0, str(ROOT))
     from multimodal_vqvae_compression_audio_tactile_amd import build_proposed, synth
     if not torch.cuda.is_available():
@@ -138,15 +171,22 @@ def main():
         a, t = synth.audio_segments(S_max, seed=11), synth.tactile_segments(S_max, seed=11)        # on the host, [S, 1, 24000]
         assert a.shape[-1] == SIGNAL_TOK * HOP and not a.is_cuda
         modes = ("window", "stateful") if args.encoder == "both" else (args.encoder,)
-        solos = {m: spread(lockstep_steps(net, a, t, 1, args.warmup, args.repeats, m)) for m in modes}
+        av = av_kw(args.fec) if args.link == "av" else None
+        if av is not None:
+            out.update(link="av", fec=args.fec)
+        solos = {m: spread(lockstep_steps(net, a, t, 1, args.warmup, args.repeats, m, av)) for m in modes}
         for S, mode in ((S, m) for S in sizes for m in modes):
             solo = solos[mode]
-            rounds, emit, append = pool_ticks(net, a, t, S, True, args.warmup, args.repeats, mode)
+            host = {} if av is not None else None
+            rounds, emit, append = pool_ticks(net, a, t, S, True, args.warmup, args.repeats, mode, av, host)
             if S >= ROUND:                                            # every tick of the staggered workload emits
-                append = pool_ticks(net, a, t, S, False, 0, max(1, args.repeats // 5), mode)[2]
-            lock = spread(lockstep_steps(net, a, t, S, args.warmup, args.repeats, mode))
+                append = pool_ticks(net, a, t, S, False, 0, max(1, args.repeats // 5), mode, av)[2]
+            lock = spread(lockstep_steps(net, a, t, S, args.warmup, args.repeats, mode, av))
             row = {"S": S, "encoder": mode, "emitting_per_tick": S / ROUND, "tick_emit_ms": spread(emit), "tick_append_ms": spread(append),
                    "round_ms": spread(rounds), "lockstep_ms": lock, "solo_ms": solo, "solo_total_ms": S * solo["median"]}
+            if av is not None:
+                plain = spread(pool_ticks(net, a, t, S, True, args.warmup, args.repeats, mode)[0])
+                row.update(plain_round_ms=plain, round_over_plain=row["round_ms"]["median"] / plain["median"], **host)
             row["round_over_lockstep"] = row["round_ms"]["median"] / lock["median"]
             row["round_over_solo"] = row["round_ms"]["median"] / row["solo_total_ms"]
             row["real_time_factor"] = row["round_ms"]["median"] / CHUNK_MS
