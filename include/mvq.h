@@ -41,7 +41,8 @@ extern "C" {
  * mvq_plc_mask_fill_bwd_f32 of the packet-loss-concealment model, and its evaluation: mvq_frame_subsets, mvq_mel_ssim_f32,
  * mvq_subset_stats_f32; the lossy-channel receiver: mvq_idx_pack_packets_u8, mvq_idx_unpack_packets, mvq_rvq_dequant_layers_f32;
  * forward error correction: mvq_fec_parity_u8, mvq_fec_recover_u8, mvq_fec_rs_parity_u8, mvq_fec_rs_recover_u8; audio concealment: mvq_attention_masked_f32,
- * mvq_attention_seq_masked_f32, mvq_hold_fill_f32; the audio/FEC pools: mvq_hold_fill_slots_f32;
+ * mvq_attention_seq_masked_f32, mvq_hold_fill_f32; the audio/FEC pools: mvq_hold_fill_slots_f32; training under the link:
+ * mvq_attention_masked_bwd_f32, mvq_attention_seq_masked_bwd_f32, mvq_channel_draw_u8;
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
@@ -405,7 +406,7 @@ int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float*
  * stages (one ballot per wave, slot = popcount of the present keys below), the sequence kernel skips absent columns in every
  * pass (their e_j is +0, whose addition to l is exact; the value chain is predicated, not multiplied).  kmask == NULL is the
  * unmasked launch.  Shape limits, addressing and refusals (before any launch) are those of the unmasked entry points.
- * Forward only. */
+ * The backward is mvq_attention_masked_bwd_f32 / mvq_attention_seq_masked_bwd_f32 below. */
 int mvq_attention_masked_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, float* ctx,
                              int batch, int heads, int dh, int tq, int tk,
                              size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b,
@@ -502,6 +503,31 @@ size_t mvq_attention_seq_bwd_scratch_bytes(int batch, int heads, int tq, int tk)
 int mvq_attention_seq_bwd_f32(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
                               void* scratch, int batch, int heads, int dh, int tq, int tk,
                               size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, void* stream);
+/* Backward under a KEY MASK (kmask as in mvq_attention_masked_f32): gq is, bit for bit, what mvq_attention_bwd_f32 /
+ * mvq_attention_seq_bwd_f32 return on the item's K and V compacted to J(b) with Tk = |J(b)|; gk / gv at a present column are
+ * that launch's values at the column's slot, and at an absent column they are written as +0 (every output element is
+ * defined).  |J(b)| = 0 gives gq = +0 and gk = gv = +0 for that item.  K and V of an absent column never reach any output (NaN
+ * or 1e30 there changes nothing): the chunk kernel compacts while it stages, the sequence kernels predicate every chain on
+ * presence and never multiply by the mask.  kmask == NULL is the unmasked launch.  Shape limits and refusals (before any
+ * launch) are those of mvq_attention_bwd_f32 (Tq, Tk <= 32, 64 KiB of LDS) and mvq_attention_seq_bwd_f32 (Tq, Tk <= 512,
+ * dh <= 256); the scratch of the sequence form has the unmasked size. */
+int mvq_attention_masked_bwd_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                 float* gq, float* gk, float* gv, int batch, int heads, int dh, int tq, int tk,
+                                 size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b,
+                                 void* stream);
+int mvq_attention_seq_masked_bwd_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                     float* gq, float* gk, float* gv, void* scratch, int batch, int heads, int dh, int tq, int tk,
+                                     size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c,
+                                     size_t m_stride_b, void* stream);
+/* Loss pattern of a lossy link for the training step: counts[batch, t] uint8, token tk takes packet tk / packet_tok; 0 = the
+ * packet is lost, otherwise the number of books (of nb) that arrive.  Per item a two-state Gilbert-Elliott chain over its packets,
+ * drawn from a stateless 32-bit hash of (seed, step, stream_id, item_base + b, packet, draw): pure integer arithmetic, equal bit
+ * for bit to packets.channel_counts (which documents the hash and the four draws), and row b depends on item_base + b alone.  The
+ * thresholds are min(2^32, int(q * 2^32)) of the probabilities loss, thin, p_gb, p_bg, loss_bad.  One thread walks one item's
+ * chain.  Refused before any launch: packet_tok < 1, min_books outside 1..nb, nb outside 1..255, a threshold above 2^32. */
+int mvq_channel_draw_u8(uint8_t* counts, int batch, int t, int packet_tok, int nb, int min_books,
+                        uint64_t thr_loss, uint64_t thr_thin, uint64_t thr_gb, uint64_t thr_bg, uint64_t thr_loss_bad,
+                        uint32_t seed, uint32_t step, uint32_t stream_id, uint32_t item_base, void* stream);
 /* Packet-loss fill (PLC/PLC1.py:401-410) on [batch, c, t] tensors with element (b,c,t) at b*stride_b + c*stride_c + t
  * (0,0 = contiguous; stride_b = t, stride_c = batch*t is the token-folded [C, B*T] layout); mask is uint8 [batch, t],
  * contiguous, non-zero = token lost.

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import subprocess
-from ctypes import c_char_p, c_float, c_int, c_size_t, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
@@ -114,6 +114,9 @@ EXPORTS = {
     "mvq_attention_seq_masked_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_hold_fill_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "mvq_hold_fill_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "mvq_attention_masked_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
+    "mvq_attention_seq_masked_bwd_f32": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
+    "mvq_channel_draw_u8": (c_int, [c_void_p] + [c_int] * 5 + [c_uint64] * 5 + [c_uint32] * 4 + [c_void_p]),
     "mvq_attention_seq_bwd_scratch_bytes": (c_size_t, [c_int] * 4),
     "mvq_attention_seq_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_size_t] * 4 + [c_void_p]),
     "mvq_plc_mask_fill_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_size_t] * 2 + [c_void_p]),

@@ -1111,6 +1111,26 @@ int mvq_attention_bwd_f32(const float* q, const float* k, const float* v, const 
     return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_bwd");
 }
 
+int mvq_attention_masked_bwd_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                 float* gq, float* gk, float* gv, int batch, int heads, int dh, int tq, int tk,
+                                 size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c, size_t m_stride_b,
+                                 void* stream)
+{
+    if (!kmask || tk <= 0)                   /* NULL mask, or no key to mask: the existing launch and the existing bits */
+        return mvq_attention_bwd_f32(q, k, v, g, gq, gk, gv, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, stream);
+    if (batch < 0 || heads <= 0 || dh <= 0 || tq < 0 || tq > 32 || tk > 32) return fail(MVQ_EINVAL, "attention_masked_bwd: bad shape (Tq, Tk <= 32)");
+    if (((size_t)dh * (2 * tq + 2 * tk) + 2 * (size_t)tq * tk) * sizeof(float) > 64 * 1024)
+        return fail(MVQ_EINVAL, "attention_masked_bwd: head slices must fit 64 KiB of LDS");
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !g || !gq || !k || !v || !gk || !gv) return fail(MVQ_EINVAL, "attention_masked_bwd: null tensor");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_masked_bwd(q, k, v, kmask, g, gq, gk, gv, batch, heads, dh, tq, tk, q_stride_b, q_stride_c,
+                                                    k_stride_b, k_stride_c, m_stride_b, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_masked_bwd");
+}
+
 static const int kAttnSeqMaxT = 8192, kAttnSeqBwdMaxT = 512, kAttnSeqBwdMaxDh = 256;
 
 int mvq_attention_seq_f32(const float* q, const float* k, const float* v, float* ctx,
@@ -1173,6 +1193,51 @@ int mvq_attention_seq_bwd_f32(const float* q, const float* k, const float* v, co
     hipError_t e = mvq::launch_attention_seq_bwd(q, k, v, g, gq, gk, gv, static_cast<float*>(scratch), batch, heads, dh, tq, tk,
                                                  q_stride_b, q_stride_c, k_stride_b, k_stride_c, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq_bwd");
+}
+
+int mvq_attention_seq_masked_bwd_f32(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                     float* gq, float* gk, float* gv, void* scratch, int batch, int heads, int dh, int tq, int tk,
+                                     size_t q_stride_b, size_t q_stride_c, size_t k_stride_b, size_t k_stride_c,
+                                     size_t m_stride_b, void* stream)
+{
+    if (!kmask || tk <= 0)                   /* NULL mask, or no key to mask: the existing launch and the existing bits */
+        return mvq_attention_seq_bwd_f32(q, k, v, g, gq, gk, gv, scratch, batch, heads, dh, tq, tk, q_stride_b, q_stride_c, k_stride_b,
+                                         k_stride_c, stream);
+    if (batch < 0 || heads <= 0 || dh <= 0 || dh > kAttnSeqBwdMaxDh || tq < 0 || tq > kAttnSeqBwdMaxT || tk > kAttnSeqBwdMaxT)
+        return fail(MVQ_EINVAL, "attention_seq_masked_bwd: bad shape (Tq, Tk <= %d, dh <= %d)", kAttnSeqBwdMaxT, kAttnSeqBwdMaxDh);
+    if (batch == 0 || tq == 0) return MVQ_OK;
+    if (!q || !g || !gq || !k || !v || !gk || !gv || !scratch) return fail(MVQ_EINVAL, "attention_seq_masked_bwd: null tensor");
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(MVQ_EINVAL, "attention_seq_masked_bwd: scratch must be 16-byte aligned");
+    const size_t c = (size_t)heads * dh;
+    if (q_stride_b == 0 && q_stride_c == 0) { q_stride_b = c * tq; q_stride_c = (size_t)tq; }
+    if (k_stride_b == 0 && k_stride_c == 0) { k_stride_b = c * tk; k_stride_c = (size_t)tk; }
+    hipError_t e = mvq::launch_attention_seq_masked_bwd(q, k, v, kmask, g, gq, gk, gv, static_cast<float*>(scratch), batch, heads, dh,
+                                                        tq, tk, q_stride_b, q_stride_c, k_stride_b, k_stride_c, m_stride_b, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "attention_seq_masked_bwd");
+}
+
+static inline uint32_t chan_fold_host(uint32_t h, uint32_t f)
+{
+    uint32_t x = (h ^ f) + 0x9e3779b9u;
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+int mvq_channel_draw_u8(uint8_t* counts, int batch, int t, int packet_tok, int nb, int min_books,
+                        uint64_t thr_loss, uint64_t thr_thin, uint64_t thr_gb, uint64_t thr_bg, uint64_t thr_loss_bad,
+                        uint32_t seed, uint32_t step, uint32_t stream_id, uint32_t item_base, void* stream)
+{
+    const uint64_t one = (uint64_t)1 << 32;
+    if (batch < 0 || t < 0 || packet_tok <= 0 || nb < 1 || nb > 255 || min_books < 1 || min_books > nb)
+        return fail(MVQ_EINVAL, "channel_draw: bad shape (packet_tok >= 1, 1 <= min_books <= nb <= 255)");
+    if (thr_loss > one || thr_thin > one || thr_gb > one || thr_bg > one || thr_loss_bad > one)
+        return fail(MVQ_EINVAL, "channel_draw: a threshold above 2^32");
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!counts) return fail(MVQ_EINVAL, "channel_draw: null tensor");
+    const uint32_t hs = chan_fold_host(chan_fold_host(chan_fold_host(0u, seed), step), stream_id);
+    hipError_t e = mvq::launch_channel_draw(counts, batch, t, packet_tok, nb, min_books, thr_loss, thr_thin, thr_gb, thr_bg,
+                                            thr_loss_bad, hs, item_base, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "channel_draw");
 }
 
 int mvq_plc_mask_fill_f32(const float* zt, const float* z_pred, const uint8_t* mask, float* zt_in, float* z_filled,

@@ -8,7 +8,7 @@
 // Structure: one block per (batch, head, query tile of QT rows).  The QT probability rows stay resident in LDS (row pitch
 // TkP); K and V go through one [dh][KT] LDS tile, K in the score pass and V in the value pass.  QT is the largest of 16, 8, 4,
 // 2, 1 whose footprint fits the 160 KiB of a CU (attn_seq_plan); at Tk = 8192, dh = 128 that is QT = 4.
-// MASKED (mvq_attention_seq_masked_f32, forward only): key j of item b is present when kmask[b*msb + j] != 0.  P keeps its
+// MASKED (mvq_attention_seq_masked_f32; its backward is below): key j of item b is present when kmask[b*msb + j] != 0.  P keeps its
 // pitch and the plan its footprint; absent columns are not staged, the max / exp / value passes skip them and their e_j is
 // written as +0, whose addition to l is exact; the value chain is predicated by the tile's ballot of the mask, never
 // multiplied.  So the result is the plain kernel's on the compacted K / V, bit for bit, and no present key gives +0.
@@ -236,9 +236,16 @@ hipError_t launch_attention_seq_masked(const float* q, const float* k, const flo
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int ASB_T = 16;      // 16 x 16 (i, j) pairs per block of the score pass
 
+// MASKED (mvq_attention_seq_masked_bwd_f32): key j of item b is present when kmask[b*msb + j] != 0.  The scratch keeps its
+// [B*H][Tq][Tk] layout.  Absent columns are never loaded: the score pass writes S = dP = +0 there, the softmax pass skips
+// them in max, l, dot and the final row (so P = dS = +0 stay), the gQ chain is predicated on presence (never multiplied:
+// NaN in an absent column cannot leak) and the gK / gV pass stores +0 without running the chains.  Every chain then takes
+// the present columns in ascending order: the plain launch on the compacted K / V, bit for bit.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void attention_seq_bwd_scores_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, const float* __restrict__ G,
-    float* __restrict__ S, float* __restrict__ dP, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+    float* __restrict__ S, float* __restrict__ dP, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+    const uint8_t* __restrict__ kmask, size_t msb)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Qs = sm;                    // [dh][16]
@@ -252,7 +259,7 @@ __global__ __launch_bounds__(256) void attention_seq_bwd_scores_kernel(
     const size_t qo = (size_t)b * qsb + (size_t)hd * dh * qsc, ko = (size_t)b * ksb + (size_t)hd * dh * ksc;
     for (int e = tid; e < dh * ASB_T; e += 256) {
         const int d = e / ASB_T, x = e - d * ASB_T;
-        const bool iq = x < nq, ik = x < nk;
+        const bool iq = x < nq, ik = x < nk && (!MASKED || kmask[(size_t)b * msb + j0 + x] != 0);
         Qs[e] = iq ? Q[qo + (size_t)d * qsc + i0 + x] : 0.0f;
         Gs[e] = iq ? G[qo + (size_t)d * qsc + i0 + x] : 0.0f;
         Ks[e] = ik ? K[ko + (size_t)d * ksc + j0 + x] : 0.0f;
@@ -268,16 +275,31 @@ __global__ __launch_bounds__(256) void attention_seq_bwd_scores_kernel(
         dp = dfma(Gs[d * ASB_T + i], Vs[d * ASB_T + j], dp);
     }
     const size_t r = ((size_t)bh * Tq + i0 + i) * Tk + j0 + j;
+    if (MASKED && kmask[(size_t)b * msb + j0 + j] == 0) { S[r] = 0.0f; dP[r] = 0.0f; return; }
     S[r] = a / rs;
     dP[r] = dp;
 }
 
-__global__ void attention_seq_bwd_softmax_kernel(float* __restrict__ S, float* __restrict__ dP, int rows, int Tk, float rs)
+// rows_per_item = H * Tq: row r belongs to item r / rows_per_item (MASKED only)
+template <bool MASKED>
+__global__ void attention_seq_bwd_softmax_kernel(float* __restrict__ S, float* __restrict__ dP, int rows, int Tk, float rs,
+                                                 const uint8_t* __restrict__ kmask, size_t msb, int rows_per_item)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     float* pr = S + (size_t)r * Tk;
     float* dr = dP + (size_t)r * Tk;
+    if (MASKED) {
+        const uint8_t* mk = kmask + (size_t)(r / rows_per_item) * msb;
+        float m = -__builtin_inff();
+        for (int j = 0; j < Tk; ++j) if (mk[j] != 0) m = __builtin_fmaxf(m, pr[j]);
+        float l = 0.0f;
+        for (int j = 0; j < Tk; ++j) if (mk[j] != 0) { const float e = det_exp(pr[j] - m); pr[j] = e; l += e; }
+        float dot = 0.0f;
+        for (int j = 0; j < Tk; ++j) if (mk[j] != 0) { pr[j] = pr[j] / l; dot = dfma(dr[j], pr[j], dot); }
+        for (int j = 0; j < Tk; ++j) if (mk[j] != 0) dr[j] = pr[j] * (dr[j] - dot) / rs;
+        return;
+    }
     float m = -__builtin_inff();
     for (int j = 0; j < Tk; ++j) m = __builtin_fmaxf(m, pr[j]);
     float l = 0.0f;
@@ -288,8 +310,10 @@ __global__ void attention_seq_bwd_softmax_kernel(float* __restrict__ S, float* _
 }
 
 // gQ[d][i] = sum_j dS[i][j] K[d][j]: one thread per (bh, d, i), i fastest
+template <bool MASKED>
 __global__ void attention_seq_bwd_gq_kernel(const float* __restrict__ K, const float* __restrict__ dS, float* __restrict__ gQ,
-                                            int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+                                            int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                            const uint8_t* __restrict__ kmask, size_t msb)
 {
     const size_t n = (size_t)B * H * dh * Tq;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -300,15 +324,22 @@ __global__ void attention_seq_bwd_gq_kernel(const float* __restrict__ K, const f
         const float* kr = K + (size_t)b * ksb + ((size_t)hd * dh + d) * ksc;
         const float* sr = dS + ((size_t)bh * Tq + i) * Tk;
         float a = 0.0f;
-        for (int j = 0; j < Tk; ++j) a = dfma(sr[j], kr[j], a);
+        if (MASKED) {
+            const uint8_t* mk = kmask + (size_t)b * msb;
+            for (int j = 0; j < Tk; ++j) if (mk[j] != 0) a = dfma(sr[j], kr[j], a);
+        } else {
+            for (int j = 0; j < Tk; ++j) a = dfma(sr[j], kr[j], a);
+        }
         gQ[(size_t)b * qsb + ((size_t)hd * dh + d) * qsc + i] = a;
     }
 }
 
 // gK[d][j] = sum_i dS[i][j] Q[d][i],  gV[d][j] = sum_i P[i][j] G[d][i]: one thread per (bh, d, j), j fastest
+template <bool MASKED>
 __global__ void attention_seq_bwd_gkv_kernel(const float* __restrict__ Q, const float* __restrict__ G, const float* __restrict__ P,
                                              const float* __restrict__ dS, float* __restrict__ gK, float* __restrict__ gV,
-                                             int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+                                             int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+                                             const uint8_t* __restrict__ kmask, size_t msb)
 {
     const size_t n = (size_t)B * H * dh * Tk;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -320,9 +351,11 @@ __global__ void attention_seq_bwd_gkv_kernel(const float* __restrict__ Q, const 
         const float* pc = P + (size_t)bh * Tq * Tk + j;
         const float* sc = dS + (size_t)bh * Tq * Tk + j;
         float a = 0.0f, c = 0.0f;
-        for (int i = 0; i < Tq; ++i) {
-            a = dfma(sc[(size_t)i * Tk], Q[qr + i], a);
-            c = dfma(pc[(size_t)i * Tk], G[qr + i], c);
+        if (!MASKED || kmask[(size_t)b * msb + j] != 0) {
+            for (int i = 0; i < Tq; ++i) {
+                a = dfma(sc[(size_t)i * Tk], Q[qr + i], a);
+                c = dfma(pc[(size_t)i * Tk], G[qr + i], c);
+            }
         }
         const size_t o = (size_t)b * ksb + ((size_t)hd * dh + d) * ksc + j;
         gK[o] = a;
@@ -336,33 +369,58 @@ static inline unsigned grid_for(size_t n)
     return (unsigned)(b < 65536 ? (b ? b : 1) : 65536);
 }
 
-hipError_t launch_attention_seq_bwd(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
-                                    float* scratch, int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb,
-                                    size_t ksc, hipStream_t s)
+// kmask == NULL: the plain kernels; otherwise the masked instantiations (same grids, same scratch)
+static hipError_t launch_attention_seq_bwd_any(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                               float* gq, float* gk, float* gv, float* scratch, int B, int H, int dh, int Tq, int Tk,
+                                               size_t qsb, size_t qsc, size_t ksb, size_t ksc, size_t msb, hipStream_t s)
 {
     if (B * H == 0 || Tq == 0) return hipSuccess;
     if (Tk == 0) {                                           // ctx = 0 whatever Q is: gQ = 0 (no keys: no gK / gV)
-        hipLaunchKernelGGL(attention_seq_bwd_gq_kernel, dim3(grid_for((size_t)B * H * dh * Tq)), dim3(256), 0, s,
-                           k, scratch, gq, B, H, dh, Tq, 0, qsb, qsc, ksb, ksc);
+        hipLaunchKernelGGL(attention_seq_bwd_gq_kernel<false>, dim3(grid_for((size_t)B * H * dh * Tq)), dim3(256), 0, s,
+                           k, scratch, gq, B, H, dh, Tq, 0, qsb, qsc, ksb, ksc, (const uint8_t*)nullptr, (size_t)0);
         return hipGetLastError();
     }
     const size_t lds = (size_t)4 * dh * ASB_T * sizeof(float);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     float* S = scratch;
     float* dS = scratch + (size_t)B * H * Tq * Tk;
-    const int pi = prof_enabled() ? prof_begin("attention_seq_bwd (4 kernels)", 8.0 * B * H * (double)Tq * Tk * dh, s) : -1;
-    hipLaunchKernelGGL(attention_seq_bwd_scores_kernel, dim3(B * H, (Tq + ASB_T - 1) / ASB_T, (Tk + ASB_T - 1) / ASB_T), dim3(256), lds, s,
-                       q, k, v, g, S, dS, H, dh, Tq, Tk, qsb, qsc, ksb, ksc);
+    const int pi = prof_enabled() ? prof_begin(kmask ? "attention_seq_masked_bwd (4 kernels)" : "attention_seq_bwd (4 kernels)",
+                                               8.0 * B * H * (double)Tq * Tk * dh, s) : -1;
+    const dim3 sgrid(B * H, (Tq + ASB_T - 1) / ASB_T, (Tk + ASB_T - 1) / ASB_T);
     const int rows = B * H * Tq;
-    hipLaunchKernelGGL(attention_seq_bwd_softmax_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, S, dS, rows, Tk,
-                       __builtin_sqrtf((float)dh));
-    hipLaunchKernelGGL(attention_seq_bwd_gq_kernel, dim3(grid_for((size_t)B * H * dh * Tq)), dim3(256), 0, s,
-                       k, dS, gq, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc);
-    hipLaunchKernelGGL(attention_seq_bwd_gkv_kernel, dim3(grid_for((size_t)B * H * dh * Tk)), dim3(256), 0, s,
-                       q, g, S, dS, gk, gv, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc);
+    const float rs = __builtin_sqrtf((float)dh);
+#define MVQ_ATT_SEQ_BWD(M)                                                                                                            \
+    do {                                                                                                                              \
+        hipLaunchKernelGGL(attention_seq_bwd_scores_kernel<M>, sgrid, dim3(256), lds, s,                                              \
+                           q, k, v, g, S, dS, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, kmask, msb);                                         \
+        hipLaunchKernelGGL(attention_seq_bwd_softmax_kernel<M>, dim3((rows + 63) / 64), dim3(64), 0, s, S, dS, rows, Tk, rs,          \
+                           kmask, msb, H * Tq);                                                                                       \
+        hipLaunchKernelGGL(attention_seq_bwd_gq_kernel<M>, dim3(grid_for((size_t)B * H * dh * Tq)), dim3(256), 0, s,                  \
+                           k, dS, gq, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, kmask, msb);                                              \
+        hipLaunchKernelGGL(attention_seq_bwd_gkv_kernel<M>, dim3(grid_for((size_t)B * H * dh * Tk)), dim3(256), 0, s,                 \
+                           q, g, S, dS, gk, gv, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, kmask, msb);                                    \
+    } while (0)
+    if (kmask) MVQ_ATT_SEQ_BWD(true);
+    else MVQ_ATT_SEQ_BWD(false);
+#undef MVQ_ATT_SEQ_BWD
     const hipError_t e = hipGetLastError();
     prof_end(pi, s);
     return e;
+}
+
+hipError_t launch_attention_seq_bwd(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
+                                    float* scratch, int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb,
+                                    size_t ksc, hipStream_t s)
+{
+    return launch_attention_seq_bwd_any(q, k, v, nullptr, g, gq, gk, gv, scratch, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, 0, s);
+}
+
+// kmask != NULL, Tk > 0 (the entry point sends the other cases to launch_attention_seq_bwd)
+hipError_t launch_attention_seq_masked_bwd(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                           float* gq, float* gk, float* gv, float* scratch, int B, int H, int dh, int Tq, int Tk,
+                                           size_t qsb, size_t qsc, size_t ksb, size_t ksc, size_t msb, hipStream_t s)
+{
+    return launch_attention_seq_bwd_any(q, k, v, kmask, g, gq, gk, gv, scratch, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc, msb, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

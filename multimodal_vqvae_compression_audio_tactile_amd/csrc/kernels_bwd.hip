@@ -240,13 +240,27 @@ hipError_t launch_scale_tanh_bwd(const float* u, const float* g, float s, float*
 
 // ---------------------------------------------------------------------------------------------------------------
 // attention backward, one block per (batch, head); same staging as the forward.  P is recomputed.
+// MASKED (mvq_attention_masked_bwd_f32): item b's key j is present when kmask[b*msb + j] != 0.  Tk <= 32 is one wave, so every
+// wave takes ONE ballot of the item's mask row; K / V are staged compacted (slot = popcount of the present keys below, absent
+// columns are never loaded) and from there on the body is the plain one at Tk = the number of present keys: gQ, and gK / gV
+// at the present columns, are those of the plain launch on the compacted K / V, bit for bit.  The final loop runs over the
+// columns in memory: a present column takes its slot's chains, an absent one stores +0.  LDS is sized by the Tk in memory.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool MASKED>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(
     const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, const float* __restrict__ G,
     float* __restrict__ gQ, float* __restrict__ gK, float* __restrict__ gV,
-    int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc)
+    int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
+    const uint8_t* __restrict__ kmask, size_t msb)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    unsigned long long present = 0;
+    const int TkAll = Tk;                 // columns in memory
+    if (MASKED) {
+        const int lane = threadIdx.x & 63;
+        present = __ballot(lane < TkAll && kmask[(size_t)(blockIdx.x / H) * msb + lane] != 0);
+        Tk = __popcll(present);           // the same in every wave
+    }
     float* Qs = sm;                       // [dh][Tq]
     float* Ks = Qs + dh * Tq;             // [dh][Tk]
     float* Vs = Ks + dh * Tk;             // [dh][Tk]
@@ -257,7 +271,18 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
     const int b = blockIdx.x / H, hd = blockIdx.x - b * H;
     const size_t qo = (size_t)b * qsb + (size_t)hd * dh * qsc, ko = (size_t)b * ksb + (size_t)hd * dh * ksc;
     for (int e = tid; e < dh * Tq; e += 256) { const int d = e / Tq, i = e - d * Tq; Qs[e] = Q[qo + (size_t)d * qsc + i]; Gs[e] = G[qo + (size_t)d * qsc + i]; }
-    for (int e = tid; e < dh * Tk; e += 256) { const int d = e / Tk, j = e - d * Tk; Ks[e] = K[ko + (size_t)d * ksc + j]; Vs[e] = V[ko + (size_t)d * ksc + j]; }
+    if (MASKED) {
+        for (int e = tid; e < dh * TkAll; e += 256) {
+            const int d = e / TkAll, j = e - d * TkAll;
+            if ((present >> j) & 1ull) {
+                const int slot = __popcll(present & ((1ull << j) - 1ull));
+                Ks[d * Tk + slot] = K[ko + (size_t)d * ksc + j];
+                Vs[d * Tk + slot] = V[ko + (size_t)d * ksc + j];
+            }
+        }
+    } else {
+        for (int e = tid; e < dh * Tk; e += 256) { const int d = e / Tk, j = e - d * Tk; Ks[e] = K[ko + (size_t)d * ksc + j]; Vs[e] = V[ko + (size_t)d * ksc + j]; }
+    }
     __syncthreads();
     const float rs = __builtin_sqrtf((float)dh);
     for (int p = tid; p < Tq * Tk; p += 256) {
@@ -284,6 +309,19 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
         for (int j = 0; j < Tk; ++j) a = dfma(dS[i * Tk + j], Ks[d * Tk + j], a);
         gQ[qo + (size_t)d * qsc + i] = a;
     }
+    if (MASKED) {                                                               // over the columns in memory
+        for (int e = tid; e < dh * TkAll; e += 256) {
+            const int d = e / TkAll, j = e - d * TkAll;
+            float a = 0.0f, c = 0.0f;
+            if ((present >> j) & 1ull) {
+                const int slot = __popcll(present & ((1ull << j) - 1ull));
+                for (int i = 0; i < Tq; ++i) { a = dfma(dS[i * Tk + slot], Qs[d * Tq + i], a); c = dfma(P[i * Tk + slot], Gs[d * Tq + i], c); }
+            }
+            gK[ko + (size_t)d * ksc + j] = a;
+            gV[ko + (size_t)d * ksc + j] = c;
+        }
+        return;
+    }
     for (int e = tid; e < dh * Tk; e += 256) {                                  // dK[d][j] = sum_i dS[i][j] Q[d][i]; dV[d][j] = sum_i P[i][j] G[d][i]
         const int d = e / Tk, j = e - d * Tk;
         float a = 0.0f, c = 0.0f;
@@ -299,7 +337,21 @@ hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, 
     if (B * H == 0 || Tq == 0) return hipSuccess;
     const size_t lds = ((size_t)dh * (2 * Tq + 2 * Tk) + 2 * (size_t)Tq * Tk) * sizeof(float);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_bwd_kernel, dim3(B * H), dim3(256), lds, s, q, k, v, g, gq, gk, gv, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc);
+    hipLaunchKernelGGL(attention_bwd_kernel<false>, dim3(B * H), dim3(256), lds, s, q, k, v, g, gq, gk, gv, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc,
+                       (const uint8_t*)nullptr, (size_t)0);
+    return hipGetLastError();
+}
+
+// kmask != NULL, Tk > 0 (the entry point sends the other cases to launch_attention_bwd)
+hipError_t launch_attention_masked_bwd(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                       float* gq, float* gk, float* gv, int B, int H, int dh, int Tq, int Tk,
+                                       size_t qsb, size_t qsc, size_t ksb, size_t ksc, size_t msb, hipStream_t s)
+{
+    if (B * H == 0 || Tq == 0) return hipSuccess;
+    const size_t lds = ((size_t)dh * (2 * Tq + 2 * Tk) + 2 * (size_t)Tq * Tk) * sizeof(float);
+    if (lds > 64 * 1024 || Tk > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_bwd_kernel<true>, dim3(B * H), dim3(256), lds, s, q, k, v, g, gq, gk, gv, B, H, dh, Tq, Tk, qsb, qsc, ksb, ksc,
+                       kmask, msb);
     return hipGetLastError();
 }
 

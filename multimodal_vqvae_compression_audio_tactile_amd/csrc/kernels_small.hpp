@@ -69,6 +69,9 @@ hipError_t launch_scale_tanh_bwd(const float* u, const float* g, float s, float*
                                  hipStream_t st);
 hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
                                 int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc, hipStream_t s);
+hipError_t launch_attention_masked_bwd(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                       float* gq, float* gk, float* gv, int B, int H, int dh, int Tq, int Tk,
+                                       size_t qsb, size_t qsc, size_t ksb, size_t ksc, size_t msb, hipStream_t s);
 bool attn_seq_plan(int dh, int tk, int* qt, int* kt, size_t* lds_floats);      // attention_seq.hip
 hipError_t launch_attention_seq(const float* q, const float* k, const float* v, float* ctx,
                                 int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc, hipStream_t s);
@@ -78,6 +81,12 @@ hipError_t launch_attention_seq_masked(const float* q, const float* k, const flo
 hipError_t launch_attention_seq_bwd(const float* q, const float* k, const float* v, const float* g, float* gq, float* gk, float* gv,
                                     float* scratch, int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb,
                                     size_t ksc, hipStream_t s);
+hipError_t launch_attention_seq_masked_bwd(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* g,
+                                           float* gq, float* gk, float* gv, float* scratch, int B, int H, int dh, int Tq, int Tk,
+                                           size_t qsb, size_t qsc, size_t ksb, size_t ksc, size_t msb, hipStream_t s);
+hipError_t launch_channel_draw(uint8_t* out, int B, int T, int ptok, int nb, int min_books, uint64_t thr_loss, uint64_t thr_thin,
+                               uint64_t thr_gb, uint64_t thr_bg, uint64_t thr_loss_bad, uint32_t h_stream, uint32_t item_base,
+                               hipStream_t s);                                                             // channel.hip
 hipError_t launch_plc_mask_fill(const float* zt, const float* zp, const uint8_t* mask, float* zt_in, float* zf,
                                 int B, int C, int T, size_t sb, size_t sc, hipStream_t s);
 hipError_t launch_plc_mask_fill_bwd(const float* g, const uint8_t* mask, float* gzp, int B, int C, int T, size_t sb, size_t sc,

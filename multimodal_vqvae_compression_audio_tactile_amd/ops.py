@@ -808,7 +808,18 @@ def layernorm_c(x, gamma, beta, pe=None, eps=1e-5, do_tanh=False, post_scale=1.0
     return y
 
 
-def attention(q, k, v, heads, folded_batch=None):
+def _chunk_key_mask(who, kmask, m_stride, B, Tk, device):
+    """The flat uint8 key mask of a chunk call (item b's key j at b*m_stride + j, m_stride defaults to Tk) -> (kmask, m_stride)."""
+    kmask = _key_mask_u8(who, kmask, device)
+    ms = int(Tk if m_stride is None else m_stride)
+    if ms < 0 or (B and Tk and (B - 1) * ms + Tk > kmask.numel()):
+        raise MvqError(f"{who}: an item's mask row reaches past the end of kmask ({kmask.numel()} entries, B={B}, Tk={Tk}, m_stride={ms})")
+    return kmask, ms
+
+
+def attention(q, k, v, heads, folded_batch=None, kmask=None, m_stride=None):
+    """``kmask`` (uint8 on the device, nonzero = key present; item b's key j at b*m_stride + j, ``m_stride`` defaults to Tk, so a
+    contiguous [B, Tk] mask serves the plain and the token-folded layout alike): mvq_attention_masked_f32."""
     q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v")
     B, C, Tq = q.shape
     Tk = k.shape[2]
@@ -818,6 +829,11 @@ def attention(q, k, v, heads, folded_batch=None):
         Tq, Tk = Tq // B, Tk // B
         strides = (Tq, B * Tq, Tk, B * Tk)
     ctx = torch.empty_like(q)
+    if kmask is not None:
+        kmask, ms = _chunk_key_mask("attention", kmask, m_stride, B, Tk, q.device)
+        check(_lib.lib().mvq_attention_masked_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), kmask.data_ptr(), ctx.data_ptr(), B, heads,
+                                                  C // heads, Tq, Tk, *strides, ms, _stream()), "mvq_attention_masked_f32")
+        return ctx
     check(_lib.lib().mvq_attention_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), ctx.data_ptr(), B, heads, C // heads,
                                        Tq, Tk, *strides, _stream()), "mvq_attention_f32")
     return ctx
@@ -900,7 +916,7 @@ def attention_seq(q, k, v, heads, folded_batch=None, kmask=None):
     """softmax(Q K^T / sqrt(dh)) V over whole sequences (Tq, Tk <= 8192): the arithmetic of ``attention`` -- bit-equal to it
     wherever that kernel accepts the shape -- without its 64-token limit.
     ``kmask`` (uint8 [B, Tk] on the device, nonzero = key present): mvq_attention_seq_masked_f32, item b attends over its present
-    keys only, bit-equal to this call on the compacted K / V.  Forward only."""
+    keys only, bit-equal to this call on the compacted K / V; its backward is attention_seq_bwd(kmask=)."""
     q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v")
     B, Tq, Tk, strides = _attn_dims(q, k, folded_batch)
     C = q.shape[1]
@@ -918,18 +934,46 @@ def attention_seq(q, k, v, heads, folded_batch=None, kmask=None):
     return ctx
 
 
-def attention_seq_bwd(q, k, v, g, heads, folded_batch=None):
-    """-> (gq, gk, gv) of attention_seq for Tq, Tk <= 512."""
+def attention_seq_bwd(q, k, v, g, heads, folded_batch=None, kmask=None):
+    """-> (gq, gk, gv) of attention_seq for Tq, Tk <= 512.  ``kmask`` (uint8 [B, Tk], nonzero = key present):
+    mvq_attention_seq_masked_bwd_f32 -- gq, and gk / gv at the present columns, are this call's on the compacted K / V bit for
+    bit; gk / gv at an absent column are +0."""
     q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v"); g = _dev(g, "g")
     B, Tq, Tk, strides = _attn_dims(q, k, folded_batch)
     C = q.shape[1]
     gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     nbytes = _lib.lib().mvq_attention_seq_bwd_scratch_bytes(B, heads, Tq, Tk) if Tq <= ATTN_SEQ_BWD_MAX_T and Tk <= ATTN_SEQ_BWD_MAX_T else 0
     scratch = torch.empty(max(nbytes // 4, 4), device=q.device, dtype=torch.float32)
+    if kmask is not None:
+        kmask = _key_mask_u8("attention_seq_bwd", kmask, q.device)
+        if tuple(kmask.shape) != (B, Tk):
+            raise MvqError(f"attention_seq_bwd: kmask {tuple(kmask.shape)} does not match [B={B}, Tk={Tk}]")
+        check(_lib.lib().mvq_attention_seq_masked_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), kmask.data_ptr(), g.data_ptr(),
+                                                          gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), scratch.data_ptr(), B, heads,
+                                                          C // heads, Tq, Tk, *strides, Tk, _stream()),
+              "mvq_attention_seq_masked_bwd_f32")
+        return gq, gk, gv
     check(_lib.lib().mvq_attention_seq_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), gq.data_ptr(),
                                                gk.data_ptr(), gv.data_ptr(), scratch.data_ptr(), B, heads, C // heads, Tq, Tk,
                                                *strides, _stream()), "mvq_attention_seq_bwd_f32")
     return gq, gk, gv
+
+
+def channel_draw(ch, nb, T, packet_tok, B, stream=0, step=0, item_base=0, device=None):
+    """Per-token loss pattern uint8 [B, T] of a packets.Channel on the device (mvq_channel_draw_u8): token t takes packet
+    t // packet_tok; 0 = lost, otherwise the books that arrive.  Equals np.repeat(packets.channel_counts(ch, nb, P, B, stream,
+    step, item_base), packet_tok, axis=1)[:, :T] bit for bit; no host read."""
+    from . import packets
+    if not isinstance(ch, packets.Channel):
+        raise MvqError("channel_draw: ch must be a packets.Channel")
+    nb, T, packet_tok, B = int(nb), int(T), int(packet_tok), int(B)
+    if B < 0 or T < 0 or packet_tok < 1 or not 1 <= ch.min_books <= nb <= 255:
+        raise MvqError(f"channel_draw: bad shape (B={B}, T={T}, packet_tok={packet_tok}, min_books={ch.min_books}, nb={nb})")
+    out = torch.empty((B, T), device=torch.device("cuda") if device is None else device, dtype=torch.uint8)
+    m = 0xFFFFFFFF
+    check(_lib.lib().mvq_channel_draw_u8(out.data_ptr(), B, T, packet_tok, nb, ch.min_books, *ch.thresholds(), ch.seed & m,
+                                         int(step) & m, int(stream) & m, int(item_base) & m, _stream()), "mvq_channel_draw_u8")
+    return out
 
 
 def hold_fill_(x, valid, carry=None, slots=None, slots_dev=None):
@@ -1621,7 +1665,9 @@ def scale_tanh_bwd(u, g, scale: float):
     return gu, dscale.reshape(())
 
 
-def attention_bwd(q, k, v, g, heads, folded_batch=None):
+def attention_bwd(q, k, v, g, heads, folded_batch=None, kmask=None, m_stride=None):
+    """-> (gq, gk, gv) of ``attention``.  ``kmask`` / ``m_stride`` as there: mvq_attention_masked_bwd_f32 -- gq, and gk / gv at
+    the present columns, are this call's on the compacted K / V bit for bit; gk / gv at an absent column are +0."""
     q = _dev(q, "q"); k = _dev(k, "k"); v = _dev(v, "v"); g = _dev(g, "g")
     B, C, Tq = q.shape
     Tk = k.shape[2]
@@ -1631,6 +1677,12 @@ def attention_bwd(q, k, v, g, heads, folded_batch=None):
         Tq, Tk = Tq // B, Tk // B
         strides = (Tq, B * Tq, Tk, B * Tk)
     gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    if kmask is not None:
+        kmask, ms = _chunk_key_mask("attention_bwd", kmask, m_stride, B, Tk, q.device)
+        check(_lib.lib().mvq_attention_masked_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), kmask.data_ptr(), g.data_ptr(),
+                                                      gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), B, heads, C // heads, Tq, Tk,
+                                                      *strides, ms, _stream()), "mvq_attention_masked_bwd_f32")
+        return gq, gk, gv
     check(_lib.lib().mvq_attention_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), gq.data_ptr(),
                                            gk.data_ptr(), gv.data_ptr(), B, heads, C // heads, Tq, Tk, *strides,
                                            _stream()), "mvq_attention_bwd_f32")

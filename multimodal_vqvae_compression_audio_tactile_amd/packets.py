@@ -636,3 +636,99 @@ def fec_kbps(info: StreamInfo, fec: Fec, nb_sent=None, headers: bool = True, tok
     """The rate of ``fec_bits`` in kbit/s at ``token_rate`` tokens per second: the overhead FEC adds to ``sent_kbps``."""
     info = _check(info)
     return fec_bits(info, fec, nb_sent, headers) * float(token_rate) / (1000.0 * info.T) if info.T else 0.0
+
+
+# ------------------------------------------------------- the loss pattern shared by training and the tools (csrc/channel.hip)
+_U32 = 0xFFFFFFFF
+
+
+@dataclasses.dataclass(frozen=True)
+class Channel:
+    """A lossy packet channel: a two-state Gilbert-Elliott chain per item over its packets (``p_gb`` good -> bad, ``p_bg`` bad ->
+    good; p_gb = 0 is the i.i.d. channel).  A packet is lost with probability ``loss`` in the good state and ``loss_bad`` in the
+    bad one; a surviving packet is thinned with probability ``thin`` to min_books .. nb-1 of its nb books.  ``seed`` selects the
+    pattern; the draws are a stateless hash (channel_counts), so the same arguments give the same pattern on host and device."""
+    loss: float = 0.0
+    thin: float = 0.0
+    min_books: int = 1
+    p_gb: float = 0.0
+    p_bg: float = 1.0
+    loss_bad: float = 1.0
+    seed: int = 0
+
+    def __post_init__(self):
+        for name in ("loss", "thin", "p_gb", "p_bg", "loss_bad"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"Channel: {name} = {v!r} is not a probability in [0, 1]")
+        for name in ("min_books", "seed"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Channel: {name} = {v!r} is not an integer")
+        if self.min_books < 1:
+            raise ValueError(f"Channel: min_books = {self.min_books} (at least one book per surviving packet)")
+
+    def thresholds(self):
+        """(loss, thin, p_gb, p_bg, loss_bad) as 64-bit integers: an event of probability q happens when u < min(2**32, int(q * 2**32))."""
+        return tuple(min(1 << 32, int(float(getattr(self, n)) * 4294967296.0)) for n in ("loss", "thin", "p_gb", "p_bg", "loss_bad"))
+
+
+@dataclasses.dataclass(frozen=True)
+class Link:
+    """The link of a training step: the tactile stream's Channel, the audio stream's (None: the audio arrives whole) and the
+    tokens per packet of both."""
+    tactile: Channel
+    audio: Optional[Channel] = None
+    packet_tok: int = 2
+
+    def __post_init__(self):
+        if not isinstance(self.tactile, Channel) or not (self.audio is None or isinstance(self.audio, Channel)):
+            raise ValueError("Link: tactile must be a Channel, audio a Channel or None")
+        if isinstance(self.packet_tok, bool) or not isinstance(self.packet_tok, (int, np.integer)) or self.packet_tok < 1:
+            raise ValueError(f"Link: packet_tok = {self.packet_tok!r} must be an integer >= 1")
+
+
+def _chan_mix(x):
+    x = x ^ (x >> np.uint32(16)); x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15)); x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def _chan_fold(h, f):
+    return _chan_mix((h ^ f) + np.uint32(0x9e3779b9))
+
+
+def channel_counts(ch: Channel, nb: int, P: int, items: int, stream: int = 0, step: int = 0, item_base: int = 0) -> np.ndarray:
+    """The definition of a Channel's pattern: uint8 [items, P], 0 = packet lost, otherwise the books (of ``nb``) that arrive.
+    Pure uint32 / uint64 integer arithmetic on a stateless hash, every field taken mod 2**32:
+        mix(x):     x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+        fold(h, f) = mix((h ^ f) + 0x9e3779b9)
+        u(draw)    = fold(fold(fold(fold(fold(fold(0, seed), step), stream), item_base + b), p), draw)
+    An event of probability q happens when u < min(2**32, int(q * 2**32)) (Channel.thresholds).  Per item, from the good state:
+        draw 0 moves the state before EVERY packet, packet 0 included (good -> bad on p_gb, bad -> good on p_bg);
+        draw 1 loses the packet (``loss`` in the good state, ``loss_bad`` in the bad one): count 0;
+        draw 2 thins a surviving packet (``thin``) when nb > min_books;
+        draw 3 gives the books a thinned packet keeps: min_books + ((u * (nb - min_books)) >> 32), i.e. min_books .. nb-1.
+    Row b depends on item_base + b alone: rows 0..5 of 256 items are the 6 items.  ops.channel_draw is this on the device."""
+    nb, P, items = int(nb), int(P), int(items)
+    if P < 0 or items < 0 or not 1 <= ch.min_books <= nb <= 255:
+        raise ValueError(f"channel_counts: bad shape (items={items}, P={P}, min_books={ch.min_books}, nb={nb}; 1 <= min_books <= nb <= 255)")
+    t_loss, t_thin, t_gb, t_bg, t_lbad = (np.uint64(t) for t in ch.thresholds())
+    with np.errstate(over="ignore"):
+        h = np.uint32(0)
+        for f in (ch.seed, step, stream):
+            h = _chan_fold(h, np.uint32(int(f) & _U32))
+        item = ((np.arange(items, dtype=np.uint64) + np.uint64(int(item_base) & _U32)) & np.uint64(_U32)).astype(np.uint32)
+        h_item = _chan_fold(np.full(items, h, dtype=np.uint32), item)
+        out = np.zeros((items, P), dtype=np.uint8)
+        bad = np.zeros(items, dtype=bool)
+        span = np.uint64(nb - ch.min_books)
+        for p in range(P):
+            hp = _chan_fold(h_item, np.uint32(p))
+            u = [_chan_fold(hp, np.uint32(d)).astype(np.uint64) for d in range(4)]
+            bad = np.where(bad, ~(u[0] < t_bg), u[0] < t_gb)
+            lost = u[1] < np.where(bad, t_lbad, t_loss)
+            thinned = (u[2] < t_thin) & (nb > ch.min_books)
+            kept = np.uint64(ch.min_books) + ((u[3] * span) >> np.uint64(32))
+            out[:, p] = np.where(lost, 0, np.where(thinned, kept, nb)).astype(np.uint8)
+    return out

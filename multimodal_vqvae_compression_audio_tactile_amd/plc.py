@@ -71,8 +71,15 @@ class AllPredPLC(nn.Module):
         return make_token_loss_mask(B, T_lat, PACKET_TOK, PACKET_LOSS_PROB, device)
 
     def forward_step(self, a_1T, tc_1T, mask: Optional[torch.Tensor] = None,
-                     mask_fn: Optional[Callable[[int, int, torch.device], torch.Tensor]] = None):
-        """a_1T, tc_1T: [B,1,T_wav] -> {"y_hat", "tgt", "latent_mask" [B,1,T_lat] bool}."""
+                     mask_fn: Optional[Callable[[int, int, torch.device], torch.Tensor]] = None, *, na_valid=None,
+                     audio_conceal="zero"):
+        """a_1T, tc_1T: [B,1,T_wav] -> {"y_hat", "tgt", "latent_mask" [B,1,T_lat] bool}.
+        ``na_valid`` (uint8 [B, Ta] on the device: the audio stages of each token that arrive) / ``audio_conceal`` ("zero",
+        "mask", "hold"): the audio side as the receiver reconstructs it under loss (decode_latents) -- qa from the codes with the
+        stages that arrived, then "hold" fills lost tokens and "mask" takes them out of the predictor's keys (masked
+        full-sequence attention and its backward, T_lat <= 512 under autograd).  Defaults: the reference's step."""
+        if na_valid is not None or audio_conceal != "zero":
+            return self._forward_step_link(a_1T, tc_1T, mask, mask_fn, na_valid, audio_conceal)
         Tw = tc_1T.shape[-1]
         with torch.no_grad():                                                   # frozen backbones: no graph
             qa, *_ = self.A_QUANT(self.A_ENC(a_1T))
@@ -92,6 +99,43 @@ class AllPredPLC(nn.Module):
         T = min(y_hat.shape[-1], tc_1T.shape[-1], Tw)
         fz = lambda x: torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)    # finite_or_zero (PLC1.py:94-95)
         return {"y_hat": fz(y_hat[..., :T]), "tgt": fz(tc_1T[..., :T]), "latent_mask": m.unsqueeze(1)}
+
+
+    def _forward_step_link(self, a_1T, tc_1T, mask, mask_fn, na_valid, audio_conceal):
+        from .proposed import link_step_refusals
+        link_step_refusals("AllPredPLC.forward_step", self, a_1T, tc_1T, None, na_valid, audio_conceal, None)
+        Tw = tc_1T.shape[-1]
+        with torch.no_grad():                                                   # frozen backbones: no graph
+            _, codes, *_ = self.A_QUANT(self.A_ENC(a_1T))
+            zt = self.T_ENC(tc_1T)
+            B, C, T_lat = zt.shape
+            if tuple(na_valid.shape) != (B, codes.shape[2]):
+                raise ValueError(f"AllPredPLC: na_valid {tuple(na_valid.shape)} does not match the codes' [B={B}, Ta={codes.shape[2]}]")
+            na_valid = na_valid.contiguous()
+            qa = ops._dev(self.A_QUANT.from_codes(codes, nq_valid=na_valid)[0], "qa")
+            if audio_conceal == "hold":
+                ops.hold_fill_(qa, na_valid)
+        key_mask = na_valid if audio_conceal == "mask" else None
+        m = self._mask(B, T_lat, zt.device, mask, mask_fn)
+        zt_in, _ = ops.plc_mask_fill(zt, None, m)
+        y_hat = self._fill_decode(zt, zt_in, qa, m, key_mask)
+        T = min(y_hat.shape[-1], tc_1T.shape[-1], Tw)
+        fz = lambda x: torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)
+        return {"y_hat": fz(y_hat[..., :T]), "tgt": fz(tc_1T[..., :T]), "latent_mask": m.unsqueeze(1), "codes": codes,
+                "na_valid": na_valid}
+
+    def _fill_decode(self, zt, zt_in, qa, m, key_mask):
+        """z_pred = predict(zt_in, qa) under ``key_mask``, the fill and the decoder: recorded under autograd (run_train, called
+        directly: CrossPredictor.forward keeps key_mask for inference), the inference kernels without."""
+        B, C, T_lat = zt.shape
+        if torch.is_grad_enabled() and T_lat and any(p.requires_grad for p in self.predict.parameters()):
+            fold = lambda x: x.permute(1, 0, 2).reshape(1, C, -1).contiguous()
+            z_pred = self.predict.run_train(fold(zt_in), fold(qa), B, key_mask=key_mask)
+            z_pred = z_pred.reshape(C, B, T_lat).permute(1, 0, 2).contiguous()
+            return self.T_DEC(train.PlcFill.apply(zt, z_pred, m, None))
+        with torch.no_grad():
+            z_pred = self.predict(zt_in, qa, key_mask=key_mask) if T_lat else zt_in
+            return self.T_DEC(ops.plc_mask_fill(zt, z_pred, m, want_zt_in=False)[1])
 
 
 # ---------------------------------------------------------------------- masked / unmasked metrics (PLC/PLC1_eval.py:200-224)

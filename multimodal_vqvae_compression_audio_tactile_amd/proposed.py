@@ -152,15 +152,19 @@ class CrossPredictor(nn.Module):
         hdn = L["f1"](hdn, gelu=True)                                       # nn.GELU() in the GEMM epilogue
         return L["f3"](hdn, residual=y1)                                    # ffn(y) + y
 
-    def run_train(self, zt_prev, za, folded_batch):
-        """Same computation as run() on token-folded tensors, recorded for autograd (train.py Functions)."""
+    def run_train(self, zt_prev, za, folded_batch, key_mask=None):
+        """Same computation as run() on token-folded tensors, recorded for autograd (train.py Functions).
+        key_mask (uint8 [B, Tk] on the device, nonzero = key present; not differentiated): item b attends over its present keys
+        alone -- the masked chunk kernel and its backward where the shape fits them, else the masked full-sequence pair."""
         fb, pe, L = folded_batch, self.pos.pe, self._lin
+        if key_mask is not None and za.shape[-1] == 0:
+            key_mask = None                                                     # no key to mask
         lin = lambda n, mod, x, res=None: train.Linear.apply(x, mod.weight, getattr(mod, "bias", None), res, L[n])
         q = train.LayerNormC.apply(zt_prev, self.ln_q.weight, self.ln_q.bias, pe, self.ln_q.eps, fb)
         kv = train.LayerNormC.apply(za, self.ln_kv.weight, self.ln_kv.bias, pe, self.ln_kv.eps, fb)
         Q, K, V = lin("q", self.q_proj, q), lin("k", self.k_proj, kv), lin("v", self.v_proj, kv)
         attn = train.Attention if self._chunk_kernels_fit(Q, K, fb, bwd=True) else train.AttentionSeq
-        ctx = attn.apply(Q, K, V, self.h, fb)
+        ctx = attn.apply(Q, K, V, self.h, fb) if key_mask is None else attn.apply(Q, K, V, self.h, fb, key_mask)
         if self.training and self.drop.p > 0:
             ctx = train.Dropout.apply(ctx, float(self.drop.p))
         y1 = lin("o", self.out, ctx, q)
@@ -1211,6 +1215,46 @@ class ProposedWrapper(_ProposedBase):
         return self.T_DEC(self._ar_latents(qa, zt, int(books_use))[0])
 
 
+def encoder_out_len(enc, t: int):
+    """Latent tokens a dac.Encoder gives for ``t`` samples, from its strides alone (the k = 7 / 3 convs and the ResidualUnits keep
+    the length; a block's strided conv has k = 2s, padding ceil(s/2)); None for another kind of module.  Lets the training entry
+    points refuse a mask of the wrong length before anything is launched."""
+    desc = getattr(enc, "_desc", None)
+    if not isinstance(desc, tuple) or len(desc) != 3:
+        return None
+    t = int(t)
+    for s in desc[1]:
+        t = (t + 2 * math.ceil(s / 2) - 2 * s) // s + 1
+        if t <= 0:
+            return 0
+    return t
+
+
+def link_step_refusals(who, net, a_1T, tc_1T, nb_valid, na_valid, audio_conceal, link, tactile=True):
+    """The refusals of a training step under a lossy link (AllPredAR / AllPredPLC.forward_step), before any launch."""
+    from . import packets
+    if audio_conceal not in ("zero", "mask", "hold"):
+        raise MvqError(f"{who}: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
+    if link is not None:
+        if not isinstance(link, packets.Link):
+            raise MvqError(f"{who}: link must be a packets.Link")
+        if nb_valid is not None or na_valid is not None:
+            raise MvqError(f"{who}: link draws the masks itself; it goes with neither nb_valid nor na_valid")
+    B = a_1T.shape[0]
+    for m, name, enc, x in ((nb_valid, "nb_valid", net.T_ENC, tc_1T), (na_valid, "na_valid", net.A_ENC, a_1T)):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.uint8:
+            raise MvqError(f"{who}: {name} must be a uint8 tensor [B, T]")
+        n = encoder_out_len(enc, x.shape[-1])
+        if m.dim() != 2 or m.shape[0] != B or (n is not None and m.shape[1] != n):
+            raise MvqError(f"{who}: {name} {tuple(m.shape)} does not match [B={B}, T={'?' if n is None else n}]")
+        if m.device != x.device:
+            raise MvqError(f"{who}: {name} must be on the device of the signals ({x.device}), not {m.device}")
+    if audio_conceal != "zero" and na_valid is None and (link is None or link.audio is None):
+        raise MvqError(f"{who}: audio_conceal={audio_conceal!r} conceals lost audio tokens; it needs na_valid or a link with an audio channel")
+
+
 class AllPredAR(_ProposedBase):
     """Training/compare_dacvsproposal_5.py:279-326.  Under ``torch.no_grad()`` (validation, ...:411-414) this is the
     fused inference path; with autograd enabled it records the HIP-backed graph of train.py for ``.backward()``."""
@@ -1230,8 +1274,92 @@ class AllPredAR(_ProposedBase):
         fz = lambda x: torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)   # finite_or_zero (...5.py:99-100)
         return {"y_hat": fz(y_hat[..., :T]), "tgt": fz(tc_1T[..., :T]), "r_tokens": r_tokens}, qa, zt
 
-    def forward_step(self, a_1T, tc_1T):
-        return self._forward_step(a_1T, tc_1T)[0]
+    def forward_step(self, a_1T, tc_1T, *, nb_valid=None, na_valid=None, audio_conceal="zero", link=None, step=0):
+        """With every keyword at its default: the reference's step.  Otherwise the step under a lossy link, closed-loop in the
+        RECEIVER's arithmetic: ``nb_valid`` (uint8 [B, T_lat]: the tactile books of each token that arrive, 0 = lost) and
+        ``na_valid`` (uint8 [B, Ta]: the audio stages that arrive) as decode_latents takes them, ``audio_conceal`` its three modes,
+        or ``link`` (a packets.Link) with ``step``: both masks are drawn on the device (ops.channel_draw, streams 0 and 1).
+        Returns the default keys plus "z_run", "idx" [n_books, B, T_lat], "codes", "nb_valid", "na_valid"."""
+        if nb_valid is None and na_valid is None and audio_conceal == "zero" and link is None:
+            return self._forward_step(a_1T, tc_1T)[0]
+        return self._forward_step_link(a_1T, tc_1T, nb_valid, na_valid, audio_conceal, link, step)
+
+    def _forward_step_link(self, a_1T, tc_1T, nb_valid, na_valid, audio_conceal, link, step):
+        who = "AllPredAR.forward_step"
+        link_step_refusals(who, self, a_1T, tc_1T, nb_valid, na_valid, audio_conceal, link)
+        dev = self.proj_up.weight.device
+        Tw = tc_1T.shape[-1]
+        with torch.no_grad():                                                  # frozen backbones: no graph
+            qa, codes, *_ = self.A_QUANT(self.A_ENC(a_1T))
+            zt = self.T_ENC(tc_1T)
+        B, C, Tlat = zt.shape
+        Ta = codes.shape[2]
+        nbk = len(self.vq.books)
+        if link is not None:
+            nb_valid = ops.channel_draw(link.tactile, nbk, Tlat, link.packet_tok, B, stream=0, step=step, device=dev)
+            if link.audio is not None:
+                na_valid = ops.channel_draw(link.audio, codes.shape[1], Ta, link.packet_tok, B, stream=1, step=step, device=dev)
+        if nb_valid is not None and (tuple(nb_valid.shape) != (B, Tlat) or nb_valid.device != zt.device):
+            raise MvqError(f"{who}: nb_valid {tuple(nb_valid.shape)} on {nb_valid.device} does not match [B={B}, T_lat={Tlat}] on {zt.device}")
+        if na_valid is not None and (tuple(na_valid.shape) != (B, Ta) or na_valid.device != zt.device):
+            raise MvqError(f"{who}: na_valid {tuple(na_valid.shape)} on {na_valid.device} does not match the codes' [B={B}, Ta={Ta}] on {zt.device}")
+        key_mask = None
+        with torch.no_grad():
+            if na_valid is not None:
+                na_valid = na_valid.contiguous()
+                qa = self.A_QUANT.from_codes(codes, nq_valid=na_valid)[0]
+                qa = ops._dev(qa, "qa")
+                if audio_conceal == "hold":
+                    ops.hold_fill_(qa, na_valid)
+                elif audio_conceal == "mask":
+                    key_mask = na_valid
+        nbv = nb_valid.contiguous() if nb_valid is not None else torch.full((B, Tlat), min(nbk, 255), device=zt.device, dtype=torch.uint8)
+        z_run, r_tokens, idx = self._ar_latents_link(qa, zt, nbv, key_mask)
+        y_hat = self.T_DEC(z_run)
+        T = min(y_hat.shape[-1], tc_1T.shape[-1], Tw)
+        fz = lambda x: torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)
+        return {"y_hat": fz(y_hat[..., :T]), "tgt": fz(tc_1T[..., :T]), "r_tokens": r_tokens, "z_run": z_run, "idx": idx,
+                "codes": codes, "nb_valid": nb_valid, "na_valid": na_valid}
+
+    def _ar_latents_link(self, qa, zt, nb_valid, key_mask):
+        """_ar_latents_train under a lossy link: the quantiser is the layered straight-through one (the receiver's sum of the books
+        that arrive), the predictor attends under ``key_mask``, and z_hat -- what the receiver will hold -- feeds the next chunk.
+        Under torch.no_grad() the same ops run without recording.  -> (z_run, r_tokens, idx [n_books, B, T_lat])."""
+        B, C, Tlat = zt.shape
+        dev = zt.device
+        ln = self.tokennorm.ln
+        scale_raw = self._scale_raw()
+        books = self.vq.stacked()
+        chunks, r_toks, idxs, prev = [], [], [], None
+        for s in range(0, Tlat, AR_CHUNK_TOK):
+            e = min(Tlat, s + AR_CHUNK_TOK)
+            n = e - s
+            zt_c = ops.fold_time_slice(zt, s, e)
+            if prev is None:
+                zt_prev = torch.zeros(1, C, B * n, device=dev, dtype=torch.float32)
+            else:
+                last = prev.reshape(C, B, -1)[:, :, -1:]                                 # z_run[..., s-1], with graph
+                zt_prev = torch.cat([last, torch.zeros(C, B, n - 1, device=dev)], dim=2).reshape(1, C, B * n)
+            ka = min(qa.shape[-1], e) - min(qa.shape[-1], s)
+            qa_c = ops.fold_time_slice(qa, s, s + ka) if ka > 0 else torch.zeros(1, C, 0, device=dev)
+            km_c = key_mask[:, s:s + ka].contiguous() if (key_mask is not None and ka > 0) else None
+            z_pred = self.predict.run_train(zt_prev, qa_c, B, key_mask=km_c)
+            r = ops.sub(zt_c, z_pred.detach())
+            u = train.LayerNormC.apply(r, ln.weight, ln.bias, None, ln.eps, B)
+            rN = train.ScaleTanh.apply(u, self.scale, scale_raw)
+            rD = train.Linear.apply(rN, self.proj_down.weight, self.proj_down.bias, None, self._pd)
+            qD, idx_c = train.RvqSteLayers.apply(rD, books, nb_valid[:, s:e].contiguous())
+            z_hat = train.Linear.apply(qD, self.proj_up.weight, self.proj_up.bias, z_pred, self._pu)
+            chunks.append(z_hat.reshape(C, B, n))
+            r_toks.append(rD.detach().reshape(CODE_DIM, B, n))
+            idxs.append(idx_c.reshape(-1, B, n))
+            prev = z_hat
+        if not chunks:
+            z = torch.zeros(B, C, 0, device=dev)
+            return z, torch.zeros(B, CODE_DIM, 0, device=dev), torch.zeros(len(self.vq.books), B, 0, device=dev, dtype=torch.int64)
+        z_run = torch.cat(chunks, dim=2).permute(1, 0, 2).contiguous()
+        r_tokens = torch.cat(r_toks, dim=2).permute(1, 0, 2).contiguous()
+        return z_run, r_tokens, torch.cat(idxs, dim=2).contiguous()
 
 
 class AllPredAR3(AllPredAR):

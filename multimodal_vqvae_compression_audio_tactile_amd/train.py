@@ -84,33 +84,40 @@ class Gelu(Function):
 
 
 class Attention(Function):
+    """``kmask`` (optional, uint8 [B, Tk], nonzero = key present) is not differentiated."""
+
     @staticmethod
-    def forward(ctx, q, k, v, heads, fb):
+    def forward(ctx, q, k, v, heads, fb, kmask=None):
         ctx.save_for_backward(q, k, v)
-        ctx.heads, ctx.fb = heads, fb
-        return ops.attention(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb)
+        ctx.heads, ctx.fb, ctx.kmask = heads, fb, kmask
+        if kmask is None:
+            return ops.attention(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb)
+        return ops.attention(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb, kmask=kmask)
 
     @staticmethod
     def backward(ctx, g):
         q, k, v = ctx.saved_tensors
-        gq, gk, gv = ops.attention_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb)
-        return gq, gk, gv, None, None
+        if ctx.kmask is None:
+            gq, gk, gv = ops.attention_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb)
+        else:
+            gq, gk, gv = ops.attention_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb, kmask=ctx.kmask)
+        return gq, gk, gv, None, None, None
 
 
 class AttentionSeq(Function):
     """Full-sequence attention (ops.attention_seq / attention_seq_bwd): the PLC predictor's call over all T_lat tokens."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, fb):
+    def forward(ctx, q, k, v, heads, fb, kmask=None):
         ctx.save_for_backward(q, k, v)
-        ctx.heads, ctx.fb = heads, fb
-        return ops.attention_seq(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb)
+        ctx.heads, ctx.fb, ctx.kmask = heads, fb, kmask
+        return ops.attention_seq(q.detach(), k.detach(), v.detach(), heads, folded_batch=fb, kmask=kmask)
 
     @staticmethod
     def backward(ctx, g):
         q, k, v = ctx.saved_tensors
-        gq, gk, gv = ops.attention_seq_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb)
-        return gq, gk, gv, None, None
+        gq, gk, gv = ops.attention_seq_bwd(q.detach(), k.detach(), v.detach(), _c(g), ctx.heads, folded_batch=ctx.fb, kmask=ctx.kmask)
+        return gq, gk, gv, None, None, None
 
 
 class PlcFill(Function):
@@ -179,3 +186,26 @@ class RvqSte(Function):
     @staticmethod
     def backward(ctx, g):
         return g * float(ctx.nb), None, None
+
+
+class RvqSteLayers(Function):
+    """The layered straight-through quantiser of the training step under a lossy link: the full greedy search (whose first m
+    indices do not depend on m), then the sum of the first nb_valid[b, t] books in the RECEIVER's order (ops.rvq_dequant_layers,
+    what ResidualVQEMA.from_indices(nb_valid=) runs).  ``nb_valid``: uint8 [B, n] for the folded z[1, D, B*n].  Returns
+    (q, idx); d q / d z = nb_valid[b, t] * I per token -- the reference STE's nb * I at the token's own book count, 0 for a lost
+    token, which then trains the predictor alone.  books receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, books, nb_valid):
+        zd = z.detach()
+        _, idx = ops.rvq_ema_forward(zd, books, None, return_indices=True)
+        B, n = nb_valid.shape
+        q = torch.empty_like(zd)                                              # token-folded [1, D, B*n]
+        ops.rvq_dequant_layers(idx.reshape(books.shape[0], B, n), books, nb_valid, out=q, out_strides=(n, B * n))
+        ctx.scale = nb_valid.reshape(1, 1, -1).to(zd.dtype)
+        ctx.mark_non_differentiable(idx)
+        return q, idx
+
+    @staticmethod
+    def backward(ctx, g, _gidx):
+        return g * ctx.scale, None, None
