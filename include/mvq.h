@@ -50,7 +50,8 @@ extern "C" {
  * mvq_dac_rvq_rate_workspace_bytes; the stateful streaming decoder: mvq_stream_stage_window_f32, mvq_stream_stage_window_slots_f32,
  * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32; the
  * stateful streaming encoder: mvq_stream_stage_window_snake_f32, mvq_stream_stage_window_snake_slots_f32, mvq_encoder_stream_plan,
- * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32).
+ * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32; the receiver's audio output:
+ * mvq_audio_fade_f32, mvq_audio_fade_slots_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -427,6 +428,34 @@ int mvq_hold_fill_f32(float* x, const uint8_t* valid, float* carry, int batch, i
  * the host).  carry_pool and slots are required; n_group <= n_slots. */
 int mvq_hold_fill_slots_f32(float* x, const uint8_t* valid, float* carry_pool, const int32_t* slots, int n_group, int n_slots,
                             int c, int t, void* stream);
+
+/* Audio fade (the receiver's audio OUTPUT; packets.AudioFade is the definition): the waveform of audio tokens
+ * that never arrived fades out and back in.  With v[t] = "some stage of audio token t arrived":
+ *   r[-1] = 0;  r[t] = v[t] ? 0 : min(r[t-1] + 1, H + F)                  H = hold_tok >= 0, F = fade_tok >= 1, H + F <= 255
+ *   g[-1] = 1;  g[t] = r[t] <= H ? 1.0f : (float)(H + F - r[t]) / (float)F       one IEEE division
+ *   sample s = 320*t + j:  gain = g[t-1] + (g[t] - g[t-1]) * ((float)(j + 1) / 320.0f)    each operation rounded, no fma
+ *                          y[s] = gain == 0 ? +0 : y[s] * gain
+ * so a sample between two gains of 1 keeps its value (-0 and a quiet NaN keep their bits) and a sample of gain 0 is +0 whatever it
+ * held -- predicated, not multiplied.  In place on a PIECE y[batch, 1, len] that starts at a token border, sample 320*tok0 of the
+ * item, for the step that brings valid[batch, n] (uint8, nonzero = arrived), the counts of its n new tokens.  The piece is what a
+ * streaming step emits (stream.schedule): with `back` = the tokens of the piece in front of the new ones, a push has
+ * len = 320*(n - 10 + back) -- it ends 10 tokens (DEC_HALO_TOK) behind the newest -- and a finish len = 320*(n + back) - 8; back is
+ * thereby a function of n and len, 0 <= back <= 10 and back == 10 unless tok0 == 0.  The whole item is the finish with tok0 = 0,
+ * n = T, len = 320*T - 8.
+ * state[sessions, 11] int32, updated in place: r of the last DEC_HALO_TOK + 1 = 11 tokens received, the current run last -- the 10
+ * tokens not yet emitted and the one in front of them, whose gain the first sample of the next piece starts from.  Zeros mean "no
+ * loss so far"; with tok0 == 0 and back == 0 (a session's first step) the row is not read at all, so a new session needs no
+ * clearing.  ONE launch, one block per session: the block reads its row, a barrier, then it stores the row; no row and no sample
+ * is touched by two blocks.  No host read.
+ * MVQ_EINVAL before any launch: fade_tok < 1, hold_tok < 0, hold_tok + fade_tok > 255, a negative size, a len that is not the
+ * sample count of such a step, a null pointer where data is needed (state always; y with len > 0; valid with n > 0).  batch = 0
+ * returns MVQ_OK without a launch.
+ * mvq_audio_fade_slots_f32: the same kernel body for the sessions slots[n_group] of a pool, state[n_slots, 11]; the slot rules of
+ * the receiver pool below (a slot outside [0, n_slots) reads "no loss so far" and stores no row; n_group = 0: no launch). */
+int mvq_audio_fade_f32(float* y, const uint8_t* valid, int32_t* state, int batch, int n, int tok0, int len, int hold_tok, int fade_tok,
+                       void* stream);
+int mvq_audio_fade_slots_f32(float* y, const uint8_t* valid, int32_t* state, const int32_t* slots, int n_group, int n_slots, int n,
+                             int tok0, int len, int hold_tok, int fade_tok, void* stream);
 
 /* y = gelu_erf(x) elementwise (nn.GELU() in CrossPredictor.ffn). */
 int mvq_gelu_f32(const float* x, float* y, size_t n, void* stream);

@@ -22,6 +22,9 @@ Drop-in surface:
     sessions that come and go ``ProposedEval.stream_receiver_pool`` / ``StreamReceiverPool`` (one batched step per tick), and
     the sending half ``ProposedEval.stream_sender`` / ``StreamSender`` (packets chunk by chunk, byte-equal to the whole item)
     and ``ProposedEval.stream_sender_pool`` / ``StreamSenderPool`` (sender sessions that come and go, one batched encode per tick);
+    the receiver's audio output: ``ProposedEval.set_audio_decoder`` / ``build_proposed(audio_decoder=True)``, ``decode_av``,
+    ``audio_out=True`` on ``decompress_packets_av`` / ``stream_receiver`` / ``StreamReceiverPoolAV`` (the audio waveform beside the
+    tactile one) and ``packets.AudioFade`` (lost audio tokens fade out and back in);
   * ``ops`` -- tensor-level wrappers over the C ABI (include/mvq.h), ``synth`` -- seeded weights / signals.
 All compute runs in libmvq_hip.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
@@ -41,15 +44,21 @@ from .plc import (AllPredPLC, make_token_loss_mask, mae_subset, masked_metrics, 
                   make_category_token_loss_mask, category_mask_fn)
 
 
-def build_proposed(state_dict=None, rvq_books=8, rvq_embed=512, n_codebooks=32, device="cuda", cls=None):
+def build_proposed(state_dict=None, rvq_books=8, rvq_embed=512, n_codebooks=32, device="cuda", cls=None, audio_decoder=False):
     """Assemble ProposedEval exactly as the reference does (build_backbones_for_eval + ProposedEval(...),
-    Evaluation/dac_vcpwq_proposed6_latency.py:527-535,660-667) and optionally load a checkpoint-shaped state dict."""
+    Evaluation/dac_vcpwq_proposed6_latency.py:527-535,660-667) and optionally load a checkpoint-shaped state dict.
+    ``audio_decoder=True`` keeps the audio DAC's decoder and attaches it for the receiver's audio output
+    (``net.set_audio_decoder(da.decoder)``; it is no submodule and no key of ``state_dict``: the caller loads its weights from the
+    audio DAC's own checkpoint, ``net.audio_decoder.load_state_dict(...)``)."""
     da, dt = DAC(n_codebooks=n_codebooks), DAC(n_codebooks=n_codebooks)
     net = (cls or ProposedEval)(da.encoder, da.quantizer, dt.encoder, dt.decoder, c_lat=1024,
                                rvq_books=rvq_books, rvq_embed=rvq_embed)
     if state_dict is not None:
         net.load_state_dict(state_dict, strict=True)
-    return net.to(device).eval()
+    net = net.to(device).eval()
+    if audio_decoder:
+        net.set_audio_decoder(da.decoder)
+    return net
 
 
 def build_plc(state_dict=None, n_codebooks=32, device="cuda"):

@@ -114,6 +114,8 @@ EXPORTS = {
     "mvq_attention_seq_masked_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_hold_fill_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "mvq_hold_fill_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "mvq_audio_fade_f32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
+    "mvq_audio_fade_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "mvq_attention_masked_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_attention_seq_masked_bwd_f32": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_size_t] * 5 + [c_void_p]),
     "mvq_channel_draw_u8": (c_int, [c_void_p] + [c_int] * 5 + [c_uint64] * 5 + [c_uint32] * 4 + [c_void_p]),

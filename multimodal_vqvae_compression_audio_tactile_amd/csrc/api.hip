@@ -1610,6 +1610,50 @@ int mvq_hold_fill_slots_f32(float* x, const uint8_t* valid, float* carry_pool, c
     return e == hipSuccess ? MVQ_OK : hipfail(e, "hold_fill_slots");
 }
 
+// The one argument check of the audio fade (`who`: the entry point; `sessions` = batch or n_group) -> the launch's `back` (the piece
+// starts that many tokens in front of the step's new ones) and `fresh` (nothing came before the step).  The step's tokens fix len:
+// a push emits 320*(n - 10 + back) samples, a finish 320*(n + back) - 8.
+struct AudioFadePlan { int back, fresh; };
+static int audio_fade_plan(const char* who, int sessions, int n, int tok0, int len, int hold_tok, int fade_tok, AudioFadePlan* p)
+{
+    if (sessions < 0 || n < 0 || tok0 < 0 || len < 0) return fail(MVQ_EINVAL, "%s: negative size", who);
+    if (hold_tok < 0 || fade_tok < 1 || (long long)hold_tok + fade_tok > 255)
+        return fail(MVQ_EINVAL, "%s: hold_tok = %d, fade_tok = %d (hold_tok >= 0, fade_tok >= 1, hold_tok + fade_tok <= 255)", who, hold_tok, fade_tok);
+    if (n > (1 << 22) || len > (1 << 30)) return fail(MVQ_EINVAL, "%s: n = %d tokens / len = %d samples", who, n, len);
+    long long back;
+    if (len % 320 == 320 - 8) back = (long long)(len + 8) / 320 - n;                     // a finish: up to the item's last sample
+    else if (len % 320 == 0) back = (long long)len / 320 + 10 - n;                       // a push: up to 10 tokens behind the newest
+    else return fail(MVQ_EINVAL, "%s: len = %d is no 320*m (a push) and no 320*m - 8 (a finish)", who, len);
+    if (back < 0 || back > 10 || (tok0 > 0 && back != 10))
+        return fail(MVQ_EINVAL, "%s: a piece of %d samples from token %d on is not what a step of %d new tokens emits", who, len, tok0, n);
+    p->back = (int)back;
+    p->fresh = tok0 == 0 && back == 0;
+    return MVQ_OK;
+}
+
+int mvq_audio_fade_f32(float* y, const uint8_t* valid, int32_t* state, int batch, int n, int tok0, int len, int hold_tok, int fade_tok,
+                       void* stream)
+{
+    AudioFadePlan p;
+    if (int rc = audio_fade_plan("audio_fade", batch, n, tok0, len, hold_tok, fade_tok, &p)) return rc;
+    if (batch == 0) return MVQ_OK;
+    if (!state || (!y && len) || (!valid && n)) return fail(MVQ_EINVAL, "audio_fade: null tensor");
+    hipError_t e = mvq::launch_audio_fade(y, valid, state, nullptr, batch, 0, len, n, p.back, p.fresh, hold_tok, fade_tok, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "audio_fade");
+}
+
+int mvq_audio_fade_slots_f32(float* y, const uint8_t* valid, int32_t* state, const int32_t* slots, int n_group, int n_slots, int n,
+                             int tok0, int len, int hold_tok, int fade_tok, void* stream)
+{
+    AudioFadePlan p;
+    if (int rc = audio_fade_plan("audio_fade_slots", n_group, n, tok0, len, hold_tok, fade_tok, &p)) return rc;
+    if (int rc = slots_shape_bad("audio_fade_slots", n_group, n_slots, 1)) return rc;
+    if (n_group == 0) return MVQ_OK;
+    if (!state || !slots || (!y && len) || (!valid && n)) return fail(MVQ_EINVAL, "audio_fade_slots: null tensor");
+    hipError_t e = mvq::launch_audio_fade(y, valid, state, slots, n_group, n_slots, len, n, p.back, p.fresh, hold_tok, fade_tok, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "audio_fade_slots");
+}
+
 int mvq_sumsq_partial_f32(const float* x, float* partial, int n_partial, size_t n, void* stream)
 {
     if (!partial || n_partial <= 0 || n_partial > 4096 || (!x && n)) return fail(MVQ_EINVAL, "sumsq_partial: bad argument");

@@ -6,7 +6,7 @@
 // the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
 // instantiated for the dense addressing and for the slot list (Sessions<SLOTS> below), the sample-state kernel likewise
 // (SampleRows<SLOTS>: a pool's sender sessions also bring their own fill / n / drop, section 17), and stream_rows_kernel moves
-// the carried tokens.
+// the carried tokens; audio_fade_kernel (the receiver's audio output, mvq_audio_fade_f32) is one body over Sessions<SLOTS> too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -284,6 +284,93 @@ __global__ __launch_bounds__(SMP_THREADS) void stream_samples_kernel(float* buf,
             if (i < keep) b[i] = v[u];
         }
     }
+}
+
+// ---- the receiver's audio output: lost tokens fade out and back in ---------------------------------------------
+// packets.AudioFade is the definition.  r = the saturated run length of lost tokens ending at a token (0 at an arrived one, at
+// most cap = H + F), g = 1 for r <= H, else (cap - r) / F; sample j of token t is scaled by g[t-1] + (g[t] - g[t-1]) * ((j+1)/320),
+// every operation rounded on its own, and is +0 where that gain is 0, whatever it held.
+// A launch works on the piece y[g][0 .. len) of every session g, which starts `back` tokens in front of the step's n new tokens
+// valid[g][0 .. n): piece token p is the step's token q = p - back.  state[session][0 .. AF_STATE) holds r of the AF_STATE tokens in
+// front of the new ones, the newest last, so q in [-AF_STATE, 0) is state[AF_STATE + q] and the piece's first sample finds g[t-1]
+// there (back <= AF_HALO).  `fresh` (nothing came before the step): the row is not read, every r in front is 0.
+// Ownership: ONE block per session.  Its first AF_STATE threads copy the state row to LDS (clamped to [0, cap], so a row that was
+// never written cannot index past anything); the barrier ends every read of the row; only then the same threads store r of the
+// last AF_STATE tokens of [row | new] to it, from the LDS copy and valid alone.  Distinct sessions are distinct rows (the wrapper
+// refuses a repeated slot) and a session's samples are its block's, so neither the row nor y is touched by two blocks.  A slot
+// outside [0, n_slots) reads "no loss so far" and stores no row.  The run of a new token is found by walking back over valid, at
+// most cap <= 255 bytes; the gains of AF_TILE tokens at a time go through LDS.
+namespace {
+constexpr int AF_HOP = 320;           // samples per token
+constexpr int AF_HALO = 10;           // stream.DEC_HALO_TOK: a step emits samples this many tokens behind the newest one
+constexpr int AF_STATE = AF_HALO + 1; // ... and a sample needs g[t-1] too
+constexpr int AF_TILE = 64;           // tokens whose gains one pass keeps in LDS
+}  // namespace
+
+__device__ __forceinline__ int fade_run(const uint8_t* __restrict__ valid, const int* st, int q, int cap)
+{
+    if (q < 0) return st[AF_STATE + q];
+    for (int d = 0; d < cap; ++d) {
+        if (q - d < 0) {                                                // the d new tokens up to q are lost: the run in front goes on
+            const int r = st[AF_STATE - 1] + d;
+            return r < cap ? r : cap;
+        }
+        if (valid[q - d]) return d;
+    }
+    return cap;
+}
+
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void audio_fade_kernel(float* y, const uint8_t* __restrict__ valid, int32_t* state, int len, int n,
+                                                         int back, int fresh, int H, int F, Sessions<SLOTS> ses)
+{
+    __shared__ int st[AF_STATE];
+    __shared__ float gs[AF_TILE + 1];
+    const int g = blockIdx.x, tid = threadIdx.x, cap = H + F;
+    size_t s;
+    const bool ok = ses.session(g, s);
+    int32_t* row = state + (ok ? s : 0) * AF_STATE;
+    if (tid < AF_STATE) {
+        const int v = ok && !fresh ? row[tid] : 0;
+        st[tid] = v < 0 ? 0 : (v > cap ? cap : v);
+    }
+    __syncthreads();                                                     // every read of the state row is done
+    const uint8_t* vb = valid + (size_t)g * n;
+    if (ok && tid < AF_STATE) row[tid] = fade_run(vb, st, n - AF_STATE + tid, cap);
+    float* yb = y + (size_t)g * len;
+    const int np = (len + AF_HOP - 1) / AF_HOP;                          // piece tokens with a sample (the last one lacks 8)
+    for (int p0 = 0; p0 < np; p0 += AF_TILE) {
+        const int cnt = np - p0 < AF_TILE ? np - p0 : AF_TILE;
+        if (tid <= cnt) {                                                // gs[i] = g of piece token p0 + i - 1
+            const int r = fade_run(vb, st, p0 + tid - 1 - back, cap);
+            gs[tid] = r <= H ? 1.0f : (float)(cap - r) / (float)F;
+        }
+        __syncthreads();
+        const int s_hi = (p0 + cnt) * AF_HOP < len ? (p0 + cnt) * AF_HOP : len;
+        for (int i = p0 * AF_HOP + tid; i < s_hi; i += 256) {
+            const int p = i / AF_HOP, j = i - p * AF_HOP;
+            const float g0 = gs[p - p0], g1 = gs[p - p0 + 1];
+            const float w = (float)(j + 1) / (float)AF_HOP;
+            const float gain = g0 + (g1 - g0) * w;                       // three roundings: the library is built with -ffp-contract=off
+            yb[i] = gain == 0.0f ? 0.0f : yb[i] * gain;
+        }
+        __syncthreads();                                                 // before the next pass rewrites gs
+    }
+}
+
+// slots == nullptr: the dense instantiation; else the group slots[G] of a pool of n_slots sessions.  The entry points have checked
+// every size (np - back <= n, back <= AF_HALO).
+hipError_t launch_audio_fade(float* y, const uint8_t* valid, int32_t* state, const int32_t* slots, int G, int n_slots, int len, int n,
+                             int back, int fresh, int H, int F, hipStream_t s)
+{
+    if (G == 0) return hipSuccess;
+    if (slots)
+        hipLaunchKernelGGL(audio_fade_kernel<true>, dim3(G), dim3(256), 0, s, y, valid, state, len, n, back, fresh, H, F,
+                           Sessions<true>{slots, n_slots, 1});
+    else
+        hipLaunchKernelGGL(audio_fade_kernel<false>, dim3(G), dim3(256), 0, s, y, valid, state, len, n, back, fresh, H, F,
+                           Sessions<false>{});
+    return hipGetLastError();
 }
 
 // ---- the session pool: the carried tokens ----------------------------------------------------------------------------------------

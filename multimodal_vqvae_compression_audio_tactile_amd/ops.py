@@ -1350,7 +1350,7 @@ def stream_window(hist, h_in, z_new, h_out):
 
 
 # ---------------------------------------------------------------------------------- receiver pool
-def _slot_host(who, slots, pool, dims):
+def _slot_host(who, slots, pool, dims, dtype=torch.float32):
     """The slot rule of every pool call: ``slots`` as HOST integers, refused here, before anything else is looked at, when one is
     out of range or repeated, so no unchecked index reaches the device.  -> the list.  ``pool``: the state buffer, [n_slots, ...]
     of ``dims`` dimensions."""
@@ -1368,15 +1368,15 @@ def _slot_host(who, slots, pool, dims):
         raise MvqError(f"{who}: slot {bad[0]} outside the pool's [0, {n_slots})")
     if len(set(host)) != len(host):
         raise MvqError(f"{who}: a slot is listed twice in {host} (two blocks would update one row)")
-    if pool.dtype != torch.float32 or not pool.is_cuda or not pool.is_contiguous():
-        raise MvqError(f"{who}: the pool buffer must be a contiguous fp32 HIP tensor")
+    if pool.dtype != dtype or not pool.is_cuda or not pool.is_contiguous():
+        raise MvqError(f"{who}: the pool buffer must be a contiguous {'fp32' if dtype == torch.float32 else dtype} HIP tensor")
     return host
 
 
-def _slot_list(who, slots, pool, dims, slots_dev):
+def _slot_list(who, slots, pool, dims, slots_dev, dtype=torch.float32):
     """_slot_host -> (G, int32 device tensor [G]); ``slots_dev`` is that tensor when the caller uploaded the list already
     (StreamReceiverPool sends the lists of a whole tick with its packet bodies), else it is uploaded here."""
-    host = _slot_host(who, slots, pool, dims)
+    host = _slot_host(who, slots, pool, dims, dtype)
     if slots_dev is None:
         slots_dev = torch.tensor(host, dtype=torch.int32).to(pool.device)
     elif not isinstance(slots_dev, torch.Tensor) or slots_dev.dtype != torch.int32 or slots_dev.device != pool.device \
@@ -1400,6 +1400,56 @@ def stream_rows(pool, slots, rows=None, slots_dev=None):
     check(_lib.lib().mvq_stream_rows_f32(pool.data_ptr(), sd.data_ptr(), G, S, rows.data_ptr(), C, int(scatter), _stream()),
           "mvq_stream_rows_f32")
     return pool if scatter else rows
+
+
+AUDIO_FADE_STATE = 11       # stream.DEC_HALO_TOK + 1 run lengths per session (include/mvq.h, mvq_audio_fade_f32)
+
+
+def audio_fade_state(rows, device):
+    """A fade state for ``rows`` sessions: zeros int32 [rows, 11] -- "no loss so far" (layout: include/mvq.h).  A session's first
+    step does not read its row, so a pool never has to clear one."""
+    return torch.zeros(int(rows), AUDIO_FADE_STATE, device=device, dtype=torch.int32)
+
+
+def audio_fade_(y, valid, state, fade, tok0, slots=None, slots_dev=None):
+    """packets.AudioFade in place on a piece y[G, 1, len] (contiguous fp32 on the device) that starts at sample 320*tok0 of its item,
+    for the step that brings ``valid`` (uint8 [G, n], nonzero = some stage of the token arrived; None: a finish without new
+    tokens); ``state`` (audio_fade_state) moves on in place (mvq_audio_fade_f32, one launch, no host read).  The piece is what a
+    streaming step emits: 320*(n - 10) + 320*min(tokens before, 10) samples for a push, everything up to 320*T - 8 for a finish;
+    the whole item is tok0 = 0 with all T tokens and a scratch state row.  Returns y.
+    ``slots`` (host integers, one per item; ``slots_dev`` their int32 device copy): the items are sessions of a pool and ``state`` is
+    the pool's [S, 11]; an out-of-range or repeated slot is refused here (mvq_audio_fade_slots_f32, the same kernel body)."""
+    from .packets import AudioFade
+    if not isinstance(fade, AudioFade):
+        raise MvqError("audio_fade_: fade must be a packets.AudioFade")
+    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32 or y.dim() != 3 or y.shape[1] != 1 \
+            or not y.is_contiguous():
+        raise MvqError("audio_fade_: y must be a contiguous fp32 tensor [G, 1, len] on the device (it is faded in place)")
+    G, _, n_len = y.shape
+    n = 0
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.device != y.device or valid.dtype != torch.uint8 or valid.dim() != 2 \
+                or valid.shape[0] != G or not valid.is_contiguous():
+            raise MvqError(f"audio_fade_: valid must be a contiguous uint8 tensor [G={G}, n] on the device of y")
+        n = valid.shape[1]
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != AUDIO_FADE_STATE \
+            or state.device != y.device or not state.is_contiguous():
+        raise MvqError(f"audio_fade_: state must be a contiguous int32 tensor [sessions, {AUDIO_FADE_STATE}] on the device of y "
+                       "(ops.audio_fade_state)")
+    tail = (n, int(tok0), n_len, int(fade.hold_tok), int(fade.fade_tok), _stream())
+    if slots is not None or slots_dev is not None:
+        if slots is None:
+            raise MvqError("audio_fade_: slots_dev is the device copy of slots; the host list is required")
+        n_list, slots_dev = _slot_list("audio_fade_", slots, state, 2, slots_dev, dtype=torch.int32)
+        if n_list != G:
+            raise MvqError(f"audio_fade_: {n_list} slots for a piece of {G} items")
+        check(_lib.lib().mvq_audio_fade_slots_f32(_p(y) if n_len else None, _p(valid) if n else None, state.data_ptr(), slots_dev.data_ptr(),
+                                                  G, state.shape[0], *tail), "mvq_audio_fade_slots_f32")
+        return y
+    if state.shape[0] != G:
+        raise MvqError(f"audio_fade_: a state of {state.shape[0]} sessions for a piece of {G} items")
+    check(_lib.lib().mvq_audio_fade_f32(_p(y) if n_len else None, _p(valid) if n else None, state.data_ptr(), G, *tail), "mvq_audio_fade_f32")
+    return y
 
 
 def stream_window_slots(hist, slots, h_in, z_new, h_out, slots_dev=None):

@@ -35,6 +35,9 @@ definition the device kernels (ops.fec_parity / ops.fec_recover) equal bit for b
 with r parity packets per group.  Parity i has coefficient A[i][u] = 2^(i*u) for the group's packet u, so parity 0 is the XOR
 packet above, byte for byte (magic ``MF``); parity i >= 1 travels with magic ``MR`` and one index byte behind the header.  Every
 square submatrix of A (4 x 16) is nonsingular: any d deficient packets of a group come back from any d of its parity packets.
+
+THE RECEIVER'S AUDIO OUTPUT (``AudioFade``): what the audio waveform does where audio tokens never arrived -- hold, fade to silence,
+fade back in.  ``AudioFade.apply`` is the definition the device kernel (ops.audio_fade_) equals bit for bit.
 """
 from __future__ import annotations
 
@@ -636,6 +639,74 @@ def fec_kbps(info: StreamInfo, fec: Fec, nb_sent=None, headers: bool = True, tok
     """The rate of ``fec_bits`` in kbit/s at ``token_rate`` tokens per second: the overhead FEC adds to ``sent_kbps``."""
     info = _check(info)
     return fec_bits(info, fec, nb_sent, headers) * float(token_rate) / (1000.0 * info.T) if info.T else 0.0
+
+
+# ------------------------------------------------------------------------- the receiver's audio output (DESIGN.md section 27)
+AUDIO_HOP = 320                             # samples per audio token
+AUDIO_TAIL = 8                              # the decoder gives 320*T - 8 samples for T tokens
+
+
+@dataclasses.dataclass(frozen=True)
+class AudioFade:
+    """What the receiver's audio OUTPUT does with audio tokens that never arrived: the waveform is repeated for ``hold_tok`` = H
+    tokens, fades to silence over ``fade_tok`` = F tokens, stays silent, and fades back in over one token when a token arrives.
+    H >= 0, F >= 1, H + F <= 255.  ``apply`` is the definition the device kernel (ops.audio_fade_, mvq_audio_fade_f32) equals bit
+    for bit.  With v[t] = "some stage of audio token t arrived" (na_valid[b, t] > 0):
+
+        r[-1] = 0;  r[t] = 0 if v[t] else min(r[t-1] + 1, H + F)                          (integers)
+        g[-1] = 1;  g[t] = 1.0f if r[t] <= H else float32(H + F - r[t]) / float32(F)      (one IEEE fp32 division)
+        sample s of the 320*T - 8:  t = s // 320, j = s % 320
+            w    = float32(j + 1) / float32(320)
+            gain = g[t-1] + (g[t] - g[t-1]) * w        (three fp32 operations, each rounded, no fma)
+            out[s] = +0 if gain == 0 else y[s] * gain
+
+    Where g[t-1] == g[t] == 1 the gain is exactly 1 and the sample keeps its bits (-0 and a quiet NaN too).  Where the gain is 0 the
+    result is +0 whatever y holds -- predicated, not multiplied, so junk decoded from a lost region (NaN, inf) reaches nothing.
+    g never leaves [0, 1].  AudioFade(0, 1) is "mute with a one-token ramp", AudioFade(1, 4) "repeat once, fade over four tokens"."""
+    hold_tok: int = 1
+    fade_tok: int = 4
+
+    def __post_init__(self):
+        for name in ("hold_tok", "fade_tok"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"AudioFade: {name} = {v!r} is not an integer")
+        if self.hold_tok < 0 or self.fade_tok < 1 or self.hold_tok + self.fade_tok > 255:
+            raise ValueError(f"AudioFade: hold_tok = {self.hold_tok}, fade_tok = {self.fade_tok}; hold_tok >= 0, fade_tok >= 1 and "
+                             "hold_tok + fade_tok <= 255")
+
+    def runs(self, valid, r_prev: int = 0) -> np.ndarray:
+        """r[t] of one item's ``valid`` [T] (nonzero = arrived), continuing a run of ``r_prev`` -> int64 [T]."""
+        cap, r, out = int(self.hold_tok) + int(self.fade_tok), int(r_prev), []
+        for v in np.asarray(valid).reshape(-1):
+            r = 0 if v else min(r + 1, cap)
+            out.append(r)
+        return np.asarray(out, np.int64)
+
+    def gains(self, r) -> np.ndarray:
+        """g of the run lengths ``r`` -> float32, same shape."""
+        r = np.asarray(r, np.int64)
+        H, F = int(self.hold_tok), int(self.fade_tok)
+        return np.where(r <= H, np.float32(1), (H + F - r).astype(np.float32) / np.float32(F)).astype(np.float32)
+
+    def apply(self, y, valid) -> np.ndarray:
+        """The faded waveform of y [B, 1, 320*T - 8] (or [B, 320*T - 8]) under valid [B, T] -> float32, y's shape."""
+        y = np.asarray(y, np.float32)
+        valid = np.asarray(valid)
+        B, T = valid.shape
+        flat = y.reshape(B, -1)
+        if flat.shape[1] != max(0, AUDIO_HOP * T - AUDIO_TAIL):
+            raise ValueError(f"AudioFade.apply: {flat.shape[1]} samples for {T} tokens ({AUDIO_HOP}*T - {AUDIO_TAIL})")
+        out = np.empty_like(flat)
+        s = np.arange(flat.shape[1])
+        t, w = s // AUDIO_HOP, (s % AUDIO_HOP + 1).astype(np.float32) / np.float32(AUDIO_HOP)
+        for b in range(B):
+            g = np.concatenate([np.ones(1, np.float32), self.gains(self.runs(valid[b]))])      # g[-1] first
+            g0, g1 = g[t], g[t + 1]
+            gain = (g0 + ((g1 - g0) * w).astype(np.float32)).astype(np.float32)
+            with np.errstate(invalid="ignore", over="ignore"):
+                out[b] = np.where(gain == 0, np.float32(0), flat[b] * gain)
+        return out.reshape(y.shape)
 
 
 # ------------------------------------------------------- the loss pattern shared by training and the tools (csrc/channel.hip)

@@ -561,7 +561,7 @@ class _ProposedBase(nn.Module):
     @torch.no_grad()
     def decode_latents(self, audio_codes=None, idx=None, *, qa=None, books_use=None, tactile_only=False, nb_valid=None,
                        conceal="predict", plc=None, z_prev=None, z_last_out=None, na_valid=None, audio_conceal="zero", qa_prev=None,
-                       qa_last_out=None, qa_slots=None, qa_slots_dev=None):
+                       qa_last_out=None, qa_slots=None, qa_slots_dev=None, return_qa=False):
         """The receiver: z_run from what encode_latents_with_indices transmits -- audio codes[B,32,Ta] (int) and the RVQ
         indices idx[nb,B,Tlat] (int) -- or from ``qa`` directly instead of the codes.  The transmitter's loop without T_ENC,
         TokenNorm, proj_down and the search: z_hat = proj_up(qD) + z_pred, qD = the summed code vectors (from_indices),
@@ -607,7 +607,11 @@ class _ProposedBase(nn.Module):
         today.  ``z_last_out`` ([B, C] fp32 on the device; may be the z_prev buffer itself) receives this piece's last token
         BEFORE the ``conceal`` post-pass, which is what the next piece's z_prev must be ("zero" would otherwise erase a lost
         last token that the whole-item recursion still reads).  Not with conceal="plc" (its predictor attends over the whole
-        sequence) and not with tactile_only (no recursion to carry).  Both None: today's launch sequence exactly."""
+        sequence) and not with tactile_only (no recursion to carry).  Both None: today's launch sequence exactly.
+
+        ``return_qa``: -> (z_run, qa), qa [B, C, Ta] the audio latent AS THE PREDICTOR SAW IT -- under "hold" the held token at a lost
+        one, under "zero" and "mask" +0 there (from_codes(nq_valid=) writes +0 and "mask" leaves it) -- which is what the
+        receiver's audio decoder is fed (decode_av).  Not with tactile_only; no extra launch."""
         if idx is None:
             raise MvqError("decode_latents: idx (the RVQ indices [n_books, B, T_lat]) is required")
         dev = self.proj_up.weight.device
@@ -634,6 +638,8 @@ class _ProposedBase(nn.Module):
                 if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32
                                           and tuple(t.shape) == (B, C) and t.is_contiguous()):
                     raise MvqError(f"decode_latents: {name} must be a contiguous fp32 tensor [B={B}, C={C}] on {dev}")
+        if return_qa and tactile_only:
+            raise MvqError("decode_latents: return_qa hands back the audio latent; tactile_only has none")
         if nb_valid is None:
             conceal = "predict"                                               # every token arrived whole: nothing to conceal
         else:
@@ -681,7 +687,8 @@ class _ProposedBase(nn.Module):
             if tuple(na_valid.shape) != (B, audio_codes.shape[2]):
                 raise MvqError(f"decode_latents: na_valid {tuple(na_valid.shape)} does not match the codes' [B={B}, Ta={audio_codes.shape[2]}]")
         if B == 0 or Tlat == 0:
-            return torch.zeros(B, C, Tlat, device=dev)
+            z0 = torch.zeros(B, C, Tlat, device=dev)
+            return (z0, torch.zeros(B, C, Ta, device=dev)) if return_qa else z0
         if na_valid is not None:
             na_valid = na_valid.to(dev).contiguous()
             if na_valid.dtype == torch.bool:                                  # all or none: 255 caps at the stages there are
@@ -719,16 +726,18 @@ class _ProposedBase(nn.Module):
         if z_last_out is not None:                                            # before the post-pass: what the recursion reads
             ops.copy_strided_(z_last_out, 0, (C, 1), z_run, Tlat - 1, (C * Tlat, Tlat), B, C, 1)
         if conceal == "predict":
-            return z_run
+            return (z_run, qa) if return_qa else z_run
         lost = nb_valid == 0
         if conceal == "zero":
-            return ops.plc_mask_fill(z_run, None, lost)[0]                    # z_run * ~lost
+            z_run = ops.plc_mask_fill(z_run, None, lost)[0]                   # z_run * ~lost
+            return (z_run, qa) if return_qa else z_run
         zt_in, _ = ops.plc_mask_fill(z_run, None, lost)                       # what AllPredPLC's predictor is fed
         if key_mask is not None:                                              # the PLC predictor sees what the AR predictor saw
             z_plc = plc.predict(zt_in, qa, key_mask=key_mask)
         else:
             z_plc = plc.predict(zt_in, qa)
-        return ops.plc_mask_fill(z_run, z_plc, lost, want_zt_in=False)[1]
+        z_run = ops.plc_mask_fill(z_run, z_plc, lost, want_zt_in=False)[1]
+        return (z_run, qa) if return_qa else z_run
 
     def _rx_two_pass(self, qa, idx, books_use, nb_valid=None, z_prev=None, key_mask=None):
         """Layout: every [.., B*Tlat] tensor of the plan is token-folded and PADDED per chunk -- column (b*NC + c)*16 + i holds
@@ -873,6 +882,64 @@ class ProposedEval(_ProposedBase):
         ``conceal`` / ``plc`` / ``na_valid`` / ``audio_conceal``: the lossy-channel arguments of decode_latents."""
         return self.T_DEC(self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc,
                                               na_valid=na_valid, audio_conceal=audio_conceal))
+
+    # ------------------------------------------------------------------------------------- receiver audio output (section 27)
+    @property
+    def audio_decoder(self):
+        """The audio DAC's decoder (set_audio_decoder), or None: what turns the received audio codes into a waveform."""
+        return self.__dict__.get("_audio_decoder")
+
+    def __setattr__(self, name, value):                    # nn.Module would register a Module assigned here, past the property
+        if name == "audio_decoder":
+            raise AttributeError("ProposedEval.audio_decoder is read-only: set_audio_decoder(dec) attaches it outside the state dict")
+        super().__setattr__(name, value)
+
+    def set_audio_decoder(self, dec):
+        """Attach the audio DAC's decoder for the receiver's audio output (decode_av, decompress_packets_av(audio_out=True),
+        stream_receiver(audio_out=True)).  ``dec``: a dac.Decoder with T_DEC's geometry (ValueError otherwise); it is moved to the
+        model's device and frozen here.  It is NOT a submodule: checkpoints hold no key of it, so state_dict() and
+        load_state_dict(strict=True) are what they are without it, and .to() / .eval() on the model do not reach it -- its weights
+        come from the audio DAC's own checkpoint, loaded by the caller.  None detaches it."""
+        from .dac import Decoder
+        if dec is not None:
+            if not isinstance(dec, Decoder):
+                raise ValueError(f"set_audio_decoder: a dac.Decoder is required, not {type(dec).__name__}")
+            if tuple(dec._desc) != tuple(self.T_DEC._desc):
+                raise ValueError(f"set_audio_decoder: decoder geometry {tuple(dec._desc)} is not T_DEC's {tuple(self.T_DEC._desc)} "
+                                 "(input channels, width, rates, output channels, output_padding)")
+            dec = dec.to(self.proj_up.weight.device).eval().requires_grad_(False)
+        self.__dict__["_audio_decoder"] = dec              # past nn.Module.__setattr__: not registered, not in the state dict
+        return self
+
+    def _audio_out_args(self, who, audio_out, audio_fade):
+        """The refusals every audio_out entry point shares, before any launch."""
+        from .packets import AudioFade
+        from .stream import _f32_only
+        if audio_fade is not None and not audio_out:
+            raise ValueError(f"{who}: audio_fade shapes the audio output; it goes with audio_out=True")
+        if not audio_out:
+            return
+        if self.audio_decoder is None:
+            raise ValueError(f"{who}: audio_out needs the audio decoder (set_audio_decoder, or build_proposed(audio_decoder=True))")
+        if audio_fade is not None and not isinstance(audio_fade, AudioFade):
+            raise ValueError(f"{who}: audio_fade must be a packets.AudioFade or None, not {audio_fade!r}")
+        _f32_only(f"{who}(audio_out=True)")
+
+    @torch.no_grad()
+    def decode_av(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None, na_valid=None, audio_conceal="zero",
+                  audio_fade=None):
+        """Receiver, both modalities -> (y_tactile, y_audio): decode(...) and y_audio = fade(audio_decoder(qa)) [B, 1, 320*Ta - 8]
+        with qa the audio latent as the predictor saw it (decode_latents(return_qa=True)).  ``audio_fade`` (packets.AudioFade): the
+        waveform of tokens with na_valid == 0 fades out and back in (ops.audio_fade_, one launch); None, or na_valid None, skips it."""
+        self._audio_out_args("decode_av", True, audio_fade)
+        z, qa = self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
+                                    audio_conceal=audio_conceal, return_qa=True)
+        y_audio = self.audio_decoder(qa)
+        if audio_fade is not None and na_valid is not None and y_audio.shape[-1] > 0:
+            valid = na_valid.to(qa.device).contiguous()
+            valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+            y_audio = ops.audio_fade_(y_audio.contiguous(), valid, ops.audio_fade_state(qa.shape[0], qa.device), audio_fade, 0)
+        return self.T_DEC(z), y_audio
 
     @torch.no_grad()
     def decode_latents_tactile_only(self, idx, books_use=None, nb_valid=None, conceal="predict"):
@@ -1064,7 +1131,8 @@ class ProposedEval(_ProposedBase):
 
     @torch.no_grad()
     def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None,
-                              fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None, audio_conceal="zero"):
+                              fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None, audio_conceal="zero", audio_out=False,
+                              audio_fade=None):
         """-> (y [B,1,T], lost [B,T_lat] bool, audio_lost [B,Ta] bool) from whatever packets of BOTH streams arrived (missing,
         reordered, duplicated, thinned; items of one StreamInfo per stream): packets.gather per item and stream on the host, ONE
         upload of both streams' bodies and per-packet counts, the bit unpacking of both on the device (the audio indices are
@@ -1075,8 +1143,13 @@ class ProposedEval(_ProposedBase):
         ``fec`` / ``fec_packets`` / ``audio_fec`` / ``audio_fec_packets``: decompress_packets(fec=) per stream -- packets.gather_fec per
         item and stream, the parity rows and ``got`` flags of both behind the existing arrays in the ONE upload, ops.fec_recover on
         each stream ahead of its ops.idx_unpack_packets.  The return values do not change; ``lost`` / ``audio_lost`` are what is still
-        lost after recovery.  The closed loop: as decompress_packets(fec=) says, on each stream."""
+        lost after recovery.  The closed loop: as decompress_packets(fec=) says, on each stream.
+
+        ``audio_out=True`` (needs set_audio_decoder): -> (y, lost, audio_lost, y_audio), the first three exactly as
+        without it and y_audio [B, 1, 320*Ta - 8] the audio waveform, decode_av's: the audio decoder on the audio latent the predictor
+        saw, then ``audio_fade`` (packets.AudioFade or None) over the tokens that are still lost after recovery."""
         from . import packets
+        self._audio_out_args("decompress_packets_av", audio_out, audio_fade)
         if audio_conceal not in ("zero", "mask", "hold"):
             raise MvqError(f"decompress_packets_av: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
         if (fec is None and fec_packets is not None) or (audio_fec is None and audio_fec_packets is not None):
@@ -1125,19 +1198,25 @@ class ProposedEval(_ProposedBase):
         idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
         aidx, na_valid = ops.idx_unpack_packets(uab, uar, ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
         codes = aidx.permute(1, 0, 2).contiguous()                            # [nq, B, Ta] -> [B, nq, Ta], on the device
+        if audio_out:
+            y, y_audio = self.decode_av(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
+                                        audio_conceal=audio_conceal, audio_fade=audio_fade)
+            return y, nb_valid == 0, na_valid == 0, y_audio
         y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
                         audio_conceal=audio_conceal)
         return y, nb_valid == 0, na_valid == 0
 
     def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                        fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
+                        fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
         time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit.
-        ``decoder="stateful"``: the same tensors from the stateful decoder (per-stage history instead of the 36-token window)."""
+        ``decoder="stateful"``: the same tensors from the stateful decoder (per-stage history instead of the 36-token window).
+        ``audio_out=True`` (``audio_fade``: packets.AudioFade or None): push / finish return (y_tactile, y_audio), the audio waveform
+        chunk by chunk, equal to decompress_packets_av(audio_out=True)'s."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
                               out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,
-                              decoder=decoder)
+                              decoder=decoder, audio_out=audio_out, audio_fade=audio_fade)
 
     def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
                              decoder="window"):
@@ -1179,7 +1258,9 @@ class ProposedEval(_ProposedBase):
                                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
         """stream_receiver_pool for the whole link (stream.StreamReceiverPoolAV): ``audio=(K_a, na)``, ``fec`` / ``audio_fec``,
         ``audio_conceal`` and ``decoder`` mean what they mean on stream_receiver, and each session gets what a
-        stream_receiver(batch=1) with the same options would return.  ``audio=None``: the audio codes arrive as codes."""
+        stream_receiver(batch=1) with the same options would return.  ``audio=None``: the audio codes arrive as codes.
+        The audio output (``audio_out`` / ``audio_fade``, as on stream_receiver) is the class's: StreamReceiverPoolAV(net, K, nb,
+        ..., audio_out=True); this factory's signature is pinned as it is."""
         from .stream import StreamReceiverPoolAV
         return StreamReceiverPoolAV(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
                                     out_rate=out_rate, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,

@@ -981,7 +981,7 @@ class _ReceiverCore:
     pool session computes what a solo one does."""
 
     def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None,
-                 audio_conceal="zero", decoder="window", who="StreamReceiver"):
+                 audio_conceal="zero", decoder="window", who="StreamReceiver", audio_out=False, audio_fade=None):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check, body_bytes
@@ -989,6 +989,8 @@ class _ReceiverCore:
         if decoder not in ("window", "stateful"):
             raise ValueError(f"{who}: decoder must be 'window' or 'stateful', not {decoder!r}")
         self.decoder = decoder
+        if audio_out or audio_fade is not None:                                        # ValueError before any session state exists
+            net._audio_out_args(who, audio_out, audio_fade)
         if decoder == "stateful":
             _f32_only(f"{who}(decoder='stateful')")
             if tuple(net.T_DEC._desc[2]) != DEC_RATES or net.T_DEC._desc[4]:
@@ -1027,6 +1029,17 @@ class _ReceiverCore:
             self.hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)   # per session: the last <= 20 latent tokens
         else:                                                                          # per session: every decoder stage's tail (section 23)
             self.dec_state = net.T_DEC.stream_state(rows)
+        # the audio output (section 27): a second decoder state fed with qa -- hist [rows, C, 20] or the audio decoder's stage tails --
+        # and the fade's run lengths [rows, 11]; audio_out=False allocates nothing and launches nothing
+        self.audio_out, self.audio_fade = bool(audio_out), audio_fade
+        self.a_hist = self.a_dec_state = self.fade_state = None
+        if self.audio_out:
+            if decoder == "window":
+                self.a_hist = torch.zeros(rows, self.C, 2 * DEC_HALO_TOK, device=self.dev)
+            else:
+                self.a_dec_state = net.audio_decoder.stream_state(rows)
+            if audio_fade is not None and self.audio is not None:         # codes that arrive as codes lose nothing: no fade
+                self.fade_state = ops.audio_fade_state(rows, self.dev)
         self.rs_state = self.rs_kernel = None
         if self.out_rate != proposed.EVAL_SR:
             from .resample import sinc_resample_kernel
@@ -1074,7 +1087,8 @@ class _ReceiverCore:
     def _latents(self, up, codes, n, sl=None, last=False):
         """Device: upload (the G*P packet bodies, then their G*P counts) and codes [G, 32, n] -> indices -> latents [G, C, n].  The carried
         token moves on in place; for slots through a dense [G, C] copy, not written back for sessions that end (``last``: the
-        next open() resets the slot)."""
+        next open() resets the slot).  With audio_out: -> (z, qa, nav), the audio latent as the predictor saw it and the chunk's
+        per-token stage counts (None when the codes arrived as codes: nothing of them is ever lost)."""
         from . import ops
         from .packets import StreamInfo
         G, full = (self.carry.shape[0] if codes is None else codes.shape[0]) if sl is None else len(sl[0]), self.full
@@ -1102,44 +1116,70 @@ class _ReceiverCore:
                                                self.audio[1], n, self.packet_tok)
             codes = aidx.permute(1, 0, 2).contiguous()                                 # [na, G, n] -> [G, na, n], on the device
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
+        want_qa = {"return_qa": True} if self.audio_out else {}
         if self.audio_conceal == "zero":
-            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav)
+            z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav,
+                                        **want_qa)
         else:                                                 # "mask" is stateless per chunk; "hold" moves qa_carry on in place
             z = self.net.decode_latents(codes, idx, books_use=self.books_use, nb_valid=nbv, z_prev=carry, z_last_out=carry, na_valid=nav,
                                         audio_conceal=self.audio_conceal, qa_prev=self.qa_carry, qa_last_out=self.qa_carry,
-                                        **({} if sl is None or self.qa_carry is None else {"qa_slots": sl[0], "qa_slots_dev": sl[1]}))
+                                        **({} if sl is None or self.qa_carry is None else {"qa_slots": sl[0], "qa_slots_dev": sl[1]}),
+                                        **want_qa)
+        qa = None
+        if self.audio_out:
+            z, qa = z
         if sl is not None and not last:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
         if self.conceal == "zero":                            # the post-pass of decode_latents(conceal="zero"), after the carry
             z = ops.plc_mask_fill(z, None, nbv == 0)[0]
-        return z
+        return (z, qa, nav) if self.audio_out else z
 
-    def _window_decode(self, z, h_in, h_out, e0, e1, sl=None, last=False):
+    def _window_decode(self, z, h_in, h_out, e0, e1, sl=None, last=False, audio=False):
         """Device: window = [history | z] (history updated in place), T_DEC on it, samples [e0, e1) of the window's output.
         decoder="stateful": the same samples from T_DEC.forward_stream, every stage on [its tail | its new columns] (dec_state updated
         in place).  h_in = min(tokens_before, 20) stands for tokens_before there: the stage plan depends on it only through
-        min(tokens_before, 16)."""
+        min(tokens_before, 16).  ``audio``: the same plan on the audio branch -- z is qa, the decoder the attached audio decoder, the
+        state a_hist / a_dec_state."""
         from . import ops
-        if self.dec_state is not None:
-            y = self.net.T_DEC.forward_stream(self.dec_state, z, h_in, last, slots=None if sl is None else sl[0],
-                                              slots_dev=None if sl is None else sl[1])
+        dec, hist, dec_state = (self.net.audio_decoder, self.a_hist, self.a_dec_state) if audio else (self.net.T_DEC, self.hist, self.dec_state)
+        if dec_state is not None:
+            y = dec.forward_stream(dec_state, z, h_in, last, slots=None if sl is None else sl[0],
+                                   slots_dev=None if sl is None else sl[1])
             assert y.shape[-1] == e1 - e0
             return y
         if sl is None:
-            win = ops.stream_window(self.hist, h_in, z, h_out)
+            win = ops.stream_window(hist, h_in, z, h_out)
         else:
-            win = ops.stream_window_slots(self.hist, sl[0], h_in, z, h_out, slots_dev=sl[1])
-        return self.net.T_DEC(win)[..., e0:e1]
+            win = ops.stream_window_slots(hist, sl[0], h_in, z, h_out, slots_dev=sl[1])
+        return dec(win)[..., e0:e1]
+
+    def _audio_step(self, qa, nav, h_in, h_out, e0, e1, sl, last):
+        """Device, behind the tactile decode and on its stream: the same window plan / stage plan on qa through the audio decoder,
+        then the fade in place on the emitted piece (ops.audio_fade_; fade_state moves on).  The piece starts at token
+        max(0, tokens_before - 10); the fade launch depends on that only through "is it 0", which min(tokens_before, 20) = h_in tells.
+        A session whose codes arrive as codes (audio=None) loses nothing and has no fade state: no fade launch."""
+        from . import ops
+        y = self._window_decode(qa, h_in, h_out, e0, e1, sl, last, audio=True).contiguous()
+        if self.fade_state is not None and y.shape[-1] > 0:
+            ops.audio_fade_(y, nav, self.fade_state, self.audio_fade, max(0, h_in - DEC_HALO_TOK),
+                            slots=None if sl is None else sl[0], slots_dev=None if sl is None else sl[1])
+        return y
 
     def _device_step(self, up, codes, n, h_in, h_out, e0, e1, sl=None, last=False):
         """A step up to the emit slice -> y [G, 1, e1 - e0].  n = 0 (a finish without a partial chunk) decodes the history alone;
-        without a history either (a session that never got a token) nothing runs."""
+        without a history either (a session that never got a token) nothing runs.  With audio_out -> (y, y_audio), the audio
+        branch (``_audio_step``) after the tactile one, one after the other on the one stream."""
         import torch
         G = self.carry.shape[0] if sl is None else len(sl[0])
         if h_in + n == 0:
-            return torch.empty(G, 1, 0, device=self.dev)
+            y = torch.empty(G, 1, 0, device=self.dev)
+            return (y, torch.empty(G, 1, 0, device=self.dev)) if self.audio_out else y
         z = self._latents(up, codes, n, sl, last) if n else torch.empty(G, self.C, 0, device=self.dev)
-        return self._window_decode(z, h_in, h_out, e0, e1, sl, last)
+        if not self.audio_out:
+            return self._window_decode(z, h_in, h_out, e0, e1, sl, last)
+        z, qa, nav = z if n else (z, torch.empty(G, self.C, 0, device=self.dev), None)
+        y = self._window_decode(z, h_in, h_out, e0, e1, sl, last)
+        return y, self._audio_step(qa, nav, h_in, h_out, e0, e1, sl, last)
 
     def _decimate(self, y, consumed, last, sl=None):
         """out_rate=3000: the emitted piece through the streamed resampler, ``consumed`` = the samples the sessions emitted before
@@ -1199,10 +1239,19 @@ class StreamReceiver(_ReceiverCore):
     ``decoder="stateful"`` (the default "window" is the sequence above, launch for launch): instead of T_DEC on
     the 36-token window, T_DEC.forward_stream -- every decoder stage keeps the tail of its own input in dec_state [B, S] (it replaces
     the history [B, C, 20]) and computes only its new columns.  Every push / finish returns exactly the window mode's tensor; the
-    steady step stays ONE captured graph; everything in front of the latents and behind the samples is untouched."""
+    steady step stays ONE captured graph; everything in front of the latents and behind the samples is untouched.
+
+    ``audio_out=True`` (needs net.set_audio_decoder; False: everything above, launch for launch): ``push`` and
+    ``finish`` return (y_tactile, y_audio).  y_audio [B, 1, n] is the audio waveform of the same samples at 24 kHz (``out_rate``
+    acts on the tactile output only): after the tactile decode the step runs the same window plan (a second history a_hist
+    [B, C, 20]) or stage plan (a second a_dec_state) on qa, the audio latent the predictor saw, through the audio decoder, on the
+    same stream.  ``audio_fade`` (packets.AudioFade): with ``audio=(K_a, na)`` the emitted piece then goes through ops.audio_fade_,
+    whose state fade_state [B, 11] carries the loss runs across chunks.  The concatenated y_audio equals
+    decompress_packets_av(audio_out=True, audio_fade=)'s.  With graph=True the steady step stays ONE captured graph, with two
+    output buffers."""
 
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window"):
+                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
@@ -1210,7 +1259,7 @@ class StreamReceiver(_ReceiverCore):
         if fec is not None or audio_fec is not None:
             _f32_only("StreamReceiver")
         super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
-                         audio_conceal=audio_conceal, decoder=decoder)
+                         audio_conceal=audio_conceal, decoder=decoder, audio_out=audio_out, audio_fade=audio_fade)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -1294,6 +1343,8 @@ class StreamReceiver(_ReceiverCore):
             else:
                 y = self._device_step(torch.from_numpy(host).to(self.dev), None if codes is None else codes.to(self.dev), n, *plan)
             self.h, self.tokens = plan[1], self.tokens + n
+            if self.audio_out:
+                return self._decimate(y[0], consumed, False), y[1]
             return self._decimate(y, consumed, False)
 
     def _audio_arg(self, what, audio_codes, audio_packets):
@@ -1340,6 +1391,8 @@ class StreamReceiver(_ReceiverCore):
                 up, codes = torch.from_numpy(host).to(self.dev), None if codes is None else codes.to(self.dev)
             y = self._device_step(up, codes, n, *plan, last=True)
             self.h, self.tokens, self.finished = plan[1], self.tokens + n, True
+            if self.audio_out:
+                return self._decimate(y[0], consumed, True), y[1]
             return self._decimate(y, consumed, True)
 
     def _replay(self, host, codes, n, plan):
@@ -1350,7 +1403,8 @@ class StreamReceiver(_ReceiverCore):
             up_s = torch.from_numpy(host).to(self.dev)
             codes_s = None if codes is None else codes.to(self.dev).long().clone()
             state = (self.hist if self.dec_state is None else self.dec_state, self.carry) + \
-                ((self.qa_carry,) if self.qa_carry is not None else ())
+                ((self.qa_carry,) if self.qa_carry is not None else ()) + \
+                tuple(t for t in (self.a_hist, self.a_dec_state, self.fade_state) if t is not None)
             g, y_s = _capture(self.dev, state, lambda: self._device_step(up_s, codes_s, n, *plan))
             self._g = (g, up_s, codes_s, y_s)
             if self.fec is not None or self.audio_fec is not None:            # the eager run before the capture recovered in place
@@ -1388,9 +1442,11 @@ class StreamReceiverPool(_ReceiverCore):
     _who = "StreamReceiverPool"
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
-                 decoder="window"):
+                 decoder="window", audio_out=False, audio_fade=None):
         if audio_conceal is not None:
             raise ValueError("StreamReceiverPool: the pool takes no audio= packets and so no audio_conceal")
+        if audio_out or audio_fade is not None:
+            raise ValueError("StreamReceiverPool: the pool has no audio output; audio_out / audio_fade go with StreamReceiverPoolAV")
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
         _receiver_args("StreamReceiverPool", net, K, nb, packet_tok, conceal, out_rate)
         if slots < 1:
@@ -1759,19 +1815,25 @@ class StreamReceiverPoolAV(StreamReceiverPool):
     ONE of the audio codes, for audio=None only); then per group _ReceiverCore's sequence on the group's slots: ops.fec_recover in
     place, both unpacks, the carried token through ops.stream_rows, decode_latents -- "hold" addresses the held audio token qa_carry
     [S, C] through the slot list (ops.hold_fill_(slots=)) -- and the decode.  Nothing is read back.  ``open`` resets the slot's
-    carried token, held audio token and resampler state."""
+    carried token, held audio token and resampler state.
+
+    ``audio_out`` / ``audio_fade`` (StreamReceiver's): a session's result is (y_tactile, y_audio).  The pool
+    holds a second decoder state (a_hist [S, C, 20] or a_dec_state) and the fade's run lengths fade_state [S, 11]; a group's step
+    runs the audio branch on the group's slots after the tactile one.  ``open`` clears none of them: a new session reads no
+    history, no tail and no run length."""
 
     _who = "StreamReceiverPoolAV"
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio=None, fec=None,
-                 audio_fec=None, audio_conceal="zero", decoder="window"):
+                 audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
         _receiver_args(self._who, net, K, nb, packet_tok, conceal, out_rate)
         if slots < 1:
             raise ValueError(f"{self._who}: slots must be at least 1")
         _f32_only(self._who)
         _ReceiverCore.__init__(self, net, K, nb, packet_tok, slots, books_use, conceal, out_rate, audio=audio, fec=fec,
-                               audio_fec=audio_fec, audio_conceal=audio_conceal, decoder=decoder, who=self._who)
+                               audio_fec=audio_fec, audio_conceal=audio_conceal, decoder=decoder, who=self._who, audio_out=audio_out,
+                               audio_fade=audio_fade)
         self.slots = slots
         self._free = list(range(slots))                                                # ascending: open() takes the lowest
         self._sess = {}                                                                # sid -> [slot, tokens, late]
@@ -1891,10 +1953,12 @@ class StreamReceiverPoolAV(StreamReceiverPool):
                     codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n)
                     c0 += G * self.n_audio_books * n
                 seg = up[o:o + lay.size] if lay is not None else None
-                y = self._decimate(self._device_step(seg, codes, n, *g.plan, sl=sl, last=last), g.consumed, last, sl)
+                y = self._device_step(seg, codes, n, *g.plan, sl=sl, last=last)
+                y, ya = y if self.audio_out else (y, None)
+                y = self._decimate(y, g.consumed, last, sl)
                 s0 += G
                 for i, sid in enumerate(g.sids):
-                    out[sid] = y[i:i + 1]
+                    out[sid] = (y[i:i + 1], ya[i:i + 1]) if self.audio_out else y[i:i + 1]
         for sid, w in work.items():
             if w[1]:
                 self.close(sid)

@@ -23,6 +23,7 @@ shape-only fake implementation; the real one is the HIP kernel behind ``ops.py``
   attention_seq_f32           mvq_attention_seq_f32      CrossPredictor attention over a whole sequence (PLC/PLC1.py:316-317)
   attention_seq_masked_f32    mvq_attention_seq_masked_f32 the same under a key mask uint8 [B,Tk] (receiver audio concealment "mask")
   mel_ssim_f32                mvq_mel_ssim_f32           mel ST-SIM of column-listed image pairs (PLC/PLC1_eval.py:270-333)
+  audio_fade                  mvq_audio_fade_f32         receiver audio output: lost tokens fade out and in (mutates `y` and `state`)
 
 Weights are the PACKED images of ``ops.pack_conv1d`` / ``ops.pack_conv_transpose1d`` (made once per weight load).  Import this module
 to register (``import multimodal_vqvae_compression_audio_tactile_amd.torch_ops``); the package does not import it by itself.
@@ -145,7 +146,7 @@ def _(z, gy, stack):
 
 REGISTERED = ("encoder_fwd", "decoder_fwd", "decoder_bwd_input", "conv1d_snake_f32", "conv_transpose1d_snake_f32", "residual_unit_f32", "vq_rvq_search_f32", "vq_cosine_rvq_f32",
               "ema_update_f32", "attention_seq_f32", "attention_seq_masked_f32", "mel_ssim_f32", "rvq_dequant", "dac_rvq_from_codes",
-              "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets", "dac_rvq_from_codes_layers")
+              "rvq_dequant_layers", "idx_pack_packets", "idx_unpack_packets", "dac_rvq_from_codes_layers", "audio_fade")
 
 
 @torch.library.custom_op(f"{NS}::attention_seq_f32", mutates_args=())
@@ -242,3 +243,14 @@ def idx_unpack_packets(bodies: Tensor, nb_recv: Tensor, k: int, nb: int, t: int,
 def _(bodies, nb_recv, k, nb, t, packet_tok):
     B = bodies.shape[0]
     return bodies.new_empty(nb, B, t, dtype=torch.int64), bodies.new_empty(B, t, dtype=torch.uint8)
+
+
+@torch.library.custom_op(f"{NS}::audio_fade", mutates_args=("y", "state"))
+def audio_fade(y: Tensor, valid: Optional[Tensor], state: Tensor, hold_tok: int, fade_tok: int, tok0: int) -> None:
+    from .packets import AudioFade
+    ops.audio_fade_(y, valid, state, AudioFade(hold_tok, fade_tok), tok0)
+
+
+@audio_fade.register_fake
+def _(y, valid, state, hold_tok, fade_tok, tok0):
+    return None
