@@ -311,17 +311,23 @@ class _ProposedBase(nn.Module):
         return fec
 
     @staticmethod
-    def _fec_gather(fec, fec_packets, info, B, who, what="fec"):
-        """Host: per item whatever parity packets arrived -> (rows uint8 [B, G, g + W], got uint8 [B, G]); with fec.parity = r > 1
-        rows uint8 [B, G, r, g + W] and got the bitmask of the arrived parity indices."""
-        from . import packets
+    def _fec_packets(fec, fec_packets, B, who, what="fec"):
+        """The parity packets of a whole-item call, per item -> ``fec_packets``, or B times None for a stream without a Fec."""
+        if fec is None:
+            return [None] * B
         if fec_packets is None or len(fec_packets) != B:
             raise MvqError(f"{who}: {what}= needs {what}_packets, one list of parity packets per item (empty when none arrived)")
-        rshape = fec.rows_shape(info)
-        rows, got = np.empty((B, *rshape), np.uint8), np.empty((B, rshape[0]), np.uint8)
+        return fec_packets
+
+    @staticmethod
+    def _rx_host(front, B, T, *per_item):
+        """Host: the whole-item upload of ``B`` items through the front end (stream._RxFront, which owns its format): gather_item
+        and fill per item; ``per_item`` = the tactile, audio, parity and audio parity packets, each a list per item -> (lay, host)."""
+        lay = front.layout(B, T)
+        host = np.empty(lay.size, np.uint8)
         for b in range(B):
-            rows[b], got[b] = packets.gather_fec(fec_packets[b], info, fec)
-        return rows, got
+            front.fill(host, lay, b, front.gather_item(*(pk[b] for pk in per_item), T))
+        return lay, host
 
     @torch.no_grad()
     def _ar_latents(self, qa, zt, books_use=None, want_tokens=False, tactile_only=False, want_indices=False, z_prev=None,
@@ -1045,6 +1051,7 @@ class ProposedEval(_ProposedBase):
         With ``fec.parity = r > 1`` the upload carries r rows per group and ``got`` as a bitmask of the arrived parity indices; a
         group gets back any d <= (arrived parities) deficient packets, still in the one launch."""
         from . import bitstream, packets
+        from .stream import _RxFront
         if fec is None and fec_packets is not None:
             raise MvqError("decompress_packets: fec_packets needs fec=, the packets.Fec both ends agreed on")
         if not (len(infos) == len(tactile_packets) == len(audio_payloads)):
@@ -1058,25 +1065,13 @@ class ProposedEval(_ProposedBase):
             raise ValueError("decompress_packets: the items of a batch must share one StreamInfo")
         if info.K != self.vq.n_embed:
             raise ValueError(f"decompress_packets: the stream has K = {info.K}, the model's codebook has {self.vq.n_embed}")
-        P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
-        n_fec = 0
         if fec is not None:
             self._fec_resolve(fec, info.K, info.nb, info.packet_tok)
-            frows, fgot = self._fec_gather(fec, fec_packets, info, B, "decompress_packets")
-            n_fec = frows.size + fgot.size
-        host = np.empty(B * P * (full + 1) + n_fec, np.uint8)                 # bodies, then nb_recv (then parity rows, flags): one upload
-        hb, hr = host[:B * P * full].reshape(B, P, full), host[B * P * full:B * P * (full + 1)].reshape(B, P)
-        for b in range(B):
-            hb[b], hr[b] = packets.gather(tactile_packets[b], info)
-        if fec is not None:
-            o = B * P * (full + 1)
-            host[o:o + frows.size], host[o + frows.size:] = frows.reshape(-1), fgot.reshape(-1)
+        none = [None] * B
+        front = _RxFront(info.K, info.nb, info.packet_tok, fec=fec)           # bodies, then nb_recv (then parity rows, flags): one upload
+        lay, host = self._rx_host(front, B, info.T, tactile_packets, none, self._fec_packets(fec, fec_packets, B, "decompress_packets"), none)
         codes = [self._payload(bitstream, p, self.A_QUANT.codebook_size, "audio") for p in audio_payloads]
-        up = torch.from_numpy(host).to(dev)
-        ub, ur = up[:B * P * full].view(B, P, full), up[B * P * full:B * P * (full + 1)].view(B, P)
-        if fec is not None:
-            ops.fec_recover(ub, ur, up[o:o + frows.size].view(frows.shape), up[o + frows.size:].view(fgot.shape), info, fec)
-        idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
+        idx, nb_valid, _, _ = front.unpack(torch.from_numpy(host).to(dev), lay, B, info.T)
         codes_t = torch.from_numpy(np.stack(codes, axis=0)).to(dev)
         y = self.decode(codes_t, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc)
         return y, nb_valid == 0
@@ -1149,6 +1144,7 @@ class ProposedEval(_ProposedBase):
         without it and y_audio [B, 1, 320*Ta - 8] the audio waveform, decode_av's: the audio decoder on the audio latent the predictor
         saw, then ``audio_fade`` (packets.AudioFade or None) over the tokens that are still lost after recovery."""
         from . import packets
+        from .stream import _RxFront
         self._audio_out_args("decompress_packets_av", audio_out, audio_fade)
         if audio_conceal not in ("zero", "mask", "hold"):
             raise MvqError(f"decompress_packets_av: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
@@ -1173,31 +1169,14 @@ class ProposedEval(_ProposedBase):
         if ainfo.T != info.T:
             raise ValueError(f"decompress_packets_av: the audio stream has T = {ainfo.T} tokens, the tactile stream {info.T}; the two "
                              "modalities advance together")
-        P, full = info.P, packets.body_bytes(info.packet_tok, info.nb, info.K)
-        Pa, afull = ainfo.P, packets.body_bytes(ainfo.packet_tok, ainfo.nb, ainfo.K)
-        extra = []                                                            # (fec, info, rows, got, slot of the stream's bodies)
-        for f, fp, inf, slot, what in ((fec, fec_packets, info, 0, "fec"), (audio_fec, audio_fec_packets, ainfo, 2, "audio_fec")):
+        parity = []
+        for f, fp, inf, what in ((fec, fec_packets, info, "fec"), (audio_fec, audio_fec_packets, ainfo, "audio_fec")):
             if f is not None:
                 self._fec_resolve(f, inf.K, inf.nb, inf.packet_tok, what=what)
-                extra.append((f, inf, *self._fec_gather(f, fp, inf, B, "decompress_packets_av", what), slot))
-        cuts = np.cumsum([0, B * P * full, B * P, B * Pa * afull, B * Pa] + [x.size for e in extra for x in e[2:4]])
-        host = np.empty(cuts[-1], np.uint8)                                   # both streams' bodies and counts (parity rows, flags): one upload
-        hb, hr, ab, ar = (host[cuts[i]:cuts[i + 1]] for i in range(4))
-        hb, hr, ab, ar = hb.reshape(B, P, full), hr.reshape(B, P), ab.reshape(B, Pa, afull), ar.reshape(B, Pa)
-        for b in range(B):
-            hb[b], hr[b] = packets.gather(tactile_packets[b], info)
-            ab[b], ar[b] = packets.gather(audio_packets[b], ainfo)
-        for i, e in enumerate(extra):
-            host[cuts[4 + 2 * i]:cuts[5 + 2 * i]], host[cuts[5 + 2 * i]:cuts[6 + 2 * i]] = e[2].reshape(-1), e[3].reshape(-1)
-        up = torch.from_numpy(host).to(dev)
-        ub, ur, uab, uar = (up[cuts[i]:cuts[i + 1]] for i in range(4))
-        ub, ur, uab, uar = ub.view(B, P, full), ur.view(B, P), uab.view(B, Pa, afull), uar.view(B, Pa)
-        for i, (f, inf, rows, got, slot) in enumerate(extra):
-            ops.fec_recover(*((ub, ur) if slot == 0 else (uab, uar)), up[cuts[4 + 2 * i]:cuts[5 + 2 * i]].view(rows.shape),
-                            up[cuts[5 + 2 * i]:cuts[6 + 2 * i]].view(got.shape), inf, f)
-        idx, nb_valid = ops.idx_unpack_packets(ub, ur, info.K, info.nb, info.T, info.packet_tok)
-        aidx, na_valid = ops.idx_unpack_packets(uab, uar, ainfo.K, ainfo.nb, ainfo.T, ainfo.packet_tok)
-        codes = aidx.permute(1, 0, 2).contiguous()                            # [nq, B, Ta] -> [B, nq, Ta], on the device
+            parity.append(self._fec_packets(f, fp, B, "decompress_packets_av", what))
+        front = _RxFront(info.K, info.nb, info.packet_tok, (ainfo.K, ainfo.nb), fec, audio_fec)
+        lay, host = self._rx_host(front, B, info.T, tactile_packets, audio_packets, *parity)   # both streams' arrays: one upload
+        idx, nb_valid, codes, na_valid = front.unpack(torch.from_numpy(host).to(dev), lay, B, info.T)
         if audio_out:
             y, y_audio = self.decode_av(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
                                         audio_conceal=audio_conceal, audio_fade=audio_fade)

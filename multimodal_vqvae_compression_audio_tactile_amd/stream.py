@@ -38,10 +38,13 @@ tick batches whichever sessions have a chunk ready, grouped by ``pool_groups`` (
 is a session's host arithmetic, ``sender_pool_groups`` the sessions of a tick that share an encode.
 ``StreamSenderPoolAV`` / ``StreamReceiverPoolAV`` (``ProposedEval.stream_sender_pool_av`` / ``stream_receiver_pool_av``) are the two
 pools with every option of the lockstep sessions -- rate control, audio packets, FEC on both streams, audio concealment: the same
-sessions and groups, ``receiver_layout`` the upload of a group, ``_SenderCore._frame_one`` a session's framing.
+sessions and groups, ``_SenderCore._frame_one`` a session's framing.  ``_RxFront`` is every receiver's front
+end -- the whole-item calls', the lockstep session's and the pools': it owns the format of the upload (``receiver_layout``), fills
+it on the host and unpacks it on the device; ``_SessionTable`` is the session bookkeeping the four pools share.
 """
 from __future__ import annotations
 
+import functools
 from typing import List, NamedTuple, Tuple
 
 HOP = 320                         # samples per latent token (the product of the decoder rates)
@@ -357,8 +360,8 @@ class RxLayout(NamedTuple):
 
 
 def receiver_layout(G: int, n: int, full: int, afull, fec, audio_fec, packet_tok: int) -> RxLayout:
-    """The layout of what a receiver step uploads for ``G`` items of ``n`` tokens, as _ReceiverCore._latents reads it (host
-    arithmetic; StreamReceiver._gather with G = batch and StreamReceiverPoolAV.step with G = a group's sessions both build it):
+    """The layout of what a receiver uploads for ``G`` items of ``n`` tokens (host arithmetic; ``_RxFront`` is its one user and
+    every receiver goes through that -- G = the batch of a whole-item call or a lockstep session, or a pool group's sessions):
     the tactile bodies uint8 [G, P, full], their counts [G, P]; with ``afull`` not None (audio packets) the audio bodies
     [G, P, afull] and their counts [G, P]; then per stream with a Fec -- ``fec`` / ``audio_fec`` = (group g, parity r, width W) as
     Fec.resolve gives them for the stream, or None -- its parity rows [G, Gr, r*(g + W)], Gr = ceil(P / g), then ``got`` [G, Gr]."""
@@ -379,6 +382,77 @@ def receiver_layout(G: int, n: int, full: int, afull, fec, audio_fec, packet_tok
         at.append((o, o + nr))
         o += nr + G * ((P + g - 1) // g)
     return RxLayout(P, 0, G * P * full, ab, ac, at[0], at[1], o)
+
+
+class _RxFront:
+    """THE receiver front end, from "the packets that arrived" to indices and per-token counts on the device: the owner of the
+    upload's format.  decompress_packets / decompress_packets_av, StreamReceiver and both receiver pools
+    build their upload and read it through this object and hold no offset of their own.  A stream is the tactile one
+    (``K``, ``nb``, ``fec``) and, with ``audio`` = (K_a, na), the audio one (``audio_fec``); one ``packet_tok`` serves both."""
+
+    def __init__(self, K, nb, packet_tok, audio=None, fec=None, audio_fec=None):
+        from .packets import body_bytes, gather, gather_fec
+        self._gather, self._gather_fec = gather, gather_fec
+        self.K, self.nb, self.packet_tok, self.audio, self.fec, self.audio_fec = K, nb, packet_tok, audio, fec, audio_fec
+        self.full = body_bytes(packet_tok, nb, K)
+        self.afull = None if audio is None else body_bytes(packet_tok, audio[1], audio[0])
+        # pure functions of n, (G, n) and the layout, and a session asks for the same ones with every chunk: computed once each
+        self._streams, self.layout, self._spans = (functools.lru_cache(None)(f) for f in (self._streams, self.layout, self._spans))
+
+    def _streams(self, n):
+        """(StreamInfo of ``n`` tokens, Fec or None) per stream: tactile, then audio."""
+        from .packets import StreamInfo
+        out = ((StreamInfo(self.K, self.nb, n, self.packet_tok), self.fec),)
+        return out if self.audio is None else out + ((StreamInfo(*self.audio, n, self.packet_tok), self.audio_fec),)
+
+    def layout(self, G, n) -> RxLayout:
+        """receiver_layout of ``G`` items of ``n`` tokens for these streams, every Fec resolved against its stream."""
+        code = [None if f is None else (f.resolve(inf)[0], f.r, f.resolve(inf)[3]) for inf, f in self._streams(n)] + [None]
+        return receiver_layout(G, n, self.full, self.afull, code[0], code[1], self.packet_tok)
+
+    @staticmethod
+    def _spans(lay):
+        """[start, end) of every part of a segment, in layout order: the one place that turns an RxLayout into slices."""
+        starts = [lay.bodies, lay.counts] + ([lay.abodies, lay.acounts] if lay.abodies is not None else [])
+        starts += [o for at in (lay.fec, lay.audio_fec) if at is not None for o in at]
+        return tuple(zip(starts, starts[1:] + [lay.size]))
+
+    def gather_item(self, tactile, audio, fec_pk, audio_fec_pk, n, seq_base=0, late=None):
+        """Host: whatever packets of ONE item's ``n`` tokens arrived -> its arrays in layout order: packets.gather per stream,
+        then packets.gather_fec per stream with a Fec (None: no parity packet arrived).  ``seq_base`` / ``late`` as packets.gather
+        takes them; a stream's groups are numbered from seq_base // fec.group."""
+        streams, parts = self._streams(n), []
+        for (inf, _), pk in zip(streams, (tactile, audio)):
+            parts += self._gather(pk, inf, seq_base, late)
+        for (inf, f), pk in zip(streams, (fec_pk, audio_fec_pk)):
+            if f is not None:
+                parts += self._gather_fec(() if pk is None else pk, inf, f, seq_base // int(f.group), late)
+        return parts
+
+    def fill(self, seg, lay, i, parts):
+        """Host: item ``i``'s ``parts`` (gather_item's) into ``seg``, the uint8 segment of a group laid out by ``lay``: every
+        part of the segment is [G, bytes of one item]."""
+        for (at, _), part in zip(self._spans(lay), parts):
+            at += i * part.size
+            seg[at:at + part.size] = part.reshape(-1)
+
+    def unpack(self, up, lay, G, n):
+        """Device: views of the uploaded segment ``up`` by ``lay``, then per stream ops.fec_recover in place and
+        ops.idx_unpack_packets -- recover tactile, unpack tactile, recover audio, unpack audio, the order inside the captured
+        steady step -> (idx [nb, G, n], nb_valid [G, n], audio codes [G, na, n] or None, na_valid [G, n] or None)."""
+        from . import ops
+        streams = self._streams(n)
+        part = iter([up[a:b] for a, b in self._spans(lay)])               # consumed in layout order: data parts, then parity parts
+        data = [(next(part).view(G, lay.P, full), next(part).view(G, lay.P)) for _, full in zip(streams, (self.full, self.afull))]
+        out = []
+        for (inf, f), (bodies, counts) in zip(streams, data):
+            if f is not None:
+                shape = f.rows_shape(inf)
+                ops.fec_recover(bodies, counts, next(part).view(G, *shape), next(part).view(G, shape[0]), inf, f)
+            out += ops.idx_unpack_packets(bodies, counts, inf.K, inf.nb, n, self.packet_tok)
+        if self.audio is None:
+            return out[0], out[1], None, None
+        return out[0], out[1], out[2].permute(1, 0, 2).contiguous(), out[3]   # [na, G, n] -> [G, na, n], on the device
 
 
 class SenderStep(NamedTuple):
@@ -526,6 +600,53 @@ def _capture(dev, state, step):
             out = step()
     torch.cuda.current_stream().wait_stream(s)
     return g, out
+
+
+class _SessionTable:
+    """The session bookkeeping of a pool, receiver and sender alike: ``slots`` row blocks of the state buffers, the free ones
+    ascending, and per open session ``_sess[sid]`` = [slot, ...the kind's host state]; a sid is never reused."""
+
+    def _init_sessions(self, slots):
+        self.slots = slots
+        self._free = list(range(slots))                                                # ascending: open() takes the lowest
+        self._sess = {}
+        self._next_sid = 0
+
+    @property
+    def active(self):
+        """The sids of the open sessions, ascending."""
+        return tuple(sorted(self._sess))
+
+    @property
+    def free(self):
+        """Slots no session holds."""
+        return len(self._free)
+
+    def _get(self, sid, what):
+        from ._lib import MvqError
+        try:
+            return self._sess[sid]
+        except (KeyError, TypeError):
+            raise MvqError(f"{self._who}: {what}: no open session {sid!r} (never opened, finished or closed)") from None
+
+    def _take_slot(self):
+        """The lowest free slot, for ``open`` to reset and hand to ``_new_session``."""
+        from ._lib import MvqError
+        if not self._free:
+            raise MvqError(f"{self._who}: all {self.slots} slots hold a session")
+        return self._free.pop(0)
+
+    def _new_session(self, slot, *state):
+        sid, self._next_sid = self._next_sid, self._next_sid + 1
+        self._sess[sid] = [slot, *state]
+        return sid
+
+    def close(self, sid):
+        """Abandon session ``sid`` without flushing it; its slot is free again."""
+        import bisect
+        slot = self._get(sid, "close")[0]
+        del self._sess[sid]
+        bisect.insort(self._free, slot)
 
 
 def _sender_samples(who, what, a, t, B, fill, tail=False):
@@ -984,7 +1105,7 @@ class _ReceiverCore:
                  audio_conceal="zero", decoder="window", who="StreamReceiver", audio_out=False, audio_fade=None):
         import torch
         from . import ops, proposed
-        from .packets import StreamInfo, _check, body_bytes
+        from .packets import StreamInfo, _check
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
         if decoder not in ("window", "stateful"):
             raise ValueError(f"{who}: decoder must be 'window' or 'stateful', not {decoder!r}")
@@ -1014,13 +1135,13 @@ class _ReceiverCore:
                 raise ValueError(f"{who}: the audio stream has K = {K_a}, nb = {na}; the model's audio quantiser has "
                                  f"K = {net.A_QUANT.codebook_size} and {net.A_QUANT.n_codebooks} stages")
             _check(StreamInfo(K_a, na, CHUNK_TOK, packet_tok))
-            self.audio, self.afull = (K_a, na), body_bytes(packet_tok, na, K_a)
+            self.audio = (K_a, na)
             if audio_fec is not None:
                 net._fec_resolve(audio_fec, K_a, na, packet_tok, what="audio_fec")
+        self.front = _RxFront(K, nb, packet_tok, self.audio, fec, audio_fec)           # the upload's format, host and device side
         self.books_use, self.conceal, self.out_rate = books_use, conceal, int(out_rate)
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
-        self.full = body_bytes(packet_tok, nb, K)
         self.n_audio_books = net.A_QUANT.n_codebooks
         self.carry = torch.zeros(rows, self.C, device=self.dev)                        # per session: z_run[..., -1] of the chunk before
         self.qa_carry = torch.zeros(rows, self.C, device=self.dev) if audio_conceal == "hold" else None   # the last held audio token
@@ -1071,50 +1192,21 @@ class _ReceiverCore:
         return codes
 
     def _layout(self, G, n):
-        """receiver_layout of ``G`` items of ``n`` tokens for this session's streams."""
-        from .packets import StreamInfo
-
-        def code(f, K, nb):
-            if f is None:
-                return None
-            g, _, _, W = f.resolve(StreamInfo(K, nb, n, self.packet_tok))
-            return g, f.r, W
-
-        return receiver_layout(G, n, self.full, self.afull if self.audio is not None else None, code(self.fec, self.K, self.nb),
-                               code(self.audio_fec, *self.audio) if self.audio_fec is not None else None, self.packet_tok)
+        """The front end's layout of ``G`` items of ``n`` tokens for this session's streams."""
+        return self.front.layout(G, n)
 
     # ------------------------------------------------------------------------------------------------ the device sequence
     def _latents(self, up, codes, n, sl=None, last=False):
-        """Device: upload (the G*P packet bodies, then their G*P counts) and codes [G, 32, n] -> indices -> latents [G, C, n].  The carried
+        """Device: the upload (a segment of the front end's layout) and codes [G, 32, n] -> indices -> latents [G, C, n].  The carried
         token moves on in place; for slots through a dense [G, C] copy, not written back for sessions that end (``last``: the
         next open() resets the slot).  With audio_out: -> (z, qa, nav), the audio latent as the predictor saw it and the chunk's
         per-token stage counts (None when the codes arrived as codes: nothing of them is ever lost)."""
         from . import ops
-        from .packets import StreamInfo
-        G, full = (self.carry.shape[0] if codes is None else codes.shape[0]) if sl is None else len(sl[0]), self.full
-        P = (n + self.packet_tok - 1) // self.packet_tok
-        ub, ur = up[:G * P * full].view(G, P, full), up[G * P * full:G * P * (full + 1)].view(G, P)
-        o_fec = G * P * (full + 1) + (G * P * (self.afull + 1) if self.audio is not None else 0)   # the parity rows, flags: behind everything
-
-        def recover(f, inf, bodies, counts, o):               # packets.fec_recover in place, ahead of the unpack -> the offset behind
-            if f is None:
-                return o
-            g, _, Gr, W = f.resolve(inf)
-            nr = G * Gr * f.r * (g + W)                       # r parity rows per group; ``got`` is then a bitmask
-            ops.fec_recover(bodies, counts, up[o:o + nr].view(G, *f.rows_shape(inf)), up[o + nr:o + nr + G * Gr].view(G, Gr), inf, f)
-            return o + nr + G * Gr
-
-        o_fec = recover(self.fec, StreamInfo(self.K, self.nb, n, self.packet_tok), ub, ur, o_fec)
-        idx, nbv = ops.idx_unpack_packets(ub, ur, self.K, self.nb, n, self.packet_tok)
-        nav = None
-        if self.audio is not None:                            # behind the tactile arrays: the audio bodies, then their counts
+        G = (self.carry.shape[0] if codes is None else codes.shape[0]) if sl is None else len(sl[0])
+        idx, nbv, acodes, nav = self.front.unpack(up, self._layout(G, n), G, n)
+        if self.audio is not None:                            # the audio codes arrived as packets
             assert codes is None
-            o, afull = G * P * (full + 1), self.afull
-            uab, uar = up[o:o + G * P * afull].view(G, P, afull), up[o + G * P * afull:o + G * P * (afull + 1)].view(G, P)
-            recover(self.audio_fec, StreamInfo(self.audio[0], self.audio[1], n, self.packet_tok), uab, uar, o_fec)
-            aidx, nav = ops.idx_unpack_packets(uab, uar, self.audio[0],
-                                               self.audio[1], n, self.packet_tok)
-            codes = aidx.permute(1, 0, 2).contiguous()                                 # [na, G, n] -> [G, na, n], on the device
+            codes = acodes
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
         want_qa = {"return_qa": True} if self.audio_out else {}
         if self.audio_conceal == "zero":
@@ -1205,9 +1297,10 @@ class StreamReceiver(_ReceiverCore):
     is claimed for them.  A push returns the samples up to 10 tokens (the decoder look-ahead) before the newest token, so the
     algorithmic latency is one chunk plus the halo, 213.3 + 133.3 ms, instead of the whole item.
 
-    ``push`` runs, in order: packets.gather(seq_base=) per item -> ONE upload of the packet bodies and counts ->
-    ops.idx_unpack_packets -> decode_latents(nb_valid=, z_prev=carry, z_last_out=carry) -> ops.stream_window (window = history
-    | new latents; history updated in place) -> T_DEC on the window -> the emit slice (-> ops.resample_stream for out_rate=3000):
+    ``push`` runs, in order: _RxFront.gather_item(seq_base=) and .fill per item -> ONE upload, the front end's segment for the batch
+    (what it holds and where: _RxFront) -> _RxFront.unpack -> decode_latents(nb_valid=, z_prev=carry, z_last_out=carry) ->
+    ops.stream_window (window = history | new latents; history updated in place) -> T_DEC on the window -> the emit slice (->
+    ops.resample_stream for out_rate=3000):
     _ReceiverCore's sequence.  All session state is in fixed device buffers (carry [B, C], history [B, C, 20], rs_state [B, 105]).
 
     ``graph=True``: the steady step (36-token window, from the third push on) is captured once as a graph on one stream and
@@ -1230,8 +1323,8 @@ class StreamReceiver(_ReceiverCore):
 
     ``fec`` / ``audio_fec`` (packets.Fec, the sender's; ``audio_fec`` needs ``audio=``; both None: today's behaviour exactly):
     ``push(..., fec_packets=, audio_fec_packets=)`` and ``finish(...)`` likewise take, per item, whatever parity packets of the chunk
-    arrived (None: none did).  packets.gather_fec(seq_base=the chunk's first group) per item, the parity rows and ``got`` flags behind
-    the existing arrays in the ONE upload, ops.fec_recover in place ahead of each stream's unpack: recovery is inside the captured
+    arrived (None: none did).  The front end gathers them (packets.gather_fec(seq_base=the chunk's first group) per item) behind
+    the existing arrays of the ONE upload and runs ops.fec_recover in place ahead of each stream's unpack: recovery is inside the captured
     steady step, whose only input stays the static upload buffer, so the graph replays under any loss pattern.  A parity packet of
     an earlier chunk is counted in ``late`` and ignored, as a late data packet is.  The concatenated output equals
     decompress_packets(fec=) / decompress_packets_av(fec=, audio_fec=) on the same packets.
@@ -1269,32 +1362,16 @@ class StreamReceiver(_ReceiverCore):
 
     # ------------------------------------------------------------------------------------------------------------ stages
     def _gather(self, tactile_packets, n, audio_packets=None, fec_packets=None, audio_fec_packets=None):
-        """Host: per item whatever packets of this chunk arrived -> one uint8 array laid out by ``receiver_layout``: bodies then
-        counts (then, with audio packets, the audio bodies and their counts; then, with a Fec, per stream the parity rows and their
-        ``got`` flags)."""
+        """Host: per item whatever packets of this chunk arrived -> one uint8 array, the front end's segment for the batch
+        (_RxFront.gather_item and .fill per item, against the session's sequence number)."""
         import numpy as np
-        from .packets import StreamInfo, gather, gather_fec
-        info = StreamInfo(self.K, self.nb, n, self.packet_tok)
-        ainfo = StreamInfo(*self.audio, n, self.packet_tok) if self.audio is not None else None
         B, lay = self.batch, self._layout(self.batch, n)
-        P, full = lay.P, self.full
-        par = [(f, inf, [[] for _ in range(B)] if pk is None else self._packets_ok(pk), at)       # before anything is gathered
-               for f, inf, pk, at in ((self.fec, info, fec_packets, lay.fec), (self.audio_fec, ainfo, audio_fec_packets, lay.audio_fec))
-               if f is not None]
-        host = np.empty(lay.size, np.uint8)
-        hb, hr = host[lay.bodies:lay.counts].reshape(B, P, full), host[lay.counts:lay.counts + B * P].reshape(B, P)
-        base, late = self.tokens // self.packet_tok, []
+        audio, fec, afec = ([None] * B if pk is None else self._packets_ok(pk)        # before anything is gathered
+                            for pk in (audio_packets, fec_packets, audio_fec_packets))
+        host, late = np.empty(lay.size, np.uint8), []
         for b in range(B):
-            hb[b], hr[b] = gather(tactile_packets[b], info, seq_base=base, late=late)
-        if self.audio is not None:
-            ab, ar = host[lay.abodies:lay.acounts].reshape(B, P, self.afull), host[lay.acounts:lay.acounts + B * P].reshape(B, P)
-            for b in range(B):
-                ab[b], ar[b] = gather(audio_packets[b], ainfo, seq_base=base, late=late)
-        for f, inf, pk, (o_rows, o_got) in par:
-            fr = host[o_rows:o_got].reshape(B, *f.rows_shape(inf))
-            fg = host[o_got:o_got + B * fr.shape[1]].reshape(B, fr.shape[1])
-            for b in range(B):                                                # the chunk's first group, in the stream's numbers
-                fr[b], fg[b] = gather_fec(pk[b], inf, f, seq_base=base // int(f.group), late=late)
+            self.front.fill(host, lay, b, self.front.gather_item(tactile_packets[b], audio[b], fec[b], afec[b], n,
+                                                                 seq_base=self.tokens // self.packet_tok, late=late))
         self.late += len(late)
         return host
 
@@ -1418,7 +1495,20 @@ class StreamReceiver(_ReceiverCore):
         return y_s
 
 
-class StreamReceiverPool(_ReceiverCore):
+class PoolChunk(NamedTuple):
+    """What StreamReceiverPoolAV.step takes for one session of a tick: the chunk's tactile packets that arrived, its ``audio`` --
+    the audio packets that arrived for a pool opened with audio=(K_a, na), else the audio codes int [32, n] -- then, for a pool
+    opened with fec= / audio_fec=, the parity packets of each stream that arrived (None: none did); ``tokens`` (1..15) belongs to
+    a finish whose audio travels as packets, as StreamReceiver.finish(tokens=).  A plain tuple of the first 2..5 values does too.
+    StreamReceiverPool.step takes exactly the first two values."""
+    tactile_packets: object
+    audio: object
+    fec_packets: object = None
+    audio_fec_packets: object = None
+    tokens: object = None
+
+
+class StreamReceiverPool(_SessionTable, _ReceiverCore):
     """Receiver sessions that join, run for different lengths and leave independently, served together: ``open`` takes a
     session slot, ``step`` is one tick that advances whichever sessions have a chunk ready (and flushes the ones that end),
     ``close`` abandons one.  Every session gets back exactly what a ``StreamReceiver(batch=1)`` fed the same data returns from
@@ -1426,12 +1516,13 @@ class StreamReceiverPool(_ReceiverCore):
 
     The state of all ``slots`` sessions lies in one set of device buffers allocated once -- carry [S, C], hist [S, C, 20] and, for
     out_rate=3000, the resampler's [S, 105] -- and a session is a row block of each (its slot).  A tick runs, in order:
-      host   every session's input checked and gathered (packets.gather against ITS seq_base, the audio codes' shape, the sids);
-             an error leaves every session as it was, the late counters too;
+      host   every session's input checked and gathered (_RxFront.gather_item against ITS seq_base, the audio codes' shape, the
+             sids); an error leaves every session as it was, the late counters too;
              pool_groups: the sessions that share a launch sequence -- at most three groups of pushes (first, second, steady
              chunk), one more per kind of finisher;
-      copy   ONE upload of all groups' slot lists, packet bodies and counts, ONE of all audio codes;
-      device per group of G sessions: ops.idx_unpack_packets -> ops.stream_rows (the carried tokens, pool -> dense [G, C]) ->
+      copy   ONE upload of all groups' slot lists and then per group ONE segment of the front end's layout (_RxFront.fill
+             session by session: here the packet bodies and counts), ONE of all audio codes;
+      device per group of G sessions: _RxFront.unpack -> ops.stream_rows (the carried tokens, pool -> dense [G, C]) ->
              decode_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.stream_window_slots -> T_DEC on [G, C, window]
              -> the emit slice (-> ops.resample_stream_slots): _ReceiverCore's sequence on the group's slots.
     ``step`` reads nothing back from the device.  Nothing is captured as a graph: the group sizes change from tick to tick.
@@ -1440,6 +1531,7 @@ class StreamReceiverPool(_ReceiverCore):
     T_DEC.forward_stream on the group's slots.  ``open`` leaves a slot's dec_state as it is: a new session reads no tail."""
 
     _who = "StreamReceiverPool"
+    _item_fields = 2                                                                   # an item is (packets, audio_codes), no more
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
                  decoder="window", audio_out=False, audio_fade=None):
@@ -1447,35 +1539,20 @@ class StreamReceiverPool(_ReceiverCore):
             raise ValueError("StreamReceiverPool: the pool takes no audio= packets and so no audio_conceal")
         if audio_out or audio_fade is not None:
             raise ValueError("StreamReceiverPool: the pool has no audio output; audio_out / audio_fade go with StreamReceiverPoolAV")
+        self._init_pool(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, decoder=decoder)
+
+    def _init_pool(self, net, K, nb, packet_tok, slots, books_use, conceal, out_rate, **options):
+        """What both receiver pools' constructors do: the refusals, _ReceiverCore's buffers with ``slots`` rows, an empty session
+        table (sid -> [slot, tokens, late])."""
         K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
-        _receiver_args("StreamReceiverPool", net, K, nb, packet_tok, conceal, out_rate)
+        _receiver_args(self._who, net, K, nb, packet_tok, conceal, out_rate)
         if slots < 1:
-            raise ValueError("StreamReceiverPool: slots must be at least 1")
-        _f32_only("StreamReceiverPool")
-        super().__init__(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, decoder=decoder)
-        self.slots = slots
-        self._free = list(range(slots))                                                # ascending: open() takes the lowest
-        self._sess = {}                                                                # sid -> [slot, tokens, late]
-        self._next_sid = 0
+            raise ValueError(f"{self._who}: slots must be at least 1")
+        _f32_only(self._who)
+        super().__init__(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, **options)
+        self._init_sessions(slots)
 
     # ----------------------------------------------------------------------------------------------------------- sessions
-    @property
-    def active(self):
-        """The sids of the open sessions, ascending."""
-        return tuple(sorted(self._sess))
-
-    @property
-    def free(self):
-        """Slots no session holds."""
-        return len(self._free)
-
-    def _get(self, sid, what):
-        from ._lib import MvqError
-        try:
-            return self._sess[sid]
-        except (KeyError, TypeError):
-            raise MvqError(f"{self._who}: {what}: no open session {sid!r} (never opened, finished or closed)") from None
-
     def tokens(self, sid):
         """Tokens session ``sid`` has received."""
         return self._get(sid, "tokens")[1]
@@ -1487,52 +1564,84 @@ class StreamReceiverPool(_ReceiverCore):
     def open(self):
         """A new session -> its sid (never reused).  Takes the lowest free slot and resets it: the carried token and the
         resampler state to zero on the device, the history count (the session's tokens) to zero."""
-        from ._lib import MvqError
-        if not self._free:
-            raise MvqError(f"{self._who}: all {self.slots} slots hold a session")
-        slot = self._free.pop(0)
+        slot = self._take_slot()
         self.carry[slot].zero_()
         if self.qa_carry is not None:                                                  # StreamReceiverPoolAV(audio_conceal="hold")
             self.qa_carry[slot].zero_()
         if self.rs_state is not None:
             self.rs_state[slot].zero_()
-        sid, self._next_sid = self._next_sid, self._next_sid + 1
-        self._sess[sid] = [slot, 0, 0]
-        return sid
-
-    def close(self, sid):
-        """Abandon session ``sid`` without flushing it; its slot is free again."""
-        import bisect
-        slot = self._get(sid, "close")[0]
-        del self._sess[sid]
-        bisect.insort(self._free, slot)
+        return self._new_session(slot, 0, 0)
 
     # --------------------------------------------------------------------------------------------------------------- tick
     def _inputs(self, pushes, finishes):
         """Host: every session's input of this tick, checked and gathered; raises before anything has changed.
-        -> {sid: (n, last, bodies uint8 [P, full] or None, counts uint8 [P] or None, codes [32, n] or None, late packets)}"""
-        from .packets import StreamInfo, gather
-        work = {}
+        -> {sid: (n, last, parts, codes [32, n] or None, late packets)}; ``parts``: the session's arrays in the front end's layout
+        order (_RxFront.gather_item: bodies, counts[, audio bodies, audio counts][, rows, got per stream with a Fec]) or None."""
+        who, work = self._who, {}
         for sid in pushes:
             if sid in finishes:
-                raise ValueError(f"StreamReceiverPool: session {sid!r} is both pushed and finished in one tick")
+                raise ValueError(f"{who}: session {sid!r} is both pushed and finished in one tick")
+        audio_what = "audio_packets" if self.audio is not None else "audio_codes"
+        item_what = f"(packets, {audio_what}" + (")" if self._item_fields == 2 else "[, fec_packets, audio_fec_packets[, tokens]])")
         for last, items in ((False, pushes), (True, finishes)):
             for sid, item in items.items():
                 tokens = self._get(sid, "finish" if last else "push")[1]
                 if item is None:
                     if not last:
-                        raise ValueError(f"StreamReceiverPool: session {sid}: a push needs (packets, audio_codes)")
-                    work[sid] = (0, True, None, None, None, 0)
+                        raise ValueError(f"{who}: session {sid}: a push needs (packets, {audio_what})")
+                    work[sid] = (0, True, None, None, 0)
                     continue
                 try:
-                    pkts, audio_codes = item
-                except (TypeError, ValueError):
-                    raise ValueError(f"StreamReceiverPool: session {sid}: (packets, audio_codes) expected") from None
-                codes = self._codes(audio_codes, 1, CHUNK_TOK - 1, sid) if last else self._codes(audio_codes, CHUNK_TOK, CHUNK_TOK, sid)
-                n, late = int(codes.shape[1]), []
-                bodies, counts = gather(pkts, StreamInfo(self.K, self.nb, n, self.packet_tok), seq_base=tokens // self.packet_tok, late=late)
-                work[sid] = (n, last, bodies, counts, codes, len(late))
+                    item = tuple(item)
+                    if len(item) > self._item_fields:
+                        raise TypeError
+                    item = PoolChunk(*item)
+                except TypeError:
+                    raise ValueError(f"{who}: session {sid}: {item_what} expected") from None
+                if item.tactile_packets is None or item.audio is None:
+                    raise ValueError(f"{who}: session {sid}: a chunk needs both its packets and its {audio_what}")
+                if (item.fec_packets is not None and self.fec is None) or (item.audio_fec_packets is not None and self.audio_fec is None):
+                    raise ValueError(f"{who}: session {sid}: fec_packets / audio_fec_packets need a pool opened with fec= / audio_fec=")
+                codes = None
+                if self.audio is not None:
+                    if not last:
+                        if item.tokens is not None:
+                            raise ValueError(f"{who}: session {sid}: tokens= belongs to a finish; a push is a {CHUNK_TOK}-token chunk")
+                        n = CHUNK_TOK
+                    elif item.tokens is None or not 1 <= int(item.tokens) <= CHUNK_TOK - 1:
+                        raise ValueError(f"{who}: session {sid}: tokens = {item.tokens!r}; a last chunk of audio packets has "
+                                         f"1..{CHUNK_TOK - 1} tokens")
+                    else:
+                        n = int(item.tokens)
+                else:
+                    if item.tokens is not None:
+                        raise ValueError(f"{who}: session {sid}: tokens= counts a last chunk of audio PACKETS (a pool with "
+                                         "audio=(K_a, na)); audio codes carry their own length")
+                    codes = self._codes(item.audio, 1, CHUNK_TOK - 1, sid) if last else self._codes(item.audio, CHUNK_TOK, CHUNK_TOK, sid)
+                    n = int(codes.shape[1])
+                late = []
+                parts = self.front.gather_item(item.tactile_packets, item.audio, item.fec_packets, item.audio_fec_packets, n,
+                                               seq_base=tokens // self.packet_tok, late=late)
+                work[sid] = (n, last, parts, codes, len(late))
         return work
+
+    def _upload(self, work):
+        """Host: the tick's groups and its ONE uint8 array -- the slot lists of all groups (int32, first: aligned), then per group
+        that takes tokens its segment in the front end's layout -> (groups, slot_lists, [(segment offset, RxLayout or None)], host)."""
+        import numpy as np
+        groups = pool_groups((sid, self._sess[sid][1], w[0], w[1]) for sid, w in work.items())
+        size, where = 4 * sum(len(g.sids) for g in groups), []
+        for g in groups:
+            lay = self._layout(len(g.sids), g.key[1]) if g.key[1] else None
+            where.append((size, lay))
+            size += lay.size if lay is not None else 0
+        host = np.empty(size, np.uint8)
+        slot_lists = [[self._sess[sid][0] for sid in g.sids] for g in groups]
+        host[:where[0][0]] = np.asarray([s for sl in slot_lists for s in sl], np.int32).view(np.uint8)
+        for g, (o, lay) in zip(groups, where):
+            for i, sid in enumerate(g.sids if lay is not None else ()):
+                self.front.fill(host[o:o + lay.size], lay, i, work[sid][2])
+        return groups, slot_lists, where, host
 
     def step(self, pushes, finishes=None):
         """One tick.  ``pushes``: {sid: (packets of its current chunk that arrived, audio_codes int [32, 16] or [1, 32, 16])};
@@ -1540,34 +1649,18 @@ class StreamReceiverPool(_ReceiverCore):
         -> {sid: y [1, 1, n_emit]}: per session what StreamReceiver(batch=1).push / .finish returns (views of the group's
         output).  A finished session's slot is freed.  ValueError / MvqError for any one session (a packet of a later chunk, a
         wrong code shape, an unknown sid, a sid in both maps) comes before the first device call and leaves every session as it
-        was."""
-        import numpy as np
+        was.  StreamReceiverPoolAV: an item is a PoolChunk or (packets, audio[, fec_packets[, audio_fec_packets]]) -- ``audio`` the
+        chunk's audio packets (a pool with audio=(K_a, na)) or its audio codes; a last chunk of audio packets is PoolChunk(...,
+        tokens=n); with audio_out a session's result is (y, y_audio); parity packets without the matching fec= and a missing
+        tokens= are refused like the rest."""
         import torch
         pushes, finishes = dict(pushes or {}), dict(finishes or {})
-        _f32_only("StreamReceiverPool")
+        _f32_only(self._who)
         work = self._inputs(pushes, finishes)
         if not work:
             return {}
-        groups = pool_groups((sid, self._sess[sid][1], w[0], w[1]) for sid, w in work.items())
-        # ONE host array: the slot lists of all groups (int32, first: aligned), then per group its bodies and its counts
-        n_sess = sum(len(g.sids) for g in groups)
-        size, where = 4 * n_sess, []
-        for g in groups:
-            G, n = len(g.sids), g.key[1]
-            P = (n + self.packet_tok - 1) // self.packet_tok
-            where.append((size, size + G * P * self.full, P))
-            size += G * P * (self.full + 1)
-        host = np.empty(size, np.uint8)
-        slot_lists = [[self._sess[sid][0] for sid in g.sids] for g in groups]
-        host[:4 * n_sess] = np.asarray([s for sl in slot_lists for s in sl], np.int32).view(np.uint8)
-        flat_codes = []
-        for g, (o_b, o_c, P) in zip(groups, where):
-            G = len(g.sids)
-            if P:
-                hb, hc = host[o_b:o_c].reshape(G, P, self.full), host[o_c:o_c + G * P].reshape(G, P)
-                for i, sid in enumerate(g.sids):
-                    hb[i], hc[i] = work[sid][2], work[sid][3]
-                    flat_codes.append(work[sid][4].reshape(-1))
+        groups, slot_lists, where, host = self._upload(work)
+        flat_codes =[work[sid][3].reshape(-1) for g in groups if g.key[1] and self.audio is None for sid in g.sids]
         out = {}
         with torch.no_grad():
             up = torch.from_numpy(host).to(self.dev)
@@ -1576,26 +1669,32 @@ class StreamReceiverPool(_ReceiverCore):
                     codes_all = torch.cat([c.to(self.dev, torch.int64) for c in flat_codes])
                 else:
                     codes_all = torch.cat([c.to(torch.int64) for c in flat_codes]).to(self.dev)
-            slots_all = up[:4 * n_sess].view(torch.int32)
+            slots_all = up[:where[0][0]].view(torch.int32)                   # the slot lists lie in front of the first segment
             s0 = c0 = 0
-            for g, slots, (o_b, o_c, P) in zip(groups, slot_lists, where):
+            for g, slots, (o, lay) in zip(groups, slot_lists, where):
                 G, (_, n, last) = len(g.sids), g.key
                 sl = (slots, slots_all[s0:s0 + G])
-                codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n) if n else None
-                y = self._decimate(self._device_step(up[o_b:o_c + G * P], codes, n, *g.plan, sl=sl, last=last), g.consumed, last, sl)
-                s0, c0 = s0 + G, c0 + G * self.n_audio_books * n
+                codes = None
+                if n and self.audio is None:
+                    codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n)
+                    c0 += G * self.n_audio_books * n
+                seg = up[o:o + lay.size] if lay is not None else None
+                y = self._device_step(seg, codes, n, *g.plan, sl=sl, last=last)
+                y, ya = y if self.audio_out else (y, None)
+                y = self._decimate(y, g.consumed, last, sl)
+                s0 += G
                 for i, sid in enumerate(g.sids):
-                    out[sid] = y[i:i + 1]
+                    out[sid] = (y[i:i + 1], ya[i:i + 1]) if self.audio_out else y[i:i + 1]
         for sid, w in work.items():
             if w[1]:
                 self.close(sid)
             else:
                 self._sess[sid][1] += w[0]
-                self._sess[sid][2] += w[5]
+                self._sess[sid][2] += w[4]
         return out
 
 
-class StreamSenderPool(_SenderCore):
+class StreamSenderPool(_SessionTable, _SenderCore):
     """Sender sessions that join at any time, push 1..16 tokens of samples at a time and end after different lengths, served
     together: ``open`` takes a session slot, ``step`` is one tick that takes the samples of whichever sessions have some (and
     flushes the ones that end), ``close`` abandons one.  Every session gets back exactly what a ``StreamSender(batch=1)`` fed
@@ -1625,32 +1724,17 @@ class StreamSenderPool(_SenderCore):
     _who = "StreamSenderPool"
 
     def __init__(self, net, packet_tok=2, slots=64, books_use=None, encoder="window"):
+        self._init_pool(net, packet_tok, slots, books_use, encoder=encoder)
+
+    def _init_pool(self, net, packet_tok, slots, books_use, **options):
+        """What both sender pools' constructors do: _SenderCore's checks and buffers with ``slots`` rows, an empty session table
+        (sid -> [slot, fill, start, chunk])."""
         packet_tok, slots = int(packet_tok), int(slots)
-        super().__init__("StreamSenderPool", net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), encoder=encoder)
-        self.slots = slots
-        self._free = list(range(slots))                                                # ascending: open() takes the lowest
-        self._sess = {}                                                                # sid -> [slot, fill, start, chunk]
-        self._next_sid = 0
+        super().__init__(self._who, net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), **options)
+        self._init_sessions(slots)
         self.last_groups = ()                                                          # the SenderGroups of the last tick
 
     # ----------------------------------------------------------------------------------------------------------- sessions
-    @property
-    def active(self):
-        """The sids of the open sessions, ascending."""
-        return tuple(sorted(self._sess))
-
-    @property
-    def free(self):
-        """Slots no session holds."""
-        return len(self._free)
-
-    def _get(self, sid, what):
-        from ._lib import MvqError
-        try:
-            return self._sess[sid]
-        except (KeyError, TypeError):
-            raise MvqError(f"{self._who}: {what}: no open session {sid!r} (never opened, finished or closed)") from None
-
     def tokens(self, sid):
         """Tokens of samples session ``sid`` has received."""
         _, fill, start, _ = self._get(sid, "tokens")
@@ -1659,21 +1743,9 @@ class StreamSenderPool(_SenderCore):
     def open(self):
         """A new session -> its sid (never reused).  Takes the lowest free slot and resets it: the carried token to zero on the
         device, the fill to zero on the host (which makes whatever the slot's buffer rows hold irrelevant)."""
-        from ._lib import MvqError
-        if not self._free:
-            raise MvqError(f"{self._who}: all {self.slots} slots hold a session")
-        slot = self._free.pop(0)
+        slot = self._take_slot()
         self.carry[slot].zero_()
-        sid, self._next_sid = self._next_sid, self._next_sid + 1
-        self._sess[sid] = [slot, 0, 0, 0]
-        return sid
-
-    def close(self, sid):
-        """Abandon session ``sid`` without flushing it; its slot is free again."""
-        import bisect
-        slot = self._get(sid, "close")[0]
-        del self._sess[sid]
-        bisect.insort(self._free, slot)
+        return self._new_session(slot, 0, 0, 0)
 
     # --------------------------------------------------------------------------------------------------------------- tick
     def _inputs(self, pushes, finishes):
@@ -1790,18 +1862,6 @@ class StreamSenderPool(_SenderCore):
         return out
 
 
-class PoolChunk(NamedTuple):
-    """What StreamReceiverPoolAV.step takes for one session of a tick: the chunk's tactile packets that arrived, its ``audio`` --
-    the audio packets that arrived for a pool opened with audio=(K_a, na), else the audio codes int [32, n] -- then, for a pool
-    opened with fec= / audio_fec=, the parity packets of each stream that arrived (None: none did); ``tokens`` (1..15) belongs to
-    a finish whose audio travels as packets, as StreamReceiver.finish(tokens=).  A plain tuple of the first 2..5 values does too."""
-    tactile_packets: object
-    audio: object
-    fec_packets: object = None
-    audio_fec_packets: object = None
-    tokens: object = None
-
-
 class StreamReceiverPoolAV(StreamReceiverPool):
     """StreamReceiverPool for the whole link: the options of StreamReceiver -- ``audio=(K_a, na)`` (the audio
     codes arrive as layered packets), ``fec`` / ``audio_fec``, ``audio_conceal``, beside ``conceal``, ``out_rate`` and ``decoder`` --
@@ -1809,13 +1869,14 @@ class StreamReceiverPoolAV(StreamReceiverPool):
     Every session gets from ``step`` exactly what a ``StreamReceiver(batch=1)`` with the same options, fed the same data, returns
     from ``push`` / ``finish``, bit for bit.
 
-    A tick is StreamReceiverPool's with a wider upload: per group of G sessions (``pool_groups``, unchanged) ONE segment laid out by
-    ``receiver_layout`` -- tactile bodies, counts, audio bodies, counts, per stream the parity rows and their ``got`` flags -- filled
-    session by session (packets.gather / gather_fec against ITS token count); ONE upload of the slot lists and all segments (and
-    ONE of the audio codes, for audio=None only); then per group _ReceiverCore's sequence on the group's slots: ops.fec_recover in
-    place, both unpacks, the carried token through ops.stream_rows, decode_latents -- "hold" addresses the held audio token qa_carry
-    [S, C] through the slot list (ops.hold_fill_(slots=)) -- and the decode.  Nothing is read back.  ``open`` resets the slot's
-    carried token, held audio token and resampler state.
+    A tick IS StreamReceiverPool's -- the class adds its constructor and nothing else; the base class's ``step`` serves both and an
+    item may carry all of PoolChunk's fields here.  The options only widen the group's segment, whose format the front end owns
+    (_RxFront: tactile bodies, counts, audio bodies, counts, per stream the parity rows and their ``got`` flags); ONE upload of the
+    slot lists and all segments (and ONE of the audio codes, for audio=None only); then per group _ReceiverCore's sequence on the
+    group's slots: _RxFront.unpack (ops.fec_recover in place ahead of each stream's unpack), the carried token through
+    ops.stream_rows, decode_latents -- "hold" addresses the held audio token qa_carry [S, C] through the slot list
+    (ops.hold_fill_(slots=)) -- and the decode.  Nothing is read back.  ``open`` resets the slot's carried token, held audio token
+    and resampler state.
 
     ``audio_out`` / ``audio_fade`` (StreamReceiver's): a session's result is (y_tactile, y_audio).  The pool
     holds a second decoder state (a_hist [S, C, 20] or a_dec_state) and the fade's run lengths fade_state [S, 11]; a group's step
@@ -1823,149 +1884,12 @@ class StreamReceiverPoolAV(StreamReceiverPool):
     history, no tail and no run length."""
 
     _who = "StreamReceiverPoolAV"
+    _item_fields = len(PoolChunk._fields)
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio=None, fec=None,
                  audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
-        K, nb, packet_tok, slots = int(K), int(nb), int(packet_tok), int(slots)
-        _receiver_args(self._who, net, K, nb, packet_tok, conceal, out_rate)
-        if slots < 1:
-            raise ValueError(f"{self._who}: slots must be at least 1")
-        _f32_only(self._who)
-        _ReceiverCore.__init__(self, net, K, nb, packet_tok, slots, books_use, conceal, out_rate, audio=audio, fec=fec,
-                               audio_fec=audio_fec, audio_conceal=audio_conceal, decoder=decoder, who=self._who, audio_out=audio_out,
-                               audio_fade=audio_fade)
-        self.slots = slots
-        self._free = list(range(slots))                                                # ascending: open() takes the lowest
-        self._sess = {}                                                                # sid -> [slot, tokens, late]
-        self._next_sid = 0
-
-    def _inputs(self, pushes, finishes):
-        """Host: every session's input of this tick, checked and gathered; raises before anything has changed.
-        -> {sid: (n, last, parts, codes [32, n] or None, late packets)}; ``parts``: the session's arrays in the order of
-        ``receiver_layout`` -- (bodies, counts[, audio bodies, audio counts][, rows, got per stream with a Fec]) -- or None."""
-        from .packets import StreamInfo, gather, gather_fec
-        who, work = self._who, {}
-        for sid in pushes:
-            if sid in finishes:
-                raise ValueError(f"{who}: session {sid!r} is both pushed and finished in one tick")
-        audio_what = "audio_packets" if self.audio is not None else "audio_codes"
-        for last, items in ((False, pushes), (True, finishes)):
-            for sid, item in items.items():
-                tokens = self._get(sid, "finish" if last else "push")[1]
-                if item is None:
-                    if not last:
-                        raise ValueError(f"{who}: session {sid}: a push needs (packets, {audio_what})")
-                    work[sid] = (0, True, None, None, 0)
-                    continue
-                try:
-                    item = PoolChunk(*item)
-                except TypeError:
-                    raise ValueError(f"{who}: session {sid}: (packets, {audio_what}[, fec_packets, audio_fec_packets[, tokens]]) "
-                                     "expected") from None
-                if item.tactile_packets is None or item.audio is None:
-                    raise ValueError(f"{who}: session {sid}: a chunk needs both its packets and its {audio_what}")
-                if (item.fec_packets is not None and self.fec is None) or (item.audio_fec_packets is not None and self.audio_fec is None):
-                    raise ValueError(f"{who}: session {sid}: fec_packets / audio_fec_packets need a pool opened with fec= / audio_fec=")
-                codes = None
-                if self.audio is not None:
-                    if not last:
-                        if item.tokens is not None:
-                            raise ValueError(f"{who}: session {sid}: tokens= belongs to a finish; a push is a {CHUNK_TOK}-token chunk")
-                        n = CHUNK_TOK
-                    elif item.tokens is None or not 1 <= int(item.tokens) <= CHUNK_TOK - 1:
-                        raise ValueError(f"{who}: session {sid}: tokens = {item.tokens!r}; a last chunk of audio packets has "
-                                         f"1..{CHUNK_TOK - 1} tokens")
-                    else:
-                        n = int(item.tokens)
-                else:
-                    if item.tokens is not None:
-                        raise ValueError(f"{who}: session {sid}: tokens= counts a last chunk of audio PACKETS (a pool with "
-                                         "audio=(K_a, na)); audio codes carry their own length")
-                    codes = self._codes(item.audio, 1, CHUNK_TOK - 1, sid) if last else self._codes(item.audio, CHUNK_TOK, CHUNK_TOK, sid)
-                    n = int(codes.shape[1])
-                base, late = tokens // self.packet_tok, []
-                info = StreamInfo(self.K, self.nb, n, self.packet_tok)
-                parts = list(gather(item.tactile_packets, info, seq_base=base, late=late))
-                ainfo = None
-                if self.audio is not None:
-                    ainfo = StreamInfo(*self.audio, n, self.packet_tok)
-                    parts += gather(item.audio, ainfo, seq_base=base, late=late)
-                for f, inf, pk in ((self.fec, info, item.fec_packets), (self.audio_fec, ainfo, item.audio_fec_packets)):
-                    if f is not None:                                        # the chunk's first group, in the stream's numbers
-                        parts += gather_fec([] if pk is None else pk, inf, f, seq_base=base // int(f.group), late=late)
-                work[sid] = (n, last, parts, codes, len(late))
-        return work
-
-    def step(self, pushes, finishes=None):
-        """One tick.  ``pushes``: {sid: PoolChunk or (packets, audio[, fec_packets[, audio_fec_packets]])} -- ``audio`` the chunk's
-        audio packets (a pool with audio=(K_a, na)) or its audio codes int [32, 16] / [1, 32, 16]; ``finishes``: {sid: the same for
-        a last chunk of 1..15 tokens -- with audio packets PoolChunk(..., tokens=n) -- or None} for the sessions that end with this
-        tick.  -> {sid: y [1, 1, n_emit]}: per session what StreamReceiver(batch=1, the pool's options).push / .finish returns.
-        A finished session's slot is freed.  ValueError / MvqError for any one session (a packet of a later chunk, parity packets
-        without the matching fec=, a missing tokens=, a wrong code shape, an unknown sid, a sid in both maps) comes before the first
-        device call and leaves every session as it was."""
-        import numpy as np
-        import torch
-        pushes, finishes = dict(pushes or {}), dict(finishes or {})
-        _f32_only(self._who)
-        work = self._inputs(pushes, finishes)
-        if not work:
-            return {}
-        groups = pool_groups((sid, self._sess[sid][1], w[0], w[1]) for sid, w in work.items())
-        # ONE host array: the slot lists of all groups (int32, first: aligned), then per group its segment (receiver_layout)
-        n_sess = sum(len(g.sids) for g in groups)
-        size, where = 4 * n_sess, []
-        for g in groups:
-            lay = self._layout(len(g.sids), g.key[1]) if g.key[1] else None
-            where.append((size, lay))
-            size += lay.size if lay is not None else 0
-        host = np.empty(size, np.uint8)
-        slot_lists = [[self._sess[sid][0] for sid in g.sids] for g in groups]
-        host[:4 * n_sess] = np.asarray([s for sl in slot_lists for s in sl], np.int32).view(np.uint8)
-        flat_codes = []
-        for g, (o, lay) in zip(groups, where):
-            if lay is None:
-                continue
-            G = len(g.sids)
-            starts = [lay.bodies, lay.counts] + ([lay.abodies, lay.acounts] if lay.abodies is not None else []) + \
-                [v for at in (lay.fec, lay.audio_fec) if at is not None for v in at]
-            for i, sid in enumerate(g.sids):                             # every part is [G, bytes of one session]
-                for at, end, part in zip(starts, starts[1:] + [lay.size], work[sid][2]):
-                    per = (end - at) // G
-                    host[o + at + i * per:o + at + (i + 1) * per] = np.asarray(part, np.uint8).reshape(-1)
-                if self.audio is None:
-                    flat_codes.append(work[sid][3].reshape(-1))
-        out = {}
-        with torch.no_grad():
-            up = torch.from_numpy(host).to(self.dev)
-            if flat_codes:
-                if any(c.is_cuda for c in flat_codes):
-                    codes_all = torch.cat([c.to(self.dev, torch.int64) for c in flat_codes])
-                else:
-                    codes_all = torch.cat([c.to(torch.int64) for c in flat_codes]).to(self.dev)
-            slots_all = up[:4 * n_sess].view(torch.int32)
-            s0 = c0 = 0
-            for g, slots, (o, lay) in zip(groups, slot_lists, where):
-                G, (_, n, last) = len(g.sids), g.key
-                sl = (slots, slots_all[s0:s0 + G])
-                codes = None
-                if n and self.audio is None:
-                    codes = codes_all[c0:c0 + G * self.n_audio_books * n].view(G, self.n_audio_books, n)
-                    c0 += G * self.n_audio_books * n
-                seg = up[o:o + lay.size] if lay is not None else None
-                y = self._device_step(seg, codes, n, *g.plan, sl=sl, last=last)
-                y, ya = y if self.audio_out else (y, None)
-                y = self._decimate(y, g.consumed, last, sl)
-                s0 += G
-                for i, sid in enumerate(g.sids):
-                    out[sid] = (y[i:i + 1], ya[i:i + 1]) if self.audio_out else y[i:i + 1]
-        for sid, w in work.items():
-            if w[1]:
-                self.close(sid)
-            else:
-                self._sess[sid][1] += w[0]
-                self._sess[sid][2] += w[4]
-        return out
+        self._init_pool(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
+                        audio_conceal=audio_conceal, decoder=decoder, who=self._who, audio_out=audio_out, audio_fade=audio_fade)
 
 
 class StreamSenderPoolAV(StreamSenderPool):
@@ -1983,14 +1907,8 @@ class StreamSenderPoolAV(StreamSenderPool):
 
     def __init__(self, net, packet_tok=2, slots=64, books_use=None, rate=None, audio="packets", audio_books=None, audio_rate=None,
                  fec=None, audio_fec=None, encoder="window"):
-        packet_tok, slots = int(packet_tok), int(slots)
-        _SenderCore.__init__(self, self._who, net, packet_tok, books_use, slots, (slots, 2, SEND_CAP_TOK * HOP), rate=rate, audio=audio,
-                             audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec, encoder=encoder)
-        self.slots = slots
-        self._free = list(range(slots))                                                # ascending: open() takes the lowest
-        self._sess = {}                                                                # sid -> [slot, fill, start, chunk]
-        self._next_sid = 0
-        self.last_groups = ()                                                          # the SenderGroups of the last tick
+        self._init_pool(net, packet_tok, slots, books_use, rate=rate, audio=audio, audio_books=audio_books, audio_rate=audio_rate,
+                        fec=fec, audio_fec=audio_fec, encoder=encoder)
 
     def _nothing(self):
         """What a push that completes no chunk returns (StreamSender._nothing for the one item)."""

@@ -238,6 +238,6 @@ def test_a_bad_session_leaves_every_session_as_it_was(cpu_net):
     assert not pool.carry.any() and not pool.hist.any()
     # the same inputs without the bad session pass the host phase: its gather counts the stragglers, per session
     work = pool._inputs({a: good_a, b: good_b}, {c: ([pk[0]], codes[:, :2])})
-    assert {s: (w[0], w[1], w[5]) for s, w in work.items()} == {a: (16, False, 2), b: (16, False, 1), c: (2, True, 0)}
-    assert work[a][3].tolist() == [2] * 8 and work[b][3].tolist() == [2] + [0] * 7 and work[c][3].tolist() == [2]
+    assert {s: (w[0], w[1], w[4]) for s, w in work.items()} == {a: (16, False, 2), b: (16, False, 1), c: (2, True, 0)}
+    assert work[a][2][1].tolist() == [2] * 8 and work[b][2][1].tolist() == [2] + [0] * 7 and work[c][2][1].tolist() == [2]
     assert {s: (pool.tokens(s), pool.late(s)) for s in (a, b, c)} == before
