@@ -51,7 +51,8 @@ extern "C" {
  * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32; the
  * stateful streaming encoder: mvq_stream_stage_window_snake_f32, mvq_stream_stage_window_snake_slots_f32, mvq_encoder_stream_plan,
  * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32; the receiver's audio output:
- * mvq_audio_fade_f32, mvq_audio_fade_slots_f32).
+ * mvq_audio_fade_f32, mvq_audio_fade_slots_f32; the native-rate sender: mvq_resample_stream_rational_f32,
+ * mvq_resample_stream_rational_slots_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -759,6 +760,26 @@ int mvq_resample_ragged_f32(const float* x, const float* kern, float* y, const i
  * launch does not depend on `consumed`, so a captured steady step replays. */
 int mvq_resample_stream_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new, long long consumed,
                             int final, int len_out, int orig, int newf, int width, int ks, void* stream);
+/* mvq_resample_stream_rational_f32: mvq_resample_f32 fed piece by piece for ANY ratio orig : newf, with the
+ * lag chosen by the caller.  A filter block is orig input samples and newf outputs; block q reads xpad[q*orig .. q*orig + ks) and is
+ * complete once sample q*orig + width + orig - 1 has arrived.  `hold` >= ceil(width/orig) is the lag in blocks: after L samples (a
+ * multiple of orig) the calls have written the blocks q < max(0, L/orig - hold), that is newf * max(0, L/orig - hold) outputs, and the
+ * call with final = 1 pads zeros on the right and writes the rest, up to output ceil(newf*(consumed + n_new)/orig): its last block may
+ * be partial in its inputs and in its outputs.  len_out must equal the count of the call (MVQ_EINVAL: the message names it).
+ * hold = ceil(width/orig) is the smallest lag (with newf == 1 then mvq_resample_stream_f32's outputs and state exactly); a larger one
+ * aligns the pieces with something else: the native-rate sender passes the blocks of one 320-sample token at 24 kHz (4 for
+ * 44.1 kHz, 40 for 3 kHz), so every call completes whole tokens.
+ * STATE LAYOUT: state[batch, S] fp32, S = hold*orig + width (600 for 44.1 -> 24 kHz at hold 4, 47 for 3 -> 24 kHz at hold 40;
+ * S <= 1024, else MVQ_EUNSUPPORTED), row b holds the last S samples of (zeros | x received so far), oldest first; a new session starts
+ * from all zeros.  The kernel moves it up by n_new samples after the outputs are written (one block per item, a barrier between).
+ * kern[newf][ks] is the bank of mvq_resample_f32 (ks = 2*width + orig); every output is that call's fma chain (k ascending, the taps
+ * on padding skipped): concatenated, the pieces equal the whole-signal call bit for bit.  With consumed >= S and a fixed n_new the launch
+ * does not depend on `consumed`.  MVQ_EINVAL before any launch on ks != 2*width + orig, a negative size, hold < ceil(width/orig),
+ * consumed or a non-final n_new that is no multiple of orig, a wrong len_out, or a null pointer with a non-empty shape; batch = 0
+ * returns MVQ_OK without a launch. */
+int mvq_resample_stream_rational_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
+                                     long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
+                                     void* stream);
 /* mvq_stream_window_f32: the decoder window of a session.  hist[batch, c, cap] (row pitch cap, the first h_in columns valid) and
  * z_new[batch, c, n] (contiguous) -> win[batch, c, h_in + n] = [hist | z_new] (contiguous, a buffer of its own), then
  * hist <- the last h_out columns of win, all in ONE launch: a block owns 32 (b, c) rows, reads them completely, and rewrites only
@@ -836,6 +857,13 @@ int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* 
                                   float* y, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
                                   void* stream);
 int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_slots, float* rows, int c, int scatter, void* stream);
+/* mvq_resample_stream_rational_slots_f32: mvq_resample_stream_rational_f32 on the sessions slots[n_group] of a pool state[n_slots, S],
+ * as mvq_resample_stream_slots_f32 is to mvq_resample_stream_f32: item g of x_new[n_group, n_new] and y[n_group, len_out] on
+ * state[slots[g]], the same kernel body, the same refusals and those of the pool calls above; `consumed` names the group's launch
+ * class, 0 or at least S (a value in (0, S) is MVQ_EINVAL). */
+int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
+                                           int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
+                                           int newf, int width, int ks, int hold, void* stream);
 /* mvq_stream_samples_slots_f32: the sample state of a group of SENDER sessions of a pool: the kernel body of
  * mvq_stream_samples_f32 under the slot addressing, with fill, n and drop PER SESSION.  buf[n_slots, 2, cap] fp32: slot s owns row 2s
  * (audio) and row 2s + 1 (tactile).  desc[n_group][5] int32 on the DEVICE, per session (slot, fill, n, drop, x_off): its n new audio

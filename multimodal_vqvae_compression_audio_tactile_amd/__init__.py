@@ -29,8 +29,8 @@ Drop-in surface:
 All compute runs in libmvq_hip.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
 from . import bitstream, ops, optim, packets, stream, synth, train  # noqa: F401
-from .resample import Resample, StreamResample, resample_to  # noqa: F401
-from .stream import StreamReceiver, StreamReceiverPool, StreamSender, StreamSenderPool  # noqa: F401
+from .resample import Resample, StreamResample, StreamResampleRational, resample_to  # noqa: F401
+from .stream import StreamReceiver, StreamReceiverPool, StreamSender, StreamSenderNative, StreamSenderPool  # noqa: F401
 from .stream import PoolChunk, StreamReceiverPoolAV, StreamSenderPoolAV  # noqa: F401
 from .losses import MelCosineLoss, MultiResSTFTLoss, TrainingLoss, safe_l1, stsim_batch  # noqa: F401
 from ._lib import MvqError, build, lib  # noqa: F401

@@ -1453,6 +1453,71 @@ int mvq_resample_stream_slots_f32(const float* x_new, const float* kern, float* 
     return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_slots");
 }
 
+// The one argument check of the rational streamed resampler: resample_stream_plan with a bank of newf phases and the lag `hold`
+// (in blocks of orig inputs / newf outputs) chosen by the caller.
+static int resample_rational_plan(const char* who, int batch, int n_new, long long consumed, int final, int len_out, int orig, int newf,
+                                  int width, int ks, int hold, ResampleStreamPlan* p)
+{
+    if (batch < 0 || n_new < 0 || consumed < 0 || len_out < 0 || orig <= 0 || newf <= 0 || width < 0 || hold < 0 || ks != 2 * width + orig)
+        return fail(MVQ_EINVAL, "%s: bad shape (ks must be 2*width + orig)", who);
+    if (consumed > (1LL << 40)) return fail(MVQ_EINVAL, "%s: consumed = %lld", who, consumed);
+    if (hold < (width + orig - 1) / orig)
+        return fail(MVQ_EINVAL, "%s: hold = %d blocks is less than ceil(width/orig) = %d", who, hold, (width + orig - 1) / orig);
+    const long long ns = (long long)hold * orig + width;
+    if (ns > 1024) return fail(MVQ_EUNSUPPORTED, "%s: state of %lld samples exceeds 1024", who, ns);
+    if (consumed % orig) return fail(MVQ_EINVAL, "%s: consumed = %lld is no multiple of orig = %d", who, consumed, orig);
+    if (!final && n_new % orig)
+        return fail(MVQ_EINVAL, "%s: n_new = %d is no multiple of orig = %d (only the final call may be)", who, n_new, orig);
+    if (ns + n_new > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: n_new = %d", who, n_new);
+    const long long q0 = consumed / orig;
+    const long long done = q0 > hold ? q0 - hold : 0;                    // blocks emitted by earlier calls
+    long long n_out;
+    if (final) {
+        n_out = ((long long)newf * (consumed + n_new) + orig - 1) / orig - (long long)newf * done;
+    } else {
+        const long long q1 = q0 + n_new / orig - hold;
+        n_out = q1 > done ? (long long)newf * (q1 - done) : 0;
+    }
+    if (n_out != len_out) return fail(MVQ_EINVAL, "%s: len_out = %d, this call completes %lld outputs", who, len_out, n_out);
+    const int base = (int)(q0 < hold ? (hold - q0) * orig : 0);
+    const int lead = (int)(consumed < ns ? ns - consumed : 0);
+    *p = {(int)ns, (int)n_out, base, lead};
+    return MVQ_OK;
+}
+
+int mvq_resample_stream_rational_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
+                                     long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
+                                     void* stream)
+{
+    ResampleStreamPlan p;
+    if (int rc = resample_rational_plan("resample_stream_rational", batch, n_new, consumed, final, len_out, orig, newf, width, ks, hold, &p))
+        return rc;
+    if (batch == 0) return MVQ_OK;
+    if (!kern || !state || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "resample_stream_rational: null tensor");
+    hipError_t e = mvq::launch_resample_stream_rational(x_new, kern, state, nullptr, y, batch, n_new, p.n_out, orig, newf, ks, p.ns, p.base,
+                                                        p.lead, 0, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_rational");
+}
+
+int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
+                                           int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
+                                           int newf, int width, int ks, int hold, void* stream)
+{
+    const char* who = "resample_stream_rational_slots";
+    if (int rc = slots_shape_bad(who, n_group, n_slots, 1)) return rc;
+    ResampleStreamPlan p;
+    if (int rc = resample_rational_plan(who, n_group, n_new, consumed, final, len_out, orig, newf, width, ks, hold, &p)) return rc;
+    if (consumed && consumed < p.ns)
+        return fail(MVQ_EINVAL, "%s: consumed = %lld inside the %d-sample state names no launch class (0, or at least %d)", who, consumed,
+                    p.ns, p.ns);
+    if ((long long)n_group * p.n_out > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: %d x %d outputs", who, n_group, p.n_out);
+    if (n_group == 0) return MVQ_OK;
+    if (!kern || !state || !slots || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "%s: null tensor", who);
+    hipError_t e = mvq::launch_resample_stream_rational(x_new, kern, state, slots, y, n_group, n_new, p.n_out, orig, newf, ks, p.ns, p.base,
+                                                        p.lead, n_slots, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, who);
+}
+
 // The size checks of the history window, `who` the entry point's name; `sessions` = batch or n_group.
 static int stream_window_sizes_bad(const char* who, int sessions, int h_in, int n, int h_out, int cap, int c)
 {

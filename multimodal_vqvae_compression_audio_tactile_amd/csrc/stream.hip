@@ -203,6 +203,68 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float* __res
     }
 }
 
+// Stateful resampling by any rational ratio orig : newf: resample_stream_kernel with the polyphase bank of
+// resample_kernel and a lag the caller chooses.  state[s][0 .. S), S = hold*orig + width, holds the last S samples of
+// (zeros | x received so far) of session s, hold >= ceil(width / orig) the lag in filter blocks (a block: orig inputs, newf outputs).
+// With v = [state | x_new], output m of this call is phase p = m - q*newf of block q = m / newf and reads v[base + q*orig + k]
+// against bank row p, kern[p*ks + k], k < ks; taps outside [lead, S + n_new) are skipped, exactly the taps resample_kernel skips,
+// and the chain is one dfma per tap, k ascending: an output's arithmetic is the whole-signal kernel's bit for bit.  n_out counts
+// outputs, not blocks: the final call's last block may be partial in its inputs (right padding) and in its outputs.  base / lead /
+// n_out are one launch's (a pool group shares a launch class, as above); both are 0 once consumed >= S.  The bank sits in LDS
+// when the launcher says so, rows `kp` floats apart: an odd pitch, so that the 64 lanes of a wave, which walk the phases, hit
+// distinct banks (ks = 94 of 24 kHz -> 44.1 kHz would pair them up).  One block per session, the state moved as above (keep[4]).
+// A slot outside [0, n_slots) reads a zero state and stores none.
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void resample_stream_rational_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
+                                                                       float* __restrict__ state, float* __restrict__ y, int n_new,
+                                                                       int n_out, int orig, int newf, int ks, int kp, int S, int base,
+                                                                       int lead, int kern_in_lds, Sessions<SLOTS> ses)
+{
+    extern __shared__ __attribute__((aligned(16))) float ksm[];
+    if (kern_in_lds) {
+        for (int e = threadIdx.x; e < newf * ks; e += 256) {
+            const int p = e / ks;
+            ksm[p * kp + (e - p * ks)] = kern[e];
+        }
+        __syncthreads();
+    }
+    const float* kt = kern_in_lds ? ksm : kern;
+    const int b = blockIdx.x;
+    size_t at;
+    const bool ok = ses.session(b, at);
+    float* st = state + (ok ? at : 0) * S;
+    const float* xb = x_new + (size_t)b * n_new;
+    const int V = S + n_new;
+    for (int m = threadIdx.x; m < n_out; m += 256) {
+        const int q = m / newf, p = m - q * newf;
+        const float* kr = kt + (size_t)p * kp;
+        const int j0 = base + q * orig;
+        const int k_lo = j0 < lead ? lead - j0 : 0;
+        int k_hi = ks; if (j0 + k_hi > V) k_hi = V - j0;
+        float acc = 0.0f;
+        for (int k = k_lo; k < k_hi; ++k) {
+            const int j = j0 + k;
+            acc = dfma(kr[k], j < S ? (ok ? st[j] : 0.0f) : xb[j - S], acc);
+        }
+        y[(size_t)b * n_out + m] = acc;
+    }
+    if (!ok) return;                                                     // block-uniform: the whole block leaves before the barriers
+    __syncthreads();
+    float keep[4];                                                       // S <= 1024 (checked by the entry point)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        const int j = i + n_new;
+        keep[u] = i < S ? (j < S ? st[j] : xb[j - S]) : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        if (i < S) st[i] = keep[u];
+    }
+}
+
 // Which row of the sender's sample state block `blk` of stream_samples_kernel works on and with which parameters, fixed at
 // compile time.  Dense (a lockstep StreamSender): row blk of buf[rows, cap], x_new[rows, n] and win[rows, w], with the ONE
 // (fill, n, drop) of the launch -- nothing is loaded and the check folds away (the entry point has made it).  Slots (a group of G
@@ -490,6 +552,26 @@ hipError_t launch_resample_stream(const float* x_new, const float* kern, float* 
     else
         hipLaunchKernelGGL(resample_stream_kernel<false>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new, n_out,
                            orig, ks, S, base, lead, in_lds, Sessions<false>{});
+    return hipGetLastError();
+}
+
+// The bank [newf][ks] goes to LDS when it fits 64 KB at an odd row pitch (ks, or ks + 1 for an even ks); else it is read from
+// memory at pitch ks.
+hipError_t launch_resample_stream_rational(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B,
+                                           int n_new, int n_out, int orig, int newf, int ks, int S, int base, int lead, int n_slots,
+                                           hipStream_t s)
+{
+    if (B == 0) return hipSuccess;
+    const int odd = ks | 1;
+    const size_t lds = (size_t)newf * odd * sizeof(float);
+    const int in_lds = lds <= 64 * 1024;
+    const int kp = in_lds ? odd : ks;
+    if (slots)
+        hipLaunchKernelGGL(resample_stream_rational_kernel<true>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new,
+                           n_out, orig, newf, ks, kp, S, base, lead, in_lds, Sessions<true>{slots, n_slots, 1});
+    else
+        hipLaunchKernelGGL(resample_stream_rational_kernel<false>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new,
+                           n_out, orig, newf, ks, kp, S, base, lead, in_lds, Sessions<false>{});
     return hipGetLastError();
 }
 

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import MvqError, check
-from .stream import resample_stream_out_len  # noqa: F401  (host arithmetic, kept where no torch is needed)
+from .stream import resample_stream_out_len, resample_stream_rational_out_len  # noqa: F401  (host arithmetic, kept where no torch is needed)
 
 
 def _stream():
@@ -1544,6 +1544,68 @@ def resample_stream_slots(x_new, kern, state, slots, consumed, orig, newf, width
     least the state's length that one member has consumed (include/mvq.h)."""
     _, sd = _slot_list("resample_stream_slots", slots, state, 2, slots_dev)
     return _resample_stream("resample_stream_slots", x_new, kern, state, sd, consumed, orig, newf, width, final)
+
+
+def _rational_hold(orig, width, hold):
+    return (int(width) + int(orig) - 1) // int(orig) if hold is None else int(hold)
+
+
+def resample_stream_rational_state(orig, width, batch, device, hold=None):
+    """A new session's state for resample_stream_rational: zeros [batch, hold*orig + width], ``hold`` (None: ceil(width/orig)) the
+    lag in filter blocks (layout: include/mvq.h)."""
+    return torch.zeros(int(batch), _rational_hold(orig, width, hold) * int(orig) + int(width), device=device, dtype=torch.float32)
+
+
+def _resample_stream_rational(who, x_new, kern, state, sd, consumed, orig, newf, width, hold, final):
+    """resample_stream_rational and resample_stream_rational_slots: ``sd`` None for the dense sessions state[B, S], else the
+    group's device slot list (_slot_list has checked ``state`` then).  The checks of _resample_stream, and the bank's."""
+    x_new = _dev(x_new, "x_new")
+    if state.dim() != 2 or state.dtype != torch.float32 or not state.is_cuda or not state.is_contiguous() or x_new.dim() != 2 \
+            or x_new.shape[0] != (state.shape[0] if sd is None else sd.shape[0]) or x_new.device != state.device:
+        raise MvqError(f"{who}: x_new must be [B, n_new], one row per session, on the device of state, a contiguous fp32 HIP tensor "
+                       f"[sessions, S]; got {tuple(x_new.shape)} and {tuple(state.shape)}")
+    B, n_new = x_new.shape
+    consumed, orig, newf, width = int(consumed), int(orig), int(newf), int(width)
+    if orig <= 0 or newf <= 0 or width < 0:
+        raise MvqError(f"{who}: orig={orig}, newf={newf}, width={width}")
+    hold = _rational_hold(orig, width, hold)
+    if hold < (width + orig - 1) // orig or state.shape[1] != hold * orig + width:
+        raise MvqError(f"{who}: state {tuple(state.shape)} does not fit orig={orig}, width={width}, hold={hold} "
+                       f"(hold >= {(width + orig - 1) // orig})")
+    if not isinstance(kern, torch.Tensor) or kern.dtype != torch.float32 or not kern.is_contiguous() or kern.device != state.device \
+            or tuple(kern.shape) != (newf, 2 * width + orig):
+        raise MvqError(f"{who}: kern must be the contiguous fp32 bank [{newf}, {2 * width + orig}] on the device of state")
+    if consumed < 0 or consumed % orig:
+        raise MvqError(f"{who}: consumed = {consumed} is no multiple of {orig}")
+    if not final and n_new % orig:
+        raise MvqError(f"{who}: a piece of {n_new} samples is no multiple of {orig}; only the final one may be")
+    n_out = resample_stream_rational_out_len(consumed, n_new, orig, newf, width, hold, final)
+    y = torch.empty(B, n_out, device=x_new.device, dtype=torch.float32)
+    tail = (n_new, consumed, int(bool(final)), n_out, orig, newf, width, kern.shape[1], hold, _stream())
+    if sd is None:
+        check(_lib.lib().mvq_resample_stream_rational_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, *tail),
+              "mvq_resample_stream_rational_f32")
+    else:
+        check(_lib.lib().mvq_resample_stream_rational_slots_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), B,
+                                                                state.shape[0], y.data_ptr(), *tail),
+              "mvq_resample_stream_rational_slots_f32")
+    return y
+
+
+def resample_stream_rational(x_new, kern, state, consumed, orig, newf, width, hold=None, final=False):
+    """The next piece x_new[B, n_new] of a stream resampled by orig : newf -> the outputs y[B, n_out] it completes
+    (mvq_resample_stream_rational_f32; stream.resample_stream_rational_out_len counts them).  ``kern`` [newf, 2*width + orig] is
+    resample.sinc_resample_kernel's bank, ``state`` (resample_stream_rational_state) is updated in place, ``consumed`` = samples
+    given to earlier calls, ``hold`` the lag in filter blocks the state was made for."""
+    return _resample_stream_rational("resample_stream_rational", x_new, kern, state, None, consumed, orig, newf, width, hold, final)
+
+
+def resample_stream_rational_slots(x_new, kern, state, slots, consumed, orig, newf, width, hold=None, final=False, slots_dev=None):
+    """resample_stream_rational for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots]
+    moved on in place (mvq_resample_stream_rational_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of
+    ``orig`` of at least the state's length that one member has consumed (include/mvq.h)."""
+    _, sd = _slot_list("resample_stream_rational_slots", slots, state, 2, slots_dev)
+    return _resample_stream_rational("resample_stream_rational_slots", x_new, kern, state, sd, consumed, orig, newf, width, hold, final)
 
 
 def stream_samples(buf, fill, x_new, w, drop):

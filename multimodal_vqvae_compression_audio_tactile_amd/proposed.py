@@ -1217,6 +1217,14 @@ class ProposedEval(_ProposedBase):
         return StreamSender(self, packet_tok=packet_tok, batch=batch, books_use=books_use, graph=graph, rate=rate, audio=audio,
                             audio_books=audio_books, audio_rate=audio_rate, fec=fec, audio_fec=audio_fec, encoder=encoder)
 
+    def stream_sender_native(self, in_rates=(44100, 3000), **sender_options):
+        """stream_sender fed at the sensors' own rates (stream.StreamSenderNative): ``in_rates`` = (audio Hz, tactile Hz),
+        ``sender_options`` what stream_sender takes.  ``push`` takes whole tokens of native samples (588 and 40 per token at the
+        default rates), ``finish`` the rest; the concatenated output equals compress_packets on the whole item resampled to 24 kHz
+        and crop_matched, byte for byte.  Adds one token-time (13.3 ms) of algorithmic latency."""
+        from .stream import StreamSenderNative
+        return StreamSenderNative(self, in_rates=in_rates, **sender_options)
+
     def stream_sender_pool(self, packet_tok=2, slots=64, books_use=None, encoder="window"):
         """A pool of up to ``slots`` independent sender sessions on this model (stream.StreamSenderPool): ``open`` a session,
         ``step`` once per tick with the samples that arrived (1..16 tokens per session, and the sessions that end); each

@@ -102,3 +102,60 @@ class StreamResample:
         if x is None:
             x = torch.empty(self._lead + (0,), device=self.state.device)
         return self._piece(x, True)
+
+
+class StreamResampleRational:
+    """``Resample(orig_freq, new_freq)`` fed piece by piece for ``batch`` signals in lockstep, for any ratio
+    (mvq_resample_stream_rational_f32): ``StreamResample``'s contract with a polyphase bank.  With orig / new the rates divided by
+    their gcd, a filter block is ``orig`` input samples and ``new`` outputs.  ``push(x[B, ..., n])`` returns the outputs that piece
+    completes, ``hold`` blocks behind the input (None: ceil(width/orig), the smallest lag; a larger one aligns the pieces, e.g. with
+    the 320-sample tokens of the native-rate sender); ``finish(x=None)`` pads on the right and flushes.  A pushed piece must be a
+    multiple of ``orig`` samples long, the final one need not.  The concatenated outputs equal ``Resample(orig_freq, new_freq)`` of
+    the concatenated input bit for bit.  The state is one fixed device buffer [batch, hold*orig + width] (at most 1024 samples) that
+    the kernel updates in place."""
+
+    def __init__(self, orig_freq: int, new_freq: int, batch: int, device=None, hold: int = None, lowpass_filter_width: int = 6,
+                 rolloff: float = 0.99):
+        if int(orig_freq) == int(new_freq):
+            raise ops.MvqError(f"StreamResampleRational: {orig_freq} -> {new_freq} Hz changes nothing (Resample returns its input)")
+        kern, self.width, self.orig, self.new = sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        least = (self.width + self.orig - 1) // self.orig
+        self.hold = least if hold is None else int(hold)
+        if self.hold < least:
+            raise ops.MvqError(f"StreamResampleRational: hold = {self.hold} blocks; {orig_freq} -> {new_freq} Hz needs at least {least}")
+        if self.hold * self.orig + self.width > 1024:
+            raise ops.MvqError(f"StreamResampleRational: a state of {self.hold * self.orig + self.width} samples "
+                               f"(hold = {self.hold}) exceeds the kernel's 1024")
+        self.orig_freq, self.new_freq, self.batch = int(orig_freq), int(new_freq), int(batch)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.kernel = kern.to(device)
+        self.state = ops.resample_stream_rational_state(self.orig, self.width, self.batch, device, self.hold)
+        self.consumed, self.done, self._lead = 0, False, (self.batch,)
+
+    def out_len(self, n: int, final: bool = False) -> int:
+        """Outputs the next piece of ``n`` samples would complete."""
+        from .stream import resample_stream_rational_out_len
+        return resample_stream_rational_out_len(self.consumed, int(n), self.orig, self.new, self.width, self.hold, final)
+
+    def _piece(self, x, final):
+        if self.done:
+            raise ops.MvqError("StreamResampleRational: the stream is finished")
+        if x.shape[0] != self.batch or x.numel() != self.batch * x.shape[-1]:
+            raise ops.MvqError(f"StreamResampleRational: a piece must be [B={self.batch}, ..., n], got {tuple(x.shape)}")
+        lead, n = tuple(x.shape[:-1]), x.shape[-1]
+        y = ops.resample_stream_rational(x.to(torch.float32).reshape(self.batch, n), self.kernel, self.state, self.consumed, self.orig,
+                                         self.new, self.width, hold=self.hold, final=final)
+        self._lead = lead                                                    # finish() without a piece answers in this shape
+        self.consumed += n
+        self.done = final
+        return y.reshape(lead + (y.shape[-1],))
+
+    @torch.no_grad()
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        return self._piece(x, False)
+
+    @torch.no_grad()
+    def finish(self, x: torch.Tensor = None) -> torch.Tensor:
+        if x is None:
+            x = torch.empty(self._lead + (0,), device=self.state.device)
+        return self._piece(x, True)

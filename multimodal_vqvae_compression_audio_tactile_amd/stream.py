@@ -48,6 +48,7 @@ import functools
 from typing import List, NamedTuple, Tuple
 
 HOP = 320                         # samples per latent token (the product of the decoder rates)
+LINK_SR = 24000                   # proposed.EVAL_SR, the rate both encoders run at, restated so that the host arithmetic needs no torch
 DEC_TAIL = 8                      # T_DEC(z[..., :T]) has 320*T - 8 samples
 DEC_HALO_TOK = 10                 # tokens of context on each side of what a window may emit (3200 samples)
 DEC_HALO_SAMPLES = (3132, 3141)   # inexact samples at the start / end of a window that is not at the sequence's edge
@@ -305,6 +306,40 @@ def resample_stream_out_len(consumed: int, n_new: int, orig: int, width: int, fi
     done = max(0, consumed // orig - hold)
     upto = -(-(consumed + n_new) // orig) if final else (consumed + n_new) // orig - hold
     return max(0, upto - done)
+
+
+def resample_stream_rational_out_len(consumed: int, n_new: int, orig: int, new: int, width: int, hold: int = None,
+                                     final: bool = False) -> int:
+    """Outputs a resample_stream_rational call completes after ``consumed`` samples: the count mvq_resample_stream_rational_f32
+    checks.  ``hold`` (None: ceil(width/orig)) is the lag in filter blocks of ``orig`` inputs / ``new`` outputs; a final call counts
+    outputs up to ceil(new*(consumed + n_new)/orig).  With new == 1 and the default hold this is resample_stream_out_len."""
+    hold = (width + orig - 1) // orig if hold is None else hold
+    done = max(0, consumed // orig - hold)
+    if final:
+        return max(0, -(-new * (consumed + n_new) // orig) - new * done)
+    return new * max(0, (consumed + n_new) // orig - hold - done)
+
+
+def native_token_plan(in_rate: int, out_rate: int = 24000, hop: int = HOP, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The native-rate sender's arithmetic of one modality -> (orig, new, width, hold, samples per token, state length): ``hold`` =
+    the filter blocks of one ``hop``-sample token at ``out_rate``, so a resample call completes whole tokens.  ValueError when a
+    token is no whole number of blocks (hop*orig % new), when one token of blocks is less than the filter needs, or when the state
+    hold*orig + width exceeds the kernel's 1024 samples.  (width: resample.sinc_resample_kernel's, restated so that no torch is needed.)"""
+    import math
+    g = math.gcd(int(in_rate), int(out_rate))
+    orig, new = int(in_rate) // g, int(out_rate) // g
+    width = int(math.ceil(lowpass_filter_width * orig / (min(orig, new) * rolloff)))
+    if hop * orig % new:
+        raise ValueError(f"StreamSenderNative: at {in_rate} Hz a {hop}-sample token at {out_rate} Hz is {hop * orig}/{new} input "
+                         "samples, no whole number of filter blocks")
+    hold = hop // new                                                    # blocks per token (orig and new are coprime)
+    if hold < (width + orig - 1) // orig:
+        raise ValueError(f"StreamSenderNative: at {in_rate} Hz one token is {hold} filter blocks, fewer than the filter's "
+                         f"{(width + orig - 1) // orig}")
+    state = hold * orig + width
+    if state > 1024:
+        raise ValueError(f"StreamSenderNative: at {in_rate} Hz the resampler state is {state} samples; the kernel carries at most 1024")
+    return orig, new, width, hold, hold * orig, state
 
 
 class PoolGroup(NamedTuple):
@@ -1070,6 +1105,108 @@ class StreamSender(_SenderCore):
             x_s[B:].copy_(t.reshape(B, n))
         g.replay()
         return bodies_s, codes_s.clone()
+
+
+class StreamSenderNative:
+    """``StreamSender`` fed at the sensors' own rates: ``in_rates`` = (audio Hz, tactile Hz), by default the
+    reference's 44.1 kHz microphone and 3 kHz accelerometer.  It is two ``resample.StreamResampleRational`` (-> 24 kHz) in front of
+    one inner ``StreamSender(net, **sender_options)``; each resampler lags by the filter blocks of exactly one 320-sample token
+    (``native_token_plan``: 4 blocks of 147 samples for 44.1 kHz, 40 of 1 for 3 kHz), so every call hands the inner session whole
+    tokens.  That lag is the algorithmic latency this front end adds: one token-time, 13.3 ms, on top of the inner session's
+    213.3 + 106.7 ms.
+
+    ``push(a, t)``: ``a`` [B, 1, tok_a*m], ``t`` [B, 1, tok_t*m] with one m, 1 <= m <= 16 (``samples_per_token`` = (tok_a, tok_t):
+    (588, 40) for the default rates) -> two resample launches, then the inner ``push`` of the 320*k samples they completed, whose
+    return value is returned unchanged: k = m - 1 for the first push (one token completes none: the inner session's "nothing"),
+    k = m afterwards.  ``finish(a=None, t=None)`` takes the remaining native samples (any count, per modality, or none), flushes both
+    resamplers, crops the two 24 kHz tails to the shorter (the reference's crop_match), feeds whole tokens through inner pushes of at
+    most 16 and the remainder to the inner ``finish``, and returns ``finish``'s tuple with what those pushes returned in front, per item.
+
+    Per item, all pushes and ``finish`` concatenated equal compress_packets(*crop_match(Resample(sr_a, 24000)(a), Resample(sr_t,
+    24000)(t)), ...) with the same options (compress_packets_av for audio="packets"): packets and parity byte for byte, equal
+    StreamInfos, equal audio codes.  Refused with ValueError before anything is allocated: rates at which a token is no whole number
+    of filter blocks (2800 Hz) or the resampler state would exceed 1024 samples, a rate that already is 24 kHz, and whatever the
+    inner StreamSender refuses.  ``graph=True`` passes through: the inner steady step stays its one captured graph, the two resample
+    launches run eagerly in front of it."""
+
+    def __init__(self, net, in_rates=(44100, 3000), **sender_options):
+        from .resample import StreamResampleRational
+        try:
+            ra, rt = (int(r) for r in in_rates)
+        except (TypeError, ValueError):
+            raise ValueError(f"StreamSenderNative: in_rates must be (audio Hz, tactile Hz), not {in_rates!r}") from None
+        for r in (ra, rt):
+            if r <= 0 or r == LINK_SR:
+                raise ValueError(f"StreamSenderNative: an input rate of {r} Hz (positive, and not the link's own {LINK_SR} Hz: "
+                                 "StreamSender takes those samples as they are)")
+        plans = tuple(native_token_plan(r, LINK_SR) for r in (ra, rt))                 # ValueError before any allocation
+        self.in_rates = (ra, rt)
+        self.samples_per_token = (plans[0][4], plans[1][4])
+        self.inner = StreamSender(net, **sender_options)
+        self.batch, self.dev = self.inner.batch, self.inner.dev
+        self.rs = tuple(StreamResampleRational(r, LINK_SR, self.batch, device=self.dev, hold=p[3]) for r, p in zip((ra, rt), plans))
+
+    @property
+    def tokens(self):
+        """Tokens of 24 kHz samples handed to the inner session so far."""
+        return self.inner.tokens
+
+    @property
+    def finished(self):
+        return self.inner.finished
+
+    def _native(self, x, name, what):
+        import torch
+        x = torch.as_tensor(x)
+        if x.dim() != 3 or x.shape[0] != self.batch or x.shape[1] != 1 or not x.dtype.is_floating_point:
+            raise ValueError(f"StreamSenderNative.{what}: {name} must be a float tensor [B={self.batch}, 1, samples], got {tuple(x.shape)}")
+        return x
+
+    def push(self, a, t):
+        """The next ``m`` tokens of native samples of both modalities (class docstring) -> the inner ``StreamSender.push``'s value."""
+        import torch
+        self.inner._open("push")
+        a, t = self._native(a, "a", "push"), self._native(t, "t", "push")
+        (ta, tt), (na, nt) = self.samples_per_token, (a.shape[2], t.shape[2])
+        m = na // ta
+        if na != ta * m or nt != tt * m or not 1 <= m <= PUSH_MAX_TOK:
+            raise ValueError(f"StreamSenderNative.push: {na} audio and {nt} tactile samples; a push is {ta}*m and {tt}*m samples "
+                             f"with one m, 1 <= m <= {PUSH_MAX_TOK} (anything else goes to finish)")
+        with torch.no_grad():
+            ya = self.rs[0].push(a.to(self.dev, torch.float32))
+            yt = self.rs[1].push(t.to(self.dev, torch.float32))
+        assert ya.shape == yt.shape and ya.shape[2] % HOP == 0
+        if ya.shape[2] == 0:                                                           # the first token: the resamplers' lag
+            return self.inner._nothing()
+        return self.inner.push(ya, yt)
+
+    def finish(self, a=None, t=None):
+        """Flush (class docstring): the remaining native samples of either modality, or none -> the inner ``finish``'s tuple, with
+        the packets, audio codes and parity of the inner pushes that preceded it in front, per item."""
+        import torch
+        self.inner._open("finish")
+        a = None if a is None else self._native(a, "a", "finish")
+        t = None if t is None else self._native(t, "t", "finish")
+        with torch.no_grad():
+            ya, yt = (y.reshape(self.batch, 1, y.shape[-1]) for y in
+                      (rs.finish(None if x is None else x.to(self.dev, torch.float32)) for rs, x in zip(self.rs, (a, t))))
+        T = min(ya.shape[2], yt.shape[2])                                              # crop_match
+        outs, at = [], 0
+        while T - at >= HOP:
+            n = min((T - at) // HOP, PUSH_MAX_TOK) * HOP
+            outs.append(self.inner.push(ya[:, :, at:at + n], yt[:, :, at:at + n]))
+            at += n
+        fin = self.inner.finish(ya[:, :, at:T], yt[:, :, at:T]) if T > at else self.inner.finish()
+        n_info = 2 if self.inner.audio_packets else 1
+        merged = list(fin)
+        for i in range(len(fin) - n_info):                                             # push element i is finish element i, the infos skipped
+            j = i if i < 2 else i + n_info
+            parts = [o[i] for o in outs] + [fin[j]]
+            if isinstance(fin[j], torch.Tensor):
+                merged[j] = torch.cat(parts, dim=2)
+            else:
+                merged[j] = [sum((p[b] for p in parts), []) for b in range(self.batch)]
+        return tuple(merged)
 
 
 def _receiver_args(who, net, K, nb, packet_tok, conceal, out_rate):
