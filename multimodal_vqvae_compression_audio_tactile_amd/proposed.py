@@ -500,30 +500,39 @@ class _ProposedBase(nn.Module):
     # one stream at throughput batch sizes; MVQ_TWO_STREAM_MAX_BATCH raises the cap.
     TWO_STREAM_MAX_BATCH = int(_dac.HOST_ENV_SEEN.get("MVQ_TWO_STREAM_MAX_BATCH", "64"))      # read once at import, reported by plan_overrides()
 
-    def _encode_branches(self, a_1T, t_1T):
-        """qa = A_QUANT(A_ENC(a)) and zt = T_ENC(t) are independent.  In the latency regime (few segments: every
-        launch underfills the 256 CUs) the audio branch runs on a second HIP stream beside the tactile branch."""
+    def _two_streams(self, x, audio_branch, tactile_branch):
+        """THE rule for the two encoder branches, which are independent: ``audio_branch()`` -> a tuple of tensors,
+        ``tactile_branch()`` -> zt; -> (that tuple, zt).  In the latency regime (few segments ``x.shape[0]``: every launch underfills
+        the 256 CUs) the audio branch runs on a second HIP stream beside the tactile branch and everything it returned is recorded
+        on the current stream; otherwise the audio branch, then the tactile one, on the current stream."""
         # The opt-in arithmetic modes (frozen, non-parity) keep ONE stream: round 5 saw the audio branch of the FIRST two-stream call
         # of a fresh model come back wrong in bf16x6 (B = 2, fixture G4) in 4 of 4 plain runs and in 0 of 12 runs with any
         # perturbation (a synchronisation, NaN-poisoned allocations, one more reference held, any single new kernel switched off);
         # the cause was not established (DESIGN.md section 6d), the exact path has never shown it.
-        if a_1T.shape[0] > self.TWO_STREAM_MAX_BATCH or not a_1T.is_cuda or ops.get_arith() != "f32":
-            za = self.A_ENC(a_1T)
-            qa, *_ = self.A_QUANT(za)
-            return qa, self.T_ENC(t_1T)
+        if x.shape[0] > self.TWO_STREAM_MAX_BATCH or not x.is_cuda or ops.get_arith() != "f32":
+            audio = audio_branch()
+            return audio, tactile_branch()
         cur = torch.cuda.current_stream()
         side = getattr(self, "_side_stream", None)
-        if side is None or side.device != a_1T.device:
-            side = torch.cuda.Stream(device=a_1T.device)
+        if side is None or side.device != x.device:
+            side = torch.cuda.Stream(device=x.device)
             self._side_stream = side
         side.wait_stream(cur)
         with torch.cuda.stream(side):
+            audio = audio_branch()
+        zt = tactile_branch()
+        cur.wait_stream(side)
+        for t in audio:
+            t.record_stream(cur)
+        return audio, zt
+
+    def _encode_branches(self, a_1T, t_1T):
+        """qa = A_QUANT(A_ENC(a)) and zt = T_ENC(t), on one or two HIP streams (``_two_streams``)."""
+        def audio():
             za = self.A_ENC(a_1T)
             qa, *_ = self.A_QUANT(za)
-        zt = self.T_ENC(t_1T)
-        cur.wait_stream(side)
-        for x in (za, qa):
-            x.record_stream(cur)
+            return za, qa
+        (_, qa), zt = self._two_streams(a_1T, audio, lambda: self.T_ENC(t_1T))
         return qa, zt
 
     @torch.no_grad()
@@ -1002,6 +1011,7 @@ class ProposedEval(_ProposedBase):
         over GF(2^8)) every group gets r parity packets, group-major in the item's list -- index 0 the XOR packet unchanged, the
         others with magic ``MR`` -- and "one deficient packet" above reads "at most as many as parity packets of the group arrived"."""
         from . import bitstream, packets
+        from .stream import _TxBack
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
         if fec is not None:
             self._fec_resolve(fec, self.vq.n_embed, self._rate_books(books_use), packet_tok)
@@ -1012,27 +1022,12 @@ class ProposedEval(_ProposedBase):
             _, codes, idx, nb_sent = self.encode_latents_with_indices(a_1T, t_1T, books_use=books_use, rate=rate, packet_tok=packet_tok)
         nb, B, T = idx.shape
         info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
-        bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
-        if fec is not None:                                                   # bodies, the counts under ``rate``, the parity rows: one copy
-            rows = ops.fec_parity(bodies, nb_sent, info, fec)
-            full, n_cnt = bodies.shape[2], 0 if nb_sent is None else info.P
-            host = torch.cat([bodies.reshape(B, -1)] + ([] if nb_sent is None else [nb_sent]) + [rows.reshape(B, -1)], dim=1).cpu().numpy()
-            cuts = np.cumsum([0, info.P * full, n_cnt])
-            hb, hc, hf = host[:, :cuts[1]].reshape(B, info.P, full), host[:, cuts[1]:cuts[2]], host[:, cuts[2]:]
-            codes = codes.cpu().numpy()
-            return ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b] if n_cnt else None) for b in range(B)],
-                    [bitstream.pack_indices(codes[b], self.A_QUANT.codebook_size) for b in range(B)],
-                    [packets.frame_fec(hf[b], info, fec) for b in range(B)])
-        if nb_sent is None:
-            bodies, counts = bodies.cpu().numpy(), [None] * B
-        else:
-            full = bodies.shape[2]
-            host = torch.cat([bodies.reshape(B, info.P * full), nb_sent], dim=1).cpu().numpy()
-            bodies, counts = host[:, :info.P * full].reshape(B, info.P, full), host[:, info.P * full:]
+        back = _TxBack(info.K, nb, packet_tok, counts=rate is not None, fec=fec)   # bodies, the counts under ``rate``, the parity rows
+        host = back.pack(idx, nb_sent).cpu().numpy()                           # one copy
         codes = codes.cpu().numpy()
-        k_audio = self.A_QUANT.codebook_size
-        return ([info] * B, [packets.frame(bodies[b], info, nb_sent=counts[b]) for b in range(B)],
-                [bitstream.pack_indices(codes[b], k_audio) for b in range(B)])
+        framed = [back.frame_item(host[b], T) for b in range(B)]
+        out = ([info] * B, [f[0] for f in framed], [bitstream.pack_indices(codes[b], self.A_QUANT.codebook_size) for b in range(B)])
+        return out if fec is None else out + ([f[1] for f in framed],)
 
     @torch.no_grad()
     def decompress_packets(self, infos, tactile_packets, audio_payloads, books_use=None, conceal="predict", plc=None, fec=None,
@@ -1094,6 +1089,7 @@ class ProposedEval(_ProposedBase):
         then (fec_packets, audio_fec_packets), per item one list of parity packets per stream; a stream without a Fec gets empty
         lists.  The closed loop: as compress_packets(fec=) says, on each stream."""
         from . import packets
+        from .stream import _TxBack
         audio_rate, na_use, packet_tok = self._audio_rate_resolve(audio_rate, audio_books, packet_tok)
         if fec is not None:
             self._fec_resolve(fec, self.vq.n_embed, self._rate_books(books_use), packet_tok)
@@ -1104,25 +1100,11 @@ class ProposedEval(_ProposedBase):
         nb, B, T = idx.shape
         info = packets.StreamInfo(self.vq.n_embed, nb, T, packet_tok)
         ainfo = packets.StreamInfo(self.A_QUANT.codebook_size, na_use, codes.shape[2], packet_tok)
-        bodies = ops.idx_pack_packets(idx, info.K, packet_tok)
-        abodies = ops.idx_pack_packets(codes[:, :na_use], ainfo.K, packet_tok, book_dim=1)
-        full, afull = bodies.shape[2], abodies.shape[2]
-        parts = [bodies.reshape(B, -1), nb_sent, abodies.reshape(B, -1), na_sent]
-        if fec is not None:
-            parts.append(ops.fec_parity(bodies, nb_sent, info, fec).reshape(B, -1))
-        if audio_fec is not None:
-            parts.append(ops.fec_parity(abodies, na_sent, ainfo, audio_fec).reshape(B, -1))
-        cuts = np.cumsum([0] + [int(x.shape[1]) for x in parts])
-        host = torch.cat(parts, dim=1).cpu().numpy()
-        hb, hc, ab, ac, *hf = (host[:, cuts[i]:cuts[i + 1]] for i in range(len(parts)))
-        hb, ab = hb.reshape(B, info.P, full), ab.reshape(B, ainfo.P, afull)
-        out = ([info] * B, [packets.frame(hb[b], info, nb_sent=hc[b]) for b in range(B)],
-               [ainfo] * B, [packets.frame(ab[b], ainfo, nb_sent=ac[b]) for b in range(B)])
-        if fec is None and audio_fec is None:
-            return out
-        tf = [packets.frame_fec(hf[0][b], info, fec) for b in range(B)] if fec is not None else [[] for _ in range(B)]
-        af = [packets.frame_fec(hf[-1][b], ainfo, audio_fec) for b in range(B)] if audio_fec is not None else [[] for _ in range(B)]
-        return out + (tf, af)
+        back = _TxBack(info.K, nb, packet_tok, (ainfo.K, na_use), fec=fec, audio_fec=audio_fec)
+        host = back.pack(idx, nb_sent, codes, na_sent).cpu().numpy()
+        framed = [back.frame_item(host[b], T) for b in range(B)]
+        tp, ap, *parity = ([f[i] for f in framed] for i in range(2 if fec is None and audio_fec is None else 4))
+        return ([info] * B, tp, [ainfo] * B, ap, *parity)
 
     @torch.no_grad()
     def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None,

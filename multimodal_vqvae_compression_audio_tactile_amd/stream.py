@@ -38,9 +38,10 @@ tick batches whichever sessions have a chunk ready, grouped by ``pool_groups`` (
 is a session's host arithmetic, ``sender_pool_groups`` the sessions of a tick that share an encode.
 ``StreamSenderPoolAV`` / ``StreamReceiverPoolAV`` (``ProposedEval.stream_sender_pool_av`` / ``stream_receiver_pool_av``) are the two
 pools with every option of the lockstep sessions -- rate control, audio packets, FEC on both streams, audio concealment: the same
-sessions and groups, ``_SenderCore._frame_one`` a session's framing.  ``_RxFront`` is every receiver's front
-end -- the whole-item calls', the lockstep session's and the pools': it owns the format of the upload (``receiver_layout``), fills
-it on the host and unpacks it on the device; ``_SessionTable`` is the session bookkeeping the four pools share.
+sessions and groups.  ``_RxFront`` is every receiver's front end -- the whole-item calls', the lockstep
+session's and the pools': it owns the format of the upload (``receiver_layout``), fills it on the host and unpacks it on the device.
+``_TxBack`` is its mirror, every sender's back end: it owns the format of the read-back, packs it on the device and frames it on
+the host.  ``_SessionTable`` is the session bookkeeping the four pools share.
 """
 from __future__ import annotations
 
@@ -419,26 +420,35 @@ def receiver_layout(G: int, n: int, full: int, afull, fec, audio_fec, packet_tok
     return RxLayout(P, 0, G * P * full, ab, ac, at[0], at[1], o)
 
 
-class _RxFront:
-    """THE receiver front end, from "the packets that arrived" to indices and per-token counts on the device: the owner of the
-    upload's format (DESIGN.md section 25).  decompress_packets / decompress_packets_av, StreamReceiver and both receiver pools
-    build their upload and read it through this object and hold no offset of their own.  A stream is the tactile one
-    (``K``, ``nb``, ``fec``) and, with ``audio`` = (K_a, na), the audio one (``audio_fec``); one ``packet_tok`` serves both."""
+class _Streams:
+    """What both ends of the link know of its streams: the tactile one (``K``, ``nb``, ``fec``) and, with ``audio`` = (K_a, na), the
+    audio one (``audio_fec``); one ``packet_tok`` serves both."""
 
     def __init__(self, K, nb, packet_tok, audio=None, fec=None, audio_fec=None):
-        from .packets import body_bytes, gather, gather_fec
-        self._gather, self._gather_fec = gather, gather_fec
+        from .packets import body_bytes
         self.K, self.nb, self.packet_tok, self.audio, self.fec, self.audio_fec = K, nb, packet_tok, audio, fec, audio_fec
         self.full = body_bytes(packet_tok, nb, K)
         self.afull = None if audio is None else body_bytes(packet_tok, audio[1], audio[0])
-        # pure functions of n, (G, n) and the layout, and a session asks for the same ones with every chunk: computed once each
-        self._streams, self.layout, self._spans = (functools.lru_cache(None)(f) for f in (self._streams, self.layout, self._spans))
+        self._streams = functools.lru_cache(None)(self._streams)          # a pure function of n; a session asks with every chunk
 
     def _streams(self, n):
         """(StreamInfo of ``n`` tokens, Fec or None) per stream: tactile, then audio."""
         from .packets import StreamInfo
         out = ((StreamInfo(self.K, self.nb, n, self.packet_tok), self.fec),)
         return out if self.audio is None else out + ((StreamInfo(*self.audio, n, self.packet_tok), self.audio_fec),)
+
+
+class _RxFront(_Streams):
+    """THE receiver front end, from "the packets that arrived" to indices and per-token counts on the device: the owner of the
+    upload's format (DESIGN.md section 25).  decompress_packets / decompress_packets_av, StreamReceiver and both receiver pools
+    build their upload and read it through this object and hold no offset of their own.  The streams are ``_Streams``'."""
+
+    def __init__(self, K, nb, packet_tok, audio=None, fec=None, audio_fec=None):
+        from .packets import gather, gather_fec
+        super().__init__(K, nb, packet_tok, audio, fec, audio_fec)
+        self._gather, self._gather_fec = gather, gather_fec
+        # pure functions of (G, n) and the layout, and a session asks for the same ones with every chunk: computed once each
+        self.layout, self._spans = (functools.lru_cache(None)(f) for f in (self.layout, self._spans))
 
     def layout(self, G, n) -> RxLayout:
         """receiver_layout of ``G`` items of ``n`` tokens for these streams, every Fec resolved against its stream."""
@@ -488,6 +498,67 @@ class _RxFront:
         if self.audio is None:
             return out[0], out[1], None, None
         return out[0], out[1], out[2].permute(1, 0, 2).contiguous(), out[3]   # [na, G, n] -> [G, na, n], on the device
+
+
+class _TxBack(_Streams):
+    """THE sender back end, the mirror of ``_RxFront``: from indices and per-packet counts on the device to framed packets on the
+    host, and the owner of the read-back's format.  compress_packets / compress_packets_av, StreamSender
+    and both sender pools pack their read-back and frame it through this object and hold no offset of their own.  ``counts``: the
+    per-packet book counts ride behind each stream's bodies -- under a ``rate``, and always with audio packets."""
+
+    def __init__(self, K, nb, packet_tok, audio=None, counts=False, fec=None, audio_fec=None):
+        super().__init__(K, nb, packet_tok, audio, fec, audio_fec)
+        self.counts = bool(counts) or audio is not None
+        self.layout = functools.lru_cache(None)(self.layout)
+
+    def layout(self, n):
+        """The [start, end) bytes of every part of ONE item's row for ``n`` tokens, in the row's order: per stream (tactile, then
+        audio) the bodies [P, full] and, with ``counts``, the counts [P]; then per stream with a Fec its parity rows
+        (Fec.rows_shape).  The one place that turns the options into slices."""
+        import itertools
+        import math
+        streams, sizes = self._streams(n), []
+        for (inf, _), full in zip(streams, (self.full, self.afull)):
+            sizes += [inf.P * full, inf.P] if self.counts else [inf.P * full]
+        sizes += [math.prod(f.rows_shape(inf)) for inf, f in streams if f is not None]
+        ends = list(itertools.accumulate(sizes))
+        return tuple(zip([0] + ends, ends))
+
+    def pack(self, idx, nb_sent, codes=None, na_sent=None):
+        """Device: idx [nb, G, n] and, with audio packets, the audio codes [G, >= na, n], with ``counts`` each stream's counts
+        uint8 [G, P] (else None) -> the rows uint8 [G, bytes of layout(n)] for ONE read-back: ops.idx_pack_packets per stream,
+        then ops.fec_parity per stream with a Fec -- pack tactile, pack audio, tactile parity, audio parity, the order inside the
+        captured steady step -- then one cat.  A row of a single part is the packed bodies themselves, a view: no copy kernel."""
+        import torch
+        from . import ops
+        G, n = idx.shape[1:]
+        streams, parts = self._streams(n), []
+        data = [(idx, 0)] + ([] if self.audio is None else [(codes[:, :self.audio[1]], 1)])                # indices, their book_dim
+        sent = [nb_sent, na_sent] if self.counts else [None, None]
+        bodies = [ops.idx_pack_packets(x, inf.K, self.packet_tok, book_dim=d) for (inf, _), (x, d) in zip(streams, data)]
+        for b, c in zip(bodies, sent):
+            parts += [b.reshape(G, -1)] if c is None else [b.reshape(G, -1), c]
+        parts += [ops.fec_parity(b, c, inf, f).reshape(G, -1) for (inf, f), b, c in zip(streams, bodies, sent) if f is not None]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+    def frame_item(self, row, n, seq_base=0):
+        """Host: ONE item's row of ``pack``'s array -> the headers, data packets numbered from ``seq_base`` (packets.frame) and a
+        stream's parity packets from seq_base // fec.group (packets.frame_fec): (tactile_packets,) or (tactile_packets,
+        audio_packets), then -- only when some Fec is set -- one parity list per stream that may have one: (fec_packets,), with
+        audio packets (fec_packets, audio_fec_packets), [] for a stream without a Fec."""
+        import numpy as np
+        from .packets import frame, frame_fec
+        row, spans, streams = np.asarray(row, np.uint8).reshape(-1), self.layout(n), self._streams(n)
+        if row.size != spans[-1][1]:
+            raise ValueError(f"_TxBack.frame_item: a row of {row.size} bytes for {spans[-1][1]} of {n} tokens")
+        part = iter([row[a:b] for a, b in spans])                            # consumed in layout order: data parts, then parity parts
+        out = ()
+        for inf, _ in streams:
+            body = next(part)
+            out += (frame(body, inf, nb_sent=next(part) if self.counts else None, seq_base=seq_base),)
+        if self.fec is None and self.audio_fec is None:
+            return out
+        return out + tuple([] if f is None else frame_fec(next(part), inf, f, seq_base=seq_base // int(f.group)) for inf, f in streams)
 
 
 class SenderStep(NamedTuple):
@@ -716,7 +787,7 @@ class _SenderCore:
                  audio_rate=None, fec=None, audio_fec=None, encoder="window"):
         import torch
         from . import proposed
-        from .packets import StreamInfo, body_bytes, _check
+        from .packets import StreamInfo, _check
         if packet_tok < 1 or CHUNK_TOK % packet_tok:
             raise ValueError(f"{who}: packet_tok = {packet_tok} does not divide the {CHUNK_TOK}-token chunk "
                              "(a packet must never straddle two chunks)")
@@ -739,12 +810,11 @@ class _SenderCore:
         if audio == "codes" and (audio_books is not None or audio_rate is not None):
             raise ValueError(f"{who}: audio_books / audio_rate go with audio='packets'")
         self.audio_packets = audio == "packets"
-        self.audio_rate = self.na = self.afull = None
+        self.audio_rate = self.na = None
         if self.audio_packets:                                                         # both loops run closed (proposed.encode_latents_with_indices)
             from .packets import Rate
             self.audio_rate, self.na, _ = net._audio_rate_resolve(audio_rate, audio_books, packet_tok)
             self.K_audio = int(net.A_QUANT.codebook_size)
-            self.afull = body_bytes(packet_tok, self.na, self.K_audio)
             rate = Rate() if rate is None else rate
         if rate is not None:
             net._rate_resolve(rate, books_use, packet_tok)                             # ValueError before any session state exists
@@ -756,9 +826,10 @@ class _SenderCore:
         if audio_fec is not None:
             net._fec_resolve(audio_fec, self.K_audio, self.na, packet_tok, what="audio_fec")
         self.fec, self.audio_fec = fec, audio_fec
+        self._back = _TxBack(self.K, self.nb, packet_tok, (self.K_audio, self.na) if self.audio_packets else None, rate is not None,
+                             fec, audio_fec)
         self.dev = net.proj_up.weight.device
         self.C = net.proj_up.out_channels
-        self.full = body_bytes(packet_tok, self.nb, self.K)
         self.n_audio_books = net.A_QUANT.n_codebooks
         self.buf = torch.zeros(*buf_shape, device=self.dev)                            # per session: an audio and a tactile row
         self.carry = torch.zeros(sessions, self.C, device=self.dev)                    # per session: z_run[..., -1] of the chunk before
@@ -767,157 +838,98 @@ class _SenderCore:
             self.enc_state = (net.A_ENC.stream_state(sessions), net.T_ENC.stream_state(sessions))
         self._step = sender_step if encoder == "window" else sender_step_stateful
 
-    def _branches_stateful(self, a_w, t_w, n_tok, before, last, sl=None, want_za=False):
-        """``_branches`` for encoder="stateful": the same two stack calls on the same two HIP streams under the same rule, each
-        A_ENC / T_ENC.forward_stream on the samples that were not encoded yet (``before`` samples were; enc_state moves on in
-        place).  They return exactly the chunk's n_tok tokens, so nothing is sliced."""
-        import torch
-        from . import ops
+    def _branches_stateful(self, a_w, t_w, n_tok, before, last, sl=None):
+        """``_branches`` for encoder="stateful": the same two stack calls under the same rule, each A_ENC / T_ENC.forward_stream on
+        the samples that were not encoded yet (``before`` samples were; enc_state moves on in place).  They return exactly the
+        chunk's n_tok tokens, so nothing is sliced."""
         net = self.net
         slots, slots_dev = (None, None) if sl is None else sl
         sa, st_ = self.enc_state
-        if a_w.shape[0] > net.TWO_STREAM_MAX_BATCH or not a_w.is_cuda or ops.get_arith() != "f32":
-            za_c = net.A_ENC.forward_stream(sa, a_w, before, last, slots=slots, slots_dev=slots_dev)
-            qa, codes, *_ = net.A_QUANT(za_c)
-            zt = net.T_ENC.forward_stream(st_, t_w, before, last, slots=slots, slots_dev=slots_dev)
-            assert za_c.shape[-1] == zt.shape[-1] == n_tok
-            return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
-        cur = torch.cuda.current_stream()
-        side = getattr(net, "_side_stream", None)
-        if side is None or side.device != a_w.device:
-            side = torch.cuda.Stream(device=a_w.device)
-            net._side_stream = side
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            za_c = net.A_ENC.forward_stream(sa, a_w, before, last, slots=slots, slots_dev=slots_dev)
-            qa, codes, *_ = net.A_QUANT(za_c)
-        zt = net.T_ENC.forward_stream(st_, t_w, before, last, slots=slots, slots_dev=slots_dev)
-        cur.wait_stream(side)
-        for x in (za_c, qa, codes):
-            x.record_stream(cur)
-        assert za_c.shape[-1] == zt.shape[-1] == n_tok
-        return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
 
-    def _branches(self, a_w, t_w, lo, hi, want_za=False):
-        """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt) and, with
-        ``want_za``, the encoder output the quantiser searched; the audio branch on a second HIP stream under the rule of
-        ``_encode_branches``."""
-        import torch
-        from . import ops
+        def audio():
+            za = net.A_ENC.forward_stream(sa, a_w, before, last, slots=slots, slots_dev=slots_dev)
+            qa, codes, *_ = net.A_QUANT(za)
+            return za, qa, codes
+        (za, qa, codes), zt = net._two_streams(a_w, audio, lambda: net.T_ENC.forward_stream(st_, t_w, before, last, slots=slots,
+                                                                                            slots_dev=slots_dev))
+        assert za.shape[-1] == zt.shape[-1] == n_tok
+        return qa, codes, zt, za
+
+    def _branches(self, a_w, t_w, lo, hi):
+        """The two encoders on the window and the audio quantiser on tokens [lo, hi) of it -> (qa, codes, zt, the encoder output
+        the quantiser searched); one or two HIP streams as ``ProposedEval._two_streams`` decides."""
         net = self.net
-        if a_w.shape[0] > net.TWO_STREAM_MAX_BATCH or not a_w.is_cuda or ops.get_arith() != "f32":
-            za_c = net.A_ENC(a_w)[..., lo:hi].contiguous()
-            qa, codes, *_ = net.A_QUANT(za_c)
-            zt = net.T_ENC(t_w)[..., lo:hi].contiguous()
-            return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
-        cur = torch.cuda.current_stream()
-        side = getattr(net, "_side_stream", None)
-        if side is None or side.device != a_w.device:
-            side = torch.cuda.Stream(device=a_w.device)
-            net._side_stream = side
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
+
+        def audio():
             za = net.A_ENC(a_w)
             za_c = za[..., lo:hi].contiguous()
             qa, codes, *_ = net.A_QUANT(za_c)
-        zt = net.T_ENC(t_w)[..., lo:hi].contiguous()
-        cur.wait_stream(side)
-        for x in (za, za_c, qa, codes):
-            x.record_stream(cur)
-        return (qa, codes, zt, za_c) if want_za else (qa, codes, zt)
+            return za, za_c, qa, codes
+        (_, za_c, qa, codes), zt = net._two_streams(a_w, audio, lambda: net.T_ENC(t_w)[..., lo:hi].contiguous())
+        return qa, codes, zt, za_c
 
     def _encode(self, win, lo, hi, sl=None, before=None, last=False):
-        """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (packet bodies
-        uint8 [G, P, full], audio codes int64 [G, 32, hi - lo]); the carried token moves on in place.  With ``self.rate`` the loop
-        runs closed (on the books each packet carries and on qa from the codes, as the receiver will) and the bodies come back as
-        uint8 [G, P*full + P]: every packet's body, then every packet's book count, for one read-back.  With ``self.fec`` /
-        ``self.audio_fec`` the parity rows of the window's packets (ops.fec_parity on the packed bodies and the device-side counts;
-        the window starts on a chunk, so its groups are the item's) follow everything else in the same uint8 [G, ...] array.
+        """Device: the window win[2, G, w] (audio rows, then tactile rows) -> latents of tokens [lo, hi) of it -> (the rows uint8
+        [G, bytes] of ``_TxBack.pack`` for one read-back, audio codes int64 [G, 32, hi - lo]); the carried token moves on in place.
+        With ``self.rate`` the loop runs closed (on the books each packet carries and on qa from the codes, as the receiver will),
+        with audio packets on both streams; the counts and, with ``self.fec`` / ``self.audio_fec``, the parity rows of the window's
+        packets (the window starts on a chunk, so its groups are the item's) ride in the same rows.
         encoder="stateful": ``win`` holds only the samples not encoded yet, ``before`` samples were (``last``: the finish), and the
         latents come from ``_branches_stateful``; everything behind them is the same."""
-        import torch
         from . import ops
-        from .packets import StreamInfo
-        n_tok = hi - lo
-        if self.audio_packets:      # uint8 [G, P*full + P + P*afull + P]: tactile bodies, counts, audio bodies, counts: one read-back
-            if self.enc_state is None:
-                _, codes, zt, za = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi, want_za=True)
-            else:
-                _, codes, zt, za = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, sl, want_za=True)
-            carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
-            qa, _, na_sent = self.net.A_QUANT.rate(za, codes, self.audio_rate, self.packet_tok, self.na)
-            _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
-                                                         packet_tok=self.packet_tok)
-            if sl is not None and not last:                                            # a session that ends needs no carry
-                ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
-            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
-            abodies = ops.idx_pack_packets(codes[:, :self.na], self.K_audio, self.packet_tok, book_dim=1)
-            G = bodies.shape[0]
-            parts = [bodies.reshape(G, -1), nb_sent, abodies.reshape(G, -1), na_sent]
-            if self.fec is not None:
-                parts.append(ops.fec_parity(bodies, nb_sent, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec).reshape(G, -1))
-            if self.audio_fec is not None:
-                parts.append(ops.fec_parity(abodies, na_sent, StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok),
-                                            self.audio_fec).reshape(G, -1))
-            return torch.cat(parts, dim=1), codes
+        a_w, t_w = win[0].unsqueeze(1), win[1].unsqueeze(1)
         if self.enc_state is None:
-            qa, codes, zt = self._branches(win[0].unsqueeze(1), win[1].unsqueeze(1), lo, hi)
+            qa, codes, zt, za = self._branches(a_w, t_w, lo, hi)
         else:
-            qa, codes, zt = self._branches_stateful(win[0].unsqueeze(1), win[1].unsqueeze(1), n_tok, before, last, sl)
+            qa, codes, zt, za = self._branches_stateful(a_w, t_w, hi - lo, before, last, sl)
         carry = self.carry if sl is None else ops.stream_rows(self.carry, sl[0], slots_dev=sl[1])
-        if self.rate is not None:
+        nb_sent = na_sent = None
+        if self.audio_packets:                                                         # qa of the stages each audio packet carries
+            qa, _, na_sent = self.net.A_QUANT.rate(za, codes, self.audio_rate, self.packet_tok, self.na)
+        elif self.rate is not None:                                                    # qa from the codes, as the receiver forms it
             qa = self.net.A_QUANT.from_codes(codes)[0]
+        del za                                                                         # recorded on two streams: freed no later than it was
+        if self.rate is not None:
             _, _, idx, _, nb_sent = self.net._ar_latents(qa, zt, self.books_use, z_prev=carry, z_last_out=carry, rate=self.rate,
                                                          packet_tok=self.packet_tok)
-            if sl is not None and not last:                                            # a session that ends needs no carry
-                ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
-            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
-            parts = [bodies.reshape(bodies.shape[0], -1), nb_sent]
-            if self.fec is not None:
-                parts.append(ops.fec_parity(bodies, nb_sent, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec)
-                             .reshape(bodies.shape[0], -1))
-            return torch.cat(parts, dim=1), codes
-        _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=carry, z_last_out=carry)
-        if sl is not None:
+        else:
+            _, _, idx = self.net._ar_latents(qa, zt, self.books_use, want_indices=True, z_prev=carry, z_last_out=carry)
+        # A session that ends needs no carry: ``close`` frees its slot, and StreamSenderPool.open zeroes carry[slot] before anyone
+        # reads it again.
+        if sl is not None and not last:
             ops.stream_rows(self.carry, sl[0], rows=carry, slots_dev=sl[1])
-        if self.fec is not None:
-            bodies = ops.idx_pack_packets(idx, self.K, self.packet_tok)
-            rows = ops.fec_parity(bodies, None, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), self.fec)
-            return torch.cat([bodies.reshape(bodies.shape[0], -1), rows.reshape(bodies.shape[0], -1)], dim=1), codes
-        return ops.idx_pack_packets(idx, self.K, self.packet_tok), codes
+        return self._back.pack(idx, nb_sent, codes, na_sent), codes
 
+    # ---------------------------------------------------------------------------------------------------------- what a call returns
     def _frame_one(self, row, n_tok, chunk):
-        """Host: ONE session's bytes of ``_encode``'s array (bodies, then with a rate the book counts, with audio packets the audio
-        bodies and their counts, then per stream with a Fec its parity rows) -> the headers with the stream's sequence numbers, the
-        session being at chunk ``chunk``: (tactile_packets,) or (tactile_packets, audio_packets), then one parity list per stream
-        that may have a Fec -- (fec_packets,), with audio packets (fec_packets, audio_fec_packets) -- when the session has any."""
-        import numpy as np
-        from .packets import StreamInfo, frame, frame_fec
-        info = StreamInfo(self.K, self.nb, n_tok, self.packet_tok)
-        row = np.asarray(row, np.uint8).reshape(-1)
-        base = chunk * CHUNK_TOK // self.packet_tok
+        """Host: ONE session's row of the read-back, the session being at chunk ``chunk`` -> ``_TxBack.frame_item``'s values."""
+        return self._back.frame_item(row, n_tok, chunk * CHUNK_TOK // self.packet_tok)
 
-        def parity(f, inf, rows):                                                      # the stream's group numbers
-            return [] if f is None else frame_fec(rows, inf, f, seq_base=chunk * (CHUNK_TOK // self.packet_tok // f.group))
+    def _frame(self, row, n_tok, chunk, codes):
+        """Host: ONE session's row of the read-back -> what its push returns, the session being at chunk ``chunk``."""
+        return self._with_codes(self._frame_one(row, n_tok, chunk), codes)
 
-        def rows_bytes(f, inf):
-            if f is None:
-                return 0
-            g, _, G, W = f.resolve(inf)
-            return G * f.r * (g + W)                                                   # r parity rows per group
+    def _with_codes(self, framed, codes):
+        """``_TxBack.frame_item``'s values (of one item, or per-item lists of them) -> a push's: without audio packets the audio
+        codes sit behind the tactile packets."""
+        return framed if self.audio_packets else (framed[0], codes) + framed[1:]
 
+    def _nothing(self, items=1):
+        """What a push of ONE session that completes no chunk returns: a real result's length, every list empty, the codes
+        [items, 32, 0]."""
+        import torch
         if self.audio_packets:
-            ainfo = StreamInfo(self.K_audio, self.na, n_tok, self.packet_tok)
-            cuts = np.cumsum([0, info.P * self.full, info.P, ainfo.P * self.afull, ainfo.P, rows_bytes(self.fec, info),
-                              rows_bytes(self.audio_fec, ainfo)])
-            hb, hc, ab, ac, hf, af = (row[cuts[i]:cuts[i + 1]] for i in range(6))
-            out = (frame(hb, info, nb_sent=hc, seq_base=base), frame(ab, ainfo, nb_sent=ac, seq_base=base))
-            if self.fec is None and self.audio_fec is None:
-                return out
-            return out + (parity(self.fec, info, hf), parity(self.audio_fec, ainfo, af))
-        cut, n_cnt = info.P * self.full, 0 if self.rate is None else info.P            # bodies, (counts,) parity rows
-        out = (frame(row[:cut], info, nb_sent=row[cut:cut + n_cnt] if n_cnt else None, seq_base=base),)
-        return out if self.fec is None else out + (parity(self.fec, info, row[cut + n_cnt:]),)
+            return ([], []) + (([], []) if self.fec is not None or self.audio_fec is not None else ())
+        return ([], torch.empty(items, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)) + (([],) if self.fec is not None else ())
+
+    def _infos(self, T):
+        from .packets import StreamInfo
+        info = (StreamInfo(self.K, self.nb, T, self.packet_tok),)
+        return info + (StreamInfo(self.K_audio, self.na, T, self.packet_tok),) if self.audio_packets else info
+
+    def _finished(self, out, T):
+        """finish's return value: the two data elements, the StreamInfo(s), then the parity lists (sessions with a Fec)."""
+        return tuple(out[:2]) + self._infos(T) + tuple(out[2:])
 
 
 class StreamSender(_SenderCore):
@@ -933,8 +945,8 @@ class StreamSender(_SenderCore):
 
     An emitting ``push`` runs, in order: ops.stream_samples (the sample buffer [2B, 48*320]: window out, buffer moved on, one
     launch for both modalities) -> A_ENC and T_ENC on the window (``sender_schedule``; one or two HIP streams as
-    ``_encode_branches`` decides) -> the chunk's 16 exact tokens -> A_QUANT -> _ar_latents(want_indices=True, z_prev=carry,
-    z_last_out=carry) -> ops.idx_pack_packets -> ONE device-to-host copy of the bodies -> packets.frame(seq_base=).  A push that
+    ``ProposedEval._two_streams`` decides) -> the chunk's 16 exact tokens -> A_QUANT -> _ar_latents(want_indices=True, z_prev=carry,
+    z_last_out=carry) -> _TxBack.pack -> ONE device-to-host copy of the rows -> _TxBack.frame_item(seq_base=).  A push that
     emits nothing is the append launch alone.  All session state is in fixed device buffers (samples [2B, 15360], carry [B, C]).
 
     ``graph=True``: the steady step (a push of exactly 16 tokens that completes a chunk after the first: the 32-token window) is
@@ -987,7 +999,7 @@ class StreamSender(_SenderCore):
 
     # ------------------------------------------------------------------------------------------------------------ stages
     def _device_step(self, x, fill, w, drop, lo, hi, before=None, last=False):
-        """Device: samples -> window -> latents of tokens [lo, hi) of the window -> (packet bodies uint8 [B, P, full], audio codes
+        """Device: samples -> window -> latents of tokens [lo, hi) of the window -> (_encode's rows uint8 [B, bytes], audio codes
         int64 [B, 32, hi - lo]); the buffer and the carried token move on in place (encoder="stateful": the encoder states too,
         ``before`` = the samples encoded so far)."""
         from . import ops
@@ -1005,21 +1017,13 @@ class StreamSender(_SenderCore):
         return x
 
     def _framed(self, bodies, codes, n_tok):
-        """ONE device-to-host copy of the bodies, then the headers with the stream's sequence numbers (_SenderCore._frame_one per
-        item, every item at the session's chunk)."""
-        host = bodies.cpu().numpy().reshape(self.batch, -1)
-        cols = [list(c) for c in zip(*(self._frame_one(host[b], n_tok, self.chunk) for b in range(self.batch)))]
-        if self.audio_packets:
-            return tuple(cols)
-        return (cols[0], codes) + tuple(cols[1:])
+        """ONE device-to-host copy of the rows, then the headers with the stream's sequence numbers (_frame_one per item, every
+        item at the session's chunk), each value a list per item."""
+        items = [self._frame_one(row, n_tok, self.chunk) for row in bodies.cpu().numpy().reshape(self.batch, -1)]
+        return self._with_codes(tuple(list(c) for c in zip(*items)), codes)
 
     def _nothing(self):
-        import torch
-        none = lambda: [[] for _ in range(self.batch)]
-        if self.audio_packets:
-            return (none(), none()) + ((none(), none()) if self.fec is not None or self.audio_fec is not None else ())
-        return (none(), torch.empty(self.batch, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)) + \
-            ((none(),) if self.fec is not None else ())
+        return tuple([[] for _ in range(self.batch)] if isinstance(v, list) else v for v in super()._nothing(self.batch))
 
     def _open(self, what):
         from ._lib import MvqError
@@ -1079,15 +1083,6 @@ class StreamSender(_SenderCore):
             out = self._framed(bodies, codes, st.hi - st.lo)
             self.fill, self.chunk, self.finished = st.fill, st.chunk, True
             return self._finished(out, self.start + st.hi)
-
-    def _finished(self, out, T):
-        """finish's return value: the two data elements, the StreamInfo(s), then the parity lists (sessions with a Fec)."""
-        return tuple(out[:2]) + self._infos(T) + tuple(out[2:])
-
-    def _infos(self, T):
-        from .packets import StreamInfo
-        info = (StreamInfo(self.K, self.nb, T, self.packet_tok),)
-        return info + (StreamInfo(self.K_audio, self.na, T, self.packet_tok),) if self.audio_packets else info
 
     def _replay(self, a, t, n, plan):
         """The steady step as a graph: captured at its first use (after one eager run at that shape on copies of the state, so
@@ -1849,9 +1844,9 @@ class StreamSenderPool(_SessionTable, _SenderCore):
              on the device are concatenated there);
       device per group of G sessions: ops.stream_samples_slots (per-session fill / n / drop, window [2, G, w] out, buffers moved
              on) -> A_ENC, T_ENC on [G, 1, w] -> tokens [lo, hi) -> A_QUANT -> ops.stream_rows (the carried tokens, pool -> dense
-             [G, C]) -> _ar_latents(z_prev=, z_last_out=) -> ops.stream_rows back -> ops.idx_pack_packets: _SenderCore's
-             sequence on the group's slots.  The append group is the sample-state launch alone;
-      copy   ONE device-to-host copy of all groups' packet bodies, then packets.frame(seq_base=) per session with ITS chunk.
+             [G, C]) -> _ar_latents(z_prev=, z_last_out=) -> ops.stream_rows back (not for a group that finishes: its slots are
+             freed) -> _TxBack.pack: _SenderCore's sequence on the group's slots.  The append group is the sample-state launch alone;
+      copy   ONE device-to-host copy of all groups' rows, then _TxBack.frame_item per session with ITS chunk's sequence base.
     Nothing is captured as a graph: the group sizes change from tick to tick.
 
     ``encoder="stateful"``: as for StreamSender -- enc_state (two [S, floats] buffers) beside the sample buffers, a group's encode is
@@ -1907,20 +1902,6 @@ class StreamSenderPool(_SessionTable, _SenderCore):
                 a, t, n = _sender_samples(f"{self._who}: session {sid}", "finish" if last else "push", a, t, 1, fill, tail=last)
                 work[sid] = (a, t, n, last)
         return work
-
-    def _frame(self, row, n_tok, chunk, codes):
-        """Host: one session's bytes of the tick's read-back -> what its push returns, the session being at chunk ``chunk``."""
-        from .packets import StreamInfo, frame
-        return frame(row, StreamInfo(self.K, self.nb, n_tok, self.packet_tok), seq_base=chunk * CHUNK_TOK // self.packet_tok), codes
-
-    def _nothing(self):
-        """What a push that completes no chunk returns."""
-        import torch
-        return [], torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)
-
-    def _infos(self, T):
-        from .packets import StreamInfo
-        return (StreamInfo(self.K, self.nb, T, self.packet_tok),)
 
     def step(self, pushes, finishes=None):
         """One tick.  ``pushes``: {sid: (a, t)}, the next samples [1, 1, 320*m] of both modalities, 1 <= m <= 16, m per session;
@@ -1991,7 +1972,7 @@ class StreamSenderPool(_SessionTable, _SenderCore):
                 nothing = self._nothing() if nothing is None else nothing
                 out[sid] = tuple([] if isinstance(v, list) else v for v in nothing)    # the empty codes tensor is shared
             if w[3]:                                                      # the StreamInfo(s) behind the two data elements
-                out[sid] = tuple(out[sid][:2]) + self._infos(self._sess[sid][2] + max(st.hi, 0)) + tuple(out[sid][2:])
+                out[sid] = self._finished(out[sid], self._sess[sid][2] + max(st.hi, 0))
                 self.close(sid)
             else:
                 self._sess[sid][1:] = [st.fill, st.start, st.chunk]
@@ -2036,9 +2017,10 @@ class StreamSenderPoolAV(StreamSenderPool):
     ``StreamSender(batch=1)`` with the same options, fed the same samples, returns from ``push`` / ``finish``, byte for byte: the
     one item's values (a list of packets where the lockstep sender returns a list of one list).
 
-    A tick is StreamSenderPool's -- ``sender_pool_groups`` is unchanged, the options do not enter the launch parameters -- with
-    _SenderCore._encode's wider array per group (bodies, book counts, audio bodies and counts, parity rows), still ONE
-    device-to-host copy of all groups' arrays, and _SenderCore._frame_one per session with ITS chunk number."""
+    A tick IS StreamSenderPool's -- the class adds its constructor and nothing else; ``sender_pool_groups`` is unchanged, the
+    options do not enter the launch parameters.  They only widen a group's rows, whose format the back end owns (_TxBack: bodies,
+    book counts, audio bodies and counts, parity rows): still ONE device-to-host copy of all groups' rows, and
+    _TxBack.frame_item per session with ITS chunk's sequence base."""
 
     _who = "StreamSenderPoolAV"
 
@@ -2046,19 +2028,3 @@ class StreamSenderPoolAV(StreamSenderPool):
                  fec=None, audio_fec=None, encoder="window"):
         self._init_pool(net, packet_tok, slots, books_use, rate=rate, audio=audio, audio_books=audio_books, audio_rate=audio_rate,
                         fec=fec, audio_fec=audio_fec, encoder=encoder)
-
-    def _nothing(self):
-        """What a push that completes no chunk returns (StreamSender._nothing for the one item)."""
-        import torch
-        if self.audio_packets:
-            return ([], []) + (([], []) if self.fec is not None or self.audio_fec is not None else ())
-        return ([], torch.empty(1, self.n_audio_books, 0, dtype=torch.int64, device=self.dev)) + (([],) if self.fec is not None else ())
-
-    def _frame(self, row, n_tok, chunk, codes):
-        framed = self._frame_one(row, n_tok, chunk)
-        return framed if self.audio_packets else (framed[0], codes) + framed[1:]
-
-    def _infos(self, T):
-        from .packets import StreamInfo
-        info = (StreamInfo(self.K, self.nb, T, self.packet_tok),)
-        return info + (StreamInfo(self.K_audio, self.na, T, self.packet_tok),) if self.audio_packets else info

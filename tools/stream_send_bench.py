@@ -159,7 +159,7 @@ def main():
 
             def pack_out():
                 tx.chunk = 2
-                return tx._framed(ops.idx_pack_packets(idx, K, 2), None, 16)
+                return tx._framed(tx._back.pack(idx, None), None, 16)
             restore_ms = timed(lambda: tx.buf.copy_(keep), args.warmup, args.repeats)
             row["split"] = {"upload_ms": timed(lambda: tx._upload(a_new, t_new, STEP), args.warmup, args.repeats),
                             "samples_kernel_ms": max(0.0, timed(samples, args.warmup, args.repeats) - restore_ms),
