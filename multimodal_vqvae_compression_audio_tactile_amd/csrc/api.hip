@@ -779,9 +779,9 @@ int mvq_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_recv, int64_
     return e == hipSuccess ? MVQ_OK : hipfail(e, "idx_unpack_packets");
 }
 
-// ---- forward error correction over the packet bodies (kernels in fec.hip) ----
+// ---- forward error correction over the packet bodies: XOR parity and Reed-Solomon parity, r rows per group (kernels in fec.hip) ----
 namespace {
-// The shape checks of both FEC entry points: ceil(log2 K), or -1 with the message set.
+// The shape checks of the FEC entry points: ceil(log2 K), or -1 with the message set.
 inline int fec_bits(const char* who, int batch, int nb, int t, int k, int packet_tok, int group, int books)
 {
     const int bits = packet_bits(batch, nb, t, k, packet_tok);
@@ -801,54 +801,59 @@ inline int fec_bits(const char* who, int batch, int nb, int t, int k, int packet
     }
     return bits;
 }
+
+// The two bodies behind the four entry points: ``who`` is the name the messages print; the XOR entry points pass parity = 1 (which
+// never fails the parity check) and got_any: any nonzero got byte says "arrived"; else got is a bitmask over the parity rows.
+int fec_parity(const char* who, const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k,
+               int packet_tok, int group, int books, int parity, void* stream)
+{
+    const int bits = fec_bits(who, batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "%s: bad shape parity=%d (1..4)", who, parity);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!rows_out || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "%s: null tensor", who);
+    hipError_t e = mvq::launch_fec_parity(bodies, nb_sent, rows_out, batch, nb, t, bits, packet_tok, group, books, parity, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, who);
+}
+
+int fec_recover(const char* who, uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch,
+                int nb, int t, int k, int packet_tok, int group, int books, int parity, bool got_any, void* stream)
+{
+    const int bits = fec_bits(who, batch, nb, t, k, packet_tok, group, books);
+    if (bits < 0) return MVQ_EINVAL;
+    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "%s: bad shape parity=%d (1..4)", who, parity);
+    if (batch == 0 || t == 0) return MVQ_OK;
+    if (!nb_recv || !rows || !got || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "%s: null tensor", who);
+    hipError_t e = mvq::launch_fec_recover(bodies, nb_recv, rows, got, recovered, batch, nb, t, bits, packet_tok, group, books, parity,
+                                           got_any ? 0xffu : (1u << parity) - 1u, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, who);
+}
 }  // namespace
 
 int mvq_fec_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k, int packet_tok,
                       int group, int books, void* stream)
 {
-    const int bits = fec_bits("fec_parity", batch, nb, t, k, packet_tok, group, books);
-    if (bits < 0) return MVQ_EINVAL;
-    if (batch == 0 || t == 0) return MVQ_OK;
-    if (!rows_out || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_parity: null tensor");
-    hipError_t e = mvq::launch_fec_parity(bodies, nb_sent, rows_out, batch, nb, t, bits, packet_tok, group, books, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_parity");
+    return fec_parity("fec_parity", bodies, nb_sent, rows_out, batch, nb, t, k, packet_tok, group, books, 1, stream);
 }
 
 int mvq_fec_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch, int nb,
                        int t, int k, int packet_tok, int group, int books, void* stream)
 {
-    const int bits = fec_bits("fec_recover", batch, nb, t, k, packet_tok, group, books);
-    if (bits < 0) return MVQ_EINVAL;
-    if (batch == 0 || t == 0) return MVQ_OK;
-    if (!nb_recv || !rows || !got || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_recover: null tensor");
-    hipError_t e = mvq::launch_fec_recover(bodies, nb_recv, rows, got, recovered, batch, nb, t, bits, packet_tok, group, books, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_recover");
+    return fec_recover("fec_recover", bodies, nb_recv, rows, got, recovered, batch, nb, t, k, packet_tok, group, books, 1, true, stream);
 }
 
-// ---- Reed-Solomon parity, r rows per group (kernels in fec_rs.hip): the XOR entry points' refusals, and parity outside 1..4 ----
+// Reed-Solomon parity, r rows per group: the XOR entry points' refusals, and parity outside 1..4; got is a bitmask over the r parities.
 int mvq_fec_rs_parity_u8(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows_out, int batch, int nb, int t, int k,
                          int packet_tok, int group, int books, int parity, void* stream)
 {
-    const int bits = fec_bits("fec_rs_parity", batch, nb, t, k, packet_tok, group, books);
-    if (bits < 0) return MVQ_EINVAL;
-    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "fec_rs_parity: bad shape parity=%d (1..4)", parity);
-    if (batch == 0 || t == 0) return MVQ_OK;
-    if (!rows_out || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_rs_parity: null tensor");
-    hipError_t e = mvq::launch_fec_rs_parity(bodies, nb_sent, rows_out, batch, nb, t, bits, packet_tok, group, books, parity, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_rs_parity");
+    return fec_parity("fec_rs_parity", bodies, nb_sent, rows_out, batch, nb, t, k, packet_tok, group, books, parity, stream);
 }
 
 int mvq_fec_rs_recover_u8(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int batch,
                           int nb, int t, int k, int packet_tok, int group, int books, int parity, void* stream)
 {
-    const int bits = fec_bits("fec_rs_recover", batch, nb, t, k, packet_tok, group, books);
-    if (bits < 0) return MVQ_EINVAL;
-    if (parity < 1 || parity > 4) return fail(MVQ_EINVAL, "fec_rs_recover: bad shape parity=%d (1..4)", parity);
-    if (batch == 0 || t == 0) return MVQ_OK;
-    if (!nb_recv || !rows || !got || (bits > 0 && !bodies)) return fail(MVQ_EINVAL, "fec_rs_recover: null tensor");
-    hipError_t e = mvq::launch_fec_rs_recover(bodies, nb_recv, rows, got, recovered, batch, nb, t, bits, packet_tok, group, books, parity,
-                                              S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "fec_rs_recover");
+    return fec_recover("fec_rs_recover", bodies, nb_recv, rows, got, recovered, batch, nb, t, k, packet_tok, group, books, parity,
+                       false, stream);
 }
 
 int mvq_rvq_dequant_layers_f32(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q_out, int batch, int dim,

@@ -148,16 +148,13 @@ hipError_t launch_idx_unpack_packets(const uint8_t* bodies, const uint8_t* nb_re
                                      int T, int K, int bits, int ptok, hipStream_t s);
 hipError_t launch_rvq_dequant_layers(const int64_t* idx, const float* books, const uint8_t* nb_valid, float* q, int B, int D, int T,
                                      int nb, int K, size_t out_sb, size_t out_sd, hipStream_t s);
-// fec.hip: XOR parity over the first m books of groups of g packets (1 <= g <= 16, 1 <= m <= nb; B * ceil(P / g) <= INT_MAX)
+// fec.hip: r parity rows per group over GF(2^8) (1 <= r <= 4; r = 1 is XOR parity) over the first m books of groups of g packets
+// (1 <= g <= 16, 1 <= m <= nb; B * ceil(P / g) <= INT_MAX): rows[B, G, r, g + W]; the parities of a group that arrived are the bits
+// of got & got_mask, at r = 1 "any bit"
 hipError_t launch_fec_parity(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows, int B, int nb, int T, int bits, int ptok,
-                             int g, int m, hipStream_t s);
+                             int g, int m, int r, hipStream_t s);
 hipError_t launch_fec_recover(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int B,
-                              int nb, int T, int bits, int ptok, int g, int m, hipStream_t s);
-// fec_rs.hip: the same with r parity rows per group over GF(2^8) (1 <= r <= 4): rows[B, G, r, g + W], got a bitmask of arrived parities
-hipError_t launch_fec_rs_parity(const uint8_t* bodies, const uint8_t* nb_sent, uint8_t* rows, int B, int nb, int T, int bits, int ptok,
-                                int g, int m, int r, hipStream_t s);
-hipError_t launch_fec_rs_recover(uint8_t* bodies, uint8_t* nb_recv, const uint8_t* rows, const uint8_t* got, uint8_t* recovered, int B,
-                                 int nb, int T, int bits, int ptok, int g, int m, int r, hipStream_t s);
+                              int nb, int T, int bits, int ptok, int g, int m, int r, uint32_t got_mask, hipStream_t s);
 // rate.hip: closed-loop sender rate control (mvq_rvq_rate_f32); rvq_rate_check returns an MVQ_* code, its text through set_last_error
 int rvq_rate_check(int dim, int nb_use, int k, int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget,
                    const char* who = "rvq_rate");     // ``who`` prefixes the message (the audio rate control passes its own name)

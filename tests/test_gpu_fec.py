@@ -106,6 +106,37 @@ def test_recover_kernel(shape, B, dev):
     assert rc == 0 and torch.equal(full_b, keep_b) and torch.equal(full_r, keep_r)
 
 
+def test_got_bytes_outside_0_and_1_at_parity_one_and_the_kernel_names(dev):
+    """One kernel pair serves both codes; what ``got`` means stays with the entry point.  mvq_fec_recover_u8: any nonzero byte
+    says "arrived"; mvq_fec_rs_recover_u8 at parity = 1: bit 0 alone.  The profile keeps one name per code."""
+    from multimodal_vqvae_compression_audio_tactile_amd import _lib, ops
+    shape = fc.SHAPES[2]                                                   # P = 5, g = 2: G = 3, a tail group of one
+    K, nb, T, ptok, g, m = shape
+    it = fc.item(shape, 0)
+    info, fec = it["info"], it["fec"]
+    b0, r0 = packets.gather([p for p in it["sent"] if fc.seq_of(p) not in (0, 2, 4)], info)   # one deficient packet per group
+    got = np.array([2, 0x80, 0], np.uint8)
+    lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    d_rows, d_got = _dev(dev, it["rows"][None], got[None])
+    for name, want in (("mvq_fec_recover_u8", packets.fec_recover(b0, r0, it["rows"], got, info, fec)),
+                       ("mvq_fec_rs_recover_u8", packets.fec_recover(b0, r0, it["rows"], got & 1, info, fec))):
+        body, cnt = _dev(dev, b0[None], r0[None])
+        rec = torch.full((1, info.P), 0xAB, dtype=torch.uint8, device=dev)
+        args = (body.data_ptr(), cnt.data_ptr(), d_rows.data_ptr(), d_got.data_ptr(), rec.data_ptr(), 1, nb, T, K, ptok, g, m)
+        rc = lib.mvq_fec_recover_u8(*args, stream) if name == "mvq_fec_recover_u8" else lib.mvq_fec_rs_recover_u8(*args, 1, stream)
+        assert rc == 0, lib.mvq_last_error()
+        for k, x in enumerate((body, cnt, rec)):
+            assert np.array_equal(x.cpu().numpy()[0], want[k]), (name, k)
+        assert list(want[2]) == ([1, 0, 1, 0, 0] if name == "mvq_fec_recover_u8" else [0] * 5), name
+    bodies, nb_sent = _dev(dev, it["bodies"][None].astype(np.uint8), it["nb_sent"][None].astype(np.uint8))
+    for code, names in ((fec, {"fec_parity_kernel", "fec_recover_kernel"}), (Fec(g, m, 2), {"fec_rs_parity_kernel", "fec_rs_recover_kernel"})):
+        body, cnt = _dev(dev, b0[None], r0[None])
+        ops.profile_begin()
+        rows = ops.fec_parity(bodies, nb_sent, info, code)
+        ops.fec_recover(body, cnt, rows, torch.ones(1, 3, dtype=torch.uint8, device=dev), info, code)
+        assert set(ops.profile_end()) == names
+
+
 def test_the_kernel_inputs_see_every_outcome():
     seen = set()
     for shape in fc.SHAPES:
