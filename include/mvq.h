@@ -140,6 +140,18 @@ int mvq_conv_transpose1d_dual_f32(const float* x, const float* wp, const float* 
  * assumed.  For transposed convs pass the torch shape (cin, cout, ks = 2*stride, stride). */
 int mvq_conv_kernel_name(int batch, int cin, int cout, int ks, int stride, int dil, int transposed, int tin,
                          char* buf, int len);
+/* The same for the three forward entry points that choose a kernel by token count (batch * t), width and alignment:
+ * mvq_layernorm_c_f32 / _sub_f32, mvq_rvq_ema_forward_f32 (and the assignment pass of mvq_rvq_ema_step_f32) and
+ * mvq_dac_rvq_*_f32.  Host arithmetic: nothing is launched and no device is needed; batch, t >= 1.
+ *   layernorm:  "layernorm_c_lat_kernel" | "layernorm_c_tile_kernel<8>" | "layernorm_c_tile_kernel<4>" | "layernorm_c_kernel"
+ *   rvq search: "rvq_ema_forward_rows_kernel<24>" | "rvq_ema_forward_token_kernel" | "rvq_ema_forward_kernel<8>" | "<32>" |
+ *               "rvq_ema_forward_mfma_kernel [tpb=16]" | "[tpb=32]" (one kernel; live tokens per block are an argument).
+ *               books_aligned: the books pointer is 16-byte aligned.
+ *   dac rvq:    "dac_rvq_lat_kernel<C/16, 4, 1>" | "<C/16, 4, 2>" | "dac_rvq_kernel<C/16, 8>".  prepared: cb_normalised and
+ *               cb_norm2 are given; aligned: in_w, out_w, codebook and cb_normalised are all 16-byte aligned. */
+int mvq_layernorm_kernel_name(int batch, int c, int t, char* buf, int len);
+int mvq_rvq_ema_forward_kernel_name(int batch, int dim, int t, int k, int books_aligned, char* buf, int len);
+int mvq_dac_rvq_kernel_name(int batch, int c, int t, int k, int prepared, int aligned, char* buf, int len);
 
 /* One upstream dac ResidualUnit:  y = snake_next?( x + conv1( snake_b( conv7_dil( snake_a(x) ) + b7 ) ) + b1 ),
  * 7-tap conv with dilation `dil` and padding 3*dil, then a 1x1 conv, both C -> C.  For C in {64, 96, 128} (the

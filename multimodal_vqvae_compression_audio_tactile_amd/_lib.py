@@ -56,6 +56,9 @@ EXPORTS = {
     "mvq_conv_transpose1d_packed_floats": (c_size_t, [c_int, c_int, c_int]),
     "mvq_conv_transpose1d_pack_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mvq_conv_kernel_name": (c_int, [c_int] * 8 + [c_char_p, c_int]),
+    "mvq_layernorm_kernel_name": (c_int, [c_int] * 3 + [c_char_p, c_int]),
+    "mvq_rvq_ema_forward_kernel_name": (c_int, [c_int] * 5 + [c_char_p, c_int]),
+    "mvq_dac_rvq_kernel_name": (c_int, [c_int] * 6 + [c_char_p, c_int]),
     "mvq_conv1d_f32": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_void_p]),
     "mvq_bf16x3_split_bytes": (c_size_t, [c_int] * 3),
     "mvq_bf16x3_split_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

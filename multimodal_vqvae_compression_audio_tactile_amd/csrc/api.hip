@@ -352,6 +352,32 @@ int mvq_conv_kernel_name(int batch, int cin, int cout, int ks, int stride, int d
     return MVQ_OK;
 }
 
+/* ... and which kernel the three forward launchers that choose by token count, width and alignment run (the launchers' own
+ * decision functions: kernels_small.hpp).  Host arithmetic only: nothing is launched, no device is needed. */
+int mvq_layernorm_kernel_name(int batch, int c, int t, char* buf, int len)
+{
+    if (!buf || len <= 0) return fail(MVQ_EINVAL, "layernorm_kernel_name: bad buffer");
+    if (c <= 0 || batch <= 0 || t <= 0) return fail(MVQ_EINVAL, "layernorm_kernel_name: bad shape B=%d C=%d T=%d", batch, c, t);
+    snprintf(buf, len, "%s", mvq::layernorm_form_name(mvq::layernorm_form(batch * t, c)));
+    return MVQ_OK;
+}
+int mvq_rvq_ema_forward_kernel_name(int batch, int dim, int t, int k, int books_aligned, char* buf, int len)
+{
+    if (!buf || len <= 0) return fail(MVQ_EINVAL, "rvq_ema_forward_kernel_name: bad buffer");
+    if (batch <= 0 || t <= 0 || dim <= 0 || dim > 128 || dim % 4 != 0 || k <= 0)
+        return fail(MVQ_EINVAL, "rvq_ema_forward_kernel_name: bad shape B=%d D=%d T=%d K=%d", batch, dim, t, k);
+    mvq::rvq_ema_forward_form_name(mvq::rvq_ema_forward_form(batch * t, dim, k, books_aligned != 0), buf, len);
+    return MVQ_OK;
+}
+int mvq_dac_rvq_kernel_name(int batch, int c, int t, int k, int prepared, int aligned, char* buf, int len)
+{
+    if (!buf || len <= 0) return fail(MVQ_EINVAL, "dac_rvq_kernel_name: bad buffer");
+    if (batch <= 0 || t <= 0 || k <= 0 || (c != 1024 && c != 512 && c != 256))
+        return fail(MVQ_EINVAL, "dac_rvq_kernel_name: bad shape B=%d C=%d T=%d K=%d (C in {256,512,1024})", batch, c, t, k);
+    mvq::dac_rvq_form_name(mvq::dac_rvq_form(batch * t, c, k, prepared != 0, aligned != 0), c, buf, len);
+    return MVQ_OK;
+}
+
 int mvq_conv1d_dual_f32(const float* x, const float* wp, const float* bias, const float* alpha_in,
                         const float* residual, const float* alpha_out, float* y, float* y2, const float* alpha2,
                         int batch, int cin, int tin, int cout, int ks, int stride, int dil, int pad, int act, void* stream);

@@ -365,12 +365,12 @@ hipError_t launch_convtr_direct(const DirectConvArgs& a, hipStream_t s)
 // ------------------------------------------------------------------------------------------------
 // LayerNorm over C of channel-major x (+ optional positional-encoding add, tanh, scale); element (b,c,t) at
 // b*sb + c*sc + t.  The contract fixes the reduction order (channel ascending, sequential), so a block stages a
-// [C][32-token] tile in LDS with coalesced loads, 32 threads walk their token's channel column out of LDS
+// [C][LN_TOK-token] tile in LDS with coalesced loads, LN_TOK threads walk their token's channel column out of LDS
 // (conflict-free: lane = token), and all 256 threads normalise and store coalesced.
 // Fallback (C too large for LDS): one thread per token straight from global memory.
 // ------------------------------------------------------------------------------------------------
-// LN_TOK tokens per block: 32 for throughput; 4 when there are only a few tokens (one AR chunk of one segment): the block's
-// staging and normalise passes shrink 8x and 8x more blocks share the work -- the ordered per-token chain is unchanged.
+// LN_TOK tokens per block: 8 for throughput; 4 when there are only a few tokens (one AR chunk of one segment): the block's
+// staging and normalise passes shrink and more blocks share the work -- the ordered per-token chain is unchanged.
 
 template <int LN_TOK>
 __global__ __launch_bounds__(256) void layernorm_c_tile_kernel(
@@ -536,23 +536,47 @@ __global__ void layernorm_c_kernel(const float* __restrict__ x, const float* __r
     }
 }
 
+// The tile kernels and the latency form serve C <= LN_TILE_MAX_C: the width whose [C][32-token] tile (+ 64 floats) filled the CU's
+// 160 KiB when 32-token tiles were the throughput form.  The bound outlived that tile: wider inputs take the one-thread-per-token
+// kernel, and every decision below depends on it.
+constexpr int LN_TILE_MAX_C = 1278;
+static_assert(((size_t)LN_TILE_MAX_C * 8 + 16) * sizeof(float) <= 64 * 1024, "the 8-token tile fits the default dynamic LDS limit");
+
+LnForm layernorm_form(int n, int C)
+{
+    if (C > LN_TILE_MAX_C) return LnForm::Scalar;
+    // The per-token chain (2 x C dependent operations) is latency, not bandwidth: what shortens a call is MORE BLOCKS walking
+    // chains side by side.  8-token tiles (32 KB of LDS at C = 1024: five blocks per CU) put 2 400 blocks on the 19 200 tokens
+    // of a 256-segment batch where a 32-token tile (128 KB, one block per CU) put 600 -- round 4: 2.3 -> see DESIGN 6c ms per step.
+    if (n <= 1024 && C % 64 == 0 && ln_lat_lds_floats(C) * sizeof(float) <= 64 * 1024) return LnForm::Lat;
+    return n > 64 ? LnForm::Tile8 : LnForm::Tile4;
+}
+
+const char* layernorm_form_name(LnForm f)
+{
+    switch (f) {
+        case LnForm::Lat:   return "layernorm_c_lat_kernel";
+        case LnForm::Tile8: return "layernorm_c_tile_kernel<8>";
+        case LnForm::Tile4: return "layernorm_c_tile_kernel<4>";
+        default:            return "layernorm_c_kernel";
+    }
+}
+
 hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamma, const float* beta, float* y,
                               int B, int C, int T, size_t sb, size_t sc, float eps, int do_tanh, float post_scale,
                               const float* sub, hipStream_t s)
 {
     const int n = B * T;
     if (n == 0) return hipSuccess;
-    const size_t lds = ((size_t)C * 32 + 2 * 32) * sizeof(float);
-    if (lds <= 160 * 1024) {
-        static BigLdsOptIn opt32, opt8, opt4;
-        hipError_t e = opt32.ensure(reinterpret_cast<const void*>(layernorm_c_tile_kernel<32>));
-        if (e == hipSuccess) e = opt8.ensure(reinterpret_cast<const void*>(layernorm_c_tile_kernel<8>));
+    const LnForm form = layernorm_form(n, C);
+    if (form != LnForm::Scalar) {
+        static BigLdsOptIn opt8, opt4;
+        hipError_t e = opt8.ensure(reinterpret_cast<const void*>(layernorm_c_tile_kernel<8>));
         if (e == hipSuccess) e = opt4.ensure(reinterpret_cast<const void*>(layernorm_c_tile_kernel<4>));
         if (e != hipSuccess) return e;
-        // The per-token chain (2 x C dependent operations) is latency, not bandwidth: what shortens a call is MORE BLOCKS walking
-        // chains side by side.  8-token tiles (32 KB of LDS at C = 1024: five blocks per CU) put 2 400 blocks on the 19 200 tokens
-        // of a 256-segment batch where the 32-token tile (128 KB, one block per CU) put 600 -- round 4: 2.3 -> see DESIGN 6c ms per step.
-        if (n <= 1024 && C % 64 == 0 && ln_lat_lds_floats(C) * sizeof(float) <= 64 * 1024) {
+    }
+    switch (form) {
+        case LnForm::Lat: {
             LnIo io{};
             io.x = x; io.x_sb = sb; io.x_sc = sc;
             io.sub = sub; io.sub_sb = sb; io.sub_sc = sc;
@@ -560,20 +584,20 @@ hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamm
             io.y0 = y; io.y0_sb = sb; io.y0_sc = sc;
             io.eps = eps; io.post_scale = post_scale; io.do_tanh = do_tanh;
             hipLaunchKernelGGL(layernorm_c_lat_kernel, dim3((n + LN_LAT_TOK - 1) / LN_LAT_TOK), dim3(256), ln_lat_lds_floats(C) * sizeof(float), s, io, B, C, T);
-            return hipGetLastError();
+            break;
         }
-        if (n > 64 && ((size_t)C * 8 + 16) * sizeof(float) <= 64 * 1024)
+        case LnForm::Tile8:
             hipLaunchKernelGGL(layernorm_c_tile_kernel<8>, dim3((n + 7) / 8), dim3(256), ((size_t)C * 8 + 16) * sizeof(float), s,
                                x, pe, gamma, beta, y, B, C, T, sb, sc, eps, do_tanh, post_scale, sub);
-        else if (n <= 64)
+            break;
+        case LnForm::Tile4:
             hipLaunchKernelGGL(layernorm_c_tile_kernel<4>, dim3((n + 3) / 4), dim3(256), ((size_t)C * 4 + 8) * sizeof(float), s,
                                x, pe, gamma, beta, y, B, C, T, sb, sc, eps, do_tanh, post_scale, sub);
-        else
-            hipLaunchKernelGGL(layernorm_c_tile_kernel<32>, dim3((n + 31) / 32), dim3(256), lds, s,
-                               x, pe, gamma, beta, y, B, C, T, sb, sc, eps, do_tanh, post_scale, sub);
-    } else {
-        hipLaunchKernelGGL(layernorm_c_kernel, dim3((n + 63) / 64), dim3(64), 0, s, x, pe, gamma, beta, y, B, C, T, sb, sc,
-                           eps, do_tanh, post_scale, sub);
+            break;
+        case LnForm::Scalar:
+            hipLaunchKernelGGL(layernorm_c_kernel, dim3((n + 63) / 64), dim3(64), 0, s, x, pe, gamma, beta, y, B, C, T, sb, sc,
+                               eps, do_tanh, post_scale, sub);
+            break;
     }
     return hipGetLastError();
 }

@@ -44,6 +44,10 @@ hipError_t launch_convtr_direct(const DirectConvArgs& a, hipStream_t s);
 hipError_t launch_layernorm_c(const float* x, const float* pe, const float* gamma, const float* beta, float* y,
                               int B, int C, int T, size_t sb, size_t sc, float eps, int do_tanh, float post_scale,
                               const float* sub, hipStream_t s);
+// Which kernel launch_layernorm_c runs for n = B * T tokens of C channels: decided here and nowhere else (host arithmetic, no device).
+enum class LnForm { Lat, Tile8, Tile4, Scalar };
+LnForm layernorm_form(int n, int C);
+const char* layernorm_form_name(LnForm f);                    // the instantiation as rocprofv3 prints it
 hipError_t launch_attention(const float* q, const float* k, const float* v, float* ctx,
                             int B, int H, int dh, int Tq, int Tk, size_t qsb, size_t qsc, size_t ksb, size_t ksc,
                             hipStream_t s);
@@ -126,6 +130,17 @@ hipError_t launch_align_xcorr(const float* r, const float* e, int T, int max_shi
 
 hipError_t launch_rvq_ema_forward(const float* z, const float* books, float* q_out, int32_t* idx_out,
                                   int B, int D, int T, int nb, int K, int update_residual, hipStream_t s);
+// Which kernel launch_rvq_ema_forward runs for N = B * T tokens (host arithmetic, no device).  tpb: live tokens per block of the
+// MFMA form (16 or 32), 0 for every other form.
+enum class RvqForm { Rows, Token, Tile8, Mfma, Tile32 };
+struct RvqChoice { RvqForm form; int tpb; };
+RvqChoice rvq_ema_forward_form(int N, int D, int K, bool books_aligned);
+void rvq_ema_forward_form_name(RvqChoice c, char* buf, int len);
+// ... and launch_dac_rvq (C in {256, 512, 1024}; `prepared`: both prepared tensors given; `aligned`: in_w, out_w, codebook and
+// the prepared codebook all 16-byte aligned).  Invalid: a width no kernel is compiled for.
+enum class DacRvqForm { Lat1, Lat2, Tile, Invalid };
+DacRvqForm dac_rvq_form(int N, int C, int K, bool prepared, bool aligned);
+void dac_rvq_form_name(DacRvqForm f, int C, char* buf, int len);
 size_t ema_update_scratch_bytes(int N, int nb, int K, int D);
 hipError_t launch_ema_update(const float* z, const int32_t* idx, float* books, void* scratch, int B, int D, int T, int nb, int K,
                              float decay, hipStream_t s);

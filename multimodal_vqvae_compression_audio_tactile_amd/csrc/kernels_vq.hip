@@ -394,14 +394,23 @@ __global__ __launch_bounds__(256) void rvq_ema_forward_mfma_kernel(
     }
 }
 
+// dynamic LDS of the two staged forms (the layouts above their kernels)
+static size_t rvq_mfma_lds_bytes(int D)
+{
+    return ((size_t)RVQ_KH * (D + 1) + RVQ_KH + 2 * (size_t)D * 32 + 8 * 32 + 2 * 32) * sizeof(float);
+}
+static size_t rvq_tile_lds_bytes(int D, int toks)
+{
+    return ((size_t)D * (RVQ_KH + 1) + RVQ_KH + 2 * (size_t)D * toks + 2 * toks) * sizeof(float);
+}
+
 static hipError_t launch_rvq_mfma(const float* z, const float* books, float* q_out, int32_t* idx_out,
-                                  int B, int D, int T, int nb, int K, int update_residual, hipStream_t s)
+                                  int B, int D, int T, int nb, int K, int update_residual, int tpb, hipStream_t s)
 {
     const int N = B * T;
-    const size_t lds = ((size_t)RVQ_KH * (D + 1) + RVQ_KH + 2 * (size_t)D * 32 + 8 * 32 + 2 * 32) * sizeof(float);
+    const size_t lds = rvq_mfma_lds_bytes(D);
     static BigLdsOptIn opt;
     if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(rvq_ema_forward_mfma_kernel)); e != hipSuccess) return e;
-    const int tpb = (N + 31) / 32 < 256 ? 16 : 32;        // every CU gets a block before any block gets 32 tokens
     hipLaunchKernelGGL(rvq_ema_forward_mfma_kernel, dim3((N + tpb - 1) / tpb), dim3(256), lds, s, z, books, q_out, idx_out, B, D, T,
                        nb, K, update_residual, tpb);
     return hipGetLastError();
@@ -412,7 +421,7 @@ static hipError_t launch_rvq_t(const float* z, const float* books, float* q_out,
                                int B, int D, int T, int nb, int K, int update_residual, hipStream_t s)
 {
     const int N = B * T;
-    const size_t lds = ((size_t)D * (RVQ_KH + 1) + RVQ_KH + 2 * (size_t)D * TOKS + 2 * TOKS) * sizeof(float);
+    const size_t lds = rvq_tile_lds_bytes(D, TOKS);
     auto kern = rvq_ema_forward_kernel<TOKS>;
     static BigLdsOptIn opt;                           // per (instantiation, device)
     if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
@@ -601,33 +610,57 @@ void rvq_ema_forward_rows_kernel(
     if (q_out && tid < D) q_out[((size_t)b * D + tid) * T + t] = qs[tid];
 }
 
+RvqChoice rvq_ema_forward_form(int N, int D, int K, bool books_aligned)
+{
+    constexpr size_t LDS_MAX = 160 * 1024;
+    // a handful of tokens (latency regime): one block per token, nothing staged
+    if (N <= 256 && D == 96 && K <= 512 && books_aligned) return {RvqForm::Rows, 0};          // CODE_DIM = 96 (Training/...5.py:68)
+    if (N <= 256 && D % 4 == 0 && D <= 128) return {RvqForm::Token, 0};
+    // many tokens: the MFMA form (one block per 32 tokens, >= 32 blocks); few tokens: the scalar form with 8 tokens per block
+    // (more blocks, and the codebook staging rather than the arithmetic is what a short chunk waits for)
+    if (N >= 1024 && D % 4 == 0 && K % 32 == 0 && rvq_mfma_lds_bytes(D) <= LDS_MAX)
+        return {RvqForm::Mfma, (N + 31) / 32 < 256 ? 16 : 32};                                 // every CU gets a block before any block gets 32 tokens
+    // The 32-token tile costs 2 * D * 24 floats more than the 8-token one: at D = 128 that is 165 632 bytes, past the CU's 160 KiB
+    // (and the MFMA form, 167 168, is out as well), so such a width stays on the 8-token tile (140 864) however many tokens come.
+    return {N >= 4096 && rvq_tile_lds_bytes(D, 32) <= LDS_MAX ? RvqForm::Tile32 : RvqForm::Tile8, 0};
+}
+
+void rvq_ema_forward_form_name(RvqChoice c, char* buf, int len)
+{
+    switch (c.form) {
+        case RvqForm::Rows:   snprintf(buf, len, "rvq_ema_forward_rows_kernel<24>"); break;
+        case RvqForm::Token:  snprintf(buf, len, "rvq_ema_forward_token_kernel"); break;
+        case RvqForm::Tile8:  snprintf(buf, len, "rvq_ema_forward_kernel<8>"); break;
+        case RvqForm::Tile32: snprintf(buf, len, "rvq_ema_forward_kernel<32>"); break;
+        case RvqForm::Mfma:   snprintf(buf, len, "rvq_ema_forward_mfma_kernel [tpb=%d]", c.tpb); break;    // one kernel: tpb is an argument
+    }
+}
+
 hipError_t launch_rvq_ema_forward(const float* z, const float* books, float* q_out, int32_t* idx_out,
                                   int B, int D, int T, int nb, int K, int update_residual, hipStream_t s)
 {
     const int N = B * T;
     if (N == 0) return hipSuccess;
-    // a handful of tokens (latency regime): one block per token, nothing staged
-    if (N <= 256 && D == 96 && K <= 512 && (reinterpret_cast<uintptr_t>(books) & 15) == 0) {   // CODE_DIM = 96 (Training/...5.py:68)
-        // (Measured and not kept, both bit-equal: both halves of the NEXT book in flight -- does not fit 256 VGPRs beside the half row a
-        // thread keeps; whole rows in LDS, 256 codes per pass, the next pass in flight -- 53 instead of 43 us per 16-token chunk: only
-        // half the threads walk chains, and they are twice as long.  gpurun_out/j1.)
-        auto kern = rvq_ema_forward_rows_kernel<24>;
-        static BigLdsOptIn opt;                           // per device: 104 KB of dynamic LDS at K = 512
-        if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(N), dim3(512), ((size_t)K * 52 + 3 * 96 + 16) * sizeof(float), s, z, books, q_out, idx_out, B, T, nb, K, update_residual);
-        return hipGetLastError();
+    const RvqChoice c = rvq_ema_forward_form(N, D, K, (reinterpret_cast<uintptr_t>(books) & 15) == 0);
+    switch (c.form) {
+        case RvqForm::Rows: {
+            // (Measured and not kept, both bit-equal: both halves of the NEXT book in flight -- does not fit 256 VGPRs beside the half row a
+            // thread keeps; whole rows in LDS, 256 codes per pass, the next pass in flight -- 53 instead of 43 us per 16-token chunk: only
+            // half the threads walk chains, and they are twice as long.  gpurun_out/j1.)
+            auto kern = rvq_ema_forward_rows_kernel<24>;
+            static BigLdsOptIn opt;                           // per device: 104 KB of dynamic LDS at K = 512
+            if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(N), dim3(512), ((size_t)K * 52 + 3 * 96 + 16) * sizeof(float), s, z, books, q_out, idx_out, B, T, nb, K, update_residual);
+            return hipGetLastError();
+        }
+        case RvqForm::Token:
+            hipLaunchKernelGGL(rvq_ema_forward_token_kernel, dim3(N), dim3(256), 0, s, z, books, q_out, idx_out, B, D, T, nb, K, update_residual);
+            return hipGetLastError();
+        case RvqForm::Mfma:   return launch_rvq_mfma(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, c.tpb, s);
+        case RvqForm::Tile32: return launch_rvq_t<32>(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, s);
+        case RvqForm::Tile8:  return launch_rvq_t<8>(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, s);
     }
-    if (N <= 256 && D % 4 == 0 && D <= 128) {
-        hipLaunchKernelGGL(rvq_ema_forward_token_kernel, dim3(N), dim3(256), 0, s, z, books, q_out, idx_out, B, D, T, nb, K, update_residual);
-        return hipGetLastError();
-    }
-    // many tokens: the MFMA form (one block per 32 tokens, >= 32 blocks); few tokens: the scalar form with 8 tokens per block
-    // (more blocks, and the codebook staging rather than the arithmetic is what a short chunk waits for)
-    const size_t lds_mfma = ((size_t)RVQ_KH * (D + 1) + RVQ_KH + 2 * (size_t)D * 32 + 8 * 32 + 2 * 32) * sizeof(float);
-    if (N >= 1024 && D % 4 == 0 && K % 32 == 0 && lds_mfma <= 160 * 1024)
-        return launch_rvq_mfma(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, s);
-    return N >= 4096 ? launch_rvq_t<32>(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, s)
-                     : launch_rvq_t<8>(z, books, q_out, idx_out, B, D, T, nb, K, update_residual, s);
+    return hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1165,15 +1198,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 template <int CPT>
 static hipError_t launch_dac_rvq_lat_t(const float* z, const float* in_w, const float* in_b, const float* cb,
                                        const float* out_w, const float* out_b, float* zq, int32_t* codes, float* latents,
-                                       const int32_t* nq_item, int B, int T, int nq, hipStream_t s, const float* cbn_pre, const float* cn2_pre)
+                                       const int32_t* nq_item, int B, int T, int nq, hipStream_t s, const float* cbn_pre, const float* cn2_pre,
+                                       bool one_token)
 {
-    // Tokens per block: ONE while that is at most one block per CU (N <= 256: the 75 tokens of one segment take 240 us), TWO beyond
-    // (the reference's batch of six is 450 tokens: 225 blocks in one round instead of 450 in two).  Four share a stage's 104 KB
-    // among four tokens and interleave their chains, but a stage then takes 12.4 us instead of 6.5 and a quarter as many CUs work:
-    // 396 against 240 us at 75 tokens (gpurun_out/h8).  What a stage costs is its ~3 000 dependent-issue instructions per token on a
-    // wave that is alone on its SIMD, not the bytes.
     const int N = B * T;
-    if (N <= 256)
+    if (one_token)
         hipLaunchKernelGGL((dac_rvq_lat_kernel<CPT, 4, 1>), dim3((unsigned)N), dim3(256), 0, s,
                            z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, cbn_pre, cn2_pre);
     else
@@ -1199,26 +1228,57 @@ static hipError_t launch_dac_rvq_t(const float* z, const float* in_w, const floa
     return hipGetLastError();
 }
 
+DacRvqForm dac_rvq_form(int N, int C, int K, bool prepared, bool aligned)
+{
+    if (C != 1024 && C != 512 && C != 256) return DacRvqForm::Invalid;
+    // a handful of tokens (one segment is 75, the reference's batch of six 450): the latency form.
+    // Tokens per block: ONE while that is at most one block per CU (N <= 256: the 75 tokens of one segment take 240 us), TWO beyond
+    // (the reference's batch of six is 450 tokens: 225 blocks in one round instead of 450 in two).  Four share a stage's 104 KB
+    // among four tokens and interleave their chains, but a stage then takes 12.4 us instead of 6.5 and a quarter as many CUs work:
+    // 396 against 240 us at 75 tokens (gpurun_out/h8).  What a stage costs is its ~3 000 dependent-issue instructions per token on a
+    // wave that is alone on its SIMD, not the bytes.
+    if (N <= 1024 && K == 1024 && prepared && aligned) return N <= 256 ? DacRvqForm::Lat1 : DacRvqForm::Lat2;
+    return DacRvqForm::Tile;
+}
+
+void dac_rvq_form_name(DacRvqForm f, int C, char* buf, int len)
+{
+    switch (f) {
+        case DacRvqForm::Lat1: snprintf(buf, len, "dac_rvq_lat_kernel<%d, 4, 1>", C / 16); break;
+        case DacRvqForm::Lat2: snprintf(buf, len, "dac_rvq_lat_kernel<%d, 4, 2>", C / 16); break;
+        case DacRvqForm::Tile: snprintf(buf, len, "dac_rvq_kernel<%d, 8>", C / 16); break;
+        default:               snprintf(buf, len, "(none)"); break;
+    }
+}
+
 hipError_t launch_dac_rvq(const float* z, const float* in_w, const float* in_b, const float* cb, const float* out_w,
                           const float* out_b, float* zq, int32_t* codes, float* latents, const int32_t* nq_item,
                           int B, int C, int T, int nq, int K, int Dc, hipStream_t s, const float* cbn_pre, const float* cn2_pre)
 {
     if (B * T == 0) return hipSuccess;
     if (Dc != 8) return hipErrorInvalidValue;
-    // a handful of tokens (one segment is 75, the reference's batch of six 450): the latency form, one token per block
     const bool aligned = ((reinterpret_cast<uintptr_t>(in_w) | reinterpret_cast<uintptr_t>(out_w) | reinterpret_cast<uintptr_t>(cb) |
                            reinterpret_cast<uintptr_t>(cbn_pre)) & 15) == 0;
-    if (B * T <= 1024 && K == 1024 && cbn_pre && cn2_pre && aligned) {
-        switch (C) {
-            case 1024: return launch_dac_rvq_lat_t<64>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre);
-            case 512:  return launch_dac_rvq_lat_t<32>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre);
-            case 256:  return launch_dac_rvq_lat_t<16>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre);
+    const DacRvqForm form = dac_rvq_form(B * T, C, K, cbn_pre && cn2_pre, aligned);
+    switch (form) {
+        case DacRvqForm::Lat1:
+        case DacRvqForm::Lat2: {
+            const bool one = form == DacRvqForm::Lat1;
+            switch (C) {
+                case 1024: return launch_dac_rvq_lat_t<64>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre, one);
+                case 512:  return launch_dac_rvq_lat_t<32>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre, one);
+                case 256:  return launch_dac_rvq_lat_t<16>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, s, cbn_pre, cn2_pre, one);
+            }
+            break;
         }
-    }
-    switch (C) {
-        case 1024: return launch_dac_rvq_t<64, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
-        case 512:  return launch_dac_rvq_t<32, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
-        case 256:  return launch_dac_rvq_t<16, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
+        case DacRvqForm::Tile:
+            switch (C) {
+                case 1024: return launch_dac_rvq_t<64, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
+                case 512:  return launch_dac_rvq_t<32, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
+                case 256:  return launch_dac_rvq_t<16, 8>(z, in_w, in_b, cb, out_w, out_b, zq, codes, latents, nq_item, B, T, nq, K, s, cbn_pre, cn2_pre);
+            }
+            break;
+        case DacRvqForm::Invalid: break;
     }
     return hipErrorInvalidValue;
 }

@@ -49,6 +49,29 @@ def conv_kernel_name(cin, cout, ks, stride=1, dil=1, transposed=False, tin=24000
     return buf.value.decode()
 
 
+def _kernel_name(entry: str, *args) -> str:
+    buf = ctypes.create_string_buffer(160)
+    check(getattr(_lib.lib(), entry)(*args, buf, 160), entry)
+    return buf.value.decode()
+
+
+def layernorm_kernel_name(batch, c, t) -> str:
+    """Kernel instantiation ops.layernorm_c launches for batch * t tokens of c channels (host arithmetic, no device)."""
+    return _kernel_name("mvq_layernorm_kernel_name", int(batch), int(c), int(t))
+
+
+def rvq_ema_forward_kernel_name(batch, dim, t, k, books_aligned=True) -> str:
+    """Kernel instantiation ops.rvq_ema_forward (and the assignment pass of rvq_ema_step_) launches; the MFMA form's name ends
+    in its live tokens per block, ``[tpb=16]`` or ``[tpb=32]``.  ``books_aligned``: the books tensor is 16-byte aligned."""
+    return _kernel_name("mvq_rvq_ema_forward_kernel_name", int(batch), int(dim), int(t), int(k), int(bool(books_aligned)))
+
+
+def dac_rvq_kernel_name(batch, c, t, k, prepared=True, aligned=True) -> str:
+    """Kernel instantiation ops.dac_rvq launches.  ``prepared``: dac_rvq_prepare's tensors are passed; ``aligned``: in_w, out_w,
+    the codebook and the prepared codebook are all 16-byte aligned."""
+    return _kernel_name("mvq_dac_rvq_kernel_name", int(batch), int(c), int(t), int(k), int(bool(prepared)), int(bool(aligned)))
+
+
 def weight_norm(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """w = v * (g / ||v||) over dim 0 rows (old-style torch weight_norm fold)."""
     v = _dev(v, "v"); g = _dev(g, "g")

@@ -207,7 +207,7 @@ def test_rvq_ema_forward_ties_pick_lowest_index(orc, dev):
     D, K = 96, 512
     book = r.standard_normal((K, D)).astype(np.float32) / math.sqrt(D)
     book[300] = book[17]; book[499] = book[17]; book[40] = book[17]     # exact duplicates
-    for T in (5, 300, 1100):                                             # token form / 8-token scalar form / MFMA form
+    for T in (5, 300, 1100):                                             # rows form (D = 96, K <= 512) / 8-token scalar form / MFMA form
         z = np.repeat(book[17][None, :, None], T, axis=2).astype(np.float32)   # query == that code
         q, idx = ops.rvq_ema_forward(_t(z, dev), _t(book[None], dev), return_indices=True)
         _, want = orc.rvq_ema_forward(z, [book])
