@@ -52,7 +52,8 @@ extern "C" {
  * stateful streaming encoder: mvq_stream_stage_window_snake_f32, mvq_stream_stage_window_snake_slots_f32, mvq_encoder_stream_plan,
  * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32; the receiver's audio output:
  * mvq_audio_fade_f32, mvq_audio_fade_slots_f32; the native-rate sender: mvq_resample_stream_rational_f32,
- * mvq_resample_stream_rational_slots_f32).
+ * mvq_resample_stream_rational_slots_f32; their split form for few sessions: mvq_resample_stream_rational_split_f32,
+ * mvq_resample_stream_rational_split_slots_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -876,6 +877,18 @@ int mvq_stream_rows_f32(float* pool, const int32_t* slots, int n_group, int n_sl
 int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
                                            int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
                                            int newf, int width, int ks, int hold, void* stream);
+/* mvq_resample_stream_rational_split_f32 / _split_slots_f32: the SPLIT form of the two calls above -- the same
+ * arguments, the same refusals with the same codes, the same outputs and the same state afterwards, bit for bit, in two launches
+ * on the one stream.  The outputs launch spreads a session's outputs over a grid of (parts, sessions) blocks, each a range of
+ * phases by a range of filter blocks, which read [state | x_new] and write y only; the state launch, one block per session, then
+ * moves the state up by n_new samples.  One session's piece no longer waits on the serial work of one block: the form for few
+ * sessions.  len_out = 0 leaves the first launch out, n_new = 0 the second. */
+int mvq_resample_stream_rational_split_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
+                                           long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
+                                           void* stream);
+int mvq_resample_stream_rational_split_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
+                                                 int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
+                                                 int newf, int width, int ks, int hold, void* stream);
 /* mvq_stream_samples_slots_f32: the sample state of a group of SENDER sessions of a pool: the kernel body of
  * mvq_stream_samples_f32 under the slot addressing, with fill, n and drop PER SESSION.  buf[n_slots, 2, cap] fp32: slot s owns row 2s
  * (audio) and row 2s + 1 (tactile).  desc[n_group][5] int32 on the DEVICE, per session (slot, fill, n, drop, x_off): its n new audio

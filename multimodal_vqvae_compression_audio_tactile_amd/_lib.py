@@ -151,6 +151,9 @@ EXPORTS = {
     "mvq_resample_stream_rational_f32": (c_int, [c_void_p] * 4 + [c_int] * 2 + [ctypes.c_longlong] + [c_int] * 7 + [c_void_p]),
     "mvq_resample_stream_rational_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p, c_int, ctypes.c_longlong] + [c_int] * 7
                                                + [c_void_p]),
+    "mvq_resample_stream_rational_split_f32": (c_int, [c_void_p] * 4 + [c_int] * 2 + [ctypes.c_longlong] + [c_int] * 7 + [c_void_p]),
+    "mvq_resample_stream_rational_split_slots_f32": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p, c_int, ctypes.c_longlong] + [c_int] * 7
+                                                     + [c_void_p]),
     "mvq_stream_stage_window_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p] + [c_int] * 4 + [c_void_p] + [c_int] * 6 + [c_void_p]),
     "mvq_stream_stage_window_slots_f32": (c_int, [c_void_p, c_size_t, c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 4 + [c_void_p]
                                           + [c_int] * 5 + [c_void_p]),

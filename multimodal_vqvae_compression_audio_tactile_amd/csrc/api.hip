@@ -1516,25 +1516,26 @@ static int resample_rational_plan(const char* who, int batch, int n_new, long lo
     return MVQ_OK;
 }
 
-int mvq_resample_stream_rational_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
-                                     long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
-                                     void* stream)
+// The four entry points of the rational streamed resampler: the one-block form and the split form, dense
+// and slots, are one argument check and one launcher signature.
+using RationalLaunch = hipError_t (*)(const float*, const float*, float*, const int32_t*, float*, int, int, int, int, int, int, int, int, int,
+                                      int, hipStream_t);
+static int resample_rational_dense(const char* who, RationalLaunch launch, const float* x_new, const float* kern, float* state, float* y,
+                                   int batch, int n_new, long long consumed, int final, int len_out, int orig, int newf, int width, int ks,
+                                   int hold, void* stream)
 {
     ResampleStreamPlan p;
-    if (int rc = resample_rational_plan("resample_stream_rational", batch, n_new, consumed, final, len_out, orig, newf, width, ks, hold, &p))
-        return rc;
+    if (int rc = resample_rational_plan(who, batch, n_new, consumed, final, len_out, orig, newf, width, ks, hold, &p)) return rc;
     if (batch == 0) return MVQ_OK;
-    if (!kern || !state || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "resample_stream_rational: null tensor");
-    hipError_t e = mvq::launch_resample_stream_rational(x_new, kern, state, nullptr, y, batch, n_new, p.n_out, orig, newf, ks, p.ns, p.base,
-                                                        p.lead, 0, S(stream));
-    return e == hipSuccess ? MVQ_OK : hipfail(e, "resample_stream_rational");
+    if (!kern || !state || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "%s: null tensor", who);
+    hipError_t e = launch(x_new, kern, state, nullptr, y, batch, n_new, p.n_out, orig, newf, ks, p.ns, p.base, p.lead, 0, S(stream));
+    return e == hipSuccess ? MVQ_OK : hipfail(e, who);
 }
 
-int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
-                                           int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
-                                           int newf, int width, int ks, int hold, void* stream)
+static int resample_rational_slots(const char* who, RationalLaunch launch, const float* x_new, const float* kern, float* state,
+                                   const int32_t* slots, int n_group, int n_slots, float* y, int n_new, long long consumed, int final,
+                                   int len_out, int orig, int newf, int width, int ks, int hold, void* stream)
 {
-    const char* who = "resample_stream_rational_slots";
     if (int rc = slots_shape_bad(who, n_group, n_slots, 1)) return rc;
     ResampleStreamPlan p;
     if (int rc = resample_rational_plan(who, n_group, n_new, consumed, final, len_out, orig, newf, width, ks, hold, &p)) return rc;
@@ -1544,9 +1545,40 @@ int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern
     if ((long long)n_group * p.n_out > 0x7FFFFFFFLL) return fail(MVQ_EINVAL, "%s: %d x %d outputs", who, n_group, p.n_out);
     if (n_group == 0) return MVQ_OK;
     if (!kern || !state || !slots || (!x_new && n_new) || (!y && p.n_out)) return fail(MVQ_EINVAL, "%s: null tensor", who);
-    hipError_t e = mvq::launch_resample_stream_rational(x_new, kern, state, slots, y, n_group, n_new, p.n_out, orig, newf, ks, p.ns, p.base,
-                                                        p.lead, n_slots, S(stream));
+    hipError_t e = launch(x_new, kern, state, slots, y, n_group, n_new, p.n_out, orig, newf, ks, p.ns, p.base, p.lead, n_slots, S(stream));
     return e == hipSuccess ? MVQ_OK : hipfail(e, who);
+}
+
+int mvq_resample_stream_rational_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
+                                     long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
+                                     void* stream)
+{
+    return resample_rational_dense("resample_stream_rational", mvq::launch_resample_stream_rational, x_new, kern, state, y, batch, n_new,
+                                   consumed, final, len_out, orig, newf, width, ks, hold, stream);
+}
+
+int mvq_resample_stream_rational_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
+                                           int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
+                                           int newf, int width, int ks, int hold, void* stream)
+{
+    return resample_rational_slots("resample_stream_rational_slots", mvq::launch_resample_stream_rational, x_new, kern, state, slots, n_group,
+                                   n_slots, y, n_new, consumed, final, len_out, orig, newf, width, ks, hold, stream);
+}
+
+int mvq_resample_stream_rational_split_f32(const float* x_new, const float* kern, float* state, float* y, int batch, int n_new,
+                                           long long consumed, int final, int len_out, int orig, int newf, int width, int ks, int hold,
+                                           void* stream)
+{
+    return resample_rational_dense("resample_stream_rational_split", mvq::launch_resample_stream_rational_split, x_new, kern, state, y, batch,
+                                   n_new, consumed, final, len_out, orig, newf, width, ks, hold, stream);
+}
+
+int mvq_resample_stream_rational_split_slots_f32(const float* x_new, const float* kern, float* state, const int32_t* slots, int n_group,
+                                                 int n_slots, float* y, int n_new, long long consumed, int final, int len_out, int orig,
+                                                 int newf, int width, int ks, int hold, void* stream)
+{
+    return resample_rational_slots("resample_stream_rational_split_slots", mvq::launch_resample_stream_rational_split, x_new, kern, state,
+                                   slots, n_group, n_slots, y, n_new, consumed, final, len_out, orig, newf, width, ks, hold, stream);
 }
 
 // The size checks of the history window, `who` the entry point's name; `sessions` = batch or n_group.

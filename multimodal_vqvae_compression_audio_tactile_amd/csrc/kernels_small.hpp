@@ -193,6 +193,10 @@ hipError_t launch_resample_stream(const float* x_new, const float* kern, float* 
 hipError_t launch_resample_stream_rational(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B,
                                            int n_new, int n_out, int orig, int newf, int ks, int S, int base, int lead, int n_slots,
                                            hipStream_t s);
+// the split form: an outputs launch over (parts, sessions), then the state launch (one block per session)
+hipError_t launch_resample_stream_rational_split(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B,
+                                                 int n_new, int n_out, int orig, int newf, int ks, int S, int base, int lead, int n_slots,
+                                                 hipStream_t s);
 hipError_t launch_stream_rows(float* pool, const int32_t* slots, float* rows, int G, int C, int n_slots, int scatter, hipStream_t s);
 // stream.hip: the receiver's audio output, the fade of lost tokens (one block per session; state[sessions][11] int32)
 hipError_t launch_audio_fade(float* y, const uint8_t* valid, int32_t* state, const int32_t* slots, int G, int n_slots, int len, int n,

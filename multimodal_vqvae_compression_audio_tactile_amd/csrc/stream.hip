@@ -6,7 +6,9 @@
 // the same buffers and a launch works on the slots a device list names: the window and the resampler kernel are each ONE body,
 // instantiated for the dense addressing and for the slot list (Sessions<SLOTS> below), the sample-state kernel likewise
 // (SampleRows<SLOTS>: a pool's sender sessions also bring their own fill / n / drop, section 17), and stream_rows_kernel moves
-// the carried tokens; audio_fade_kernel (the receiver's audio output, mvq_audio_fade_f32) is one body over Sessions<SLOTS> too.
+// the carried tokens; audio_fade_kernel (the receiver's audio output, mvq_audio_fade_f32) is one body over Sessions<SLOTS> too, and so
+// are the two kernels of the rational resampler's split form (mvq_resample_stream_rational_split_f32: outputs over many blocks per
+// session, the state moved in a launch of its own).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "det_math.hpp"
@@ -250,6 +252,87 @@ __global__ __launch_bounds__(256) void resample_stream_rational_kernel(const flo
     }
     if (!ok) return;                                                     // block-uniform: the whole block leaves before the barriers
     __syncthreads();
+    float keep[4];                                                       // S <= 1024 (checked by the entry point)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        const int j = i + n_new;
+        keep[u] = i < S ? (j < S ? st[j] : xb[j - S]) : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = threadIdx.x + 256 * u;
+        if (i < S) st[i] = keep[u];
+    }
+}
+
+// The SPLIT form of resample_stream_rational_kernel: the same outputs and the same state in two launches, so
+// that one session's outputs are spread over many blocks instead of walked by one.
+// Outputs launch, grid (parts, sessions): part = qg*n_pg + pg owns the phases [pg*pp, pg*pp + pp) of the filter blocks
+// [qg*qq, qg*qq + qq) of the call -- a rectangle of the (q, p) plane, so it needs only its own pp rows of the bank (in LDS at the
+// odd pitch `kp` when the launcher says so, else read from memory at pitch ks).  It reads v = [state | x_new] and never writes the
+// state; output m = q*newf + p is the one-block kernel's expression token for token (j0, the skipped taps, one dfma per tap, k
+// ascending, from +0), so which block computes it changes nothing.  Lanes walk the part's phases first: distinct bank rows, one
+// shared v window.  Sessions beyond the grid's y limit are walked by the same blocks.  A slot outside [0, n_slots) reads a zero state.
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void resample_stream_rational_outputs_kernel(const float* __restrict__ x_new, const float* __restrict__ kern,
+                                                                               const float* __restrict__ state, float* __restrict__ y, int B,
+                                                                               int n_new, int n_out, int orig, int newf, int ks, int kp, int S,
+                                                                               int base, int lead, int kern_in_lds, int pp, int qq, int n_pg,
+                                                                               Sessions<SLOTS> ses)
+{
+    extern __shared__ __attribute__((aligned(16))) float ksm[];
+    const int qg = blockIdx.x / n_pg, pg = blockIdx.x - qg * n_pg;
+    const int p0 = pg * pp, q0 = qg * qq;
+    const int np = newf - p0 < pp ? newf - p0 : pp;                      // phases of this part (the last group may be short)
+    const float* kg = kern + (size_t)p0 * ks;                            // the part's rows of the bank
+    if (kern_in_lds) {
+        for (int e = threadIdx.x; e < np * ks; e += 256) {
+            const int r = e / ks;
+            ksm[r * kp + (e - r * ks)] = kg[e];
+        }
+        __syncthreads();
+    }
+    const float* kt = kern_in_lds ? ksm : kg;
+    const int V = S + n_new;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        size_t at;
+        const bool ok = ses.session(b, at);
+        const float* st = state + (ok ? at : 0) * S;
+        const float* xb = x_new + (size_t)b * n_new;
+        for (int e = threadIdx.x; e < np * qq; e += 256) {
+            const int ql = e / np, pl = e - ql * np;
+            const int q = q0 + ql;
+            const long long m = (long long)q * newf + (p0 + pl);
+            if (m >= n_out) continue;                                    // the call's last filter block may be partial in its outputs
+            const float* kr = kt + (size_t)pl * kp;
+            const int j0 = base + q * orig;
+            const int k_lo = j0 < lead ? lead - j0 : 0;
+            int k_hi = ks; if (j0 + k_hi > V) k_hi = V - j0;
+            float acc = 0.0f;
+            for (int k = k_lo; k < k_hi; ++k) {
+                const int j = j0 + k;
+                acc = dfma(kr[k], j < S ? (ok ? st[j] : 0.0f) : xb[j - S], acc);
+            }
+            y[(size_t)b * n_out + (size_t)m] = acc;
+        }
+    }
+}
+
+// State launch of the split form, behind the outputs launch on the same stream (no block of that launch is still reading): one
+// block per session moves its state up by n_new samples, st[i] = v[i + n_new], the one-block kernels' register-carried move.  The
+// shift overlaps itself, so every thread holds its elements across the barrier; the barrier in front of the loads, which in the
+// one-block kernels ends the reads of the outputs, has nothing to wait for here.  A slot outside [0, n_slots) stores nothing.
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void resample_stream_state_kernel(const float* __restrict__ x_new, float* __restrict__ state, int n_new, int S,
+                                                                    Sessions<SLOTS> ses)
+{
+    const int b = blockIdx.x;
+    size_t at;
+    if (!ses.session(b, at)) return;                                     // block-uniform: the whole block leaves before the barrier
+    float* st = state + at * S;
+    const float* xb = x_new + (size_t)b * n_new;
     float keep[4];                                                       // S <= 1024 (checked by the entry point)
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -572,6 +655,46 @@ hipError_t launch_resample_stream_rational(const float* x_new, const float* kern
     else
         hipLaunchKernelGGL(resample_stream_rational_kernel<false>, dim3(B), dim3(256), in_lds ? lds : 0, s, x_new, kern, state, y, n_new,
                            n_out, orig, newf, ks, kp, S, base, lead, in_lds, Sessions<false>{});
+    return hipGetLastError();
+}
+
+// The split form: the outputs launch, then the state launch, on the one stream.  A part is at most 16 phases (newf spread evenly
+// over the phase groups: 10 groups of 15 for newf = 147) by as many filter blocks as make about 256 outputs, one per thread; the
+// result does not depend on either number.  The bank goes to LDS under the one-block launcher's rule (so both forms read a given
+// bank from the same place), but only the part's pp rows of it: 5.6 KB instead of 55 KB for 24 kHz -> 44.1 kHz.  With n_out == 0 or
+// n_new == 0 the launch that would do nothing is left out.
+hipError_t launch_resample_stream_rational_split(const float* x_new, const float* kern, float* state, const int32_t* slots, float* y, int B,
+                                                 int n_new, int n_out, int orig, int newf, int ks, int S, int base, int lead, int n_slots,
+                                                 hipStream_t s)
+{
+    if (B == 0) return hipSuccess;
+    if (n_out > 0) {
+        const int odd = ks | 1;
+        const int in_lds = (size_t)newf * odd * sizeof(float) <= 64 * 1024;
+        const int kp = in_lds ? odd : ks;
+        const int groups = (newf + 15) / 16;
+        const int pp = (newf + groups - 1) / groups, n_pg = (newf + pp - 1) / pp;
+        const int qq = 256 / pp > 1 ? 256 / pp : 1;
+        const int nq = (int)(((long long)n_out + newf - 1) / newf);
+        const long long parts = (long long)n_pg * ((nq + qq - 1) / qq);
+        if (parts > 0x7FFFFFFFLL) return hipErrorInvalidConfiguration;
+        const size_t lds = in_lds ? (size_t)pp * kp * sizeof(float) : 0;
+        const dim3 grid((unsigned)parts, (unsigned)(B < 65535 ? B : 65535)), block(256);
+        if (slots)
+            hipLaunchKernelGGL(resample_stream_rational_outputs_kernel<true>, grid, block, lds, s, x_new, kern, state, y, B, n_new, n_out, orig,
+                               newf, ks, kp, S, base, lead, in_lds, pp, qq, n_pg, Sessions<true>{slots, n_slots, 1});
+        else
+            hipLaunchKernelGGL(resample_stream_rational_outputs_kernel<false>, grid, block, lds, s, x_new, kern, state, y, B, n_new, n_out, orig,
+                               newf, ks, kp, S, base, lead, in_lds, pp, qq, n_pg, Sessions<false>{});
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    if (n_new > 0) {
+        if (slots)
+            hipLaunchKernelGGL(resample_stream_state_kernel<true>, dim3(B), dim3(256), 0, s, x_new, state, n_new, S,
+                               Sessions<true>{slots, n_slots, 1});
+        else
+            hipLaunchKernelGGL(resample_stream_state_kernel<false>, dim3(B), dim3(256), 0, s, x_new, state, n_new, S, Sessions<false>{});
+    }
     return hipGetLastError();
 }
 

@@ -1579,9 +1579,16 @@ def resample_stream_rational_state(orig, width, batch, device, hold=None):
     return torch.zeros(int(batch), _rational_hold(orig, width, hold) * int(orig) + int(width), device=device, dtype=torch.float32)
 
 
-def _resample_stream_rational(who, x_new, kern, state, sd, consumed, orig, newf, width, hold, final):
+RESAMPLE_FORMS = {"block": "", "split": "_split"}                   # form -> the infix of the entry point's name
+
+
+def _resample_stream_rational(who, x_new, kern, state, sd, consumed, orig, newf, width, hold, final, form="block"):
     """resample_stream_rational and resample_stream_rational_slots: ``sd`` None for the dense sessions state[B, S], else the
-    group's device slot list (_slot_list has checked ``state`` then).  The checks of _resample_stream, and the bank's."""
+    group's device slot list (_slot_list has checked ``state`` then).  The checks of _resample_stream, and the bank's.  ``form``:
+    "block" = one block per session (mvq_resample_stream_rational[_slots]_f32), "split" = the two-launch form of the same call
+    (mvq_resample_stream_rational_split[_slots]_f32)."""
+    if form not in RESAMPLE_FORMS:
+        raise MvqError(f"{who}: form must be 'block' or 'split', not {form!r}")
     x_new = _dev(x_new, "x_new")
     if state.dim() != 2 or state.dtype != torch.float32 or not state.is_cuda or not state.is_contiguous() or x_new.dim() != 2 \
             or x_new.shape[0] != (state.shape[0] if sd is None else sd.shape[0]) or x_new.device != state.device:
@@ -1605,30 +1612,32 @@ def _resample_stream_rational(who, x_new, kern, state, sd, consumed, orig, newf,
     n_out = resample_stream_rational_out_len(consumed, n_new, orig, newf, width, hold, final)
     y = torch.empty(B, n_out, device=x_new.device, dtype=torch.float32)
     tail = (n_new, consumed, int(bool(final)), n_out, orig, newf, width, kern.shape[1], hold, _stream())
+    name = f"mvq_resample_stream_rational{RESAMPLE_FORMS[form]}{'' if sd is None else '_slots'}_f32"
+    fn = getattr(_lib.lib(), name)
     if sd is None:
-        check(_lib.lib().mvq_resample_stream_rational_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, *tail),
-              "mvq_resample_stream_rational_f32")
+        check(fn(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), y.data_ptr(), B, *tail), name)
     else:
-        check(_lib.lib().mvq_resample_stream_rational_slots_f32(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), B,
-                                                                state.shape[0], y.data_ptr(), *tail),
-              "mvq_resample_stream_rational_slots_f32")
+        check(fn(x_new.data_ptr(), kern.data_ptr(), state.data_ptr(), sd.data_ptr(), B, state.shape[0], y.data_ptr(), *tail), name)
     return y
 
 
-def resample_stream_rational(x_new, kern, state, consumed, orig, newf, width, hold=None, final=False):
+def resample_stream_rational(x_new, kern, state, consumed, orig, newf, width, hold=None, final=False, form="block"):
     """The next piece x_new[B, n_new] of a stream resampled by orig : newf -> the outputs y[B, n_out] it completes
     (mvq_resample_stream_rational_f32; stream.resample_stream_rational_out_len counts them).  ``kern`` [newf, 2*width + orig] is
     resample.sinc_resample_kernel's bank, ``state`` (resample_stream_rational_state) is updated in place, ``consumed`` = samples
-    given to earlier calls, ``hold`` the lag in filter blocks the state was made for."""
-    return _resample_stream_rational("resample_stream_rational", x_new, kern, state, None, consumed, orig, newf, width, hold, final)
+    given to earlier calls, ``hold`` the lag in filter blocks the state was made for.  ``form="split"``: the same outputs and state
+    from the two-launch form, a session's outputs spread over many blocks (the form for few sessions)."""
+    return _resample_stream_rational("resample_stream_rational", x_new, kern, state, None, consumed, orig, newf, width, hold, final, form)
 
 
-def resample_stream_rational_slots(x_new, kern, state, slots, consumed, orig, newf, width, hold=None, final=False, slots_dev=None):
+def resample_stream_rational_slots(x_new, kern, state, slots, consumed, orig, newf, width, hold=None, final=False, slots_dev=None,
+                                   form="block"):
     """resample_stream_rational for the sessions ``slots`` (host integers) of a pool: x_new[G, n_new] -> y[G, n_out], state[slots]
     moved on in place (mvq_resample_stream_rational_slots_f32).  ``consumed`` is the group's launch class -- 0, or any multiple of
-    ``orig`` of at least the state's length that one member has consumed (include/mvq.h)."""
+    ``orig`` of at least the state's length that one member has consumed (include/mvq.h).  ``form``: resample_stream_rational's."""
     _, sd = _slot_list("resample_stream_rational_slots", slots, state, 2, slots_dev)
-    return _resample_stream_rational("resample_stream_rational_slots", x_new, kern, state, sd, consumed, orig, newf, width, hold, final)
+    return _resample_stream_rational("resample_stream_rational_slots", x_new, kern, state, sd, consumed, orig, newf, width, hold, final,
+                                     form)
 
 
 def stream_samples(buf, fill, x_new, w, drop):

@@ -942,11 +942,15 @@ class ProposedEval(_ProposedBase):
 
     @torch.no_grad()
     def decode_av(self, audio_codes, idx, books_use=None, nb_valid=None, conceal="predict", plc=None, na_valid=None, audio_conceal="zero",
-                  audio_fade=None):
+                  audio_fade=None, audio_out_rate=24000):
         """Receiver, both modalities -> (y_tactile, y_audio): decode(...) and y_audio = fade(audio_decoder(qa)) [B, 1, 320*Ta - 8]
         with qa the audio latent as the predictor saw it (decode_latents(return_qa=True)).  ``audio_fade`` (packets.AudioFade): the
-        waveform of tokens with na_valid == 0 fades out and back in (ops.audio_fade_, one launch); None, or na_valid None, skips it."""
+        waveform of tokens with na_valid == 0 fades out and back in (ops.audio_fade_, one launch); None, or na_valid None, skips it.
+        ``audio_out_rate`` (the rates stream.native_out_plan admits): y_audio is then
+        Resample(24000, audio_out_rate) of that waveform, the definition the streaming sessions' audio output equals."""
+        from .stream import native_out_plan
         self._audio_out_args("decode_av", True, audio_fade)
+        native_out_plan("decode_av", audio_out_rate)
         z, qa = self.decode_latents(audio_codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
                                     audio_conceal=audio_conceal, return_qa=True)
         y_audio = self.audio_decoder(qa)
@@ -954,6 +958,9 @@ class ProposedEval(_ProposedBase):
             valid = na_valid.to(qa.device).contiguous()
             valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
             y_audio = ops.audio_fade_(y_audio.contiguous(), valid, ops.audio_fade_state(qa.shape[0], qa.device), audio_fade, 0)
+        if int(audio_out_rate) != EVAL_SR:
+            from .resample import resample_to
+            y_audio = resample_to(y_audio, EVAL_SR, int(audio_out_rate))
         return self.T_DEC(z), y_audio
 
     @torch.no_grad()
@@ -1109,7 +1116,7 @@ class ProposedEval(_ProposedBase):
     @torch.no_grad()
     def decompress_packets_av(self, infos, tactile_packets, audio_infos, audio_packets, books_use=None, conceal="predict", plc=None,
                               fec=None, fec_packets=None, audio_fec=None, audio_fec_packets=None, audio_conceal="zero", audio_out=False,
-                              audio_fade=None):
+                              audio_fade=None, audio_out_rate=24000):
         """-> (y [B,1,T], lost [B,T_lat] bool, audio_lost [B,Ta] bool) from whatever packets of BOTH streams arrived (missing,
         reordered, duplicated, thinned; items of one StreamInfo per stream): packets.gather per item and stream on the host, ONE
         upload of both streams' bodies and per-packet counts, the bit unpacking of both on the device (the audio indices are
@@ -1124,10 +1131,12 @@ class ProposedEval(_ProposedBase):
 
         ``audio_out=True`` (needs set_audio_decoder): -> (y, lost, audio_lost, y_audio), the first three exactly as
         without it and y_audio [B, 1, 320*Ta - 8] the audio waveform, decode_av's: the audio decoder on the audio latent the predictor
-        saw, then ``audio_fade`` (packets.AudioFade or None) over the tokens that are still lost after recovery."""
+        saw, then ``audio_fade`` (packets.AudioFade or None) over the tokens that are still lost after recovery.  ``audio_out_rate``
+        (decode_av's; needs audio_out=True): y_audio resampled from 24 kHz to that rate."""
         from . import packets
-        from .stream import _RxFront
+        from .stream import _RxFront, native_out_plan
         self._audio_out_args("decompress_packets_av", audio_out, audio_fade)
+        native_out_plan("decompress_packets_av", audio_out_rate, audio_out)
         if audio_conceal not in ("zero", "mask", "hold"):
             raise MvqError(f"decompress_packets_av: audio_conceal must be 'zero', 'mask' or 'hold', not {audio_conceal!r}")
         if (fec is None and fec_packets is not None) or (audio_fec is None and audio_fec_packets is not None):
@@ -1161,23 +1170,25 @@ class ProposedEval(_ProposedBase):
         idx, nb_valid, codes, na_valid = front.unpack(torch.from_numpy(host).to(dev), lay, B, info.T)
         if audio_out:
             y, y_audio = self.decode_av(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
-                                        audio_conceal=audio_conceal, audio_fade=audio_fade)
+                                        audio_conceal=audio_conceal, audio_fade=audio_fade, audio_out_rate=audio_out_rate)
             return y, nb_valid == 0, na_valid == 0, y_audio
         y = self.decode(codes, idx, books_use=books_use, nb_valid=nb_valid, conceal=conceal, plc=plc, na_valid=na_valid,
                         audio_conceal=audio_conceal)
         return y, nb_valid == 0, na_valid == 0
 
     def stream_receiver(self, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                        fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
+                        fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None,
+                        audio_out_rate=24000):
         """A streaming session on this model (stream.StreamReceiver): ``push`` one 16-token chunk of packets and audio codes at a
         time, ``finish`` to flush; the concatenated output equals decompress_packets on the same packets bit for bit.
         ``decoder="stateful"``: the same tensors from the stateful decoder (per-stage history instead of the 36-token window).
         ``audio_out=True`` (``audio_fade``: packets.AudioFade or None): push / finish return (y_tactile, y_audio), the audio waveform
-        chunk by chunk, equal to decompress_packets_av(audio_out=True)'s."""
+        chunk by chunk, equal to decompress_packets_av(audio_out=True)'s.  ``audio_out_rate`` (44100, 48000, ...: stream.native_out_plan):
+        y_audio at the playback rate, equal to decompress_packets_av(audio_out=True, audio_out_rate=)'s."""
         from .stream import StreamReceiver
         return StreamReceiver(self, K, nb, packet_tok=packet_tok, batch=batch, books_use=books_use, conceal=conceal,
                               out_rate=out_rate, graph=graph, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,
-                              decoder=decoder, audio_out=audio_out, audio_fade=audio_fade)
+                              decoder=decoder, audio_out=audio_out, audio_fade=audio_fade, audio_out_rate=audio_out_rate)
 
     def stream_receiver_pool(self, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio_conceal=None,
                              decoder="window"):
@@ -1228,8 +1239,8 @@ class ProposedEval(_ProposedBase):
         """stream_receiver_pool for the whole link (stream.StreamReceiverPoolAV): ``audio=(K_a, na)``, ``fec`` / ``audio_fec``,
         ``audio_conceal`` and ``decoder`` mean what they mean on stream_receiver, and each session gets what a
         stream_receiver(batch=1) with the same options would return.  ``audio=None``: the audio codes arrive as codes.
-        The audio output (``audio_out`` / ``audio_fade``, as on stream_receiver) is the class's: StreamReceiverPoolAV(net, K, nb,
-        ..., audio_out=True); this factory's signature is pinned as it is."""
+        The audio output (``audio_out`` / ``audio_fade`` / ``audio_out_rate``, as on stream_receiver) is the class's:
+        StreamReceiverPoolAV(net, K, nb, ..., audio_out=True); this factory's signature is pinned as it is."""
         from .stream import StreamReceiverPoolAV
         return StreamReceiverPoolAV(self, K, nb, packet_tok=packet_tok, slots=slots, books_use=books_use, conceal=conceal,
                                     out_rate=out_rate, audio=audio, fec=fec, audio_fec=audio_fec, audio_conceal=audio_conceal,

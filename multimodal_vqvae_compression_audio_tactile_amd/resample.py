@@ -112,10 +112,14 @@ class StreamResampleRational:
     the 320-sample tokens of the native-rate sender); ``finish(x=None)`` pads on the right and flushes.  A pushed piece must be a
     multiple of ``orig`` samples long, the final one need not.  The concatenated outputs equal ``Resample(orig_freq, new_freq)`` of
     the concatenated input bit for bit.  The state is one fixed device buffer [batch, hold*orig + width] (at most 1024 samples) that
-    the kernel updates in place."""
+    the kernel updates in place.  ``form``: "block" (one block per signal) or "split" (ops.resample_stream_rational: the same
+    results from the two-launch form, the faster one for few signals)."""
 
     def __init__(self, orig_freq: int, new_freq: int, batch: int, device=None, hold: int = None, lowpass_filter_width: int = 6,
-                 rolloff: float = 0.99):
+                 rolloff: float = 0.99, form: str = "block"):
+        if form not in ops.RESAMPLE_FORMS:
+            raise ops.MvqError(f"StreamResampleRational: form must be 'block' or 'split', not {form!r}")
+        self.form = form
         if int(orig_freq) == int(new_freq):
             raise ops.MvqError(f"StreamResampleRational: {orig_freq} -> {new_freq} Hz changes nothing (Resample returns its input)")
         kern, self.width, self.orig, self.new = sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
@@ -144,7 +148,7 @@ class StreamResampleRational:
             raise ops.MvqError(f"StreamResampleRational: a piece must be [B={self.batch}, ..., n], got {tuple(x.shape)}")
         lead, n = tuple(x.shape[:-1]), x.shape[-1]
         y = ops.resample_stream_rational(x.to(torch.float32).reshape(self.batch, n), self.kernel, self.state, self.consumed, self.orig,
-                                         self.new, self.width, hold=self.hold, final=final)
+                                         self.new, self.width, hold=self.hold, final=final, form=self.form)
         self._lead = lead                                                    # finish() without a piece answers in this shape
         self.consumed += n
         self.done = final

@@ -42,6 +42,10 @@ sessions and groups.  ``_RxFront`` is every receiver's fr
 session's and the pools': it owns the format of the upload (``receiver_layout``), fills it on the host and unpacks it on the device.
 ``_TxBack`` is its mirror, every sender's back end: it owns the format of the read-back, packs it on the device and frames it on
 the host.  ``_SessionTable`` is the session bookkeeping the four pools share.
+
+``audio_out_rate=`` hands the receiver's audio output out at the playback rate: ``native_out_plan`` is its host
+arithmetic and its refusals, ``_ReceiverCore._audio_rate`` the resample launch behind the fade, ``audio_resample_form`` the choice
+between the one-block and the split form of the rational streamed resampler.
 """
 from __future__ import annotations
 
@@ -341,6 +345,50 @@ def native_token_plan(in_rate: int, out_rate: int = 24000, hop: int = HOP, lowpa
     if state > 1024:
         raise ValueError(f"StreamSenderNative: at {in_rate} Hz the resampler state is {state} samples; the kernel carries at most 1024")
     return orig, new, width, hold, hold * orig, state
+
+
+def native_out_plan(who: str, audio_out_rate: int, audio_out: bool = True, hop: int = HOP, lowpass_filter_width: int = 6,
+                    rolloff: float = 0.99):
+    """The receiver's audio output at ``audio_out_rate`` Hz -> None at LINK_SR (nothing is resampled), else
+    (orig, new, width, hold, state length) of the streamed resampler LINK_SR -> audio_out_rate at the smallest lag, hold =
+    ceil(width/orig).  ValueError, with the caller's name ``who`` in front and the rate in the message, for a rate without
+    audio_out=True, a rate at which a ``hop``-sample token is no whole number of filter blocks (hop % orig: every piece a session
+    emits but its last is whole tokens, and only whole blocks can be pushed), and a state beyond the kernel's 1024 samples.  Every
+    surface that takes audio_out_rate= calls this before it allocates anything."""
+    import math
+    rate = int(audio_out_rate)
+    if rate == LINK_SR:
+        return None
+    if rate <= 0:
+        raise ValueError(f"{who}: audio_out_rate = {audio_out_rate!r} Hz")
+    if not audio_out:
+        raise ValueError(f"{who}: audio_out_rate = {rate} Hz shapes the audio output; it goes with audio_out=True")
+    g = math.gcd(LINK_SR, rate)
+    orig, new = LINK_SR // g, rate // g
+    if hop % orig:
+        raise ValueError(f"{who}: audio_out_rate = {rate} Hz is {orig} : {new} against {LINK_SR} Hz, and a {hop}-sample token is no whole "
+                         f"number of {orig}-sample filter blocks")
+    width = int(math.ceil(lowpass_filter_width * orig / (min(orig, new) * rolloff)))
+    hold = (width + orig - 1) // orig
+    state = hold * orig + width
+    if state > 1024:
+        raise ValueError(f"{who}: audio_out_rate = {rate} Hz needs a resampler state of {state} samples; the kernel carries at most 1024")
+    return orig, new, width, hold, state
+
+
+# Which form of the rational streamed resampler the receiver's audio output takes, from the sessions of the launch (a lockstep
+# session's batch, a pool group's size).  Set from tools/native_out_bench.py's same-run comparison (DESIGN.md section 32):
+# the steady 16-token piece, one block per session against split, medians of three alternating runs in ms on one MI355X --
+#   24000 -> 44100:  B = 1  0.311 / 0.026    B = 6  0.313 / 0.026    B = 256  0.314 / 0.164   (the one-block form's spread: 0.002 - 0.004)
+#   24000 -> 48000:  B = 1  0.069 / 0.025    B = 6  0.074 / 0.025    B = 256  0.078 / 0.038   (spread 0.001)
+# The split form wins at every count measured, so no count up to 256 selects the one-block form; beyond 256 nothing is measured
+# and the bound stays open until a measurement closes it.
+AUDIO_RESAMPLE_SPLIT_MAX = 1 << 30
+
+
+def audio_resample_form(sessions: int) -> str:
+    """"split" for up to AUDIO_RESAMPLE_SPLIT_MAX sessions in a launch, else "block"."""
+    return "split" if int(sessions) <= AUDIO_RESAMPLE_SPLIT_MAX else "block"
 
 
 class PoolGroup(NamedTuple):
@@ -1227,18 +1275,21 @@ def _receiver_args(who, net, K, nb, packet_tok, conceal, out_rate):
 
 class _ReceiverCore:
     """What StreamReceiver and StreamReceiverPool share: the configuration, the state buffers -- one row block per session,
-    ``rows`` of them: carry [rows, C], hist [rows, C, 20] and, for out_rate=3000, the resampler's rs_state [rows, 105] -- the
+    ``rows`` of them: carry [rows, C], hist [rows, C, 20], for out_rate=3000 the resampler's rs_state [rows, 105] and, for an
+    audio_out_rate other than 24000, the audio resampler's ars_state [rows, hold*orig + width] -- the
     check of a chunk's audio codes, and THE device sequence of a step, written once.  With ``sl`` None a step works on every
     session of the buffers (the lockstep receiver); with ``sl`` = (slots, slots_dev), the host list of a group's slots and its
     int32 device copy, on those sessions of a pool: the same launches under another addressing (csrc/stream.hip), which is why a
     pool session computes what a solo one does."""
 
     def __init__(self, net, K, nb, packet_tok, rows, books_use, conceal, out_rate, audio=None, fec=None, audio_fec=None,
-                 audio_conceal="zero", decoder="window", who="StreamReceiver", audio_out=False, audio_fade=None):
+                 audio_conceal="zero", decoder="window", who="StreamReceiver", audio_out=False, audio_fade=None, audio_out_rate=LINK_SR):
         import torch
         from . import ops, proposed
         from .packets import StreamInfo, _check
         self.net, self.K, self.nb, self.packet_tok = net, K, nb, packet_tok
+        self.ars_plan = native_out_plan(who, audio_out_rate, audio_out)                # ValueError before any session state exists
+        self.audio_out_rate = int(audio_out_rate)
         if decoder not in ("window", "stateful"):
             raise ValueError(f"{who}: decoder must be 'window' or 'stateful', not {decoder!r}")
         self.decoder = decoder
@@ -1300,6 +1351,14 @@ class _ReceiverCore:
             assert (orig, width, new) == (RS_ORIG, RS_WIDTH, 1)
             self.rs_kernel = kern.to(self.dev)
             self.rs_state = ops.resample_stream_state(orig, width, rows, self.dev)
+        # the audio output at the playback rate (section 32): a second resampler state behind the fade; 24000 allocates and launches nothing
+        self.ars_state = self.ars_kernel = None
+        if self.ars_plan is not None:
+            from .resample import sinc_resample_kernel
+            kern, width, orig, new = sinc_resample_kernel(LINK_SR, self.audio_out_rate)
+            assert (orig, new, width) == self.ars_plan[:3]
+            self.ars_kernel = kern.to(self.dev)
+            self.ars_state = ops.resample_stream_rational_state(orig, width, rows, self.dev)
 
     def _codes(self, audio_codes, n_lo, n_hi, sid=None):
         """A chunk's audio codes, checked: int [B, n_codebooks, n] for the lockstep receiver (``sid`` None), [n_codebooks, n] or
@@ -1419,6 +1478,25 @@ class _ReceiverCore:
                                            final=last, slots_dev=sl[1])
         return y3.unsqueeze(1)
 
+    def _audio_rate(self, ya, consumed, last, sl=None):
+        """audio_out_rate: the emitted audio piece, behind ``_audio_step`` and so behind the fade, through the rational streamed
+        resampler (ars_state moves on) -- ``_decimate``'s contract: ``consumed`` = the 24 kHz samples emitted before, 0 or at least
+        1920 and so a launch class of a pool group; every piece but the last is whole tokens, so whole filter blocks.  The form
+        comes from the sessions of the launch (audio_resample_form).  An empty piece launches nothing."""
+        from . import ops
+        G, n = ya.shape[0], ya.shape[-1]
+        if self.ars_state is None or n == 0:
+            return ya
+        orig, new, width, hold, _ = self.ars_plan
+        form = audio_resample_form(G)
+        if sl is None:
+            y = ops.resample_stream_rational(ya.reshape(G, n), self.ars_kernel, self.ars_state, consumed, orig, new, width, hold=hold,
+                                             final=last, form=form)
+        else:
+            y = ops.resample_stream_rational_slots(ya.reshape(G, n), self.ars_kernel, self.ars_state, sl[0], consumed, orig, new, width,
+                                                   hold=hold, final=last, slots_dev=sl[1], form=form)
+        return y.unsqueeze(1)
+
 
 class StreamReceiver(_ReceiverCore):
     """A receiver session for ``batch`` items advancing in lockstep: ``push`` one 16-token chunk at a time (whatever tactile
@@ -1473,10 +1551,17 @@ class StreamReceiver(_ReceiverCore):
     same stream.  ``audio_fade`` (packets.AudioFade): with ``audio=(K_a, na)`` the emitted piece then goes through ops.audio_fade_,
     whose state fade_state [B, 11] carries the loss runs across chunks.  The concatenated y_audio equals
     decompress_packets_av(audio_out=True, audio_fade=)'s.  With graph=True the steady step stays ONE captured graph, with two
-    output buffers."""
+    output buffers.
+
+    ``audio_out_rate`` (24000: everything above, launch for launch; needs audio_out=True): y_audio leaves at
+    that rate instead -- 44100, 48000, 22050, ... whatever ``native_out_plan`` admits.  The emitted 24 kHz piece goes, behind the
+    fade, through ops.resample_stream_rational on a second resampler state ars_state [B, hold*orig + width] (87 samples for
+    44.1 kHz), in the form ``audio_resample_form`` names for the batch, eagerly behind the captured step as the 3 kHz decimator
+    runs.  The concatenated y_audio equals Resample(24000, audio_out_rate) of decompress_packets_av(audio_out=True)'s bit for bit;
+    a push returns the outputs its samples complete, ceil(width/orig) filter blocks behind them."""
 
     def __init__(self, net, K, nb, packet_tok=2, batch=1, books_use=None, conceal="predict", out_rate=24000, graph=False, audio=None,
-                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
+                 fec=None, audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None, audio_out_rate=24000):
         K, nb, packet_tok, batch = int(K), int(nb), int(packet_tok), int(batch)
         _receiver_args("StreamReceiver", net, K, nb, packet_tok, conceal, out_rate)
         if batch < 1:
@@ -1484,7 +1569,8 @@ class StreamReceiver(_ReceiverCore):
         if fec is not None or audio_fec is not None:
             _f32_only("StreamReceiver")
         super().__init__(net, K, nb, packet_tok, batch, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
-                         audio_conceal=audio_conceal, decoder=decoder, audio_out=audio_out, audio_fade=audio_fade)
+                         audio_conceal=audio_conceal, decoder=decoder, audio_out=audio_out, audio_fade=audio_fade,
+                         audio_out_rate=audio_out_rate)
         self.batch, self.graph = batch, bool(graph)
         self.h = 0                                                                     # valid columns of hist
         self.tokens = 0                                                                # tokens received (N)
@@ -1553,7 +1639,7 @@ class StreamReceiver(_ReceiverCore):
                 y = self._device_step(torch.from_numpy(host).to(self.dev), None if codes is None else codes.to(self.dev), n, *plan)
             self.h, self.tokens = plan[1], self.tokens + n
             if self.audio_out:
-                return self._decimate(y[0], consumed, False), y[1]
+                return self._decimate(y[0], consumed, False), self._audio_rate(y[1], consumed, False)
             return self._decimate(y, consumed, False)
 
     def _audio_arg(self, what, audio_codes, audio_packets):
@@ -1601,7 +1687,7 @@ class StreamReceiver(_ReceiverCore):
             y = self._device_step(up, codes, n, *plan, last=True)
             self.h, self.tokens, self.finished = plan[1], self.tokens + n, True
             if self.audio_out:
-                return self._decimate(y[0], consumed, True), y[1]
+                return self._decimate(y[0], consumed, True), self._audio_rate(y[1], consumed, True)
             return self._decimate(y, consumed, True)
 
     def _replay(self, host, codes, n, plan):
@@ -1702,6 +1788,8 @@ class StreamReceiverPool(_SessionTable, _ReceiverCore):
             self.qa_carry[slot].zero_()
         if self.rs_state is not None:
             self.rs_state[slot].zero_()
+        if self.ars_state is not None:                                                 # StreamReceiverPoolAV(audio_out_rate=)
+            self.ars_state[slot].zero_()
         return self._new_session(slot, 0, 0)
 
     # --------------------------------------------------------------------------------------------------------------- tick
@@ -1814,6 +1902,8 @@ class StreamReceiverPool(_SessionTable, _ReceiverCore):
                 y = self._device_step(seg, codes, n, *g.plan, sl=sl, last=last)
                 y, ya = y if self.audio_out else (y, None)
                 y = self._decimate(y, g.consumed, last, sl)
+                if self.audio_out:
+                    ya = self._audio_rate(ya, g.consumed, last, sl)
                 s0 += G
                 for i, sid in enumerate(g.sids):
                     out[sid] = (y[i:i + 1], ya[i:i + 1]) if self.audio_out else y[i:i + 1]
@@ -1999,15 +2089,18 @@ class StreamReceiverPoolAV(StreamReceiverPool):
     ``audio_out`` / ``audio_fade`` (StreamReceiver's): a session's result is (y_tactile, y_audio).  The pool
     holds a second decoder state (a_hist [S, C, 20] or a_dec_state) and the fade's run lengths fade_state [S, 11]; a group's step
     runs the audio branch on the group's slots after the tactile one.  ``open`` clears none of them: a new session reads no
-    history, no tail and no run length."""
+    history, no tail and no run length.  ``audio_out_rate`` (StreamReceiver's; section 32): a group's audio piece goes through
+    ops.resample_stream_rational_slots on the group's slots of ars_state [S, hold*orig + width], its launch class the group's
+    ``consumed``; ``open`` zeroes the slot's row, as it zeroes rs_state's."""
 
     _who = "StreamReceiverPoolAV"
     _item_fields = len(PoolChunk._fields)
 
     def __init__(self, net, K, nb, packet_tok=2, slots=64, books_use=None, conceal="predict", out_rate=24000, audio=None, fec=None,
-                 audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None):
+                 audio_fec=None, audio_conceal="zero", decoder="window", audio_out=False, audio_fade=None, audio_out_rate=24000):
         self._init_pool(net, K, nb, packet_tok, slots, books_use, conceal, out_rate, audio=audio, fec=fec, audio_fec=audio_fec,
-                        audio_conceal=audio_conceal, decoder=decoder, who=self._who, audio_out=audio_out, audio_fade=audio_fade)
+                        audio_conceal=audio_conceal, decoder=decoder, who=self._who, audio_out=audio_out, audio_fade=audio_fade,
+                        audio_out_rate=audio_out_rate)
 
 
 class StreamSenderPoolAV(StreamSenderPool):
