@@ -46,7 +46,7 @@ extern "C" {
  * the streaming receiver: mvq_stream_window_f32, mvq_resample_stream_f32; the streaming sender: mvq_stream_samples_f32,
  * mvq_ar_latents_staged_carry_f32; the receiver pool: mvq_stream_window_slots_f32, mvq_resample_stream_slots_f32,
  * mvq_stream_rows_f32; the sender pool: mvq_stream_samples_slots_f32; sender rate control: mvq_rvq_rate_f32,
- * mvq_ar_latents_staged_rate_f32; audio transport: mvq_dac_rvq_from_codes_layers_f32, mvq_dac_rvq_rate_f32,
+ * mvq_ar_latents_staged_rate_f32; the sender's beam search: mvq_rvq_beam_f32, mvq_ar_latents_staged_rate_beam_f32; audio transport: mvq_dac_rvq_from_codes_layers_f32, mvq_dac_rvq_rate_f32,
  * mvq_dac_rvq_rate_workspace_bytes; the stateful streaming decoder: mvq_stream_stage_window_f32, mvq_stream_stage_window_slots_f32,
  * mvq_decoder_stream_plan, mvq_decoder_stream_state_floats, mvq_decoder_stream_workspace_bytes, mvq_decoder_stream_fwd_f32; the
  * stateful streaming encoder: mvq_stream_stage_window_snake_f32, mvq_stream_stage_window_snake_slots_f32, mvq_encoder_stream_plan,
@@ -293,6 +293,32 @@ int mvq_rvq_rate_f32(const float* z, size_t z_sb, size_t z_sd, const int32_t* id
                      const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
                      uint8_t* nb_sent, size_t nbs_sb, float* energy, int batch, int dim, int t, int nb_use, int k,
                      int packet_tok, int group_tok, int min_books, int mode, float tol2, int budget, void* stream);
+
+/* Beam search over the books at the sender (additive, same ABI version; no reference counterpart).  The
+ * search above is greedy: book by book argmax_k(res.e_k - 0.5|e_k|^2).  This one keeps up to M = beam slots per token and returns the
+ * path with the smallest FINAL residual energy; it costs no bit on the wire and nothing at the receiver, which sums whatever
+ * indices arrive.  Every step is one IEEE fp32 operation.  Per token, r = z(b, :, t):
+ *   score(r, m, k) = dot - h_k, the greedy search's own value: dot = the fma(r[d], e_m[k][d], dot) chain, d ascending from +0,
+ *                    h_k = 0.5 * (the fma(e[d], e[d], s) chain, d ascending from +0);
+ *   E(r)           = mvq_rvq_rate_f32's energy chain (...((+0 + r[0]*r[0]) + r[1]*r[1]) + ...), multiply and add rounded separately.
+ * A token carries L <= M slots (path, residual r_j, J_j = E(r_j)); before book 0, L = 1 and slot 0 is (empty, r, E(r)).  At book m:
+ *   slot 0, the greedy lineage: k* = argmax_k score(r_0, m, k), strict '>' in ascending k (lowest index on ties; no score that
+ *     compares greater than -inf -- an all-NaN row -- gives 0); new slot 0 = path_0 + k*;
+ *   the other slots, from all pairs (j < L, k < K) except (0, k*): key(j, k) = fl(J_j - fl(2 * score(r_j, m, k))); new slots
+ *     1 .. min(M, L*K) - 1 are the pairs first in the order: a number before a NaN, then key ascending (-0 == +0), then j ascending,
+ *     then k ascending;
+ *   every new slot: r' = r_parent - e_m[k] elementwise (the search's res - q), J' = E(r'); L <- min(M, L*K).
+ * After the last book the winner is the slot with the smallest J, strict '<' in ascending slot order (ties and NaN stay with slot
+ * 0); the output is its path.  So beam = 1 is the greedy search index for index, and for every token the winner's final energy is
+ * <= the greedy path's as an exact fp32 comparison.  The beam optimises the full depth nb_use: a PREFIX of its path (what a thinned
+ * packet or a tol2 / budget cut sends) is not the greedy prefix and may be worse; mvq_rvq_rate_f32 decides on the path's own E_m.
+ * z and idx are strided as mvq_rvq_rate_f32's (z (b, d, t) at b*z_sb + d*z_sd + t; index (book i, item b, token t) at
+ * idx[i*idx_sbook + b*idx_sitem + t]; a stride pair of 0 means contiguous [B, D, T] / [nb_use, B*T]).  Writes EVERY element of idx
+ * (int32) and, unless NULL, slot[batch*t] (uint8: the winning slot, 0 = the greedy path won) and energy[batch*t] (the winner's J).
+ * Refused before any launch (MVQ_EINVAL): beam outside 1..8, D % 4 != 0 or D > 128, K <= 0 (or above 2^24), nb_use > 32, a null
+ * z / idx / books, books not 16-byte aligned.  One block per 1 - 8 tokens for all books; no atomics. */
+int mvq_rvq_beam_f32(const float* z, size_t z_sb, size_t z_sd, const float* books, int32_t* idx, size_t idx_sbook, size_t idx_sitem,
+                     uint8_t* slot, float* energy, int batch, int dim, int t, int nb_use, int k, int beam, void* stream);
 
 /* Forward error correction (additive, same ABI version; no reference counterpart, and the format is not derived from anything the
  * reference contains).  Bodies are book-major, so the first m books of a body are a valid lower-rate body: one XOR parity row over
@@ -1067,6 +1093,12 @@ int mvq_ar_latents_staged_carry_f32(const mvq_ar_args* args, const float* z_prev
 int mvq_ar_latents_staged_rate_f32(const mvq_ar_args* args, int packet_tok, int min_books, int mode, float tol2, int budget,
                                    const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* mvq_ar_latents_staged_rate_f32 with the search launch of each chunk replaced by mvq_rvq_beam_f32's (on the chunk's valid tokens)
+ * when beam > 1; beam == 1 is that call, launch for launch; beam outside 1..8 is MVQ_EINVAL before any launch.  The rate launch
+ * reads the indices as before, so z_run stays the receiver's bit for bit. */
+int mvq_ar_latents_staged_rate_beam_f32(const mvq_ar_args* args, int packet_tok, int min_books, int mode, float tol2, int budget, int beam,
+                                        const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out,
+                                        void* workspace, size_t workspace_bytes, void* stream);
 /* synchronises `stream`, then: MVQ_OK when every grid barrier of the last call on this workspace completed */
 int mvq_ar_check(const void* workspace, void* stream);
 

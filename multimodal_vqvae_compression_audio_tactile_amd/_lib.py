@@ -94,6 +94,7 @@ EXPORTS = {
     "mvq_rvq_dequant_layers_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_size_t] * 2 + [c_void_p]),
     "mvq_rvq_rate_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                  c_size_t, c_void_p, c_size_t, c_void_p] + [c_int] * 9 + [c_float, c_int, c_void_p]),
+    "mvq_rvq_beam_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "mvq_dac_rvq_from_codes_layers_f32": (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     "mvq_dac_rvq_rate_workspace_bytes": (c_size_t, [c_int] * 4),
     "mvq_dac_rvq_rate_f32": (c_int, [c_void_p, c_void_p, c_size_t] + [c_void_p] * 8 + [c_size_t] + [c_int] * 9 + [c_float, c_int, c_void_p]),
@@ -206,6 +207,8 @@ EXPORTS = {
     "mvq_ar_latents_staged_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_size_t, c_void_p]),
     "mvq_ar_latents_staged_carry_f32": (c_int, [ctypes.POINTER(ArArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvq_ar_latents_staged_rate_f32": (c_int, [ctypes.POINTER(ArArgs)] + [c_int] * 3 + [c_float, c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "mvq_ar_latents_staged_rate_beam_f32": (c_int, [ctypes.POINTER(ArArgs)] + [c_int] * 3 + [c_float, c_int, c_int] + [c_void_p] * 5
+                                            + [c_size_t, c_void_p]),
     "mvq_ar_check": (c_int, [c_void_p, c_void_p]),
 }
 

@@ -496,7 +496,7 @@ int mvq_ar_latents_f32(const mvq_ar_args* args, void* workspace, size_t workspac
  * allocations cost as much host time as the kernels take on the device (eager encode 2.5 ms against 2.3 ms replayed as a graph);
  * from C a launch costs 2-3 us.  Same kernels, same bits as the Python loop (tests/test_gpu_ar_fused.py).  Needs every GEMM in the
  * latency form's range (batch <= 8: at most 1 024 16 x 16 tiles per launch). */
-struct ArRate { int packet_tok, min_books, mode, budget; float tol2; uint8_t *nb_valid, *nb_sent; };      // the rate form's extras
+struct ArRate { int packet_tok, min_books, mode, budget; float tol2; uint8_t *nb_valid, *nb_sent; int beam; };      // the rate form's extras (beam > 1: the beam search)
 
 static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last_out, void* workspace, size_t workspace_bytes, void* stream,
                      const ArRate* rate = nullptr)
@@ -510,6 +510,8 @@ static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last
         if (const int rc = rvq_rate_check(D_CODE, args->books_use, args->rvq_k, rate->packet_tok, CHUNK, rate->min_books, rate->mode, rate->tol2, rate->budget);
             rc != MVQ_OK)
             return rc;
+    if (rate && rate->beam != 1 && args && args->books_use >= 0 && args->rvq_k > 0)
+        if (const int rc = rvq_beam_check(D_CODE, args->books_use, args->rvq_k, rate->beam, "ar_latents_staged_rate_beam"); rc != MVQ_OK) return rc;
     ArKT kt;
     bool done = false;
     if (const int rc = ar_prepare(args, workspace, workspace_bytes, kt, done); rc != MVQ_OK || done) return rc;
@@ -568,7 +570,10 @@ static int ar_staged(const mvq_ar_args* args, const float* z_prev, float* z_last
                     break;
                 }
                 case ST_RVQ: {
-                    if (a.books_use > 0)
+                    if (a.books_use > 0 && rate && rate->beam > 1)      // the n valid tokens of [B][96][16]; the rate launch below writes qD16
+                        e = launch_rvq_beam(k.rD16, (size_t)D_CODE * CHUNK, CHUNK, a.books, idx_tmp, (size_t)B * CHUNK, CHUNK, nullptr, nullptr, B, D_CODE, n,
+                                            a.books_use, a.rvq_k, rate->beam, st);
+                    else if (a.books_use > 0)
                         e = launch_rvq_ema_forward(k.rD16, a.books, k.qD16, a.idx_out ? idx_tmp : nullptr, B, D_CODE, CHUNK, a.books_use, a.rvq_k, 1, st);
                     else {
                         hipLaunchKernelGGL(ar_zero_kernel, dim3(8), dim3(256), 0, st, reinterpret_cast<float4*>(k.qD16), (size_t)D_CODE * B * CHUNK / 4);
@@ -615,7 +620,18 @@ int mvq_ar_latents_staged_rate_f32(const mvq_ar_args* args, int packet_tok, int 
                                    const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out, void* workspace,
                                    size_t workspace_bytes, void* stream)
 {
-    const ArRate r{packet_tok, min_books, mode, budget, tol2, nb_valid_out, nb_sent_out};
+    const ArRate r{packet_tok, min_books, mode, budget, tol2, nb_valid_out, nb_sent_out, 1};
+    return ar_staged(args, z_prev, z_last_out, workspace, workspace_bytes, stream, &r);
+}
+
+/* ... with the search launch of each chunk replaced by the beam search (mvq_rvq_beam_f32 on the chunk's n valid tokens) when beam > 1;
+ * beam == 1 is mvq_ar_latents_staged_rate_f32, launch for launch.  The rate launch reads the indices and forms the receiver's sum as
+ * before, so z_run stays the receiver's. */
+int mvq_ar_latents_staged_rate_beam_f32(const mvq_ar_args* args, int packet_tok, int min_books, int mode, float tol2, int budget, int beam,
+                                        const float* z_prev, float* z_last_out, uint8_t* nb_valid_out, uint8_t* nb_sent_out, void* workspace,
+                                        size_t workspace_bytes, void* stream)
+{
+    const ArRate r{packet_tok, min_books, mode, budget, tol2, nb_valid_out, nb_sent_out, beam};
     return ar_staged(args, z_prev, z_last_out, workspace, workspace_bytes, stream, &r);
 }
 

@@ -177,6 +177,11 @@ hipError_t launch_rvq_rate(const float* z, size_t z_sb, size_t z_sd, const int32
                            const float* books, float* q_out, size_t out_sb, size_t out_sd, uint8_t* nb_valid, size_t nbv_sb,
                            uint8_t* nb_sent, size_t nbs_sb, float* energy, int B, int D, int T, int nb, int K, int ptok, int gtok,
                            int min_books, int mode, float tol2, int budget, hipStream_t s);
+// rvq_beam.hip: beam search over the books at the sender (mvq_rvq_beam_f32); rvq_beam_check returns an MVQ_* code, its text through
+// set_last_error; both strided like launch_rvq_rate's z and idx, slot / energy (either may be nullptr) contiguous [B*T]
+int rvq_beam_check(int dim, int nb_use, int k, int beam, const char* who = "rvq_beam");
+hipError_t launch_rvq_beam(const float* z, size_t z_sb, size_t z_sd, const float* books, int32_t* idx, size_t idx_sbook, size_t idx_sitem,
+                           uint8_t* slot, float* energy, int B, int D, int T, int nb, int K, int beam, hipStream_t s);
 // stream.hip: the streaming receiver's state kernels (rows = batch*c; S = ceil(width/orig)*orig + width <= 1024).  slots ==
 // nullptr: every session of the buffers, densely; else the G sessions slots[G] (a device list) of a pool of n_slots, C rows per
 // session and rows = G*C <= INT_MAX

@@ -603,6 +603,42 @@ def rvq_rate(z, idx, books, rate, packet_tok, n_books_use=None, folded_batch=Non
     return (q, nbv, nbs, energy) if want_energy else (q, nbv, nbs)
 
 
+def rvq_beam(z, books, beam, n_books_use=None, folded_batch=None, valid=None, want_slot=False, want_energy=False):
+    """Beam search over the books at the sender (mvq_rvq_beam_f32): ``beam`` (1..8) paths per token instead of
+    the greedy one, the path with the smallest final residual energy is returned; ``beam`` = 1 gives ops.rvq_ema_forward's indices.
+    z[B, D, T], token-folded [1, D, B*T] with ``folded_batch`` = B, or the staged loop's [B, D, W] with ``valid`` = the T <= W
+    tokens of each item that count; books[nb_all, K, D].  -> idx int32 [nb, B*T] (what ops.rvq_rate reads; token b*T + t), then
+    with ``want_slot`` the winning slot uint8 [B*T] (0: the greedy path won) and with ``want_energy`` the winner's final residual
+    energy fp32 [B*T]."""
+    z = _dev(z, "z"); books = _dev(books, "books")
+    if z.dim() != 3 or books.dim() != 3 or books.device != z.device or books.shape[2] != z.shape[1]:
+        raise MvqError(f"rvq_beam: z {tuple(z.shape)} and books {tuple(books.shape)} must be [B, D, T] and [n_books, K, D] on one device")
+    if isinstance(beam, bool) or int(beam) != beam:
+        raise MvqError(f"rvq_beam: beam = {beam!r} is not an integer")
+    D = z.shape[1]
+    if folded_batch is None:
+        B, W = z.shape[0], z.shape[2]
+        T = W if valid is None else int(valid)
+        if not 0 <= T <= W:
+            raise MvqError(f"rvq_beam: valid = {valid!r} outside 0..{W}")
+        z_sb, z_sd = D * W, W
+    else:
+        B = int(folded_batch)
+        if valid is not None or z.shape[0] != 1 or B < 1 or z.shape[2] % B:
+            raise MvqError(f"rvq_beam: z {tuple(z.shape)} is not token-folded [1, D, {B}*T] (and takes no valid=)")
+        T = z.shape[2] // B
+        z_sb, z_sd = T, B * T
+    nb_all, K, _ = books.shape
+    nb = nb_all if n_books_use is None else max(0, min(int(n_books_use), nb_all))
+    idx = torch.empty(nb, B * T, device=z.device, dtype=torch.int32)
+    slot = torch.empty(B * T, device=z.device, dtype=torch.uint8) if want_slot else None
+    energy = torch.empty(B * T, device=z.device, dtype=torch.float32) if want_energy else None
+    check(_lib.lib().mvq_rvq_beam_f32(z.data_ptr(), z_sb, z_sd, books.data_ptr(), idx.data_ptr(), B * T, T, _p(slot), _p(energy), B, D, T,
+                                      nb, K, int(beam), _stream()), "mvq_rvq_beam_f32")
+    out = (idx,) + ((slot,) if want_slot else ()) + ((energy,) if want_energy else ())
+    return out[0] if len(out) == 1 else out
+
+
 PACKET_MAX_BITS = 24           # the packet kernels cover ceil(log2 K) <= 24, nb and packet_tok <= 255 (include/mvq.h)
 
 
@@ -1151,7 +1187,7 @@ _AR_CHECKED = set()
 
 def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f, w1, b1, w3, b3, ln_eps, tok, tok_eps, scale,
                      wd, bd, wu, bu, books, books_use, heads, c_ff, code_dim, r_tokens=None, idx_out=None, tactile_only=False, chunk=16,
-                     staged=False, z_prev=None, z_last_out=None, rate=None):
+                     staged=False, z_prev=None, z_last_out=None, rate=None, beam=1):
     """The whole chunked AR loop as ONE persistent kernel (csrc/ar_fused.hip: mvq_ar_latents_f32): zt[B,C,Tlat] -> z_run[B,C,Tlat]
     (written in place), optionally r_tokens[B,96,Tlat] and idx_out[nb,B,Tlat] (int32).  ``k_all`` / ``v_all``: token-folded K / V
     of all chunks ([1,C,B*t_audio], CrossPredictor.keys_values) or None; the w* are K-major packed 1x1 weights (pack_conv1d);
@@ -1160,8 +1196,11 @@ def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f
     (tests/test_gpu_ar_fused.py).  ``z_prev`` / ``z_last_out`` ([B, C] fp32, staged only): the token carried into and out of a
     piece of a longer sequence (mvq_ar_latents_staged_carry_f32).  ``rate`` (staged only) = (packet_tok, min_books, mode, tol2,
     budget, nb_valid_out uint8 [B, Tlat], nb_sent_out uint8 [B, P]): closed-loop rate control, one mvq_rvq_rate_f32 launch per chunk
-    (mvq_ar_latents_staged_rate_f32); needs idx_out."""
+    (mvq_ar_latents_staged_rate_f32); needs idx_out.  ``beam`` > 1 (with ``rate``): each chunk's search is the beam search
+    (mvq_ar_latents_staged_rate_beam_f32); 1 is the call above, the new export is not touched."""
     carried = z_prev is not None or z_last_out is not None
+    if int(beam) != 1 and rate is None:
+        raise MvqError("ar_latents_fused: beam needs rate (the closed loop forms the receiver's sum from the beam's indices)")
     if rate is not None and (not staged or idx_out is None):
         raise MvqError("ar_latents_fused: rate needs staged=True and idx_out (the persistent kernel has no rate stage)")
     if carried and not staged:
@@ -1184,6 +1223,11 @@ def ar_latents_fused(zt, z_run, *, k_all, v_all, t_audio, pe, ln_q, wq, wo, ln_f
     ws = torch.empty(max(nbytes, 4), device=zt.device, dtype=torch.uint8)
     if rate is not None:
         packet_tok, min_books, mode, tol2, budget, nbv, nbs = rate
+        if int(beam) != 1:
+            check(L.mvq_ar_latents_staged_rate_beam_f32(ctypes.byref(a), int(packet_tok), int(min_books), int(mode), float(tol2), int(budget),
+                                                        int(beam), _p(z_prev), _p(z_last_out), nbv.data_ptr(), nbs.data_ptr(), ws.data_ptr(),
+                                                        nbytes, _stream()), "mvq_ar_latents_staged_rate_beam_f32")
+            return z_run
         check(L.mvq_ar_latents_staged_rate_f32(ctypes.byref(a), int(packet_tok), int(min_books), int(mode), float(tol2), int(budget),
                                                _p(z_prev), _p(z_last_out), nbv.data_ptr(), nbs.data_ptr(), ws.data_ptr(), nbytes,
                                                _stream()), "mvq_ar_latents_staged_rate_f32")

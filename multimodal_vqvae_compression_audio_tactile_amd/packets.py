@@ -86,10 +86,15 @@ class Rate:
       * ``budget`` (int), constant rate: the books of the 16 / packet_tok packets of a 16-token chunk sum to ``budget``, given out
         one at a time to the packet whose next book removes most residual energy (a shorter tail group of g packets gets
         max(g*min_books, budget*g // P_c)).
-    ``tol2`` and ``budget`` are mutually exclusive (ValueError).  ``resolve`` checks the values against a stream's shape."""
+    ``tol2`` and ``budget`` are mutually exclusive (ValueError).  ``resolve`` checks the values against a stream's shape.
+    ``beam`` (1..8; include/mvq.h, mvq_rvq_beam_f32): the sender searches the books with a beam of that many
+    paths per token instead of greedily and sends the path with the smallest final residual -- the same bits on the wire, nothing
+    changes at the receiver.  1: the greedy search, today's launches exactly.  The beam optimises the full depth: under ``tol2`` /
+    ``budget`` / thinning a packet carries a PREFIX of the path, which is not the greedy prefix and may be worse than it."""
     min_books: int = 1
     tol2: Optional[float] = None
     budget: Optional[int] = None
+    beam: int = 1
 
     def __post_init__(self):
         if self.tol2 is not None and self.budget is not None:
@@ -100,8 +105,14 @@ class Rate:
                 raise ValueError(f"Rate: {name} = {v!r} is not an integer")
         if self.min_books < 1:
             raise ValueError(f"Rate: min_books = {self.min_books} (at least one book per packet: the format has no empty packet)")
+        if isinstance(self.beam, bool) or not isinstance(self.beam, (int, np.integer)) or not 1 <= int(self.beam) <= 8:
+            raise ValueError(f"Rate: beam = {self.beam!r} must be an integer in 1..8 (the slots the search keeps per token)")
         if self.tol2 is not None and not (np.float32(self.tol2) > 0 and np.isfinite(np.float32(self.tol2))):
             raise ValueError(f"Rate: tol2 = {self.tol2!r} must be a finite positive fp32 value")
+
+    def __repr__(self):
+        body = f"min_books={self.min_books!r}, tol2={self.tol2!r}, budget={self.budget!r}"
+        return f"Rate({body})" if self.beam == 1 else f"Rate({body}, beam={self.beam!r})"
 
     def resolve(self, nb_use: int, packet_tok: int, group_tok: int = 16):
         """-> (min_books, mode, tol2, budget) as mvq_rvq_rate_f32 takes them (mode 0 full, 1 tol2, 2 budget); ValueError on a

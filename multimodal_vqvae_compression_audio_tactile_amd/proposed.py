@@ -295,6 +295,8 @@ class _ProposedBase(nn.Module):
             na_use = int(audio_books)
         packet_tok = packets.PACKET_TOK if packet_tok is None else int(packet_tok)
         audio_rate.resolve(na_use, packet_tok, AR_CHUNK_TOK)
+        if audio_rate.beam != 1:
+            raise ValueError(f"audio_rate: beam = {audio_rate.beam} -- the audio quantiser's search has no beam (rate= takes one)")
         return audio_rate, na_use, packet_tok
 
     def _fec_resolve(self, fec, K, nb, packet_tok, what="fec"):
@@ -347,12 +349,16 @@ class _ProposedBase(nn.Module):
         straight-through qD by the sum the receiver will form from exactly those books, so z_run -- and through z_run[..., s-1]
         every later chunk -- is what decode_latents(nb_valid=) reconstructs, bit for bit (given ``qa`` from the codes).  Implies
         ``want_indices`` and returns (z_run, r_tokens, idx, nb_valid uint8 [B, Tlat], nb_sent uint8 [B, P]).  Only in "f32"
-        arithmetic; the persistent kernel is never taken.  None: today's launches exactly."""
+        arithmetic; the persistent kernel is never taken.  None: today's launches exactly.  ``rate.beam`` > 1 (DESIGN.md section
+        33): each chunk's search is ops.rvq_beam -- the path with the smallest final residual among ``beam`` per token -- in place
+        of the greedy one; the rate launch reads its indices as it reads the greedy ones, so z_run stays the receiver's.  1:
+        today's launches exactly."""
         B, C, Tlat = zt.shape
-        rate_args = None
+        rate_args, beam = None, 1
         if rate is not None:
             packet_tok, rate_args = self._rate_resolve(rate, books_use, packet_tok)
             want_indices = True
+            beam = int(rate.beam)
         carried = z_prev is not None or z_last_out is not None
         if carried:
             if tactile_only:
@@ -391,7 +397,7 @@ class _ProposedBase(nn.Module):
         if mode is not None:
             return self._ar_latents_fused(zt, z_run, r_tokens, kv_all, 0 if tactile_only else min(qa.shape[-1], Tlat), books, books_use,
                                           tactile_only, want_indices, staged=(mode == "staged"), z_prev=z_prev, z_last_out=z_last_out,
-                                          rate=None if rate is None else (packet_tok,) + rate_args + (nb_valid, nb_sent))
+                                          rate=None if rate is None else (packet_tok,) + rate_args + (nb_valid, nb_sent), beam=beam)
         zt_prev, zp_n = None, -1      # the shift-by-one input: all zero except column 0 of each item (s > 0), so one zeroed
         for s in range(0, Tlat, AR_CHUNK_TOK):                               # buffer per chunk width serves every chunk
             e = min(Tlat, s + AR_CHUNK_TOK)
@@ -417,7 +423,10 @@ class _ProposedBase(nn.Module):
             if books is None:
                 qD = torch.zeros_like(rD)
             elif rate is not None:      # the search's int32 indices go to the rate kernel as they are: the receiver's sum over the books sent
-                _, idx = ops.rvq_ema_forward(rD, books, books_use, return_indices="int32")
+                if beam > 1:
+                    idx = ops.rvq_beam(rD, books, beam, books_use, folded_batch=B)
+                else:
+                    _, idx = ops.rvq_ema_forward(rD, books, books_use, return_indices="int32")
                 idx_all.append(idx.reshape(idx.shape[0], B, n))
                 qD = ops.rvq_rate(rD, idx, books, rate, packet_tok, books_use, folded_batch=B, nb_valid_out=nb_valid,
                                   nb_sent_out=nb_sent, col=s)[0]
@@ -472,7 +481,7 @@ class _ProposedBase(nn.Module):
                 and (books is None or (books.shape[1] <= 512 and books.shape[2] == CODE_DIM)))
 
     def _ar_latents_fused(self, zt, z_run, r_tokens, kv_all, t_audio, books, books_use, tactile_only, want_indices, staged=False,
-                          z_prev=None, z_last_out=None, rate=None):
+                          z_prev=None, z_last_out=None, rate=None, beam=1):
         B, _, Tlat = zt.shape
         p, L, ln = self.predict, self.predict._lin, self.tokennorm.ln
         nb = 0 if books is None else (books.shape[0] if books_use is None else max(0, min(int(books_use), books.shape[0])))
@@ -485,7 +494,7 @@ class _ProposedBase(nn.Module):
             w3=L["f3"].wp(), b3=det(p.ffn[3].bias), ln_eps=p.ln_q.eps, tok=(det(ln.weight), det(ln.bias)), tok_eps=ln.eps,
             scale=self._scale_value(), wd=self._pd.wp(), bd=det(self.proj_down.bias), wu=self._pu.wp(), bu=det(self.proj_up.bias),
             books=books, books_use=books_use, heads=p.h, c_ff=p.ffn[1].out_features, code_dim=CODE_DIM, r_tokens=r_tokens, idx_out=idx,
-            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged, z_prev=z_prev, z_last_out=z_last_out, rate=rate)
+            tactile_only=tactile_only, chunk=AR_CHUNK_TOK, staged=staged, z_prev=z_prev, z_last_out=z_last_out, rate=rate, beam=beam)
         if rate is not None:
             return z_run, r_tokens, idx.long(), rate[5], rate[6]
         if want_indices:
