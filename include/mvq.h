@@ -53,7 +53,8 @@ extern "C" {
  * mvq_encoder_stream_state_floats, mvq_encoder_stream_workspace_bytes, mvq_encoder_stream_fwd_f32; the receiver's audio output:
  * mvq_audio_fade_f32, mvq_audio_fade_slots_f32; the native-rate sender: mvq_resample_stream_rational_f32,
  * mvq_resample_stream_rational_slots_f32; their split form for few sessions: mvq_resample_stream_rational_split_f32,
- * mvq_resample_stream_rational_split_slots_f32).
+ * mvq_resample_stream_rational_split_slots_f32; fine-tuning the decoder: mvq_conv1d_wgrad_workspace_bytes, mvq_conv1d_wgrad_f32,
+ * mvq_channel_reduce_workspace_bytes, mvq_snake_bwd_f32, mvq_bias_grad_f32, mvq_weight_norm_bwd_f32).
  * Whole-stack entry points (mvq_encoder_fwd_f32, mvq_decoder_fwd_f32, mvq_decoder_fwd_saving_f32,
  * mvq_decoder_bwd_input_f32 and the mvq_stack handle).  2 (round 4): mvq_rvq_ema_step_f32 takes the larger 16-byte-aligned scratch that
  * mvq_rvq_ema_step_scratch_bytes() reports (version 1 documented nb*B*T int32), mvq_profile_end2() reports truncation,
@@ -543,6 +544,51 @@ int mvq_conv1d_dgrad_f32(const float* gy, const float* wp_dgrad, const float* ds
                          const float* residual, float* gx,
                          int batch, int cin, int tin, int cout, int tout, int ks, int stride, int dil, int pad,
                          void* stream);
+
+/* ---- parameter gradients of the decoder's layers (fine-tuning T_DEC; the reference freezes it) -------------------
+ * All fp32, no atomics, nothing allocated or synchronised inside a call; refusals return MVQ_EINVAL before any launch and
+ * leave every output untouched.  Checked against float64 autograd (fp32 tolerance), not part of the bit-exact contract.
+ *
+ * mvq_conv1d_wgrad_f32: gradient of a conv weight, in the torch layout of weight_v, described by the geometry of the
+ * FORWARD layer (as mvq_conv1d_dgrad_f32).  gy[B,cout,tout] is the gradient at the conv's output, a[B,cin,tin] its input.
+ *   transposed = 0, Conv1d (stride must be 1, tout = tin + 2 pad - dil (ks-1)):
+ *       dw[co][ci][k] = sum_b sum_t gy[b][co][t] * a[b][ci][t + k*dil - pad]
+ *   transposed = 1, ConvTranspose1d (ks == 2*stride, dil 1, tout = (tin-1) stride - 2 pad + ks + output_padding < stride):
+ *       dw[ci][co][k] = sum_b sum_t a[b][ci][t] * gy[b][co][t*stride - pad + k]
+ *   terms that index outside a row are 0.  snake_alpha[cin] (or NULL): `a` is the saved INPUT of the Snake1d in front of the
+ *   layer and the kernel stages snake(a, alpha) -- the arithmetic of the forward's Snake-on-load (det_snake).
+ * Summation contract.  t is the token index of the operand that is read unshifted (gy for a Conv1d, a for a
+ * ConvTranspose1d), in chunks of TK tokens (TK = 64; transposed: 64 / 32 / 32 / 16 for stride 2 / 4 / 5 / 8).  The list of
+ * (item b ascending, chunk ascending) is cut into `nsplit` contiguous ranges, range s = [n*s/nsplit, n*(s+1)/nsplit).  Inside a
+ * range every output element is ONE fp32 fma chain over the tokens in that order (v_mfma_f32_32x32x2_f32); the ranges' partial
+ * sums are added in ascending s, ((p0 + p1) + p2) + ...  nsplit = min(number of chunks, ceil(1024 / block tiles), 4096) is a
+ * function of the shape alone, so the same inputs give the same bits on every run and every device.  A layer with at most 4
+ * rows on the unshifted side (the decoder's final conv, cout = 1) takes a reduction form: chunks of 1024 tokens, each of 256
+ * threads one fma chain over its tokens (stride 256) in range order, then a fixed binary tree over the threads, then the ranges.
+ * workspace: mvq_conv1d_wgrad_workspace_bytes(same geometry) bytes of device memory, 4-byte aligned (0 when nsplit = 1; NULL
+ * is then accepted).  The query returns 0 for a geometry the call refuses. */
+size_t mvq_conv1d_wgrad_workspace_bytes(int batch, int cin, int tin, int cout, int tout, int ks, int stride, int dil, int pad,
+                                        int transposed);
+int mvq_conv1d_wgrad_f32(const float* gy, const float* a, const float* snake_alpha, float* dw, void* workspace,
+                         size_t workspace_bytes, int batch, int cin, int tin, int cout, int tout, int ks, int stride, int dil,
+                         int pad, int transposed, void* stream);
+/* Sums over the items and tokens of a [B,C,T] tensor, per channel: slabs of 2048 tokens of one item in (item, slab) order are cut
+ * into G = min(slabs, max(1, 2048 / C)) contiguous ranges; inside a range each of 256 threads chains its tokens (stride 256),
+ * a fixed binary tree adds the threads, and the ranges are added in ascending order.  workspace (both calls below):
+ * mvq_channel_reduce_workspace_bytes(batch, c, t) bytes, 4-byte aligned.
+ *   mvq_snake_bwd_f32: gs = gradient at a Snake1d's OUTPUT, x its saved input ->
+ *       gx = gs * d snake(x)/dx + residual   bit for bit the fused epilogue of mvq_conv1d_dgrad_f32 (one device function)
+ *       dalpha[c] = sum_{b,t} gs * (x sin(2 alpha x)/(alpha+1e-9) - sin(alpha x)^2/(alpha+1e-9)^2)     (NULL: not computed,
+ *       no workspace needed);  residual may be NULL;  gx must not alias an input.
+ *   mvq_bias_grad_f32: db[c] = sum_{b,t} gy[b][c][t]. */
+size_t mvq_channel_reduce_workspace_bytes(int batch, int c, int t);
+int mvq_snake_bwd_f32(const float* gs, const float* x, const float* alpha, const float* residual, float* gx, float* dalpha,
+                      void* workspace, size_t workspace_bytes, int batch, int c, int t, void* stream);
+int mvq_bias_grad_f32(const float* gy, float* db, void* workspace, size_t workspace_bytes, int batch, int c, int t, void* stream);
+/* Backward of w = g * v / ||v|| over the rows (dim 0, both conv kinds) of v[rows][cols]: with n = ||v_r||, s = <dw_r, v_r>
+ *   dg[r] = s / n        dv_r = (g_r / n) * (dw_r - (s / n^2) v_r)         (dg or dv may be NULL)
+ * One block per row: each of 256 threads chains its columns (stride 256), a fixed binary tree adds the threads. */
+int mvq_weight_norm_bwd_f32(const float* dw, const float* v, const float* g, float* dg, float* dv, int rows, int cols, void* stream);
 
 /* Backward of the reference's own trainable modules (CrossPredictor, TokenNorm, tanh*scale; Training/
  * compare_dacvsproposal_5.py:222-244,313-315 under `scaler.scale(total).backward()`, ...:393).  Same addressing as the

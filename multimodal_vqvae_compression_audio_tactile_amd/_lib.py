@@ -107,6 +107,12 @@ EXPORTS = {
     "mvq_conv1d_pack_dgrad_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mvq_conv_transpose1d_pack_dgrad_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mvq_conv1d_dgrad_f32": (c_int, [c_void_p] * 6 + [c_int] * 9 + [c_void_p]),
+    "mvq_conv1d_wgrad_workspace_bytes": (c_size_t, [c_int] * 10),
+    "mvq_conv1d_wgrad_f32": (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 10 + [c_void_p]),
+    "mvq_channel_reduce_workspace_bytes": (c_size_t, [c_int] * 3),
+    "mvq_snake_bwd_f32": (c_int, [c_void_p] * 7 + [c_size_t] + [c_int] * 3 + [c_void_p]),
+    "mvq_bias_grad_f32": (c_int, [c_void_p] * 3 + [c_size_t] + [c_int] * 3 + [c_void_p]),
+    "mvq_weight_norm_bwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 2 + [c_void_p]),
     "mvq_mul_dtanh_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvq_layernorm_c_bwd_f32": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_size_t] * 2 + [c_float, c_void_p]),
     "mvq_gelu_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

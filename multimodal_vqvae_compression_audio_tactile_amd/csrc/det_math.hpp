@@ -154,4 +154,14 @@ __device__ __forceinline__ float det_dsnake(float x, float alpha, float inv_alph
     return dfma(alpha * inv_alpha, det_sin_turns(t + t), 1.0f);
 }
 
+// d snake(x)/d alpha = x * sin(2*alpha*x) / (alpha+1e-9) - sin(alpha*x)^2 / (alpha+1e-9)^2   (fine-tuning: mvq_snake_bwd_f32).
+// Both sines are polynomials times their reduced argument, so a tiny alpha*x keeps its relative accuracy through the 1/alpha^2.
+__device__ __forceinline__ float det_dsnake_dalpha(float x, float alpha, float inv_alpha)
+{
+    const float t = x * (alpha * 0.318309886183790672f);
+    const float s2 = det_sin_turns(t + t);
+    const float q = det_sin2_turns(t);
+    return dfma(x * s2, inv_alpha, -((q * inv_alpha) * inv_alpha));
+}
+
 }  // namespace mvq

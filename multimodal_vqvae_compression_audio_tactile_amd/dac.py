@@ -168,6 +168,11 @@ class WNConv1d(_WNKeys, nn.Module):
         return ops.conv1d_dgrad(gy, self.packed_dgrad(), self.cin, tin, self.ks, 1, self.dilation, self.padding,
                                 dsnake_src=dsnake_src, dsnake_alpha=dsnake_alpha, residual=residual)
 
+    def wgrad(self, gy, a, snake_alpha=None):
+        """Gradient of the FOLDED weight [cout, cin, ks] from the gradient at this conv's output and its forward input ``a`` (with
+        snake_alpha: the saved input of the Snake in front; Snake is applied while staging).  ops.weight_norm_bwd maps it to g / v."""
+        return ops.conv1d_wgrad(gy, a, self.ks, 1, self.dilation, self.padding, snake_alpha=snake_alpha)
+
     def run(self, x, alpha_in=None, residual=None, alpha_out=None, tanh=False, alpha_dual=None, tvalid=0):
         if (alpha_dual is not None and alpha_in is None and residual is None and alpha_out is None and not tanh
                 and self.mode_eligible()):
@@ -216,6 +221,10 @@ class WNConvTranspose1d(_WNKeys, nn.Module):
     def dgrad(self, gy, tin, dsnake_src=None, dsnake_alpha=None):
         return ops.conv1d_dgrad(gy, self.packed_dgrad(), self.cin, tin, self.ks, self.stride, 1, self.padding,
                                 dsnake_src=dsnake_src, dsnake_alpha=dsnake_alpha)
+
+    def wgrad(self, gy, a, snake_alpha=None):
+        """Gradient of the FOLDED weight [cin, cout, ks]; arguments as WNConv1d.wgrad."""
+        return ops.conv1d_wgrad(gy, a, self.ks, self.stride, 1, self.padding, transposed=True, snake_alpha=snake_alpha)
 
     def run(self, x, alpha_in=None, alpha_out=None, alpha_dual=None, tout_rows=0, tvalid=0):
         return ops.conv_transpose1d(x, self.packed(), self.cout, self.stride, self.padding, bias=self.bias.detach(),
@@ -441,6 +450,10 @@ class Decoder(nn.Module):
         layers += [Snake1d(out), WNConv1d(out, d_out, 7, padding=3), nn.Tanh()]
         self.model = nn.Sequential(*layers)
         self._desc = (int(input_channel), int(channels), tuple(int(r) for r in rates), int(d_out), bool(output_padding))
+        # Training the decoder is opt-in through requires_grad (train.unfreeze_decoder): a decoder is built frozen, as the reference
+        # uses it (Training/compare_dacvsproposal_5.py:283-284), so that dec(z) with autograd enabled stays the inference path
+        # until a parameter is switched on.
+        self.requires_grad_(False)
 
     def stack(self):
         """The mvq_stack of this decoder (forward + input-gradient images), made once per parameter version."""
@@ -456,6 +469,11 @@ class Decoder(nn.Module):
         if self._stacked(z):                                       # ONE C call: mvq_decoder_fwd_saving_f32
             y, blob = self.stack().decoder_fwd_saving(z)
             return y, {"blob": blob, "batch": z.shape[0], "z_len": z.shape[-1]}
+        return self._forward_saving_plan(z)
+
+    @torch.no_grad()
+    def _forward_saving_plan(self, z):
+        """The saving forward walked from Python (the dict form): what backward_input and backward_params consume."""
         m = self.model
         nblk = len(m) - 4
         saved = {"z_len": z.shape[-1]}
@@ -505,6 +523,79 @@ class Decoder(nn.Module):
             del xin
         return m[0].dgrad(g, saved["z_len"])
 
+    # ---- fine-tuning (DESIGN.md section 34): gradients of the decoder's own parameters, opt-in through requires_grad -------------
+    def trainable(self):
+        """[(upstream state-dict name, parameter)] of the parameters that require a gradient."""
+        return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+
+    @staticmethod
+    def _conv_grads(grads, name, conv, gy, a, snake_alpha):
+        """bias / weight_g / weight_v gradients of one conv, each only if its parameter asks: gy = gradient at the conv's output,
+        a = its forward input, or the saved input of the Snake in front of it (snake_alpha given).  A frozen weight launches nothing."""
+        if conv.bias.requires_grad:
+            grads[name + ".bias"] = ops.bias_grad(gy)
+        need_g, need_v = conv.weight_g.requires_grad, conv.weight_v.requires_grad
+        if need_g or need_v:
+            dw = conv.wgrad(gy, a, snake_alpha)
+            dg, dv = ops.weight_norm_bwd(dw, conv.weight_v.detach(), conv.weight_g.detach(), need_dg=need_g, need_dv=need_v)
+            if need_g:
+                grads[name + ".weight_g"] = dg
+            if need_v:
+                grads[name + ".weight_v"] = dv
+
+    @staticmethod
+    def _snake_dgrad(grads, name, snake, conv, gy, x, residual=None):
+        """Gradient at the input of `snake -> conv` from the gradient at the conv's output.  Frozen alpha: today's launch, the Snake
+        derivative in the dgrad epilogue.  Trainable: dgrad without that epilogue, then ops.snake_bwd (the same bits, and d alpha)."""
+        kw = {} if residual is None else {"residual": residual}
+        if not snake.alpha.requires_grad:
+            return conv.dgrad(gy, x.shape[-1], dsnake_src=x, dsnake_alpha=snake.flat(), **kw)
+        gs = conv.dgrad(gy, x.shape[-1])
+        gx, dalpha = ops.snake_bwd(gs, x, snake.flat(), residual=residual)
+        grads[name + ".alpha"] = dalpha.reshape(snake.alpha.shape)
+        return gx
+
+    @torch.no_grad()
+    def backward_params(self, saved, gy, need_gz=True):
+        """-> (dL/dz or None, {state-dict name: gradient}) from dL/dy and the dict form of the saving forward (with "z", the
+        decoder input, added when model.0's weight is trainable).  The plan is backward_input's, layer for layer and with the same
+        release of every saved tensor; at each layer the gradients of its trainable parameters are computed from the gradient at
+        the conv's output, which that walk already holds.  An entry for every parameter with requires_grad, and only those."""
+        if "blob" in saved:
+            raise MvqError("Decoder.backward_params: needs the dict form of the saving forward (_forward_saving_plan), not the stack blob")
+        m = self.model
+        nblk = len(m) - 4
+        grads = {}
+        y = saved.pop("y")
+        g = ops.mul_dtanh(gy, y)
+        del y
+        hl = saved.pop("hl")
+        self._conv_grads(grads, f"model.{nblk + 2}", m[nblk + 2], g, hl, m[nblk + 1].flat())
+        g = self._snake_dgrad(grads, f"model.{nblk + 1}", m[nblk + 1], m[nblk + 2], g, hl)
+        del hl
+        for i in range(nblk, 0, -1):
+            blk = m[i].block
+            for j in (4, 3, 2):
+                ru = blk[j].block
+                pre = f"model.{i}.block.{j}.block"
+                x, t7 = saved.pop(f"b{i}.r{j}.x"), saved.pop(f"b{i}.r{j}.t7")
+                self._conv_grads(grads, pre + ".3", ru[3], g, t7, ru[2].flat())
+                g1 = self._snake_dgrad(grads, pre + ".2", ru[2], ru[3], g, t7)
+                self._conv_grads(grads, pre + ".1", ru[1], g1, x, ru[0].flat())
+                g = self._snake_dgrad(grads, pre + ".0", ru[0], ru[1], g1, x, residual=g)
+                del x, t7, g1
+            xin = saved.pop(f"b{i}.x")
+            self._conv_grads(grads, f"model.{i}.block.1", blk[1], g, xin, blk[0].flat())
+            g = self._snake_dgrad(grads, f"model.{i}.block.0", blk[0], blk[1], g, xin)
+            del xin
+        z = saved.pop("z", None)
+        if any(p.requires_grad for p in m[0].parameters()):
+            if z is None:
+                raise MvqError("Decoder.backward_params: model.0 is trainable but the saved forward does not hold the decoder input \"z\"")
+            self._conv_grads(grads, "model.0", m[0], g, z, None)
+        del z
+        return (m[0].dgrad(g, saved["z_len"]) if need_gz else None), grads
+
     # ---- stateful streaming decode (DESIGN.md section 23): T_DEC piece by piece, every stage keeping the tail of its input -----------
     def stream_state(self, rows):
         """The decoder state of ``rows`` streaming sessions, fp32 [rows, S] on the weights' device (Stack.decoder_stream_state)."""
@@ -523,8 +614,15 @@ class Decoder(nn.Module):
     def forward(self, z):
         """Inference: the fused fast path.  With autograd enabled and z.requires_grad (the reference's training step,
         Training/compare_dacvsproposal_5.py:322,393): saving forward + HIP backward w.r.t. z; weights stay frozen."""
-        if torch.is_grad_enabled() and z.requires_grad:
-            return _DecoderInputGrad.apply(z, self)
+        if torch.is_grad_enabled():
+            if z.numel() and any(p.requires_grad for p in self.parameters()):     # fine-tuning: opt-in through requires_grad
+                if ops.get_arith() != "f32":
+                    raise MvqError(f"Decoder: a trainable decoder runs in the 'f32' arithmetic only; ops.set_arith({ops.get_arith()!r}) "
+                                   "has no weight-gradient kernels (freeze the decoder or switch the mode off)")
+                named = self.trainable()
+                return _DecoderParamGrad.apply(z, self, tuple(n for n, _ in named), *[p for _, p in named])
+            if z.requires_grad:
+                return _DecoderInputGrad.apply(z, self)
         return self._forward_fast(z)
 
     @torch.no_grad()
@@ -608,6 +706,9 @@ class Decoder(nn.Module):
         return y if y.shape[-1] == t else y[..., :t].contiguous()
 
 
+_TWICE = "Decoder input-gradient: backward called twice (the saved forward is released by the first call)"
+
+
 class _DecoderInputGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, dec):
@@ -625,8 +726,31 @@ class _DecoderInputGrad(torch.autograd.Function):
     def backward(ctx, gy):
         saved, ctx.saved = ctx.saved, None                       # consumed once: nothing survives the backward
         if saved is None:
-            raise RuntimeError("Decoder input-gradient: backward called twice (the saved forward is released by the first call)")
+            raise RuntimeError(_TWICE)
         return ctx.dec.backward_input(saved, gy.contiguous()), None
+
+
+class _DecoderParamGrad(torch.autograd.Function):
+    """Decoder.forward with trainable decoder parameters: the Python-walked saving forward, then Decoder.backward_params.  The
+    parameters are inputs of the node (autograd accumulates their .grad as for any other); z may or may not need a gradient."""
+
+    @staticmethod
+    def forward(ctx, z, dec, names, *params):
+        zd = z.detach().float().contiguous()
+        y, saved = dec._forward_saving_plan(zd)
+        saved["y"] = y.detach()                                  # not the returned object: see _DecoderInputGrad.forward
+        saved["z"] = zd
+        ctx.dec, ctx.saved, ctx.names = dec, saved, names
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved, ctx.saved = ctx.saved, None
+        if saved is None:
+            raise RuntimeError(_TWICE)
+        gz, grads = ctx.dec.backward_params(saved, gy.contiguous(), need_gz=ctx.needs_input_grad[0])
+        # a parameter frozen between forward and backward gets None; one unfrozen in between has no entry and gets None as well
+        return (gz, None, None) + tuple(grads.get(n) if need else None for n, need in zip(ctx.names, ctx.needs_input_grad[3:]))
 
 
 class VectorQuantize(nn.Module):

@@ -1794,6 +1794,92 @@ def conv1d_dgrad(gy, wp_dgrad, cin, tin, ks, stride=1, dil=1, pad=0, dsnake_src=
     return gx
 
 
+# ------------------------------------------------------- parameter gradients of the decoder's layers (fine-tuning T_DEC)
+def _ws(nbytes, device):
+    """Caller-provided workspace of a native call: fp32 storage of at least nbytes (None when the call needs none)."""
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32) if nbytes else None
+
+
+def conv1d_wgrad(gy, a, ks, stride=1, dil=1, pad=0, transposed=False, snake_alpha=None):
+    """Gradient of a conv weight in the torch layout of weight_v, the layer described by its FORWARD geometry: gy[B,cout,tout]
+    the gradient at its output, a[B,cin,tin] its input -> dW[cout,cin,ks] (Conv1d) or dW[cin,cout,ks] (ConvTranspose1d, ks ==
+    2*stride).  snake_alpha[cin]: ``a`` is the saved input of the Snake in front of the layer; Snake is applied while staging."""
+    gy = _dev(gy, "gy"); a = _dev(a, "a")
+    if gy.dim() != 3 or a.dim() != 3 or gy.shape[0] != a.shape[0]:
+        raise MvqError(f"conv1d_wgrad: gy {tuple(gy.shape)} and a {tuple(a.shape)} must be [B, C, T] with one batch")
+    B, cout, tout = gy.shape
+    _, cin, tin = a.shape
+    ks, stride, dil, pad = int(ks), int(stride), int(dil), int(pad)
+    if transposed:
+        if ks != 2 * stride:
+            raise MvqError(f"conv1d_wgrad: transposed kernel {ks} != 2*stride ({stride}) is outside the path")
+        base = (tin - 1) * stride - 2 * pad + ks
+        ok = base <= tout < base + stride if tin else tout == 0
+    else:
+        ok = stride == 1 and tout == tin + 2 * pad - dil * (ks - 1)
+    if not ok:
+        raise MvqError(f"conv1d_wgrad: tout {tout} does not match tin {tin}, ks {ks}, stride {stride}, dil {dil}, pad {pad}")
+    if snake_alpha is not None:
+        snake_alpha = _dev(snake_alpha, "snake_alpha")
+        if snake_alpha.numel() != cin:
+            raise MvqError(f"conv1d_wgrad: snake_alpha has {snake_alpha.numel()} entries, the layer {cin} input channels")
+    geo = (B, cin, tin, cout, tout, ks, stride, dil, pad, int(bool(transposed)))
+    dw = torch.empty((cin, cout, ks) if transposed else (cout, cin, ks), device=gy.device, dtype=torch.float32)
+    nbytes = _lib.lib().mvq_conv1d_wgrad_workspace_bytes(*geo)
+    ws = _ws(nbytes, gy.device)
+    check(_lib.lib().mvq_conv1d_wgrad_f32(gy.data_ptr(), a.data_ptr(), _p(snake_alpha), dw.data_ptr(), _p(ws), nbytes, *geo, _stream()),
+          "mvq_conv1d_wgrad_f32")
+    return dw
+
+
+def snake_bwd(gs, x, alpha, residual=None, need_dalpha=True):
+    """Backward of Snake1d: gs the gradient at its output, x its saved input -> (gx, dalpha[C] or None).  gx = gs * dsnake(x)/dx +
+    residual is bit for bit what conv1d_dgrad's fused epilogue gives."""
+    gs = _dev(gs, "gs"); x = _dev(x, "x"); alpha = _dev(alpha, "alpha")
+    if gs.dim() != 3 or gs.shape != x.shape or alpha.numel() != gs.shape[1]:
+        raise MvqError(f"snake_bwd: gs {tuple(gs.shape)}, x {tuple(x.shape)}, alpha {tuple(alpha.shape)} do not match [B, C, T] / [C]")
+    if residual is not None:
+        residual = _dev(residual, "residual")
+        if residual.shape != gs.shape:
+            raise MvqError(f"snake_bwd: residual shape {tuple(residual.shape)} != {tuple(gs.shape)}")
+    B, C, T = gs.shape
+    gx = torch.empty_like(gs)
+    dalpha = torch.empty(C, device=gs.device, dtype=torch.float32) if need_dalpha else None
+    nbytes = _lib.lib().mvq_channel_reduce_workspace_bytes(B, C, T) if need_dalpha else 0
+    ws = _ws(nbytes, gs.device)
+    check(_lib.lib().mvq_snake_bwd_f32(gs.data_ptr(), x.data_ptr(), alpha.data_ptr(), _p(residual), gx.data_ptr(), _p(dalpha), _p(ws),
+                                       nbytes, B, C, T, _stream()), "mvq_snake_bwd_f32")
+    return gx, dalpha
+
+
+def bias_grad(gy):
+    """db[C] = sum over items and tokens of gy[B, C, T], in a fixed order."""
+    gy = _dev(gy, "gy")
+    if gy.dim() != 3:
+        raise MvqError(f"bias_grad: gy {tuple(gy.shape)} must be [B, C, T]")
+    B, C, T = gy.shape
+    db = torch.empty(C, device=gy.device, dtype=torch.float32)
+    nbytes = _lib.lib().mvq_channel_reduce_workspace_bytes(B, C, T)
+    ws = _ws(nbytes, gy.device)
+    check(_lib.lib().mvq_bias_grad_f32(gy.data_ptr(), db.data_ptr(), _p(ws), nbytes, B, C, T, _stream()), "mvq_bias_grad_f32")
+    return db
+
+
+def weight_norm_bwd(dw, v, g, need_dg=True, need_dv=True):
+    """Backward of weight_norm(v, g) over dim-0 rows: dw the gradient of the folded weight -> (dg like g, dv like v)."""
+    dw = _dev(dw, "dw"); v = _dev(v, "v"); g = _dev(g, "g")
+    if dw.shape != v.shape or v.dim() < 2 or g.numel() != v.shape[0]:
+        raise MvqError(f"weight_norm_bwd: dw {tuple(dw.shape)}, v {tuple(v.shape)}, g {tuple(g.shape)} do not match")
+    if not (need_dg or need_dv):
+        raise MvqError("weight_norm_bwd: nothing asked for")
+    rows = v.shape[0]
+    dg = torch.empty_like(g) if need_dg else None
+    dv = torch.empty_like(v) if need_dv else None
+    check(_lib.lib().mvq_weight_norm_bwd_f32(dw.data_ptr(), v.data_ptr(), g.data_ptr(), _p(dg), _p(dv), rows, v.numel() // max(rows, 1),
+                                             _stream()), "mvq_weight_norm_bwd_f32")
+    return dg, dv
+
+
 def mul_dtanh(g, y):
     g = _dev(g, "g"); y = _dev(y, "y")
     out = torch.empty_like(g)

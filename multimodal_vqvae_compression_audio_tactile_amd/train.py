@@ -209,3 +209,19 @@ class RvqSteLayers(Function):
     @staticmethod
     def backward(ctx, g, _gidx):
         return g * ctx.scale, None, None
+
+
+def unfreeze_decoder(net, *, snake=True, bias=True):
+    """Fine-tune the tactile decoder: set ``requires_grad`` on ``net.T_DEC``'s parameters (``net``: a model with a ``T_DEC``, or a
+    dac.Decoder itself) and return them for the optimiser.  The conv weights (weight_g / weight_v) always; the Snake alphas and
+    the conv biases unless switched off.  The constructors freeze T_DEC as the reference does; this is the opt-in that undoes it.
+    ``forward_step`` then trains the decoder too: dac.Decoder.forward records the weight-gradient backward (backward_params)."""
+    dec = getattr(net, "T_DEC", net)
+    out = []
+    for name, p in dec.named_parameters():
+        kind = name.rsplit(".", 1)[-1]
+        want = kind in ("weight_g", "weight_v") or (kind == "alpha" and snake) or (kind == "bias" and bias)
+        p.requires_grad_(bool(want))
+        if want:
+            out.append(p)
+    return out
